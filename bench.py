@@ -14,7 +14,16 @@ collective is the all-gather of the per-sequence factor counts (RCCL over xGMI).
 A step = one complete factorization of the rank's sequence with the text already resident in HBM:
 pack -> suffix array -> LCP -> L* -> chain -> all z factor records (start, length, ref) built in HBM.
 
-Beside `value` the same JSON line carries
+A plain run sets up, warms up, times the --steps steps (stage profiler off) and prints the JSON line: `value`,
+`ms_per_step` (one timed step), the end-to-end HBM figure of SURVEY.md 8d computed from it, and every rank's clock.
+`--dump-outputs DIR` writes what the timed step computed as DIR/<name>.npy after the timed steps (float64, at most
+64 MB: for the single sequence the factor counts, the factors covering 2^20 text positions drawn with a fixed seed and
+per-block sums over all records, see factor_outputs; for --workload fasta512 the 512 factor counts); the inputs are
+the seeded generators of tests/gen.py, so two builds can be compared output for output.
+
+`--full` adds everything else: the stage profile of the timed steps and the roofline figures derived from it, and in
+runs of their own the copy ceiling, the PCIe-inclusive run, the CPU baselines ("cpu_baseline": the oracle on a prefix
+of the same input) and
   * "stopwatches" (N = 1): the three clocks of SURVEY.md 8d -- C ABI host buffer -> host factor array,
     count_factors from a host buffer, and the Python-visible noLZSS.factorize() (tuple list) on a prefix;
   * "rc256m": BASELINE config 5 on one GPU per rank (factorize_dna_w_rc of 2^28 bases resident in HBM, SURVEY.md
@@ -22,7 +31,7 @@ Beside `value` the same JSON line carries
   * "fasta512": BASELINE config 4, the multi-sequence FASTA shard (512 records x 4 Mi bases, generator of
     config 2 with seeds 0x4000 + k) dealt over the N ranks by the longest-processing-time-first plan, one
     all-gather of the 512 factor counts -- STRONG scaling (total work fixed), records resident in HBM when
-    its clock starts.  `--workload fasta512` makes this the headline instead and also times the
+    its clock starts.  `--workload fasta512` makes this the headline instead; with --full it also times the
     file -> reader -> batch -> counts path through genomics.shard_nucleotide_fasta.
 """
 import argparse
@@ -193,6 +202,46 @@ def measured_traffic_ratio():
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE = 1 << 20        # text positions whose covering factor is written (fixed seed)
+DUMP_SEED = 0x0D0E5EED
+DUMP_BLOCKS = 4096           # equal ranges of the text: factors starting in each, counted and summed
+
+
+def factor_outputs(f: np.ndarray, n: int, counts) -> dict:
+    """--dump-outputs of the single-sequence step.  A caller of the step gets the factor count and the (start, length,
+    ref) records of the text; the records of 2^30 bases take 1.25 GB, so what is written is (float64, exact for every
+    value < 2^53):
+      factor_counts     the factor count of every rank's sequence
+      sample_positions  DUMP_SAMPLE text positions drawn with a fixed seed (distinct, ascending; rank 0's text)
+      factors_sample    (start, length, ref) of the factor that covers each of these positions
+      block_sums        per DUMP_BLOCKS-th of the text: the number of factors that start in it, the sum of their
+                        lengths and the sum of their refs (every record counts somewhere)"""
+    rng = np.random.default_rng(DUMP_SEED)
+    pos = np.unique(rng.integers(0, n, size=min(DUMP_SAMPLE, n), dtype=np.int64))
+    start = f["start"]
+    j = np.searchsorted(start, pos, side="right") - 1
+    sample = np.stack([start[j], f["length"][j], f["ref"][j]], axis=1)
+    block = (start * DUMP_BLOCKS // n).astype(np.int64)
+    sums = np.stack([np.bincount(block, minlength=DUMP_BLOCKS),
+                     np.bincount(block, weights=f["length"].astype(np.float64), minlength=DUMP_BLOCKS),
+                     np.bincount(block, weights=f["ref"].astype(np.float64), minlength=DUMP_BLOCKS)], axis=1)
+    return {"factor_counts": np.asarray(counts), "sample_positions": pos, "factors_sample": sample,
+            "block_sums": sums}
+
+
+def write_outputs(outdir, arrays: dict) -> None:
+    """DIR/<name>.npy, float64, at most DUMP_LIMIT_BYTES in all"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(out / f"{name}.npy", v)
+
+
 def make_text(workload: str, n: int, rank: int) -> np.ndarray:
     if workload == "dna1g":
         return gen.repeat_dna(n, seed=0x5EED0003 + rank)
@@ -289,19 +338,21 @@ def run_single_sequence(job: Job, a):
             dist.all_gather_into_tensor(counts, mine)
         return z
 
-    copy_ceiling = measure_copy_ceiling(job.dev) if job.rank == 0 else None
+    copy_ceiling = measure_copy_ceiling(job.dev) if (a.full and job.rank == 0) else None
     for _ in range(a.warmup):
         step()
-    native.profile_enable(True)
-    native.profile_reset()
+    if a.full:  # the stage profiler (HIP events around every stage) runs for the --full line only
+        native.profile_enable(True)
+        native.profile_reset()
     job.barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         z = step()
     job.barrier()
     elapsed = time.perf_counter() - t0
-    stats = native.profile_report()
-    native.profile_enable(False)
+    if a.full:
+        stats = native.profile_report()
+        native.profile_enable(False)
     # every rank's own clock, device and factor count, for rank 0's line
     mine_row = torch.tensor([elapsed / a.steps * 1e3, float(job.local_rank), float(z)], dtype=torch.float64, device=job.cdev)
     rank_rows = torch.zeros(job.world * 3, dtype=torch.float64, device=job.cdev)
@@ -312,35 +363,27 @@ def run_single_sequence(job: Job, a):
     rank_rows = rank_rows.view(job.world, 3).cpu().tolist()
     elapsed = job.max_over_ranks(elapsed)
 
-    # PCIe-inclusive variant (records downloaded into host memory), rank-local, one run
-    t1 = time.perf_counter()
-    z2, f = native.factorize_device(d_text.data_ptr(), n, emit=2)
-    pcie_dt = time.perf_counter() - t1
-    assert z2 == z
-    del f
+    if a.full or a.dump_outputs:
+        # one more run of the step with the records downloaded into host memory, rank-local: the PCIe-inclusive
+        # variant of the --full line, and the records --dump-outputs writes (the same text through the same pipeline
+        # as the timed steps, which leave them in HBM)
+        t1 = time.perf_counter()
+        z2, f = native.factorize_device(d_text.data_ptr(), n, emit=2)
+        pcie_dt = time.perf_counter() - t1
+        assert z2 == z
+        if a.dump_outputs and job.rank == 0:
+            write_outputs(a.dump_outputs, factor_outputs(f, n, [r[2] for r in rank_rows]))
+        del f
     del d_text
     torch.cuda.empty_cache()
     if job.rank != 0:
         return None, text, z
 
-    total_bases = float(n) * job.world * a.steps
-    # every launch of the kernel, whatever the instantiation (the library reports them by class:
-    # rs_scatter.text = first pass computing the keys, .u32 / .u64 = key width, .small = < 2^24 pairs)
-    family = {k: v for k, v in stats.items() if in_family(k)}
-    cnt = sum(v[0] for v in family.values())
-    ms = sum(v[1] for v in family.values())
-    nbytes = sum(v[2] for v in family.values())
-    achieved = (nbytes / (ms * 1e-3)) / 1e9 if ms > 0 else 0.0
-    by_class = {k: {"launches": v[0], "ms_per_step": v[1] / a.steps,
-                    "achieved_GBps": (v[2] / (v[1] * 1e-3)) / 1e9 if v[1] > 0 else 0.0}
-                for k, v in sorted(family.items())}
-    nested = {"rs_hist", "rs_scan", "bucket_scatter", "window_scatter"} | set(family)
-    ratio, ratio_file = measured_traffic_ratio()
-    pmc = step_counters()
     step_s = elapsed / a.steps
+    pmc = step_counters()
     out = {
         "metric": "bases/sec factorized (1 GB sigma=4 DNA) + HBM GB/s fraction",
-        "value": total_bases / elapsed,
+        "value": float(n) * job.world * a.steps / elapsed,
         "unit": "bases/s",
         "n_gpus": job.world,
         "steps": a.steps,
@@ -356,6 +399,36 @@ def run_single_sequence(job: Job, a):
                                "to (start,length,ref) records in HBM",
                    "bases_per_gpu": n, "factors_per_sequence": int(z),
                    "parallelism": f"{job.world} independent sequence shard(s), all-gather of counts"},
+        # SURVEY.md 8d end-to-end figure: 50 B per base of compulsory traffic over the whole pipeline
+        "pipeline_hbm": {"algorithmic_bytes_per_base": ALG_BYTES_PER_BASE,
+                         "achieved_GBps_per_gpu": ALG_BYTES_PER_BASE * n / step_s / 1e9,
+                         "frac_of_peak_per_gpu": ALG_BYTES_PER_BASE * n / step_s / 1e9 / HBM_PEAK_GBS,
+                         # what the whole step really moves: FETCH_SIZE + WRITE_SIZE summed over every kernel of one
+                         # factorization (tools/pmc_step.sh, separate passes, gfx950 correction), per base
+                         "traffic_bytes_per_base": ((pmc or {}).get("step") or {}).get("hbm_bytes_per_base")
+                         if (pmc and pmc.get("bases") == n) else None,
+                         "traffic_GBps_per_gpu": (pmc["step"]["hbm_bytes_per_base"] * n / step_s / 1e9)
+                         if (pmc and pmc.get("bases") == n and pmc["step"].get("hbm_bytes_per_base")) else None,
+                         "traffic_derived_from": f"profiles/{STEP_PMC_FILE}" if pmc else None},
+        "per_rank": [{"rank": k, "device": f"cuda:{int(r[1])}", "bases": n, "factors": int(r[2]), "ms_per_step": r[0]}
+                     for k, r in enumerate(rank_rows)],
+    }
+    if not a.full:
+        return out, text, z
+
+    # every launch of the kernel, whatever the instantiation (the library reports them by class:
+    # rs_scatter.text = first pass computing the keys, .u32 / .u64 = key width, .small = < 2^24 pairs)
+    family = {k: v for k, v in stats.items() if in_family(k)}
+    cnt = sum(v[0] for v in family.values())
+    ms = sum(v[1] for v in family.values())
+    nbytes = sum(v[2] for v in family.values())
+    achieved = (nbytes / (ms * 1e-3)) / 1e9 if ms > 0 else 0.0
+    by_class = {k: {"launches": v[0], "ms_per_step": v[1] / a.steps,
+                    "achieved_GBps": (v[2] / (v[1] * 1e-3)) / 1e9 if v[1] > 0 else 0.0}
+                for k, v in sorted(family.items())}
+    nested = {"rs_hist", "rs_scan", "bucket_scatter", "window_scatter"} | set(family)
+    ratio, ratio_file = measured_traffic_ratio()
+    out.update({
         "roofline": {"bound": "hbm", "kernel": "rs_scatter_kernel + local_sort_kernel (the radix sort family)", "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      # the second ceiling of SURVEY.md 8d: a streaming copy measured on this box before the timed region
@@ -372,24 +445,11 @@ def run_single_sequence(job: Job, a):
                      "algorithmic_bytes_per_launch": (nbytes / cnt) if cnt else None,
                      "by_class": by_class,
                      "kernels": kernel_bounds(dict(stats, _bases=n), a.steps, pmc)},
-        # SURVEY.md 8d end-to-end figure: 50 B per base of compulsory traffic over the whole pipeline
-        "pipeline_hbm": {"algorithmic_bytes_per_base": ALG_BYTES_PER_BASE,
-                         "achieved_GBps_per_gpu": ALG_BYTES_PER_BASE * n / step_s / 1e9,
-                         "frac_of_peak_per_gpu": ALG_BYTES_PER_BASE * n / step_s / 1e9 / HBM_PEAK_GBS,
-                         # what the whole step really moves: FETCH_SIZE + WRITE_SIZE summed over every kernel of one
-                         # factorization (tools/pmc_step.sh, separate passes, gfx950 correction), per base
-                         "traffic_bytes_per_base": ((pmc or {}).get("step") or {}).get("hbm_bytes_per_base")
-                         if (pmc and pmc.get("bases") == n) else None,
-                         "traffic_GBps_per_gpu": (pmc["step"]["hbm_bytes_per_base"] * n / step_s / 1e9)
-                         if (pmc and pmc.get("bases") == n and pmc["step"].get("hbm_bytes_per_base")) else None,
-                         "traffic_derived_from": f"profiles/{STEP_PMC_FILE}" if pmc else None},
-        "per_rank": [{"rank": k, "device": f"cuda:{int(r[1])}", "bases": n, "factors": int(r[2]), "ms_per_step": r[0]}
-                     for k, r in enumerate(rank_rows)],
         "pcie_inclusive_bases_per_s": n / pcie_dt,
         "stages_ms_per_step": {k: v[1] / a.steps for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1])
                                if k not in nested},
         "kernels_ms_per_step": {k: stats[k][1] / a.steps for k in sorted(nested) if k in stats},
-    }
+    })
     return out, text, z
 
 
@@ -490,10 +550,11 @@ def stopwatches(text: np.ndarray, z: int, py_log2: int):
                     "build 5*10^7 tuples)"}
 
 
-def run_fasta_shard(job: Job, a, with_file: bool):
+def run_fasta_shard(job: Job, a, headline: bool):
     """BASELINE config 4: `records` FASTA records of 2^rec_log2 bases, dealt over the ranks by the LPT
     plan of the library; per step every rank factorizes its records (resident in HBM) to factor records
-    in HBM and the 512 counts are all-gathered.  Strong scaling."""
+    in HBM and the 512 counts are all-gathered.  Strong scaling.  As the headline (--workload fasta512)
+    --dump-outputs writes the 512 counts and --full also times the file path."""
     m, L = a.fasta_records, 1 << a.fasta_record_log2
     owners = native.debug_lpt_plan([L] * m, job.world)
     mine = [j for j, o in enumerate(owners) if o == job.rank]
@@ -563,6 +624,13 @@ def run_fasta_shard(job: Job, a, with_file: bool):
                          "allgather_ms_per_step": r[1]} for k, r in enumerate(rows)],
            "total_factors": int(sum(counts)),
            "pipeline_hbm_frac_per_gpu": ALG_BYTES_PER_BASE * (total / job.world) / step_s / 1e9 / HBM_PEAK_GBS}
+    if headline and a.dump_outputs and job.rank == 0:
+        # what a caller of the step receives: the factor count of every record
+        write_outputs(a.dump_outputs, {"factor_counts": np.asarray(counts)})
+    if not a.full:
+        del d_recs
+        torch.cuda.empty_cache()
+        return out if job.rank == 0 else None
     # PCIe-inclusive: the host-buffer batch entry point (nolzss_factorize_batch), counts only
     job.barrier()
     t0 = time.perf_counter()
@@ -573,7 +641,7 @@ def run_fasta_shard(job: Job, a, with_file: bool):
     out["host_buffers_to_counts_bases_per_s"] = total / dt
     del d_recs
     torch.cuda.empty_cache()
-    if with_file:
+    if headline:
         # file -> native reader -> batch -> all-gather, through the reference's caller
         from nolzss_amd.genomics.fasta import shard_nucleotide_fasta
         tmp = Path("/dev/shm") if Path("/dev/shm").is_dir() else Path(tempfile.gettempdir())
@@ -609,14 +677,20 @@ def main():
     ap.add_argument("--log2n", type=int, default=30, help="bases per GPU = 2^log2n (default 2^30)")
     ap.add_argument("--cpu-sample-log2", type=int, default=26)
     ap.add_argument("--python-sample-log2", type=int, default=26)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stopwatches", action="store_true")
-    ap.add_argument("--no-fasta", action="store_true", help="skip the fasta512 side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the side workloads (fasta512, rc256m), "
+                         "the stopwatches, the CPU baselines, the stage profile, the roofline figures and the copy "
+                         "ceiling (and the file path of --workload fasta512)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed step computes as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-stopwatches", action="store_true", help="with --full: skip the stopwatches")
+    ap.add_argument("--no-fasta", action="store_true", help="with --full: skip the fasta512 side measurement")
     ap.add_argument("--fasta-records", type=int, default=512)
     ap.add_argument("--fasta-record-log2", type=int, default=22)
     ap.add_argument("--fasta-steps", type=int, default=2)
     ap.add_argument("--fasta-warmup", type=int, default=1)
-    ap.add_argument("--no-rc", action="store_true", help="skip the rc256m side measurement (BASELINE config 5)")
+    ap.add_argument("--no-rc", action="store_true", help="with --full: skip the rc256m side measurement (BASELINE config 5)")
     ap.add_argument("--rc-log2n", type=int, default=28)
     ap.add_argument("--rc-steps", type=int, default=3)
     ap.add_argument("--rc-warmup", type=int, default=1)
@@ -636,8 +710,8 @@ def main():
 
     if a.workload == "fasta512":
         a.fasta_steps, a.fasta_warmup = a.steps, a.warmup
-        fa = run_fasta_shard(job, a, with_file=True)
-        if job.rank == 0 and job.world == 1 and not a.no_cpu_baseline:
+        fa = run_fasta_shard(job, a, headline=True)
+        if job.rank == 0 and job.world == 1 and a.full and not a.no_cpu_baseline:
             fa["cpu_baseline"] = cpu_baseline_fasta(a)
         if job.rank == 0:
             out = {"metric": "bases/sec factorized (multi-sequence FASTA shard, 512 x 4 Mi bases) + HBM GB/s fraction",
@@ -649,8 +723,8 @@ def main():
             print(json.dumps(out), flush=True)
     else:
         out, text, z = run_single_sequence(job, a)
-        fa = None if a.no_fasta else run_fasta_shard(job, a, with_file=False)
-        rc, rc_text = (None, None) if a.no_rc else run_rc(job, a)
+        fa = None if (a.no_fasta or not a.full) else run_fasta_shard(job, a, headline=False)
+        rc, rc_text = (None, None) if (a.no_rc or not a.full) else run_rc(job, a)
         if job.rank == 0:
             if job.collectives:
                 out["collectives"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
@@ -659,9 +733,9 @@ def main():
                 out["fasta512"] = fa
             if rc is not None:
                 out["rc256m"] = rc
-            if job.world == 1 and not a.no_stopwatches:  # the host-side clocks run on the one-GPU run only
+            if a.full and job.world == 1 and not a.no_stopwatches:  # the host-side clocks run on the one-GPU run only
                 out["stopwatches"] = stopwatches(text, z, a.python_sample_log2)
-            if job.world == 1 and not a.no_cpu_baseline:  # the CPU legs run on rank 0 of the one-GPU run only
+            if a.full and job.world == 1 and not a.no_cpu_baseline:  # the CPU legs run on rank 0 of the one-GPU run only
                 out["cpu_baseline"] = cpu_baseline(text, 1 << a.cpu_sample_log2)
                 if fa is not None:
                     fa["cpu_baseline"] = cpu_baseline_fasta(a)

@@ -15,7 +15,7 @@ NOLZSS_LIB=$lib python -m pytest tests/test_gpu_primitives.py tests/test_gpu_pip
     tests/test_gpu_rc.py tests/test_gpu_scale.py::test_config2_random_64Mi_exact tests/test_gpu_scale.py::test_rc_4Mi_exact \
     -x -q -m gpu > $out/pytest_variant.log 2>&1 || { tail -30 $out/pytest_variant.log; exit 1; }
 tail -2 $out/pytest_variant.log
-args="--steps 5 --warmup 2 --no-cpu-baseline --no-stopwatches $*"
+args="--steps 5 --warmup 2 --full --no-cpu-baseline --no-stopwatches $*"
 python bench.py $args > $out/bench_default.json 2> $out/bench_default.err || exit 1
 NOLZSS_LIB=$lib python bench.py $args > $out/bench_variant.json 2> $out/bench_variant.err || exit 1
 python - $out <<'PY'
