@@ -223,6 +223,21 @@ int nolzss_factorize_batch(const uint8_t *const *texts, const size_t *lens, size
 int nolzss_factorize_batch_dna_w_rc(const uint8_t *const *texts, const size_t *lens, size_t m,
                                     const int *devices, size_t n_dev, nolzss_factor ***out, size_t **z);
 void nolzss_free_batch(nolzss_factor **out, size_t *z, size_t m);
+/* Extension: per-record factor counts in BOTH modes, from ONE suffix array per pipeline run.
+ * count_w_rc[j] == nolzss_count_factors_dna_w_rc(texts[j]), count_no_rc[j] == nolzss_count_factors(texts[j])
+ * (both caller-allocated, m entries).  The plain-mode L* is a by-product of the reverse-complement run: over
+ * S = T s0 rc(T) s1 every earlier source of a position of T lies in T and no match runs past s0, so the plain
+ * L* of S at i < |T| is the plain L* of T ("Both counts from one suffix sort").
+ * Records: upper-case A/C/G/T only.  Planned and dealt like nolzss_factorize_batch_dna_w_rc (merged runs for
+ * short records, single runs dealt longest-first over the device list).  Empty records give 0 / 0.  The first
+ * record in input order that nolzss_count_factors_dna_w_rc refuses on its own fails the call with that
+ * function's status and message (an invalid nucleotide: NOLZSS_ERR_RUNTIME, "Invalid nucleotide 'N' found in
+ * sequence 0", RuntimeError in Python as there; a record too long for the reverse-complement path:
+ * NOLZSS_ERR_INVALID_ARGUMENT).  Lower-case bases fail with NOLZSS_ERR_INVALID_ARGUMENT and a message of
+ * their own: the plain count of `acgt` is not the plain count of `ACGT`.
+ * reference: the per-record pair of compute_sequence_complexity_table, genomics/batch_factorize.py:370-429 */
+int nolzss_count_factors_batch_both(const uint8_t *const *texts, const size_t *lens, size_t m,
+                                    const int *devices, size_t n_dev, size_t *count_w_rc, size_t *count_no_rc);
 /* The plain per-sequence batch with the records already in the memory of `device` (d_texts[j] = device
  * pointer to lens[j] bytes): no PCIe leg.  emit = 0 counts, emit = 1 also builds the factor records of
  * every record in HBM and stops there.  z[j] (caller-allocated, m entries) = factors of record j.  Used by

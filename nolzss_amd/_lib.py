@@ -122,6 +122,8 @@ def _load():
     lib.nolzss_factorize_batch_dna_w_rc.argtypes = lib.nolzss_factorize_batch.argtypes
     lib.nolzss_factorize_batch_device.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), sz, C.c_int, C.c_int,
                                                   C.POINTER(C.c_size_t)]
+    lib.nolzss_count_factors_batch_both.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), sz, C.POINTER(C.c_int),
+                                                    sz, szp, szp]
     lib.nolzss_free_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), sz]
     lib.nolzss_free_batch.restype = None
     lib.nolzss_read_nucleotide_fasta.argtypes = [C.c_char_p, C.POINTER(C.c_int), sz, C.c_int, sz, sz,
@@ -167,7 +169,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_batch_counters", "nolzss_factorize_batch_dna_w_rc",
     "nolzss_debug_trim_arenas", "nolzss_debug_parse_fasta",
     "nolzss_read_nucleotide_fasta", "nolzss_free_nucleotide_fasta", "nolzss_debug_parse_nucleotide_fasta", "nolzss_debug_lpt_plan", "nolzss_debug_batch_plan", "nolzss_factorize_batch_device",
-    "nolzss_factorize_dna_w_rc_device",
+    "nolzss_factorize_dna_w_rc_device", "nolzss_count_factors_batch_both",
 ]
 
 

@@ -195,6 +195,24 @@ def factorize_batch(texts, devices=None, want_factors: bool = True, with_rc: boo
     return counts, arrays
 
 
+def count_factors_batch_both(texts, devices=None):
+    """Extension: (counts_w_rc, counts_no_rc) of every record -- count_factors_dna_w_rc and count_factors of each --
+    from one suffix array per pipeline run (C ABI nolzss_count_factors_batch_both; the per-record pair of the
+    reference's compute_sequence_complexity_table, genomics/batch_factorize.py:370-429).  Records: upper-case
+    A/C/G/T bytes; an invalid nucleotide raises what count_factors_dna_w_rc raises on that record, lower case is
+    refused (ValueError)."""
+    devices = list(devices) if devices is not None else [_default_device]
+    bufs = [_as_buffer(t) for t in texts]
+    m = len(bufs)
+    ptrs = (C.c_void_p * max(m, 1))(*[b[0] for b in bufs])
+    lens = (C.c_size_t * max(m, 1))(*[b[1] for b in bufs])
+    devs = (C.c_int * len(devices))(*devices)
+    w_rc = (C.c_size_t * max(m, 1))()
+    no_rc = (C.c_size_t * max(m, 1))()
+    check(lib.nolzss_count_factors_batch_both(ptrs, lens, m, devs, len(devices), w_rc, no_rc))
+    return list(w_rc)[:m], list(no_rc)[:m]
+
+
 def factorize_batch_device(data_ptrs, lengths, emit: int = 0):
     """Extension (measurement): per-sequence batch over records resident in device memory
     (C ABI nolzss_factorize_batch_device); returns the factor count of every record."""

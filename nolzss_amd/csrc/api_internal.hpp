@@ -124,7 +124,7 @@ void prepare_w_rc(const char *const *seqs, const size_t *lens, size_t k, HostByt
 bool rc_guards(size_t S_len, size_t start_pos);
 size_t run_rc_host(Context &ctx, const uint8_t *S, size_t m, size_t start_pos, nolzss_factor **out);
 void dna_w_rc_common(const uint8_t *text, const uint8_t *d_resident, size_t n, int device, void *stream, int emit,
-                     nolzss_factor **out, size_t *z, int lane = 0);
+                     nolzss_factor **out, size_t *z, int lane = 0, size_t *z_plain = nullptr);
 
 // ---- reference + target, v2 files (c_abi.hip, factor_file.cpp) ----------------------------------------------------
 void write_v2_file(const char *out_path, const nolzss_factor *f, size_t z, uint64_t num_sequences,
@@ -159,7 +159,7 @@ struct BatchPlan {
 BatchPlan plan_batch(const size_t *lens, size_t m, bool with_rc);
 std::vector<std::vector<size_t>> lpt_plan_singles(std::vector<size_t> &singles, const size_t *lens, size_t n_dev);
 void factorize_many(const uint8_t *const *texts, const size_t *lens, size_t m, const int *devices, size_t n_dev,
-                    bool with_rc, size_t *zs, nolzss_factor **fs, std::vector<void *> &blocks);
+                    bool with_rc, size_t *zs, nolzss_factor **fs, std::vector<void *> &blocks, size_t *zs_plain = nullptr);
 extern std::atomic<uint64_t> g_merged_records, g_single_records;
 
 struct NucleotideFastaKeep {

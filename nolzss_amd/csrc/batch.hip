@@ -2,6 +2,8 @@
 // (part of the C ABI layer of libnolzss_hip.so, include/nolzss_hip.h; shared declarations: api_internal.hpp)
 #include "api_internal.hpp"
 
+#include <array>
+
 namespace nolzss {
 namespace api {
 
@@ -103,8 +105,11 @@ void *alloc_factor_block(size_t bytes) {
     return std::malloc(bytes);
 }
 
+// zs_plain (with_rc only, fs null): also the plain-mode count of every record, from the same suffix array (rc.hip,
+// RcPlainOut); both chains then deliver factor starts only and are split at the separators the same way.
 bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *lens, const std::vector<size_t> &ids,
-                      bool with_rc, size_t *zs, nolzss_factor **fs, std::vector<void *> *blocks) {
+                      bool with_rc, size_t *zs, nolzss_factor **fs, std::vector<void *> *blocks, size_t *zs_plain) {
+    if (zs_plain && (!with_rc || fs)) throw std::logic_error("run_merged_chunk: plain counts come with reverse-complement counts only");
     const bool trace = getenv("NOLZSS_TRACE") != nullptr;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
@@ -133,7 +138,8 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
     Arena &arena = ctx.arena;
     hipStream_t s = ctx.stream;
     const size_t m2 = 2 * n + 2;  // with_rc: T' sep revcomp(T') sep
-    reserve_arena_for(ctx, with_rc ? m2 : n, (with_rc ? m2 : 0) + n + 32 * c + (size_t(1) << 20));
+    reserve_arena_for(ctx, with_rc ? m2 : n, (with_rc ? m2 : 0) + n + 32 * c + (size_t(1) << 20) +
+                                                (zs_plain ? 4 * n + (size_t(32) << 20) : 0));
     const size_t mark = arena.mark();
     struct Rewind {
         Arena &a;
@@ -156,6 +162,8 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
     void *d_recs = nullptr;
     uint32_t *d_fpos = nullptr;
     uint32_t z = 0;
+    RcPlainOut plain;
+    plain.want_fpos = c > 1;
     if (with_rc) {
         // the layout of prepare_multiple_dna_sequences_w_rc (factorizer.cpp:128-169) for any number of
         // records: segment t and segment 2c - 1 - t are a record and its reverse complement
@@ -167,7 +175,10 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
         for (size_t k = seps.size(); k-- > 0;) terms.push_back((uint32_t)(2 * n - seps[k]));
         terms.push_back((uint32_t)(2 * n + 1));
         if (!pack_independent_text(ctx, d_S, m2, terms, text, true)) return false;
-        z = run_rc_pipeline_packed(ctx, text, 0, &d_recs);
+        if (zs_plain)
+            z = run_rc_pipeline_packed(ctx, text, 0, nullptr, &plain, &d_fpos);
+        else
+            z = run_rc_pipeline_packed(ctx, text, 0, &d_recs);
     } else {
         if (!pack_independent_text(ctx, d_text, n, seps, text)) return false;
         RecordPlanScope plan_scope(ctx, seps, (uint32_t)n);
@@ -188,21 +199,32 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
     }
     nolzss_factor *recs = static_cast<nolzss_factor *>(d_recs);
     // where the records' factor lists start and end
-    std::vector<uint32_t> fidx(c, z);
+    std::vector<uint32_t> fidx(c, z), fidx_plain(zs_plain ? c : 0, plain.z);
     if (c > 1) {
         uint32_t *d_fidx = arena.alloc<uint32_t>(c);
         HIP_CHECK(hipMemsetAsync(d_fidx + (c - 1), 0, sizeof(uint32_t), s));  // error flag
-        if (with_rc)
+        if (with_rc && !zs_plain)
             batch_bounds_kernel<<<(unsigned)div_up(c - 1, 256), 256, 0, s>>>(recs, z, text.terms.pos, (uint32_t)(c - 1),
                                                                              d_fidx, d_fidx + (c - 1));
         else
             batch_bounds_pos_kernel<<<(unsigned)div_up(c - 1, 256), 256, 0, s>>>(d_fpos, z, text.terms.pos,
                                                                                  (uint32_t)(c - 1), d_fidx, d_fidx + (c - 1));
         KERNEL_CHECK();
+        uint32_t *d_fidx_plain = nullptr;
+        if (zs_plain) {  // the plain chain's factor starts, split at the same separators
+            d_fidx_plain = arena.alloc<uint32_t>(c);
+            HIP_CHECK(hipMemsetAsync(d_fidx_plain + (c - 1), 0, sizeof(uint32_t), s));  // error flag
+            batch_bounds_pos_kernel<<<(unsigned)div_up(c - 1, 256), 256, 0, s>>>(plain.fpos, plain.z, text.terms.pos,
+                                                                                 (uint32_t)(c - 1), d_fidx_plain,
+                                                                                 d_fidx_plain + (c - 1));
+            KERNEL_CHECK();
+            HIP_CHECK(hipMemcpyAsync(fidx_plain.data(), d_fidx_plain, c * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
         HIP_CHECK(hipMemcpyAsync(fidx.data(), d_fidx, c * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        if (fidx[c - 1]) throw HipError("merged batch: a separator is not a literal factor");
+        if (fidx[c - 1] || (zs_plain && fidx_plain[c - 1])) throw HipError("merged batch: a separator is not a literal factor");
         fidx[c - 1] = z;
+        if (zs_plain) fidx_plain[c - 1] = plain.z;
     }
     nolzss_factor *block = nullptr;
     if (fs && z) {
@@ -233,6 +255,7 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
         const uint32_t a = k ? fidx[k - 1] + 1 : 0, b = fidx[k];
         zs[ids[k]] = b - a;
         if (fs) fs[ids[k]] = (block && b > a) ? block + a : nullptr;
+        if (zs_plain) zs_plain[ids[k]] = (k ? fidx_plain[k] - fidx_plain[k - 1] - 1 : fidx_plain[k]);
     }
     return true;
 }
@@ -343,6 +366,57 @@ bool run_merged_chunk_device(Context &ctx, const void *const *d_texts, const siz
 }
 
 std::atomic<uint64_t> g_merged_records{0}, g_single_records{0};
+
+// The records of nolzss_count_factors_batch_both, checked on the host before any of them runs (a byte-class scan over
+// all records on up to 16 threads): the first record in input order that count_factors_dna_w_rc would refuse on its
+// own fails the call with that function's error; otherwise lower-case bases are refused -- the reverse-complement
+// path folds them to upper case, but the plain count of `acgt` is not the plain count of `ACGT`.
+void check_records_both(const uint8_t *const *texts, const size_t *lens, size_t m) {
+    size_t first_long = m;  // (dna_w_rc_common: the length is checked before the bytes)
+    for (size_t j = 0; j < m && first_long == m; ++j)
+        if (2 * lens[j] + 2 > kMaxText) first_long = j;
+    static const auto cls = [] {  // 0: A/C/G/T, 1: a/c/g/t, 2: anything else
+        std::array<uint8_t, 256> t;
+        t.fill(2);
+        for (const char *b = "ACGT"; *b; ++b) {
+            t[(unsigned char)*b] = 0;
+            t[(unsigned char)(*b + 32)] = 1;
+        }
+        return t;
+    }();
+    std::vector<size_t> start(m + 1, 0);
+    for (size_t j = 0; j < m; ++j) start[j + 1] = start[j] + lens[j];
+    std::atomic<size_t> first_bad{first_long}, first_lower{m};
+    auto lower_to = [](std::atomic<size_t> &a, size_t v) {
+        size_t cur = a.load();
+        while (v < cur && !a.compare_exchange_weak(cur, v)) {
+        }
+    };
+    host_parallel(start[m], [&](size_t lo, size_t hi) {
+        // the record holding byte lo (empty records share their start with the next one: skipped below)
+        size_t j = (size_t)(std::upper_bound(start.begin(), start.end(), lo) - start.begin()) - 1;
+        for (size_t at = lo; at < hi && j < first_bad.load(std::memory_order_relaxed);) {
+            while (start[j + 1] <= at) ++j;
+            const size_t stop = std::min(hi, start[j + 1]);
+            const uint8_t *p = texts[j] + (at - start[j]);
+            uint8_t acc = 0;
+            for (size_t k = 0, e = stop - at; k < e; ++k) acc |= cls[p[k]];
+            if (acc & 2) lower_to(first_bad, j);
+            if (acc & 1) lower_to(first_lower, j);
+            at = stop;
+        }
+    });
+    const size_t j = first_bad.load();
+    if (j < m) {
+        if (j == first_long) throw std::invalid_argument("text too long: the device pipeline uses 32-bit indices");
+        const size_t k = first_invalid_nucleotide(reinterpret_cast<const char *>(texts[j]), lens[j]);
+        throw std::runtime_error("Invalid nucleotide '" + std::string(1, (char)texts[j][k]) + "' found in sequence 0");
+    }
+    if (first_lower.load() < m)
+        throw std::invalid_argument("record " + std::to_string(first_lower.load()) +
+                                    " holds lower-case bases: both counts take upper-case A/C/G/T only (the plain count "
+                                    "of lower-case letters differs)");
+}
 
 // a worker thread failed: the same kind of error, with the same text, for the calling thread
 [[noreturn]] void rethrow_worker_error(int status, const std::string &message) {
@@ -471,8 +545,9 @@ std::vector<std::vector<size_t>> lpt_plan_singles(std::vector<size_t> &singles, 
     return plan;
 }
 
+// zs_plain (with_rc, counts only): the plain-mode count of every record as well, from the same runs
 void factorize_many(const uint8_t *const *texts, const size_t *lens, size_t m, const int *devices, size_t n_dev,
-                    bool with_rc, size_t *zs, nolzss_factor **fs, std::vector<void *> &blocks) {
+                    bool with_rc, size_t *zs, nolzss_factor **fs, std::vector<void *> &blocks, size_t *zs_plain) {
     // 1. which records are merged: short, non-empty ones, in chunks of consecutive records (plan_batch)
     BatchPlan bp = plan_batch(lens, m, with_rc);
     std::vector<std::vector<size_t>> &chunks = bp.chunks;
@@ -491,7 +566,7 @@ void factorize_many(const uint8_t *const *texts, const size_t *lens, size_t m, c
                     const size_t k = next.fetch_add(1);
                     if (k >= chunks.size()) break;
                     std::vector<void *> mine;
-                    const bool ok = run_merged_chunk(ses.ctx(), texts, lens, chunks[k], with_rc, zs, fs, &mine);
+                    const bool ok = run_merged_chunk(ses.ctx(), texts, lens, chunks[k], with_rc, zs, fs, &mine, zs_plain);
                     std::lock_guard<std::mutex> lk(out_mu);
                     if (ok) {
                         blocks.insert(blocks.end(), mine.begin(), mine.end());
@@ -533,7 +608,8 @@ void factorize_many(const uint8_t *const *texts, const size_t *lens, size_t m, c
                 if (k >= plan[d].size()) break;
                 const size_t j = plan[d][k];
                 if (with_rc)
-                    dna_w_rc_common(texts[j], nullptr, lens[j], devices[d], nullptr, fs ? 2 : 0, fs ? &fs[j] : nullptr, &zs[j], (int)lane);
+                    dna_w_rc_common(texts[j], nullptr, lens[j], devices[d], nullptr, fs ? 2 : 0, fs ? &fs[j] : nullptr, &zs[j], (int)lane,
+                                    zs_plain ? &zs_plain[j] : nullptr);
                 else
                     zs[j] = run_plain_host(ses->ctx(), texts[j], lens[j], 0, fs ? &fs[j] : nullptr, nullptr);
                 ++g_single_records;
@@ -576,8 +652,9 @@ using namespace nolzss::api;
 
 extern "C" {
 
+// zs_plain (optional, m entries, with_rc and no out): the plain-mode counts too (nolzss_count_factors_batch_both)
 static int factorize_batch_impl(const uint8_t *const *texts, const size_t *lens, size_t m, const int *devices,
-                                size_t n_dev, bool with_rc, nolzss_factor ***out, size_t **z) {
+                                size_t n_dev, bool with_rc, nolzss_factor ***out, size_t **z, size_t *zs_plain = nullptr) {
     return guarded([&] {
         if (!z) throw std::invalid_argument("output pointer is null");
         *z = nullptr;
@@ -585,6 +662,10 @@ static int factorize_batch_impl(const uint8_t *const *texts, const size_t *lens,
         if (m && (!texts || !lens)) throw std::invalid_argument("sequence array is null");
         if (!devices || n_dev == 0) throw std::invalid_argument("device list is empty");
         for (size_t j = 0; j < m; ++j) check_text_args(texts[j], lens[j], 0);
+        if (zs_plain) {
+            for (size_t j = 0; j < m; ++j) zs_plain[j] = 0;  // (empty records: 0 / 0)
+            check_records_both(texts, lens, m);
+        }
         size_t *zs = static_cast<size_t *>(std::calloc(m ? m : 1, sizeof(size_t)));
         nolzss_factor **fs = out ? static_cast<nolzss_factor **>(std::calloc(m ? m : 1, sizeof(nolzss_factor *)))
                                  : nullptr;
@@ -595,7 +676,7 @@ static int factorize_batch_impl(const uint8_t *const *texts, const size_t *lens,
         }
         std::vector<void *> blocks;
         try {
-            factorize_many(texts, lens, m, devices, n_dev, with_rc, zs, fs, blocks);
+            factorize_many(texts, lens, m, devices, n_dev, with_rc, zs, fs, blocks, zs_plain);
             if (fs) {
                 std::lock_guard<std::mutex> lk(g_batch_mu);
                 g_batch_blocks[fs] = std::move(blocks);
@@ -619,6 +700,16 @@ int nolzss_factorize_batch(const uint8_t *const *texts, const size_t *lens, size
 int nolzss_factorize_batch_dna_w_rc(const uint8_t *const *texts, const size_t *lens, size_t m, const int *devices,
                                     size_t n_dev, nolzss_factor ***out, size_t **z) {
     return factorize_batch_impl(texts, lens, m, devices, n_dev, true, out, z);
+}
+
+int nolzss_count_factors_batch_both(const uint8_t *const *texts, const size_t *lens, size_t m, const int *devices,
+                                    size_t n_dev, size_t *count_w_rc, size_t *count_no_rc) {
+    if (m && (!count_w_rc || !count_no_rc)) return set_error(NOLZSS_ERR_INVALID_ARGUMENT, "output pointer is null");
+    size_t *zs = nullptr;
+    const int rc = factorize_batch_impl(texts, lens, m, devices, n_dev, true, nullptr, &zs, count_no_rc);
+    if (rc == NOLZSS_OK && m) std::memcpy(count_w_rc, zs, m * sizeof(size_t));
+    std::free(zs);
+    return rc;
 }
 
 // The per-sequence batch with the records already resident in device memory (the measurement form: no

@@ -452,9 +452,11 @@ namespace api {
 // the n input bytes cross PCIe.  `d_resident` (optional) is the text already in device memory: nothing is
 // uploaded then and `text` is not read.
 // emit 0: count; 1: records built in HBM and left there; 2: records downloaded into *out.
+// z_plain (optional): also the plain-mode count of the sequence, from the same suffix array (rc.hip, RcPlainOut)
 void dna_w_rc_common(const uint8_t *text, const uint8_t *d_resident, size_t n, int device, void *stream, int emit,
-                            nolzss_factor **out, size_t *z, int lane) {
+                            nolzss_factor **out, size_t *z, int lane, size_t *z_plain) {
     *z = 0;
+    if (z_plain) *z_plain = 0;
     if (out) *out = nullptr;
     if (n == 0) return;  // factorizer_core.hpp:143
     if (!text && !d_resident) throw std::invalid_argument("text pointer is null");
@@ -464,7 +466,8 @@ void dna_w_rc_common(const uint8_t *text, const uint8_t *d_resident, size_t n, i
     Session ses(device, stream, lane);
     Context &ctx = ses.ctx();
     if (d_resident && !stream) order_behind_default_stream(ctx);
-    reserve_arena_for(ctx, m, m + (d_resident ? 0 : n));
+    // (z_plain: the plain L* of the n positions, and by rank below the compact size, rc.hip)
+    reserve_arena_for(ctx, m, m + (d_resident ? 0 : n) + (z_plain ? 4 * n + (size_t(32) << 20) : 0));
     const uint8_t *d_T = d_resident;
     if (!d_resident) {
         uint8_t *up = ctx.arena.alloc<uint8_t>(n);
@@ -480,7 +483,8 @@ void dna_w_rc_common(const uint8_t *text, const uint8_t *d_resident, size_t n, i
         throw std::runtime_error("Invalid nucleotide '" + std::string(1, (char)c) + "' found in sequence 0");
     }
     void *d_recs = nullptr;
-    const size_t count = run_rc_pipeline(ctx, d_S, m, 0, emit ? &d_recs : nullptr);
+    RcPlainOut plain;
+    const size_t count = run_rc_pipeline(ctx, d_S, m, 0, emit ? &d_recs : nullptr, z_plain ? &plain : nullptr);
     if (emit == 2 && count) {
         nolzss_factor *h = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * count));
         if (!h) throw std::bad_alloc();
@@ -502,6 +506,7 @@ void dna_w_rc_common(const uint8_t *text, const uint8_t *d_resident, size_t n, i
     }
     ctx.prof.collect();
     *z = count;
+    if (z_plain) *z_plain = plain.z;
 }
 
 }  // namespace api

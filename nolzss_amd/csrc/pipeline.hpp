@@ -75,9 +75,21 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
                        uint32_t **d_fpos_out = nullptr, const TermTable *rebase = nullptr);
 
 // ---- reverse-complement mode (rc.hip): whole pipeline over the prepared string S -------------
-uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m, size_t start_pos, void **d_factors_out);
-// the same over a text that has already been packed (merged batch)
-uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out);
+struct RcPlainOut;
+uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m, size_t start_pos, void **d_factors_out,
+                         RcPlainOut *plain = nullptr);
+// plain-mode counts as a by-product of a reverse-complement run: the plain L* of every position i < N comes out of
+// the same candidate kernels (rc.hip) and is chained on its own; z = nolzss_count_factors of the original strand(s),
+// fpos (want_fpos) = its factor starts in the arena, for the per-record split of a merged run
+struct RcPlainOut {
+    bool want_fpos = false;
+    uint32_t z = 0;
+    uint32_t *fpos = nullptr;
+};
+// the same over a text that has already been packed (merged batch); plain (optional): the plain-mode by-product
+// above; d_fpos_out (optional, with d_factors_out null): the factor starts of the reverse-complement chain
+uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
+                                RcPlainOut *plain = nullptr, uint32_t **d_fpos_out = nullptr);
 // d_S (2n + 2 bytes) = T' sep revcomp(T') sep for the n bytes d_T = upper-case records with separator bytes
 // between them; bytes that are not nucleotides (the separators) are copied to their mirror position.
 void prepare_batch_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t n, uint8_t separator, uint8_t *d_S);

@@ -38,22 +38,30 @@ __device__ __forceinline__ uint32_t rc_select(uint32_t fwd, uint32_t rc) {
 // combine the forward neighbours (lp/jp above, ls/js below) and the reverse-complement length
 // into the factor code of position i; returns true if i needs the exact forward search
 // (*dst then receives a forward lower bound with P(bound) true)
+// kPlain: *plain receives the plain-mode L* of i as lpf_decide (lpnf.hip) would give it -- M where the forward
+// match is final, otherwise the same provisional lo (the exact search then finishes both, rc_fallback_kernel)
+template <bool kPlain>
 __device__ __forceinline__ bool rc_decide(uint32_t i, uint32_t lp, uint32_t jp, uint32_t ls, uint32_t js,
-                                          uint32_t rc, uint32_t *__restrict__ dst) {
+                                          uint32_t rc, uint32_t *__restrict__ dst, uint32_t *__restrict__ plain) {
     const uint32_t M = lp > ls ? lp : ls;
     const bool fwd_final = (M == 0) || (lp == M && i - jp >= M) || (ls == M && i - js >= M);
     if (fwd_final) {
         *dst = rc_select(M, rc);
+        if (kPlain) *plain = M;
         return false;
     }
     uint32_t lo = 0;
     if (lp > 0) { const uint32_t c = lp < i - jp ? lp : i - jp; lo = c > lo ? c : lo; }
     if (ls > 0) { const uint32_t c = ls < i - js ? ls : i - js; lo = c > lo ? c : lo; }
     *dst = lo;  // provisional: P(lo) holds
+    if (kPlain) *plain = lo;
     return true;
 }
 
 // LDS-tiled candidate search (nearest_lds.hpp): four searches per rank of the original strand
+// kPlain: the plain-mode L* (rc_decide) of every rank of the original strand that is not far goes to plain_by_rank[rank]
+// (far ranks: written in text order by rc_far_kernel)
+template <bool kPlain>
 __global__ __launch_bounds__(kLdsThreads) void rc_tile_kernel(const uint32_t *__restrict__ sa,
                                                               const uint32_t *__restrict__ lcp, uint32_t m,
                                                               uint32_t N, uint32_t *__restrict__ code_by_rank,
@@ -62,7 +70,8 @@ __global__ __launch_bounds__(kLdsThreads) void rc_tile_kernel(const uint32_t *__
                                                               uint32_t *__restrict__ plcp1, uint32_t pending_min,
                                                               uint32_t *__restrict__ pending_flag,
                                                               const uint32_t *__restrict__ tile_off,
-                                                              uint32_t *__restrict__ cidx, uint64_t *__restrict__ cpacked) {
+                                                              uint32_t *__restrict__ cidx, uint64_t *__restrict__ cpacked,
+                                                              uint32_t *__restrict__ plain_by_rank) {
     constexpr int NS = 4, NP = 2;
     __shared__ __align__(16) uint32_t s_sa[kLdsSpan];
     __shared__ __align__(16) uint32_t s_lcp[kLdsSpan + 4];
@@ -148,8 +157,11 @@ __global__ __launch_bounds__(kLdsThreads) void rc_tile_kernel(const uint32_t *__
         far[row] = far_f || far_r;  // finished from global memory
         if (!far[row]) {
             rcl[row] = ru > rd ? ru : rd;
-            exact[row] = rc_decide(i, lp, match_pos(s_sa, s_pos[t]), ls, match_pos(s_sa, s_pos[kLdsTile + t]), rcl[row], &cv[row]);
+            uint32_t pv = 0;
+            exact[row] = rc_decide<kPlain>(i, lp, match_pos(s_sa, s_pos[t]), ls, match_pos(s_sa, s_pos[kLdsTile + t]), rcl[row],
+                                           &cv[row], &pv);
             if (!compact_out) code_by_rank[rr] = cv[row];
+            if (kPlain) plain_by_rank[rr] = pv;
         }
     }
     shard_slots<kRows>(far_q, shard, far, fslot);
@@ -194,11 +206,22 @@ __global__ __launch_bounds__(kLdsThreads) void rc_count_original_kernel(const ui
     }
 }
 
+// plain-mode L* of the original strand in text order: the by-rank values of rc_tile_kernel gathered through the
+// inverse suffix array that the permutation of the codes has just delivered (far ranks: overwritten by rc_far_kernel)
+__global__ __launch_bounds__(kThreads) void rc_plain_gather_kernel(const uint32_t *__restrict__ isa,
+                                                                   const uint32_t *__restrict__ plain_by_rank, uint32_t N,
+                                                                   uint32_t *__restrict__ plain) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride)
+        plain[i] = plain_by_rank[isa[i] - 1u];  // (1-based, pipeline.hpp)
+}
+
 // ranks whose searches leave the LDS reach: pyramid searches from global memory.  Grid (kQShards, Y).
+template <bool kPlain>
 __global__ __launch_bounds__(kThreads) void rc_far_kernel(
     ShardQueue far_q, const uint32_t *__restrict__ sa, const uint32_t *__restrict__ lcp, uint32_t m, uint32_t N,
     Pyramid Pmin, Pyramid Pmax, Pyramid Plcp, const uint32_t *__restrict__ by_rank, uint32_t *__restrict__ code,
-    ShardQueue exact_q) {
+    ShardQueue exact_q, uint32_t *__restrict__ plain) {
     const uint32_t shard = blockIdx.x;
     const uint32_t count = far_q.counts[shard * kQPad];
     const uint32_t *items = far_q.items + (size_t)shard * far_q.cap;
@@ -228,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void rc_far_kernel(
         else
             nearest_down<true>(sa, lcp, m, Pmax, Plcp, r, thr, ru > 2u ? ru : 2u, rd, unused);
         const uint32_t rc = ru > rd ? ru : rd;
-        const bool exact = rc_decide(i, lp, jp, ls, js, rc, code + i);
+        const bool exact = rc_decide<kPlain>(i, lp, jp, ls, js, rc, code + i, plain + i);
         const uint32_t eslot = shard_slot(exact_q, shard, exact);  // (a rank reaches the exact queue at most once)
         if (exact) {
             exact_q.items[eslot] = i;
@@ -237,10 +260,12 @@ __global__ __launch_bounds__(kThreads) void rc_far_kernel(
     }
 }
 
+template <bool kPlain>
 __global__ __launch_bounds__(kThreads) void rc_fallback_kernel(ShardQueue exact_q, uint32_t m,
                                                                const uint32_t *__restrict__ isa,
                                                                const uint32_t *__restrict__ lcp, Pyramid Pmin,
-                                                               Pyramid Plcp, uint32_t *__restrict__ code) {
+                                                               Pyramid Plcp, uint32_t *__restrict__ code,
+                                                               uint32_t *__restrict__ plain) {
     const uint32_t shard = blockIdx.x;
     const uint32_t count = exact_q.counts[shard * kQPad];
     const uint32_t *queue = exact_q.items + (size_t)shard * exact_q.cap;
@@ -250,6 +275,9 @@ __global__ __launch_bounds__(kThreads) void rc_fallback_kernel(ShardQueue exact_
         const uint32_t r = isa[i] - 1u;  // (1-based, pipeline.hpp)
         const uint32_t cap = (m - i) < i ? (m - i) : i;
         const uint32_t Lf = lpnf_search(Pmin, Plcp, r, i, code[i], cap);  // >= 1 for queued positions
+        // L_f is plain-mode L* exactly (lpnf_fallback_kernel makes the same search); the bound it started from is the
+        // provisional lo that rc_decide gave code[i] and plain[i] alike
+        if (kPlain) plain[i] = Lf;
         // deepest explicit ancestor of leaf(i) with depth <= L_f
         uint32_t a, b;
         lcp_interval(Plcp, r, Lf + 1, a, b);
@@ -348,12 +376,14 @@ uint32_t prepare_single_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t 
     return bad;  // 0xffffffff when every byte is a nucleotide
 }
 
-uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m_sz, size_t start_pos, void **d_factors_out) {
+uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m_sz, size_t start_pos, void **d_factors_out,
+                         RcPlainOut *plain) {
     const PackedText text = pack_text(ctx, d_S, m_sz);  // segmented 2-bit packing is detected there
-    return run_rc_pipeline_packed(ctx, text, start_pos, d_factors_out);
+    return run_rc_pipeline_packed(ctx, text, start_pos, d_factors_out, plain);
 }
 
-uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out) {
+uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
+                                RcPlainOut *plain_out, uint32_t **d_fpos_out) {
     const uint32_t m = text.n;
     const uint32_t N = m / 2 - 1;
     hipStream_t s = ctx.stream;
@@ -374,6 +404,8 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
     // code[] spans all of S (entries >= N are unused) so that rank order -> text order is a
     // permutation scatter
     uint32_t *code = arena.alloc<uint32_t>(m);
+    // plain-mode L* of the original strand in text order ("Both counts from one suffix sort")
+    uint32_t *plain = plain_out ? arena.alloc<uint32_t>(N) : nullptr;
     {
         const size_t mark = arena.mark();
         const unsigned tiles = (unsigned)div_up(m, kLdsTile);
@@ -408,6 +440,18 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
             scratch_idx = arena.alloc<uint32_t>(m);
             scratch_val = arena.alloc<uint32_t>(isa_deferred ? 2 * (size_t)m : (size_t)m);  // (two values per pair: radix_sort.hpp)
         }
+        // the plain values by rank: in by_rank itself when the output is compact (by_rank then holds only the masks of
+        // the far ranks, whose plain values come from rc_far_kernel), beside it otherwise (by_rank holds the codes)
+        uint32_t *plain_by_rank = plain ? (compact ? by_rank : arena.alloc<uint32_t>(m)) : nullptr;
+        auto launch_tile = [&](uint32_t *p1, uint32_t *p2, uint32_t *p3, uint32_t pmin, uint32_t *pflag) {
+            if (plain)
+                rc_tile_kernel<true><<<tiles, kLdsThreads, 0, s>>>(sa, lcp, m, N, by_rank, exact_q, far_q, p1, p2, p3, pmin,
+                                                                   pflag, tile_off, cidx, cpacked, plain_by_rank);
+            else
+                rc_tile_kernel<false><<<tiles, kLdsThreads, 0, s>>>(sa, lcp, m, N, by_rank, exact_q, far_q, p1, p2, p3, pmin,
+                                                                    pflag, tile_off, cidx, cpacked, nullptr);
+            KERNEL_CHECK();
+        };
         HIP_CHECK(hipMemsetAsync(qcounts, 0, 2 * kQShards * kQPad * sizeof(uint32_t), s));
         const uint32_t *h_ptrs[2] = {exact_q.counts, far_q.counts};
         HIP_CHECK(hipMemcpyAsync(count_ptrs, h_ptrs, sizeof h_ptrs, hipMemcpyHostToDevice, s));
@@ -419,12 +463,9 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
         };
         {
             ProfScope ps(ctx.profiler(), "rc_candidates", s);
-            rc_tile_kernel<<<tiles, kLdsThreads, 0, s>>>(
-                sa, lcp, m, N, by_rank, exact_q, far_q, fused_level1 ? const_cast<uint32_t *>(Pmin.lvl[1]) : nullptr,
-                fused_level1 ? const_cast<uint32_t *>(Pmax.lvl[1]) : nullptr,
-                fused_level1 ? const_cast<uint32_t *>(Plcp.lvl[1]) : nullptr, pending_threshold(), pending_flag, tile_off, cidx,
-                cpacked);
-            KERNEL_CHECK();
+            launch_tile(fused_level1 ? const_cast<uint32_t *>(Pmin.lvl[1]) : nullptr,
+                        fused_level1 ? const_cast<uint32_t *>(Pmax.lvl[1]) : nullptr,
+                        fused_level1 ? const_cast<uint32_t *>(Plcp.lvl[1]) : nullptr, pending_threshold(), pending_flag);
         }
         {
             ProfScope ps(ctx.profiler(), "pyramids", s);
@@ -447,9 +488,7 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
                 fill_pyramid(Pmax, 1, true, s);
                 fill_pyramid(Plcp, 1, false, s);
                 HIP_CHECK(hipMemsetAsync(qcounts, 0, 2 * kQShards * kQPad * sizeof(uint32_t), s));
-                rc_tile_kernel<<<tiles, kLdsThreads, 0, s>>>(sa, lcp, m, N, by_rank, exact_q, far_q, nullptr, nullptr, nullptr,
-                                                             0u, nullptr, tile_off, cidx, cpacked);
-                KERNEL_CHECK();
+                launch_tile(nullptr, nullptr, nullptr, 0u, nullptr);
             }
         }
         {
@@ -463,24 +502,48 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
                 bucketed_scatter(idx, val, m, code, m, arena, s, ctx.profiler(), true, true, nullptr, isa_deferred ? isa : nullptr);
             }
         }
+        if (plain) {
+            ProfScope ps(ctx.profiler(), "rc_plain_gather", s);
+            size_t g = div_up(N, kThreads);
+            if (g > 8192) g = 8192;
+            rc_plain_gather_kernel<<<(unsigned)g, kThreads, 0, s>>>(isa, plain_by_rank, N, plain);
+            KERNEL_CHECK();
+        }
         uint32_t h[2] = {0, 0};
         read_totals(h);
         if (h[1] > 0) {
             ProfScope ps(ctx.profiler(), "rc_far", s);
             const unsigned gy = (unsigned)std::min<size_t>(64, std::max<size_t>(1, div_up(h[1], (size_t)kQShards * kThreads)));
-            rc_far_kernel<<<dim3(kQShards, gy), kThreads, 0, s>>>(far_q, sa, lcp, m, N, Pmin, Pmax, Plcp, by_rank, code, exact_q);
+            if (plain)
+                rc_far_kernel<true><<<dim3(kQShards, gy), kThreads, 0, s>>>(far_q, sa, lcp, m, N, Pmin, Pmax, Plcp, by_rank, code,
+                                                                            exact_q, plain);
+            else
+                rc_far_kernel<false><<<dim3(kQShards, gy), kThreads, 0, s>>>(far_q, sa, lcp, m, N, Pmin, Pmax, Plcp, by_rank, code,
+                                                                             exact_q, nullptr);
             KERNEL_CHECK();
             read_totals(h);
         }
         if (h[0] > 0) {
             ProfScope ps(ctx.profiler(), "rc_fallback", s);
             const unsigned gy = (unsigned)std::min<size_t>(64, std::max<size_t>(1, div_up(h[0], (size_t)kQShards * kThreads)));
-            rc_fallback_kernel<<<dim3(kQShards, gy), kThreads, 0, s>>>(exact_q, m, isa, lcp, Pmin, Plcp, code);
+            if (plain)
+                rc_fallback_kernel<true><<<dim3(kQShards, gy), kThreads, 0, s>>>(exact_q, m, isa, lcp, Pmin, Plcp, code, plain);
+            else
+                rc_fallback_kernel<false><<<dim3(kQShards, gy), kThreads, 0, s>>>(exact_q, m, isa, lcp, Pmin, Plcp, code, nullptr);
             KERNEL_CHECK();
         }
         arena.rewind(mark);
     }
-    return resolve_chain(ctx, N, (uint32_t)start_pos, code, sa, isa, lcp, Pmin, Plcp, d_factors_out, N, &Pmax);
+    const uint32_t z = resolve_chain(ctx, N, (uint32_t)start_pos, code, sa, isa, lcp, Pmin, Plcp, d_factors_out, N, &Pmax,
+                                     d_fpos_out);
+    if (plain_out) {
+        // the plain chain over the same positions: counts (and factor starts) only, no records
+        ProfScope ps(ctx.profiler(), "plain_chain", s);
+        plain_out->fpos = nullptr;
+        plain_out->z = resolve_chain(ctx, N, 0, plain, sa, isa, lcp, Pmin, Plcp, nullptr, 0, nullptr,
+                                     plain_out->want_fpos ? &plain_out->fpos : nullptr);
+    }
+    return z;
 }
 
 }  // namespace nolzss
