@@ -1010,6 +1010,371 @@ __global__ void separator_scatter_kernel(const uint32_t *__restrict__ sep, uint3
     if (out2) out2[p] = r + 1u;
 }
 
+// ---- the two-value permutation without histograms (bucketed_scatter, texts of up to 2^30 symbols) ----------------
+// idx is a permutation of [0, n): bin d of the first pass is exactly the target range [d << (wb + 8), (d + 1) << (wb + 8)),
+// sub-bin (d, e) of the second pass exactly window d * 256 + e.  A tile's offset inside its bin is the count of the
+// digit in the tiles in front of it, found by a decoupled look-back per digit (thread d walks digit d, so the
+// descriptor reads of a step are one 2 KiB row) instead of a histogram pass and a scan.  The pair travels as ONE word
+// [code : c | rank : nb | low wb + 8 index bits] (c = 64 - nb - (wb + 8) >= 12 bits): the first pass keeps only the
+// index bits below its digit, the second pass moves the words unchanged (its digit is bits [wb, wb + 8)), the window
+// kernel takes the low wb bits as the place in the window.  A code that does not fit its field is stored as `esc` and
+// its rank goes to an exception list; escape_fixup_kernel writes those codes behind the windows.
+// 16 Ki pairs per tile and one ticket per tile: tiles start in ticket order, so a look-back only ever waits on tiles
+// that are already running (forward progress), and 2^16 tickets at 2^30 pairs stay far below the rate one atomic
+// word can hand out.  128 KiB of staged words: one workgroup of 1024 threads per CU.  (NOLZSS_LB_TILE_BITS=13: 8 Ki pairs
+// on 512 threads, two workgroups per CU -- within 0.15 ms per step of this, profiles/r05_text_order_ab.txt.)
+#ifndef NOLZSS_LB_TILE_BITS
+#define NOLZSS_LB_TILE_BITS 14
+#endif
+constexpr int kLbTileBits = NOLZSS_LB_TILE_BITS;
+constexpr int kLbTile = 1 << kLbTileBits;
+constexpr int kLbThreads = kLbTile / kKeysPerThread;
+constexpr int kLbWaves = kLbThreads / 64;
+static_assert(kLbTileBits == 13 || kLbTileBits == 14, "512 or 1024 threads, 16 pairs each");
+static_assert(kLbThreads >= kBins && kWaveSpan * kLbWaves == kLbTile, "one thread per digit");
+constexpr int kLbLook = 4;  // descriptors per lane and round trip of the walk
+
+struct LbPass {
+    const uint32_t *idx = nullptr;   // first pass: target positions (sa) ...
+    const uint32_t *code = nullptr;  // ... and the codes, in list (rank) order
+    const uint64_t *in = nullptr;    // second pass: the words of the first
+    uint64_t *out = nullptr;
+    uint64_t *desc = nullptr;  // kBins descriptors per tile, zero on entry
+    uint32_t *ctl = nullptr;   // [0] ticket, [1] look-back gave up, [2] exceptions (may exceed the cap)
+    uint32_t *exc = nullptr;   // ranks of the escaped codes
+    uint32_t exc_cap = 0;
+    uint32_t esc = 0;  // codes >= esc are escaped (esc < 2^c)
+    uint32_t n = 0;
+    int dshift = 0;     // digit = (target position >> dshift) & 255
+    int low_bits = 0;   // wb + 8
+    int rank_bits = 0;  // nb
+};
+
+template <bool kFirst>
+__global__ __launch_bounds__(kLbThreads, 4) void lb_partition_kernel(LbPass p) {  // (16 wavefronts per CU: 128 VGPRs)
+    __shared__ __align__(16) uint64_t s_rec[kLbTile];
+    __shared__ __align__(16) uint32_t s_whist[kLbWaves * kBins];  // per-wave digit counts; then the staged digits
+    __shared__ uint32_t s_glob[kBins];
+    __shared__ uint32_t s_scan[kLbWaves];
+    __shared__ uint32_t s_tile;
+    uint8_t *s_dig = reinterpret_cast<uint8_t *>(s_whist);
+    static_assert(sizeof(s_whist) >= kLbTile, "one digit byte per staged word");
+
+    const int tid = threadIdx.x;
+    const int w = tid >> 6;
+    const int lane = tid & 63;
+    if (tid == 0) s_tile = atomicAdd(p.ctl, 1u);  // tiles in start order
+    for (int i = tid; i < kLbWaves * kBins; i += kLbThreads) s_whist[i] = 0;
+    __syncthreads();
+    const uint32_t tile = s_tile;  // < gridDim.x: one ticket per workgroup
+    const size_t first = (size_t)tile << kLbTileBits;
+    const uint32_t count = (uint32_t)((size_t)p.n - first < (size_t)kLbTile ? (size_t)p.n - first : (size_t)kLbTile);
+
+    // The words go to LDS in list order first and only the digits stay in registers through the ranking: words, ranks
+    // and the ranking's own state do not fit the 128 VGPRs of 16 wavefronts per CU (43 of them spilled).  They are
+    // moved to their sorted places inside LDS once the ranks are known.
+    uint32_t lrank[kKeysPerThread];
+    uint32_t dpk[kKeysPerThread / 4] = {0, 0, 0, 0};  // the digits, four per register
+    auto digit_at = [&](int row) -> uint32_t { return (dpk[row >> 2] >> (8 * (row & 3))) & 255u; };
+    const uint32_t local0 = (uint32_t)w * kWaveSpan + lane;  // element of row `row`: local0 + 64 * row
+    if constexpr (kFirst) {
+        uint32_t ii[kKeysPerThread], cc[kKeysPerThread];
+#pragma unroll
+        for (int row = 0; row < kKeysPerThread; ++row) {
+            const uint32_t local = local0 + (uint32_t)row * 64;
+            const size_t at = first + (local < count ? local : 0u);  // (past the end: the first element again)
+            ii[row] = p.idx[at];
+            cc[row] = p.code[at];
+        }
+        const uint64_t low_mask = (1ull << p.low_bits) - 1ull;
+#pragma unroll
+        for (int row = 0; row < kKeysPerThread; ++row) {
+            const uint32_t local = local0 + (uint32_t)row * 64;
+            const uint32_t r = (uint32_t)first + local;
+            const bool escaped = local < count && cc[row] >= p.esc;
+            s_rec[local] = ((uint64_t)ii[row] & low_mask) | ((uint64_t)r << p.low_bits) |
+                           ((uint64_t)(escaped ? p.esc : cc[row]) << (p.low_bits + p.rank_bits));
+            dpk[row >> 2] |= ((ii[row] >> p.dshift) & 255u) << (8 * (row & 3));
+            const uint64_t bal = __ballot(escaped);
+            if (bal) {  // (wave-uniform; rare) one atomic per wavefront
+                const int leader = __builtin_ctzll(bal);
+                uint32_t slot = 0;
+                if (lane == leader) slot = atomicAdd(p.ctl + 2, (uint32_t)__popcll(bal));
+                slot = (uint32_t)__shfl((int)slot, leader, 64) + (uint32_t)__popcll(bal & lanemask_lt());
+                if (escaped && slot < p.exc_cap) p.exc[slot] = r;
+            }
+        }
+    } else {
+        uint64_t x[kKeysPerThread];
+#pragma unroll
+        for (int row = 0; row < kKeysPerThread; ++row) {
+            const uint32_t local = local0 + (uint32_t)row * 64;
+            x[row] = p.in[first + (local < count ? local : 0u)];
+        }
+#pragma unroll
+        for (int row = 0; row < kKeysPerThread; ++row) {
+            s_rec[local0 + (uint32_t)row * 64] = x[row];
+            dpk[row >> 2] |= ((uint32_t)(x[row] >> p.dshift) & 255u) << (8 * (row & 3));
+        }
+    }
+    // rank inside the wavefront, as in rs_scatter_kernel (rows of 64 in list order: stable)
+    uint32_t *wcount = s_whist + w * kBins;
+#pragma unroll
+    for (int row = 0; row < kKeysPerThread; ++row) {
+        const bool valid = (uint32_t)w * kWaveSpan + (uint32_t)row * 64 + lane < count;
+        const uint32_t d = digit_at(row);
+        uint32_t diff_lo = 0, diff_hi = 0;
+#pragma unroll
+        for (int b = 0; b < kRadixBits; ++b) {
+            const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)d, (unsigned)b, 1u);
+            const uint64_t bal = __ballot((int)m < 0);
+            diff_lo = __builtin_amdgcn_bitop3_b32(m, diff_lo, (uint32_t)bal, 0xde);
+            diff_hi = __builtin_amdgcn_bitop3_b32(m, diff_hi, (uint32_t)(bal >> 32), 0xde);
+        }
+        const uint64_t peers = ~(((uint64_t)diff_hi << 32) | diff_lo) & __ballot(valid);
+        const uint64_t below = peers & lanemask_lt();
+        uint32_t seen = 0;
+        if (valid && below == 0) seen = atomicAdd(&wcount[d], (uint32_t)__popcll(peers));
+        lrank[row] = seen | ((uint32_t)__popcll(below) << 11) | ((uint32_t)(peers ? __builtin_ctzll(peers) : 0) << 17);
+    }
+#pragma unroll
+    for (int row = 0; row < kKeysPerThread; ++row) {
+        const uint32_t packed = lrank[row];
+        lrank[row] = ((uint32_t)__shfl((int)packed, (int)(packed >> 17), 64) & 0x7ffu) + ((packed >> 11) & 63u);
+    }
+    __syncthreads();
+
+    // thread = digit (the first kBins threads): tile-local bin starts; the tile's count of the digit is published at once
+    const int d = tid;
+    const bool owner = tid < kBins;
+    const uint32_t chain = (uint32_t)(first >> (p.dshift + kRadixBits));  // second pass: the bucket of the first
+    const uint32_t t0 = (uint32_t)(((size_t)chain << (p.dshift + kRadixBits)) >> kLbTileBits);  // its first tile
+    uint64_t *my_desc = p.desc + (size_t)tile * kBins + d;
+    uint32_t bin_start, total = 0;
+    {
+        if (owner)
+            for (int k = 0; k < kLbWaves; ++k) total += s_whist[k * kBins + d];
+        if (owner) desc_store(my_desc, ((tile == t0 ? 2ull : 1ull) << 32) | total);
+        uint32_t tile_total;
+        bin_start = block_scan_exclusive<kLbWaves>(total, OpAdd<uint32_t>(), s_scan, tile_total);
+        if (owner) {
+            uint32_t run = bin_start;
+            for (int k = 0; k < kLbWaves; ++k) {
+                const uint32_t c = s_whist[k * kBins + d];
+                s_whist[k * kBins + d] = run;
+                run += c;
+            }
+        }
+    }
+    __syncthreads();
+    uint64_t rec[kKeysPerThread];
+#pragma unroll
+    for (int row = 0; row < kKeysPerThread; ++row) {
+        lrank[row] += s_whist[w * kBins + digit_at(row)];
+        rec[row] = s_rec[local0 + (uint32_t)row * 64];
+    }
+    __syncthreads();  // (s_whist becomes s_dig; s_rec is read)
+#pragma unroll
+    for (int row = 0; row < kKeysPerThread; ++row) {
+        if (local0 + (uint32_t)row * 64 < count) {
+            s_rec[lrank[row]] = rec[row];
+            if constexpr (kFirst) s_dig[lrank[row]] = (uint8_t)digit_at(row);
+        }
+    }
+    // the walk, as late as possible: the tiles in front have had the whole staging to publish their prefixes
+    if (owner) {
+        uint32_t excl = 0;
+        if (tile != t0) {
+            int64_t look = (int64_t)tile - 1;
+            uint32_t spins = 0;
+            for (;;) {
+                uint64_t v[kLbLook];
+#pragma unroll
+                for (int j = 0; j < kLbLook; ++j) {
+                    const int64_t k = look - j;  // in front of the chain's first tile: inclusive identity
+                    v[j] = k >= (int64_t)t0 ? desc_load(p.desc + (size_t)k * kBins + d) : (2ull << 32);
+                }
+                bool done = false, stalled = false;
+#pragma unroll
+                for (int j = 0; j < kLbLook; ++j) {
+                    if (done || stalled) continue;
+                    const uint32_t st = (uint32_t)(v[j] >> 32);
+                    if (st == 0) {
+                        stalled = true;
+                    } else {
+                        excl += (uint32_t)v[j];
+                        --look;
+                        done = st == 2;
+                    }
+                }
+                if (done) break;
+                if (stalled) {
+                    if (++spins > kSpinLimit) {  // cannot happen with ticket order; never hang the GPU
+                        atomicExch(p.ctl + 1, 1u);
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+            }
+            desc_store(my_desc, (2ull << 32) | (uint64_t)(excl + total));
+        }
+        s_glob[d] = ((((uint32_t)chain << kRadixBits) | (uint32_t)d) << p.dshift) + excl - bin_start;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kKeysPerThread; ++j) {
+        const uint32_t q = (uint32_t)j * kLbThreads + tid;
+        if (q < count) {
+            const uint64_t x = s_rec[q];
+            const uint32_t dq = kFirst ? (uint32_t)s_dig[q] : (uint32_t)(x >> p.dshift) & 255u;
+            const uint32_t g = s_glob[dq] + q;
+            if (g < p.n) p.out[g] = x;  // (always, for a permutation)
+        }
+    }
+}
+
+// the windows of the packed words: out[i] = code, out2[i] = rank + 1 for the words of window blockIdx.x (16 B per pair)
+__global__ __launch_bounds__(kWindow2Threads) void window_unpack_kernel(const uint64_t *__restrict__ in,
+                                                                        uint32_t *__restrict__ out,
+                                                                        uint32_t *__restrict__ out2, uint32_t n_out,
+                                                                        int window_bits, int low_bits, int rank_bits) {
+    __shared__ uint32_t s_out[2 << kWindowBitsMax];
+    const uint32_t W = 1u << window_bits;
+    uint32_t *s_a = s_out, *s_b = s_out + W;
+    const size_t base = (size_t)blockIdx.x << window_bits;
+    const uint32_t len = (uint32_t)((n_out - base < (size_t)W) ? (n_out - base) : (size_t)W);
+    const uint32_t rank_mask = (uint32_t)((1ull << rank_bits) - 1ull);
+    constexpr int kBatch = 4;
+    for (uint32_t t0 = 0; t0 < len; t0 += kBatch * kWindow2Threads) {
+        uint64_t vv[kBatch];
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j) {
+            const uint32_t t = t0 + (uint32_t)j * kWindow2Threads + threadIdx.x;
+            vv[j] = in[base + (t < len ? t : 0u)];  // (no branch around the loads)
+        }
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j) {
+            const uint32_t t = t0 + (uint32_t)j * kWindow2Threads + threadIdx.x;
+            if (t < len) {
+                const uint32_t at = (uint32_t)vv[j] & (W - 1u);
+                s_a[at] = (uint32_t)(vv[j] >> (low_bits + rank_bits));
+                s_b[at] = ((uint32_t)(vv[j] >> low_bits) & rank_mask) + 1u;
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < len; t += kWindow2Threads) {
+        out[base + t] = s_a[t];
+        out2[base + t] = s_b[t];
+    }
+}
+
+// out[idx[r]] = code[r] for the escaped ranks (none when the list overflowed: the caller then starts over)
+__global__ __launch_bounds__(kThreads) void escape_fixup_kernel(const uint32_t *__restrict__ exc, const uint32_t *__restrict__ ctl,
+                                                                uint32_t cap, const uint32_t *__restrict__ idx,
+                                                                const uint32_t *__restrict__ code, uint32_t *__restrict__ out) {
+    const uint32_t cnt = ctl[2];
+    if (cnt > cap) return;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < cnt; k += stride) {
+        const uint32_t r = exc[k];
+        out[idx[r]] = code[r];
+    }
+}
+
+// (NOLZSS_TRACE) cnt[k] = codes >= 2^(10 + k), k < 7: how often the escape would be taken at each field width
+__global__ __launch_bounds__(kThreads) void code_census_kernel(const uint32_t *__restrict__ code, size_t count,
+                                                               unsigned long long *__restrict__ cnt) {
+    uint32_t c[7] = {0, 0, 0, 0, 0, 0, 0};
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += stride) {
+        const uint32_t v = code[k];
+#pragma unroll
+        for (int b = 0; b < 7; ++b) c[b] += v >= (1u << (10 + b)) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int b = 0; b < 7; ++b) {
+        const uint32_t t = wave_reduce(c[b], OpAdd<uint32_t>());
+        if (lane_id() == 0 && t) atomicAdd(cnt + b, (unsigned long long)t);
+    }
+}
+
+// lstar[sa[r]] = code[r], isa[sa[r]] = r + 1 by the kernels above; false (nothing usable written) when the exception
+// list overflowed or a look-back gave up -- the caller then runs the histogram form.
+bool packed_text_order(const uint32_t *idx, const uint32_t *code, size_t count, uint32_t *out, uint32_t *out2, int nb,
+                       uint64_t *buf_a, Arena &arena, hipStream_t stream, Profiler *prof) {
+    static const char *esc_env = getenv("NOLZSS_TEXT_ORDER_ESC");  // (tests: lower escape threshold)
+    static const bool trace = getenv("NOLZSS_TRACE") != nullptr;
+    const int wb = nb > 2 * kRadixBits + 10 ? nb - 2 * kRadixBits : 10;
+    const int low_bits = wb + kRadixBits;
+    const int code_bits = 64 - nb - low_bits;  // >= 12 for nb <= 30
+    uint32_t esc = (uint32_t)((1ull << code_bits) - 1ull);
+    if (esc_env) esc = std::min<uint32_t>(esc, (uint32_t)strtoul(esc_env, nullptr, 0));
+    const uint32_t num_tiles = (uint32_t)div_up(count, kLbTile);
+    const uint32_t cap = (uint32_t)std::max<size_t>(count / 64, 1024);
+    uint64_t *buf_b = arena.alloc<uint64_t>(count);
+    uint64_t *desc = arena.alloc<uint64_t>((size_t)kBins * num_tiles);
+    uint32_t *exc = arena.alloc<uint32_t>(cap);
+    uint32_t *ctl = arena.alloc<uint32_t>(8);  // [0, 1, 2] first pass, [4, 5, 6] second pass
+    HIP_CHECK(hipMemsetAsync(ctl, 0, 8 * sizeof(uint32_t), stream));
+    LbPass p;
+    p.n = (uint32_t)count;
+    p.exc = exc;
+    p.exc_cap = cap;
+    p.esc = esc;
+    p.low_bits = low_bits;
+    p.rank_bits = nb;
+    p.desc = desc;
+    {
+        ProfScope ps(prof, "rs_scatter.u32", stream, 16.0 * (double)count);
+        HIP_CHECK(hipMemsetAsync(desc, 0, (size_t)kBins * num_tiles * sizeof(uint64_t), stream));
+        p.idx = idx;
+        p.code = code;
+        p.out = buf_a;
+        p.ctl = ctl;
+        p.dshift = wb + kRadixBits;
+        lb_partition_kernel<true><<<num_tiles, kLbThreads, 0, stream>>>(p);
+        KERNEL_CHECK();
+    }
+    {
+        ProfScope ps(prof, "rs_scatter.u32", stream, 16.0 * (double)count);
+        HIP_CHECK(hipMemsetAsync(desc, 0, (size_t)kBins * num_tiles * sizeof(uint64_t), stream));
+        p.idx = p.code = nullptr;
+        p.in = buf_a;
+        p.out = buf_b;
+        p.ctl = ctl + 4;
+        p.dshift = wb;
+        lb_partition_kernel<false><<<num_tiles, kLbThreads, 0, stream>>>(p);
+        KERNEL_CHECK();
+    }
+    {
+        ProfScope ps(prof, "window_scatter", stream, 16.0 * (double)count);
+        window_unpack_kernel<<<(unsigned)div_up(count, (size_t)1 << wb), kWindow2Threads, 0, stream>>>(
+            buf_b, out, out2, (uint32_t)count, wb, low_bits, nb);
+        KERNEL_CHECK();
+        escape_fixup_kernel<<<256, kThreads, 0, stream>>>(exc, ctl, cap, idx, code, out);
+        KERNEL_CHECK();
+    }
+    uint32_t h[8];
+    HIP_CHECK(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const bool ok = h[1] == 0 && h[5] == 0 && h[2] <= cap;
+    if (trace) {
+        unsigned long long *d_cnt = arena.alloc<unsigned long long>(7), hc[7];
+        HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(hc), stream));
+        code_census_kernel<<<1024, kThreads, 0, stream>>>(code, count, d_cnt);
+        KERNEL_CHECK();
+        HIP_CHECK(hipMemcpyAsync(hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        fprintf(stderr, "[nolzss] text order: %zu codes, >= 2^10..2^16: %llu %llu %llu %llu %llu %llu %llu\n", count, hc[0], hc[1],
+                hc[2], hc[3], hc[4], hc[5], hc[6]);
+    }
+    if (trace)
+        fprintf(stderr, "[nolzss] text order: packed look-back partition, %u escaped codes (cap %u, threshold %u)%s\n", h[2], cap,
+                esc, ok ? "" : (h[2] > cap ? ": list overflow, histogram form instead" : ": look-back gave up, histogram form instead"));
+    return ok;
+}
+
 }  // namespace
 
 bool record_scatter_plan(const std::vector<uint32_t> &h_terms, uint32_t n, Arena &arena, hipStream_t stream,
@@ -1108,7 +1473,7 @@ bool record_scatter_plan(const std::vector<uint32_t> &h_terms, uint32_t n, Arena
 
 void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out,
                       Arena &arena, hipStream_t stream, Profiler *prof, bool keep_input, bool keep_val,
-                      const RecordScatterPlan *plan, uint32_t *out2) {
+                      const RecordScatterPlan *plan, uint32_t *out2, bool short_codes) {
     if (count == 0) return;
     const size_t amark = arena.mark();
     {
@@ -1116,6 +1481,15 @@ void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t
         while (nb < 32 && (1ull << nb) < (uint64_t)n_out) ++nb;
         const bool big_perm = (size_t)n_out * 4 > (size_t(64) << 20) && count > (size_t(1) << 22) && count == n_out &&
                               nb <= 2 * kRadixBits + kWindowBitsMax && !(plan && plan->seg.desc);
+        static const bool hist_form = getenv("NOLZSS_TEXT_ORDER_HIST") != nullptr;  // (A/B switch, tests)
+        if (out2 && big_perm && short_codes && !hist_form) {
+            // one 8-byte word per pair, no histograms: 16 + 16 + 16 bytes per pair (packed_text_order); the inputs
+            // are only read, so the form below can still run when the exception list overflows
+            const bool done = packed_text_order(idx[0], val[0], count, out, out2, nb, reinterpret_cast<uint64_t *>(val[1]),
+                                                arena, stream, prof);
+            arena.rewind(amark);
+            if (done) return;
+        }
         if (out2 && big_perm) {
             // The permutation with TWO values per pair: out[idx[k]] = val[k] and out2[idx[k]] = k + 1.  The list
             // position is generated by the first pass and travels along as a second value: 20 + 22 + 18 bytes

@@ -167,10 +167,13 @@ struct RecordScatterPlan {
 };
 // out2 (optional): a second target, out2[idx[k]] = k + 1 -- for the pairs (sa[r], code[r]) of the pipeline that is
 // the inverse suffix array in its 1-based form, delivered by the same permutation.  val[1] must then hold
-// 2 * count words (the pairs travel with 64-bit values).
+// 2 * count words (the pairs travel with 64-bit values).  A permutation of up to 2^30 targets then goes without
+// histograms, each pair in ONE 8-byte word whose code field holds 72 - 2 * nb bits or more; larger codes take an
+// exception list (and, should it overflow, the histogram form runs after all).  short_codes = false keeps the
+// histogram form: codes that are mostly large (a flag in bit 31) would only overflow the list.
 void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out,
                       Arena &arena, hipStream_t stream, Profiler *prof, bool keep_input, bool keep_val = true,
-                      const RecordScatterPlan *plan = nullptr, uint32_t *out2 = nullptr);
+                      const RecordScatterPlan *plan = nullptr, uint32_t *out2 = nullptr, bool short_codes = true);
 // The same permutation for pairs that already carry both values in one 64-bit word (low half -> out, high half ->
 // out2) and are a permutation of [0, count): out[idx[k]] = (uint32_t)packed[k], out2[idx[k]] = packed[k] >> 32.
 // Both inputs are overwritten (they serve as buffers of the later passes).

@@ -498,8 +498,10 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
             } else {
                 uint32_t *idx[2] = {sa, scratch_idx};
                 uint32_t *val[2] = {by_rank, scratch_val};
-                // (isa_deferred: the same permutation writes isa[sa[r]] = r + 1)
-                bucketed_scatter(idx, val, m, code, m, arena, s, ctx.profiler(), true, true, nullptr, isa_deferred ? isa : nullptr);
+                // (isa_deferred: the same permutation writes isa[sa[r]] = r + 1; the codes carry the RC flag in bit 31,
+                // too large for the packed form)
+                bucketed_scatter(idx, val, m, code, m, arena, s, ctx.profiler(), true, true, nullptr, isa_deferred ? isa : nullptr,
+                                 false);
             }
         }
         if (plain) {
