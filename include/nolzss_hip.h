@@ -274,6 +274,53 @@ int nolzss_read_nucleotide_fasta(const char *path, const int *devices, size_t n_
                                  size_t shard_index, size_t shard_count, nolzss_nucleotide_fasta *out);
 void nolzss_free_nucleotide_fasta(nolzss_nucleotide_fasta *r);
 
+/* ---- factor-length significance against a shuffled control ------------------------------------ */
+/* reference: noLZSS.genomics.significance (src/noLZSS/genomics/significance.py) needs only the factor LENGTHS of a
+ * genome and of a shuffled copy.  These calls give them without factor records: the lengths come straight from the
+ * device's chain of factor starts ("Factor-length histograms and the keyed shuffle").
+ *   fwd[L] / rc[L] (1 <= L < threshold): factors of length L on the forward / reverse-complement strand (rc is all
+ *     zero in plain mode; index 0 is always 0);
+ *   tail_lengths[j], tail_rc[j] (tail_count entries, ascending by (tail_rc, length)): the factors of length
+ *     >= threshold;
+ *   z = number of factors; lengths (lengths_count = z entries, the *_with_lengths calls only, NULL otherwise): the
+ *     length of every factor in factor order.
+ * Free with nolzss_free_length_hist(). */
+typedef struct nolzss_length_hist {
+    uint32_t threshold;
+    uint64_t *fwd;
+    uint64_t *rc;
+    uint64_t *tail_lengths;
+    uint8_t *tail_rc;
+    size_t tail_count;
+    size_t z;
+    uint32_t *lengths;
+    size_t lengths_count;
+} nolzss_length_hist;
+void nolzss_free_length_hist(nolzss_length_hist *h);
+/* One text: plain mode (count_factors) or, with_rc != 0, the reverse-complement mode of count_factors_dna_w_rc, which
+ * refuses the same texts with the same status and message.  shuffle != 0: the text is first permuted by the keyed
+ * shuffle of nolzss_shuffle_dna(text, seed) (before the reverse complement is prepared). */
+int nolzss_factor_length_histogram(const uint8_t *text, size_t n, int with_rc, int shuffle, uint64_t seed, int device,
+                                   nolzss_length_hist *out);
+/* The same without shuffle, with the lengths in factor order as well (one pipeline run). */
+int nolzss_factor_length_histogram_with_lengths(const uint8_t *text, size_t n, int with_rc, int device,
+                                                nolzss_length_hist *out);
+/* The concatenated multiple-DNA FASTA form of nolzss_factorize_fasta_multiple_dna (same reader, sanitize_mode and
+ * limits): the histogram of the factors of the prepared string S.  shuffle != 0: every record of S is permuted by
+ * the keyed shuffle (record index = its place among the records of S), the sentinels stay where they are and the
+ * reverse-complement half is rebuilt from the shuffled records -- S is then prepare(shuffled records). */
+int nolzss_fasta_factor_length_histogram(const char *path, int with_rc, int sanitize_mode, int shuffle, uint64_t seed,
+                                         int device, nolzss_length_hist *out);
+int nolzss_fasta_factor_length_histogram_with_lengths(const char *path, int with_rc, int sanitize_mode, int device,
+                                                      nolzss_length_hist *out);
+/* The shuffled prepared string S of nolzss_fasta_factor_length_histogram (malloc'ed; nolzss_free). */
+int nolzss_fasta_shuffled_text(const char *path, int with_rc, int sanitize_mode, uint64_t seed, int device,
+                               uint8_t **S, size_t *S_len);
+/* Lengths of the z factors in factor order (plain or reverse-complement mode, as above); *out: nolzss_free. */
+int nolzss_factor_lengths(const uint8_t *text, size_t n, int with_rc, int device, uint32_t **out, size_t *z);
+/* out[i] = text[pi(i)] for the keyed bijection pi of (seed, record 0) on [0, n) (any byte values; *out: nolzss_free). */
+int nolzss_shuffle_dna(const uint8_t *text, size_t n, uint64_t seed, int device, uint8_t **out);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

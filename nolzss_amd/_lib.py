@@ -36,6 +36,13 @@ class NucleotideFasta(C.Structure):
                 ("owners", C.POINTER(C.c_size_t)), ("factors", C.POINTER(C.c_void_p)), ("keep", C.c_void_p)]
 
 
+class LengthHist(C.Structure):
+    """Mirror of nolzss_length_hist (include/nolzss_hip.h)."""
+    _fields_ = [("threshold", C.c_uint32), ("fwd", C.POINTER(C.c_uint64)), ("rc", C.POINTER(C.c_uint64)),
+                ("tail_lengths", C.POINTER(C.c_uint64)), ("tail_rc", C.POINTER(C.c_uint8)), ("tail_count", C.c_size_t),
+                ("z", C.c_size_t), ("lengths", C.POINTER(C.c_uint32)), ("lengths_count", C.c_size_t)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -134,6 +141,17 @@ def _load():
                                                         szp, szp]
     lib.nolzss_debug_lpt_plan.argtypes = [szp, sz, sz, szp]
     lib.nolzss_debug_batch_plan.argtypes = [szp, sz, sz, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), szp]
+    lib.nolzss_free_length_hist.argtypes = [C.POINTER(LengthHist)]
+    lib.nolzss_free_length_hist.restype = None
+    lib.nolzss_factor_length_histogram.argtypes = [vp, sz, C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(LengthHist)]
+    lib.nolzss_factor_length_histogram_with_lengths.argtypes = [vp, sz, C.c_int, C.c_int, C.POINTER(LengthHist)]
+    lib.nolzss_fasta_factor_length_histogram.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int,
+                                                         C.POINTER(LengthHist)]
+    lib.nolzss_fasta_factor_length_histogram_with_lengths.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int,
+                                                                      C.POINTER(LengthHist)]
+    lib.nolzss_fasta_shuffled_text.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint64, C.c_int, vpp, szp]
+    lib.nolzss_factor_lengths.argtypes = [vp, sz, C.c_int, C.c_int, vpp, szp]
+    lib.nolzss_shuffle_dna.argtypes = [vp, sz, C.c_uint64, C.c_int, vpp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -170,6 +188,9 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_trim_arenas", "nolzss_debug_parse_fasta",
     "nolzss_read_nucleotide_fasta", "nolzss_free_nucleotide_fasta", "nolzss_debug_parse_nucleotide_fasta", "nolzss_debug_lpt_plan", "nolzss_debug_batch_plan", "nolzss_factorize_batch_device",
     "nolzss_factorize_dna_w_rc_device", "nolzss_count_factors_batch_both",
+    "nolzss_free_length_hist", "nolzss_factor_length_histogram", "nolzss_factor_length_histogram_with_lengths",
+    "nolzss_fasta_factor_length_histogram", "nolzss_fasta_factor_length_histogram_with_lengths",
+    "nolzss_fasta_shuffled_text", "nolzss_factor_lengths", "nolzss_shuffle_dna",
 ]
 
 

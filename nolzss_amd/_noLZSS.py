@@ -7,6 +7,7 @@ releases the GIL around every native call just as the reference does with gil_sc
 computes on the GPU through the C ABI (there is no CPU path).
 """
 import ctypes as C
+import operator
 import os
 
 import numpy as np
@@ -211,6 +212,122 @@ def count_factors_batch_both(texts, devices=None):
     no_rc = (C.c_size_t * max(m, 1))()
     check(lib.nolzss_count_factors_batch_both(ptrs, lens, m, devs, len(devices), w_rc, no_rc))
     return list(w_rc)[:m], list(no_rc)[:m]
+
+
+# ---- factor lengths for the shuffled-control significance analysis (genomics/significance.py) ------------------
+def _seed_arg(seed) -> int:
+    """a shuffle key: an integer in [0, 2^64) (the C ABI takes a uint64_t; nothing is wrapped silently)"""
+    seed = operator.index(seed)
+    if seed < 0 or seed >= 1 << 64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    return seed
+
+
+def _take_u32(ptr, count):
+    """library-owned uint32 block -> numpy view, freed with the array (no host copy)"""
+    owner = _Owned(ptr)
+    if count == 0:
+        return np.zeros(0, dtype=np.uint32)
+    raw = (C.c_uint32 * count).from_address(ptr.value)
+    raw._owner = owner
+    return np.frombuffer(raw, dtype=np.uint32)
+
+
+def _unpack_length_hist(res):
+    """nolzss_length_hist -> dict: fwd / rc (int64, threshold bins, bin L = factors of length L), tail_lengths (int64),
+    tail_rc (bool), z, and lengths (uint32, factor order) when the call filled them."""
+    try:
+        T = res.threshold
+        out = {"threshold": T, "z": res.z,
+               "fwd": np.ctypeslib.as_array(res.fwd, shape=(T,)).astype(np.int64) if T else np.zeros(0, np.int64),
+               "rc": np.ctypeslib.as_array(res.rc, shape=(T,)).astype(np.int64) if T else np.zeros(0, np.int64)}
+        tc = res.tail_count
+        out["tail_lengths"] = (np.ctypeslib.as_array(res.tail_lengths, shape=(tc,)).astype(np.int64) if tc
+                               else np.zeros(0, np.int64))
+        out["tail_rc"] = (np.ctypeslib.as_array(res.tail_rc, shape=(tc,)).astype(bool) if tc
+                          else np.zeros(0, bool))
+        if res.lengths:  # handed over to the array (nolzss_free_length_hist then skips it)
+            ptr = C.c_void_p(C.cast(res.lengths, C.c_void_p).value)
+            res.lengths = None
+            out["lengths"] = _take_u32(ptr, res.lengths_count)
+    finally:
+        lib.nolzss_free_length_hist(C.byref(res))
+    return out
+
+
+def factor_length_histogram(data, with_rc: bool = False, shuffle_seed=None):
+    """Extension: the factor-length histogram of `data` (plain mode, or the reverse-complement mode of
+    count_factors_dna_w_rc) without factor records; shuffle_seed: histogram of the keyed shuffle shuffle_dna(data,
+    shuffle_seed) instead.  C ABI nolzss_factor_length_histogram."""
+    p, n, keep = _as_buffer(data)
+    res = _lib.LengthHist()
+    shuffle = shuffle_seed is not None
+    check(lib.nolzss_factor_length_histogram(p, n, 1 if with_rc else 0, 1 if shuffle else 0,
+                                             _seed_arg(shuffle_seed) if shuffle else 0, _default_device, C.byref(res)))
+    return _unpack_length_hist(res)
+
+
+def factor_length_histogram_with_lengths(data, with_rc: bool = False):
+    """Extension: factor_length_histogram plus the lengths in factor order ('lengths'), from one pipeline run."""
+    p, n, keep = _as_buffer(data)
+    res = _lib.LengthHist()
+    check(lib.nolzss_factor_length_histogram_with_lengths(p, n, 1 if with_rc else 0, _default_device, C.byref(res)))
+    return _unpack_length_hist(res)
+
+
+def fasta_factor_length_histogram(fasta_path, with_rc: bool = True, sanitize_mode: str = "remove_ambiguous",
+                                  shuffle_seed=None, want_lengths: bool = False):
+    """Extension: the factor-length histogram of the concatenated multiple-DNA form of a FASTA file (the factors of
+    factorize_fasta_multiple_dna_{w,no}_rc); shuffle_seed: of its records shuffled on the device; want_lengths (no
+    shuffle): also the lengths in factor order."""
+    res = _lib.LengthHist()
+    path = _str_arg(fasta_path, "fasta_path")
+    mode = _sanitize_mode(sanitize_mode)
+    if want_lengths:
+        if shuffle_seed is not None:
+            raise ValueError("want_lengths is for the unshuffled text")
+        check(lib.nolzss_fasta_factor_length_histogram_with_lengths(path, 1 if with_rc else 0, mode, _default_device,
+                                                                    C.byref(res)))
+    else:
+        shuffle = shuffle_seed is not None
+        check(lib.nolzss_fasta_factor_length_histogram(path, 1 if with_rc else 0, mode, 1 if shuffle else 0,
+                                                       _seed_arg(shuffle_seed) if shuffle else 0, _default_device,
+                                                       C.byref(res)))
+    return _unpack_length_hist(res)
+
+
+def fasta_shuffled_text(fasta_path, seed, with_rc: bool = True, sanitize_mode: str = "remove_ambiguous") -> bytes:
+    """Extension: the prepared string S of a FASTA file with its records shuffled on the device (what
+    fasta_factor_length_histogram factorizes)."""
+    S, S_len = C.c_void_p(), C.c_size_t()
+    check(lib.nolzss_fasta_shuffled_text(_str_arg(fasta_path, "fasta_path"), 1 if with_rc else 0,
+                                         _sanitize_mode(sanitize_mode), _seed_arg(seed), _default_device, C.byref(S),
+                                         C.byref(S_len)))
+    try:
+        return C.string_at(S, S_len.value) if S.value else b""
+    finally:
+        lib.nolzss_free(S)
+
+
+def factor_lengths(data, with_rc: bool = False) -> np.ndarray:
+    """Extension: the length of every factor in factor order (uint32), without factor records.  C ABI
+    nolzss_factor_lengths."""
+    p, n, keep = _as_buffer(data)
+    out, z = C.c_void_p(), C.c_size_t()
+    check(lib.nolzss_factor_lengths(p, n, 1 if with_rc else 0, _default_device, C.byref(out), C.byref(z)))
+    return _take_u32(out, z.value)
+
+
+def shuffle_dna(data, seed) -> bytes:
+    """Extension: the keyed shuffle of `data` on the device (out[i] = data[pi(i)]); any byte values."""
+    p, n, keep = _as_buffer(data)
+    out = C.c_void_p()
+    seed = _seed_arg(seed)
+    check(lib.nolzss_shuffle_dna(p, n, seed, _default_device, C.byref(out)))
+    try:
+        return C.string_at(out, n) if n else b""
+    finally:
+        lib.nolzss_free(out)
 
 
 def factorize_batch_device(data_ptrs, lengths, emit: int = 0):

@@ -90,8 +90,10 @@ struct DebugOut {
 };
 
 // the plain-mode pipeline on a device-resident text / on a host buffer (upload first); returns z
+// lengths (optional, significance.hip): factor lengths instead of records (ChainLengthsOut); the arena is then NOT
+// rewound, so that the caller can download them -- the caller owns the mark
 size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, nolzss_factor **out_host,
-                 DebugOut *dbg, bool records_on_device_only = false);
+                 DebugOut *dbg, bool records_on_device_only = false, const ChainLengthsOut *lengths = nullptr);
 size_t run_plain_host(Context &ctx, const uint8_t *text, size_t n, size_t start_pos, nolzss_factor **out,
                       DebugOut *dbg);
 

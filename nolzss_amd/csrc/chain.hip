@@ -21,6 +21,8 @@
 #include "pyramid.hpp"
 #include "scan.hpp"
 
+#include <cassert>
+
 namespace nolzss {
 namespace {
 
@@ -233,6 +235,56 @@ __global__ __launch_bounds__(64) void emit_positions_kernel(const unsigned long 
     }
 }
 
+// Factor lengths straight from the marked chain (ChainLengthsOut, pipeline.hpp): length = max(1, code & kLenMask),
+// bit 31 = reverse-complement strand (kRC only).  Each workgroup walks words of chain_bits grid-stride and counts in
+// LDS; at the end it makes one global atomic add per non-zero bin (integer counts: the result does not depend on the
+// order of the adds).  Lengths >= T go to the tail list, which cannot overflow: the lengths of the factors sum to at
+// most n, so at most floor(n / T) of them reach T.
+template <bool kRC>
+__global__ __launch_bounds__(kThreads) void length_hist_kernel(const unsigned long long *__restrict__ chain_bits,
+                                                               uint32_t nwords, const uint32_t *__restrict__ lstar,
+                                                               uint32_t *__restrict__ hist,
+                                                               uint64_t *__restrict__ tail,
+                                                               uint32_t *__restrict__ tail_count, uint32_t tail_cap) {
+    constexpr uint32_t T = kLengthHistBins;
+    constexpr uint32_t kBins = kRC ? 2 * T : T;
+    __shared__ uint32_t h[kBins];
+    for (uint32_t b = threadIdx.x; b < kBins; b += kThreads) h[b] = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * kThreads;
+    for (uint32_t w = blockIdx.x * kThreads + threadIdx.x; w < nwords; w += stride) {
+        unsigned long long b = chain_bits[w];
+        while (b) {
+            const int bit = __ffsll((long long)b) - 1;
+            b &= b - 1;
+            const uint32_t code = lstar[(size_t)w * 64 + (uint32_t)bit];
+            const uint32_t strand = kRC ? (code >> 31) : 0u;
+            uint32_t L = code & kLenMask;
+            L = L ? L : 1u;
+            if (L < T) {
+                atomicAdd(&h[strand * T + L], 1u);
+            } else {
+                const uint32_t slot = atomicAdd(tail_count, 1u);
+                assert(slot < tail_cap);
+                if (slot < tail_cap) tail[slot] = (uint64_t)L | ((uint64_t)strand << 32);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kBins; b += kThreads)
+        if (h[b]) atomicAdd(&hist[b], h[b]);
+}
+
+// fpos[k] (a factor start) -> the length of factor k, in place
+__global__ __launch_bounds__(kThreads) void gather_lengths_kernel(uint32_t *__restrict__ fpos, uint32_t z,
+                                                                  const uint32_t *__restrict__ lstar) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < z; k += stride) {
+        const uint32_t L = lstar[fpos[k]] & kLenMask;
+        fpos[k] = L ? L : 1u;
+    }
+}
+
 // ranks the factor kernel walks one by one around ISA[i] before it asks the pyramids: the interval
 // of a short factor holds all occurrences of a 12- to 14-mer, dozens to hundreds of ranks, and every
 // step of the walk is a dependent load (48 -> 4: 14.5 -> 11 ms per 52 M factors)
@@ -350,7 +402,7 @@ inline unsigned grid_for(size_t items, unsigned cap = 256u * 16u) {
 uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint32_t *lstar, const uint32_t *sa,
                        const uint32_t *isa, const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp,
                        void **d_factors_out, uint32_t rcN, const Pyramid *Pmax, uint32_t **d_fpos_out,
-                       const TermTable *rebase) {
+                       const TermTable *rebase, const ChainLengthsOut *lengths) {
     hipStream_t s = ctx.stream;
     Arena &arena = ctx.arena;
     if (d_factors_out) *d_factors_out = nullptr;
@@ -418,6 +470,33 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
     }
     uint32_t z = 0;
     ctx.read_back(d_total + 1, &z, 1);
+    if (lengths) {  // factor lengths only: no records, no factor_kernel
+        if (d_factors_out || d_fpos_out) throw HipError("resolve_chain: factor lengths come without records");
+        if (lengths->hist && z) {
+            ProfScope ps(ctx.profiler(), "length_hist", s);
+            const uint32_t nwords = num_tiles * (uint32_t)(kTile / 64);
+            const unsigned g = grid_for(nwords, 1024);
+            if (rcN)
+                length_hist_kernel<true><<<g, kThreads, 0, s>>>(cbits, nwords, lstar, lengths->hist, lengths->tail,
+                                                                lengths->tail_count, lengths->tail_cap);
+            else
+                length_hist_kernel<false><<<g, kThreads, 0, s>>>(cbits, nwords, lstar, lengths->hist, lengths->tail,
+                                                                 lengths->tail_count, lengths->tail_cap);
+            KERNEL_CHECK();
+        }
+        if (!lengths->order || z == 0) {
+            arena.rewind(mark);
+            return z;
+        }
+        fpos = arena.alloc<uint32_t>(z);
+        ProfScope ps(ctx.profiler(), "length_emit", s);
+        emit_positions_kernel<<<num_tiles, 64, 0, s>>>(cbits, tile_count, fpos);
+        KERNEL_CHECK();
+        gather_lengths_kernel<<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar);
+        KERNEL_CHECK();
+        *lengths->order = fpos;
+        return z;
+    }
     if ((!d_factors_out && !d_fpos_out) || z == 0) {
         arena.rewind(mark);
         return z;

@@ -69,15 +69,28 @@ void finish_pending_lcp(Context &ctx, const PackedText &text, const uint32_t *sa
 void inject_pending_for_test(Context &ctx, uint32_t *lcp, uint32_t n);
 
 // ---- stage 5: greedy cursor + factor records (chain.hip) ------------------------------------
+// Factor lengths without factor records ("Factor-length histograms"): the chain's marked positions and
+// their L* codes only, factor_kernel is not run.  All device buffers are caller-allocated; hist (kRC: 2 x T bins, the
+// reverse-complement ones behind the forward ones) and *tail_count are zeroed by the caller.
+constexpr uint32_t kLengthHistBins = 2048;  // T: dense bins for 1 <= L < T
+struct ChainLengthsOut {
+    uint32_t *hist = nullptr;        // per-length counts, or nullptr for no histogram
+    uint64_t *tail = nullptr;        // lengths >= T: length | strand << 32, in no particular order
+    uint32_t *tail_count = nullptr;  // entries written to tail
+    uint32_t tail_cap = 0;           // floor(n / T) + 1: the lengths sum to at most n
+    uint32_t **order = nullptr;      // optional: z lengths in factor order, left in the arena like d_fpos_out
+};
+inline uint32_t length_tail_cap(uint32_t n) { return n / kLengthHistBins + 1u; }
 uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint32_t *lstar, const uint32_t *sa,
                        const uint32_t *isa, const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp,
                        void **d_factors_out, uint32_t rcN = 0, const Pyramid *Pmax = nullptr,
-                       uint32_t **d_fpos_out = nullptr, const TermTable *rebase = nullptr);
+                       uint32_t **d_fpos_out = nullptr, const TermTable *rebase = nullptr,
+                       const ChainLengthsOut *lengths = nullptr);
 
 // ---- reverse-complement mode (rc.hip): whole pipeline over the prepared string S -------------
 struct RcPlainOut;
 uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m, size_t start_pos, void **d_factors_out,
-                         RcPlainOut *plain = nullptr);
+                         RcPlainOut *plain = nullptr, const ChainLengthsOut *lengths = nullptr);
 // plain-mode counts as a by-product of a reverse-complement run: the plain L* of every position i < N comes out of
 // the same candidate kernels (rc.hip) and is chained on its own; z = nolzss_count_factors of the original strand(s),
 // fpos (want_fpos) = its factor starts in the arena, for the per-record split of a merged run
@@ -88,8 +101,10 @@ struct RcPlainOut {
 };
 // the same over a text that has already been packed (merged batch); plain (optional): the plain-mode by-product
 // above; d_fpos_out (optional, with d_factors_out null): the factor starts of the reverse-complement chain
+// lengths (optional, with d_factors_out null): the factor lengths of the reverse-complement chain (ChainLengthsOut)
 uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
-                                RcPlainOut *plain = nullptr, uint32_t **d_fpos_out = nullptr);
+                                RcPlainOut *plain = nullptr, uint32_t **d_fpos_out = nullptr,
+                                const ChainLengthsOut *lengths = nullptr);
 // d_S (2n + 2 bytes) = T' sep revcomp(T') sep for the n bytes d_T = upper-case records with separator bytes
 // between them; bytes that are not nucleotides (the separators) are copied to their mirror position.
 void prepare_batch_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t n, uint8_t separator, uint8_t *d_S);

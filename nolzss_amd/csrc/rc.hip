@@ -377,13 +377,13 @@ uint32_t prepare_single_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t 
 }
 
 uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m_sz, size_t start_pos, void **d_factors_out,
-                         RcPlainOut *plain) {
+                         RcPlainOut *plain, const ChainLengthsOut *lengths) {
     const PackedText text = pack_text(ctx, d_S, m_sz);  // segmented 2-bit packing is detected there
-    return run_rc_pipeline_packed(ctx, text, start_pos, d_factors_out, plain);
+    return run_rc_pipeline_packed(ctx, text, start_pos, d_factors_out, plain, nullptr, lengths);
 }
 
 uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
-                                RcPlainOut *plain_out, uint32_t **d_fpos_out) {
+                                RcPlainOut *plain_out, uint32_t **d_fpos_out, const ChainLengthsOut *lengths) {
     const uint32_t m = text.n;
     const uint32_t N = m / 2 - 1;
     hipStream_t s = ctx.stream;
@@ -537,7 +537,7 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
         arena.rewind(mark);
     }
     const uint32_t z = resolve_chain(ctx, N, (uint32_t)start_pos, code, sa, isa, lcp, Pmin, Plcp, d_factors_out, N, &Pmax,
-                                     d_fpos_out);
+                                     d_fpos_out, nullptr, lengths);
     if (plain_out) {
         // the plain chain over the same positions: counts (and factor starts) only, no records
         ProfScope ps(ctx.profiler(), "plain_chain", s);
