@@ -321,6 +321,65 @@ int nolzss_factor_lengths(const uint8_t *text, size_t n, int with_rc, int device
 /* out[i] = text[pi(i)] for the keyed bijection pi of (seed, record 0) on [0, n) (any byte values; *out: nolzss_free). */
 int nolzss_shuffle_dna(const uint8_t *text, size_t n, uint64_t seed, int device, uint8_t **out);
 
+/* ---- strand-bias grid and space-scale histogram of the factors --------------------------------- */
+/* reference: noLZSS.genomics.plots, _compute_strand_bias_grid (src/noLZSS/genomics/plots.py:1961-2075) and the 2-D
+ * histogram of plot_space_scale_heatmap (:2559-2614).  Both read every factor and return a few thousand numbers: they
+ * are binned on the device from the records the pipeline leaves there ("Strand-bias and space-scale
+ * maps"), so no factor record crosses PCIe.
+ *
+ * Kept factors (:2149-2157): length >= min_factor_length, or a sentinel factor.  Everything below is over them.
+ * Strand grid: the factor plane (x = start .. start + length, y = ref + (x - start) forward, ref + length - (x - start)
+ *   reverse complement) cut into x_bins x y_bins cells over [0, x_max) x [0, y_max); x_max = y_max = total_length, or
+ *   (total_length = 0) max(start + length) and max(ref + length).  forward_units / rc_units[yi * x_bins + xi] = the
+ *   x-length of that strand's segments inside cell (yi, xi) in units of 1 / unit nucleotides, unit = x_bins * y_bins:
+ *   every crossing of a cell edge is a multiple of 1 / unit, so the integers are exact and do not depend on the order
+ *   of the adds.  Parts outside the extents are dropped.  1 <= x_bins, y_bins <= 4096; x_max, y_max <= 2^33.
+ * Space-scale histogram: numpy.histogram2d(lengths, starts, bins=[length_edges, position_edges]) per strand:
+ *   hist[li * n_position_bins + pi] counts edges[i] <= v < edges[i + 1], the last bin also v == edges[-1].  Edges: 2 to
+ *   4097 (length) / 2 to 2^20 + 1 (position) non-decreasing finite float64.  position_edges = NULL: the reference's
+ *   ladder (:2566-2574) over genome_end = the largest kept start, nb = max(position_min_bins, ceil(genome_end /
+ *   position_bin_bp)), edges[k] = k * (genome_end / nb), edges[nb] = genome_end (= numpy.linspace(0, genome_end,
+ *   nb + 1)); with genome_end = 0 or no kept factor there is no ladder: n_position_bins = 0 and no histogram.
+ * One pipeline run serves both.  Free the result with nolzss_free_factor_maps(). */
+typedef struct nolzss_factor_map_request {
+    uint32_t x_bins, y_bins;       /* 0, 0: no strand grid */
+    uint64_t total_length;         /* 0: extents from the kept factors */
+    uint64_t min_factor_length;    /* 0 or 1: keep all */
+    const double *length_edges;    /* NULL / 0: no space-scale histogram */
+    size_t n_length_edges;
+    const double *position_edges;  /* NULL / 0: the reference's ladder from the two fields below */
+    size_t n_position_edges;
+    uint32_t position_min_bins;    /* reference: 50 */
+    uint64_t position_bin_bp;      /* reference: 1 000 000 */
+} nolzss_factor_map_request;
+typedef struct nolzss_factor_maps {
+    uint64_t z, z_used;            /* factors, kept factors */
+    uint64_t x_max, y_max, unit;   /* strand grid: extents used, x_bins * y_bins */
+    uint32_t x_bins, y_bins;
+    uint64_t *forward_units, *rc_units; /* y_bins * x_bins each (NULL without a grid request) */
+    size_t n_length_bins, n_position_bins;
+    uint64_t *hist_forward, *hist_rc;   /* n_length_bins * n_position_bins each (NULL without a histogram) */
+    double *position_edges;             /* n_position_bins + 1, as used */
+    uint64_t kept_forward, kept_rc;     /* kept factors per strand */
+    uint64_t min_length, max_length, max_start; /* over the kept factors of both strands (0 if none) */
+} nolzss_factor_maps;
+void nolzss_free_factor_maps(nolzss_factor_maps *m);
+/* The factors of nolzss_factorize (with_rc = 0) or nolzss_factorize_dna_w_rc: the refusals of nolzss_count_factors /
+ * nolzss_count_factors_dna_w_rc with their status and message.  No sentinel factors. */
+int nolzss_factor_maps_text(const uint8_t *text, size_t n, int with_rc, int device,
+                            const nolzss_factor_map_request *request, nolzss_factor_maps *out);
+/* The factors of nolzss_factorize_fasta_multiple_dna (same reader, sanitize_mode and limits); sentinel factors = the
+ * factors that start at a sentinel of the prepared string. */
+int nolzss_factor_maps_fasta(const char *path, int with_rc, int sanitize_mode, int device,
+                             const nolzss_factor_map_request *request, nolzss_factor_maps *out);
+/* Host records (a v2 factor file, a test), uploaded in chunks and binned by the same kernels; sentinel factors by
+ * ascending factor index.  ref carries NOLZSS_RC_MASK. */
+int nolzss_factor_maps_records(const nolzss_factor *factors, size_t z, const uint64_t *sentinel_factor_indices,
+                               size_t n_sentinels, int device, const nolzss_factor_map_request *request,
+                               nolzss_factor_maps *out);
+/* Host only: the position ladder above (malloc'ed, *n = nb + 1 entries; nolzss_free). */
+int nolzss_debug_position_edges(uint64_t genome_end, uint32_t min_bins, uint64_t bin_bp, double **edges, size_t *n);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

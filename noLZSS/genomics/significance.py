@@ -1,5 +1,6 @@
 """noLZSS.genomics.significance (reference: src/noLZSS/genomics/significance.py): factor-length significance
-against a shuffled control; the GPU extensions take both factorizations from the device.  Plots are not provided."""
+against a shuffled control; the GPU extensions take both factorizations from the device.  The data layer of the
+reference's plots is noLZSS.genomics.plots; drawing is not provided."""
 from nolzss_amd.genomics.significance import (calculate_factor_length_threshold,  # noqa: F401
                                               clopper_pearson_upper, extract_factor_lengths,
                                               fasta_shuffled_control_significance, factor_length_histogram,

@@ -43,6 +43,25 @@ class LengthHist(C.Structure):
                 ("z", C.c_size_t), ("lengths", C.POINTER(C.c_uint32)), ("lengths_count", C.c_size_t)]
 
 
+class FactorMapRequest(C.Structure):
+    """Mirror of nolzss_factor_map_request (include/nolzss_hip.h)."""
+    _fields_ = [("x_bins", C.c_uint32), ("y_bins", C.c_uint32), ("total_length", C.c_uint64),
+                ("min_factor_length", C.c_uint64), ("length_edges", C.POINTER(C.c_double)),
+                ("n_length_edges", C.c_size_t), ("position_edges", C.POINTER(C.c_double)),
+                ("n_position_edges", C.c_size_t), ("position_min_bins", C.c_uint32), ("position_bin_bp", C.c_uint64)]
+
+
+class FactorMaps(C.Structure):
+    """Mirror of nolzss_factor_maps (include/nolzss_hip.h)."""
+    _fields_ = [("z", C.c_uint64), ("z_used", C.c_uint64), ("x_max", C.c_uint64), ("y_max", C.c_uint64),
+                ("unit", C.c_uint64), ("x_bins", C.c_uint32), ("y_bins", C.c_uint32),
+                ("forward_units", C.POINTER(C.c_uint64)), ("rc_units", C.POINTER(C.c_uint64)),
+                ("n_length_bins", C.c_size_t), ("n_position_bins", C.c_size_t),
+                ("hist_forward", C.POINTER(C.c_uint64)), ("hist_rc", C.POINTER(C.c_uint64)),
+                ("position_edges", C.POINTER(C.c_double)), ("kept_forward", C.c_uint64), ("kept_rc", C.c_uint64),
+                ("min_length", C.c_uint64), ("max_length", C.c_uint64), ("max_start", C.c_uint64)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -152,6 +171,13 @@ def _load():
     lib.nolzss_fasta_shuffled_text.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint64, C.c_int, vpp, szp]
     lib.nolzss_factor_lengths.argtypes = [vp, sz, C.c_int, C.c_int, vpp, szp]
     lib.nolzss_shuffle_dna.argtypes = [vp, sz, C.c_uint64, C.c_int, vpp]
+    rqp, fmp = C.POINTER(FactorMapRequest), C.POINTER(FactorMaps)
+    lib.nolzss_free_factor_maps.argtypes = [fmp]
+    lib.nolzss_free_factor_maps.restype = None
+    lib.nolzss_factor_maps_text.argtypes = [vp, sz, C.c_int, C.c_int, rqp, fmp]
+    lib.nolzss_factor_maps_fasta.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, rqp, fmp]
+    lib.nolzss_factor_maps_records.argtypes = [vp, sz, vp, sz, C.c_int, rqp, fmp]
+    lib.nolzss_debug_position_edges.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, vpp, szp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -191,6 +217,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_free_length_hist", "nolzss_factor_length_histogram", "nolzss_factor_length_histogram_with_lengths",
     "nolzss_fasta_factor_length_histogram", "nolzss_fasta_factor_length_histogram_with_lengths",
     "nolzss_fasta_shuffled_text", "nolzss_factor_lengths", "nolzss_shuffle_dna",
+    "nolzss_free_factor_maps", "nolzss_factor_maps_text", "nolzss_factor_maps_fasta", "nolzss_factor_maps_records",
+    "nolzss_debug_position_edges",
 ]
 
 

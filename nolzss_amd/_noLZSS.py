@@ -330,6 +330,114 @@ def shuffle_dna(data, seed) -> bytes:
         lib.nolzss_free(out)
 
 
+# ---- strand-bias grid and space-scale histogram binned on the device (genomics/plots.py) ------------------------
+def _edges_arg(edges, name):
+    if edges is None:
+        return None
+    a = np.ascontiguousarray(edges, dtype=np.float64)
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be one-dimensional")
+    return a
+
+
+def _map_request(grid, total_length, min_factor_length, length_edges, position_edges, position_min_bins,
+                 position_bin_bp):
+    """-> (nolzss_factor_map_request, keepalive).  grid: (x_bins, y_bins) or None."""
+    rq = _lib.FactorMapRequest()
+    if grid is not None:
+        rq.x_bins, rq.y_bins = (operator.index(g) for g in grid)
+    total_length = 0 if total_length is None else operator.index(total_length)
+    min_factor_length = operator.index(min_factor_length)
+    if total_length < 0 or min_factor_length < 0:
+        raise ValueError("total_length and min_factor_length must not be negative")
+    rq.total_length, rq.min_factor_length = total_length, min_factor_length
+    le, pe = _edges_arg(length_edges, "length_edges"), _edges_arg(position_edges, "position_edges")
+    if le is not None:
+        rq.length_edges, rq.n_length_edges = le.ctypes.data_as(C.POINTER(C.c_double)), le.size
+    if pe is not None:
+        rq.position_edges, rq.n_position_edges = pe.ctypes.data_as(C.POINTER(C.c_double)), pe.size
+    rq.position_min_bins, rq.position_bin_bp = operator.index(position_min_bins), operator.index(position_bin_bp)
+    return rq, (le, pe)
+
+
+def _unpack_factor_maps(res):
+    """nolzss_factor_maps -> dict of numpy arrays (copies) and integers; absent maps are None"""
+    try:
+        out = {k: int(getattr(res, k)) for k in ("z", "z_used", "x_max", "y_max", "unit", "x_bins", "y_bins",
+                                                  "kept_forward", "kept_rc", "min_length", "max_length", "max_start")}
+        shape = (res.y_bins, res.x_bins)
+        for k in ("forward_units", "rc_units"):
+            p = getattr(res, k)
+            out[k] = np.ctypeslib.as_array(p, shape=shape).copy() if p else None
+        hshape = (res.n_length_bins, res.n_position_bins)
+        for k in ("hist_forward", "hist_rc"):
+            p = getattr(res, k)
+            out[k] = np.ctypeslib.as_array(p, shape=hshape).copy() if p else None
+        out["position_edges"] = (np.ctypeslib.as_array(res.position_edges, shape=(res.n_position_bins + 1,)).copy()
+                                 if res.position_edges else None)
+    finally:
+        lib.nolzss_free_factor_maps(C.byref(res))
+    return out
+
+
+def factor_maps(data, with_rc: bool = False, grid=None, total_length=None, min_factor_length: int = 1,
+                length_edges=None, position_edges=None, position_min_bins: int = 50, position_bin_bp: int = 1_000_000):
+    """Extension: strand-bias grid units and / or the space-scale histogram of the factors of `data` (factorize, or
+    factorize_dna_w_rc with with_rc), binned on the device from one pipeline run.  C ABI nolzss_factor_maps_text."""
+    rq, keep_rq = _map_request(grid, total_length, min_factor_length, length_edges, position_edges, position_min_bins,
+                               position_bin_bp)
+    p, n, keep = _as_buffer(data)
+    res = _lib.FactorMaps()
+    check(lib.nolzss_factor_maps_text(p, n, 1 if with_rc else 0, _default_device, C.byref(rq), C.byref(res)))
+    return _unpack_factor_maps(res)
+
+
+def fasta_factor_maps(fasta_path, with_rc: bool = True, sanitize_mode: str = "remove_ambiguous", grid=None,
+                      total_length=None, min_factor_length: int = 1, length_edges=None, position_edges=None,
+                      position_min_bins: int = 50, position_bin_bp: int = 1_000_000):
+    """Extension: factor_maps over the factors of factorize_fasta_multiple_dna_{w,no}_rc (sentinel factors are kept
+    whatever min_factor_length).  C ABI nolzss_factor_maps_fasta."""
+    rq, keep_rq = _map_request(grid, total_length, min_factor_length, length_edges, position_edges, position_min_bins,
+                               position_bin_bp)
+    res = _lib.FactorMaps()
+    check(lib.nolzss_factor_maps_fasta(_str_arg(fasta_path, "fasta_path"), 1 if with_rc else 0,
+                                       _sanitize_mode(sanitize_mode), _default_device, C.byref(rq), C.byref(res)))
+    return _unpack_factor_maps(res)
+
+
+def records_factor_maps(factors, sentinel_factor_indices=(), grid=None, total_length=None, min_factor_length: int = 1,
+                        length_edges=None, position_edges=None, position_min_bins: int = 50,
+                        position_bin_bp: int = 1_000_000):
+    """Extension: factor_maps over host records: a FACTOR_DTYPE array (ref carrying RC_MASK) or an (n, 3) uint64
+    array.  C ABI nolzss_factor_maps_records."""
+    rq, keep_rq = _map_request(grid, total_length, min_factor_length, length_edges, position_edges, position_min_bins,
+                               position_bin_bp)
+    f = np.asarray(factors)
+    if f.dtype != FACTOR_DTYPE:
+        f = np.ascontiguousarray(f, dtype=np.uint64)
+        if f.size and (f.ndim != 2 or f.shape[1] != 3):
+            raise ValueError("factors must be a FACTOR_DTYPE array or an (n, 3) uint64 array")
+        z = f.shape[0] if f.size else 0
+    else:
+        f = np.ascontiguousarray(f)
+        z = f.size
+    sent = np.ascontiguousarray(sorted(operator.index(i) for i in sentinel_factor_indices), dtype=np.uint64)
+    res = _lib.FactorMaps()
+    check(lib.nolzss_factor_maps_records(f.ctypes.data if z else None, z, sent.ctypes.data if sent.size else None,
+                                         sent.size, _default_device, C.byref(rq), C.byref(res)))
+    return _unpack_factor_maps(res)
+
+
+def debug_position_edges(genome_end: int, min_bins: int = 50, bin_bp: int = 1_000_000) -> np.ndarray:
+    """Host only: the position ladder of the space-scale histogram (C ABI nolzss_debug_position_edges)."""
+    e, n = C.c_void_p(), C.c_size_t()
+    check(lib.nolzss_debug_position_edges(genome_end, min_bins, bin_bp, C.byref(e), C.byref(n)))
+    try:
+        return np.ctypeslib.as_array(C.cast(e, C.POINTER(C.c_double)), shape=(n.value,)).copy()
+    finally:
+        lib.nolzss_free(e)
+
+
 def factorize_batch_device(data_ptrs, lengths, emit: int = 0):
     """Extension (measurement): per-sequence batch over records resident in device memory
     (C ABI nolzss_factorize_batch_device); returns the factor count of every record."""

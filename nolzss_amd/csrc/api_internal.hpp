@@ -92,8 +92,11 @@ struct DebugOut {
 // the plain-mode pipeline on a device-resident text / on a host buffer (upload first); returns z
 // lengths (optional, significance.hip): factor lengths instead of records (ChainLengthsOut); the arena is then NOT
 // rewound, so that the caller can download them -- the caller owns the mark
+// d_records_out (optional, factor_maps.hip): the z factor records where resolve_chain left them in the arena, under
+// the same rule
 size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, nolzss_factor **out_host,
-                 DebugOut *dbg, bool records_on_device_only = false, const ChainLengthsOut *lengths = nullptr);
+                 DebugOut *dbg, bool records_on_device_only = false, const ChainLengthsOut *lengths = nullptr,
+                 void **d_records_out = nullptr);
 size_t run_plain_host(Context &ctx, const uint8_t *text, size_t n, size_t start_pos, nolzss_factor **out,
                       DebugOut *dbg);
 
@@ -171,6 +174,16 @@ struct NucleotideFastaKeep {
         for (void *b : blocks) free_block(b);
     }
 };
+
+// ---- the prepared string of a FASTA file and its forward records (significance.hip; also factor_maps.hip) ---------
+struct FastaText {
+    HostBytes S;
+    std::vector<std::pair<uint32_t, uint32_t>> recs;
+    uint32_t N = 0;
+    bool empty = true;
+};
+void read_fasta_text(const char *path, bool with_rc, bool strict, FastaText &ft);
+void check_sanitize_mode(int sanitize_mode);
 
 }  // namespace api
 }  // namespace nolzss

@@ -188,8 +188,9 @@ void copy_out(Context &ctx, uint32_t *host, const uint32_t *dev, size_t count) {
 // The plain-mode pipeline on a device-resident text.  Returns z; *out_host (optional) receives
 // a malloc'ed array of z factors.
 size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, nolzss_factor **out_host,
-                 DebugOut *dbg, bool records_on_device_only, const ChainLengthsOut *lengths) {
+                 DebugOut *dbg, bool records_on_device_only, const ChainLengthsOut *lengths, void **d_records_out) {
     if (out_host) *out_host = nullptr;
+    if (d_records_out) *d_records_out = nullptr;
     if (n == 0 || start_pos >= n) return 0;
     Arena &arena = ctx.arena;
     const size_t mark = arena.mark();
@@ -214,7 +215,7 @@ size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos
     }
     void *d_recs = nullptr;
     const uint32_t z = resolve_chain(ctx, (uint32_t)n, (uint32_t)start_pos, lstar, sa, isa, lcp, Psa, Plcp,
-                                     (out_host || records_on_device_only) ? &d_recs : nullptr, 0, nullptr, nullptr,
+                                     (out_host || records_on_device_only || d_records_out) ? &d_recs : nullptr, 0, nullptr, nullptr,
                                      nullptr, lengths);
     if (out_host && z) {
         nolzss_factor *h = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * (size_t)z));
@@ -239,7 +240,8 @@ size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos
         }
     }
     ctx.prof.collect();
-    if (!lengths) arena.rewind(mark);
+    if (d_records_out) *d_records_out = d_recs;
+    if (!lengths && !d_records_out) arena.rewind(mark);
     return z;
 }
 

@@ -223,13 +223,7 @@ void text_lengths(const uint8_t *text, size_t n, bool with_rc, bool shuffle, uin
 
 // the concatenated multiple-DNA form of nolzss_factorize_fasta_multiple_dna: same reader, sanitizing and limits.
 // S = the prepared string; recs = its forward records [begin, end); N = length of the forward half (rc) or m.
-struct FastaText {
-    HostBytes S;
-    std::vector<std::pair<uint32_t, uint32_t>> recs;
-    uint32_t N = 0;
-    bool empty = true;
-};
-
+// (FastaText: api_internal.hpp)
 void read_fasta_text(const char *path, bool with_rc, bool strict, FastaText &ft) {
     FastaParse parse = parse_fasta(path, strict);
     std::vector<const char *> ptrs;

@@ -8,7 +8,7 @@ threshold L* = the smallest observed L with N_real * S0^U(L) <= tau_expected_fp.
 The four names of the reference keep their signatures, dictionary keys, values, warnings and error messages.  The work
 inside runs on counts: the tail counts come from one cumulative sum over np.unique(..., return_counts=True) instead of
 one pass over all lengths per unique length, so O(N + U log U) instead of O(U N); the integer counts are the same,
-and so is every float derived from them.  Plots are not part of this package.
+and so is every float derived from them.  Drawing is not part of this package (data layer of the plots: plots.py).
 
 Extensions (GPU): shuffled_control_significance / fasta_shuffled_control_significance take the factor lengths of the
 text and of its keyed shuffle straight from the device (histograms and lengths, no factor records).
