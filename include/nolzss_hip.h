@@ -380,6 +380,75 @@ int nolzss_factor_maps_records(const nolzss_factor *factors, size_t z, const uin
 /* Host only: the position ladder above (malloc'ed, *n = nb + 1 entries; nolzss_free). */
 int nolzss_debug_position_edges(uint64_t genome_end, uint32_t min_bins, uint64_t bin_bp, double **edges, size_t *n);
 
+/* ---- self dot-plot rasters from resident factors ------------------------------------------------ */
+/* reference: the LZ factor plots of noLZSS.genomics.plots -- plot_multiple_seq_self_lz_factor_plot_from_file
+ * (src/noLZSS/genomics/plots.py:352-900), its _simple twin (:905) and the reference/target plots (:1126, :1358).
+ * Every factor is a segment from (start, ref) to (start + length, ref + length), a reverse-complement factor from
+ * (start, ref + length) down to (start + length, ref); Datashader draws them with ds.max('length'), one layer per
+ * strand (:559-595), a length-range slider filters them (:669-675), a hover overlay keeps the longest factor per x bin
+ * (:600-666), and all of it is recomputed at every zoom or pan.  Here a handle keeps the records of one factorisation
+ * in device memory (its own allocation: every other call may run between two renders) and a render turns one viewport
+ * into exact integer rasters ("Self dot-plot rasters").
+ *
+ * Kept factors: length >= min_factor_length or a sentinel factor (:451-458), and len_lo <= length <= len_hi (len_hi =
+ *   0: no upper bound; applied to sentinel factors too).
+ * View: x in [x_lo, x_hi), y in [y_lo, y_hi) over nucleotide coordinates, width x height pixels; 1 <= width, height
+ *   <= 4096; x_hi, y_hi <= 2^33; x_hi - x_lo >= width and y_hi - y_lo >= height (a pixel is at least one base wide).
+ * Base pairs: factor (start, length, ref) matches base pair t, 0 <= t < length, at x = start + t, y = ref + t
+ *   (forward) or y = ref + length - 1 - t (reverse complement).  It is in view when x and y are inside the windows;
+ *   its pixel is px = floor((x - x_lo) * width / (x_hi - x_lo)), py = floor((y - y_lo) * height / (y_hi - y_lo)).
+ * Rasters: uint32, [py * width + px], row 0 the lowest y.  max_*: the largest length (of the whole factor) among the
+ *   kept factors of that strand with a base pair in the pixel, 0 = none.  count_* (want_counts): how many such
+ *   factors, each counted once per pixel.  visible_*: kept factors with at least one base pair in view.
+ * Hover table (hover_bins = B, 1 <= B <= 4096; 0: none): a visible kept factor of either strand with
+ *   2 * x_lo <= 2 * start + length < 2 * x_hi falls in column floor((2 * start + length - 2 * x_lo) * B /
+ *   (2 * (x_hi - x_lo))) -- the reference's midpoint binning in integers; per column the factor of the greatest
+ *   length, ties to the smallest factor index: hover_start / hover_length / hover_ref[B] (ref carrying
+ *   NOLZSS_RC_MASK), hover_length = 0 for an empty column.  Deviation: "visible" is "a base pair in view", where the
+ *   reference tests the bounding box against the view padded by 10 % (:608-617); k_per_bin is 1, its default.
+ * A source with more than 2^32 - 1 factors or a length of 2^32 or more is refused when the handle is opened. */
+typedef struct nolzss_dotplot nolzss_dotplot;
+typedef struct nolzss_dotplot_summary {
+    uint64_t z;                       /* factors held */
+    uint64_t x_max, y_max;            /* max(start + length), max(ref + length) */
+    uint64_t min_length, max_length;  /* 0, 0 without factors */
+    uint64_t kept_forward, kept_rc;   /* factors per strand at min_factor_length = 1 */
+    int32_t device;
+    const uint64_t *sentinel_starts;  /* starts of the sentinel factors, ascending and distinct (the reference,
+                                       * :528-531, keeps the caller's index order); owned by the handle */
+    size_t n_sentinel_starts;
+} nolzss_dotplot_summary;
+typedef struct nolzss_dotplot_view {
+    uint64_t x_lo, x_hi, y_lo, y_hi;
+    uint32_t width, height;
+    uint64_t min_factor_length;       /* 0 or 1: keep all */
+    uint64_t len_lo, len_hi;          /* len_hi = 0: no upper bound */
+    int32_t want_counts;
+    uint32_t hover_bins;              /* 0: no hover table */
+} nolzss_dotplot_view;
+typedef struct nolzss_dotplot_raster {
+    uint32_t width, height, hover_bins;
+    uint32_t *max_forward, *max_rc;       /* height * width each */
+    uint32_t *count_forward, *count_rc;   /* NULL unless want_counts */
+    uint64_t visible_forward, visible_rc;
+    uint64_t *hover_start, *hover_length, *hover_ref; /* hover_bins each (NULL without a table) */
+} nolzss_dotplot_raster;
+/* The factors of nolzss_factorize (with_rc = 0) or nolzss_factorize_dna_w_rc, with the refusals of
+ * nolzss_factor_maps_text; an empty text gives a valid handle with z = 0.  Close every handle. */
+int nolzss_dotplot_open_text(const uint8_t *text, size_t n, int with_rc, int device, nolzss_dotplot **h);
+/* The reader of nolzss_factor_maps_fasta; sentinel factors = the factors that start at a sentinel. */
+int nolzss_dotplot_open_fasta(const char *path, int with_rc, int sanitize_mode, int device, nolzss_dotplot **h);
+/* Host records (ref carrying NOLZSS_RC_MASK), uploaded once; sentinel factors by factor index. */
+int nolzss_dotplot_open_records(const nolzss_factor *factors, size_t z, const uint64_t *sentinel_factor_indices,
+                                size_t n_sentinels, int device, nolzss_dotplot **h);
+int nolzss_dotplot_info(const nolzss_dotplot *h, nolzss_dotplot_summary *info);
+/* Any number of renders per handle; the handle is not changed.  Free the result with the function below. */
+int nolzss_dotplot_render(const nolzss_dotplot *h, const nolzss_dotplot_view *view, nolzss_dotplot_raster *out);
+void nolzss_free_dotplot_raster(nolzss_dotplot_raster *out);
+/* NULL is a no-op.  Renders of one handle may run from several threads, but the close must not overlap any other call
+ * on that handle: it frees the records at once.  The calling thread's current device is left as it was. */
+int nolzss_dotplot_close(nolzss_dotplot *h);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

@@ -62,6 +62,31 @@ class FactorMaps(C.Structure):
                 ("min_length", C.c_uint64), ("max_length", C.c_uint64), ("max_start", C.c_uint64)]
 
 
+class DotPlotSummary(C.Structure):
+    """Mirror of nolzss_dotplot_summary (include/nolzss_hip.h)."""
+    _fields_ = [("z", C.c_uint64), ("x_max", C.c_uint64), ("y_max", C.c_uint64), ("min_length", C.c_uint64),
+                ("max_length", C.c_uint64), ("kept_forward", C.c_uint64), ("kept_rc", C.c_uint64),
+                ("device", C.c_int32), ("sentinel_starts", C.POINTER(C.c_uint64)), ("n_sentinel_starts", C.c_size_t)]
+
+
+class DotPlotView(C.Structure):
+    """Mirror of nolzss_dotplot_view (include/nolzss_hip.h)."""
+    _fields_ = [("x_lo", C.c_uint64), ("x_hi", C.c_uint64), ("y_lo", C.c_uint64), ("y_hi", C.c_uint64),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("min_factor_length", C.c_uint64),
+                ("len_lo", C.c_uint64), ("len_hi", C.c_uint64), ("want_counts", C.c_int32),
+                ("hover_bins", C.c_uint32)]
+
+
+class DotPlotRaster(C.Structure):
+    """Mirror of nolzss_dotplot_raster (include/nolzss_hip.h)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("hover_bins", C.c_uint32),
+                ("max_forward", C.POINTER(C.c_uint32)), ("max_rc", C.POINTER(C.c_uint32)),
+                ("count_forward", C.POINTER(C.c_uint32)), ("count_rc", C.POINTER(C.c_uint32)),
+                ("visible_forward", C.c_uint64), ("visible_rc", C.c_uint64),
+                ("hover_start", C.POINTER(C.c_uint64)), ("hover_length", C.POINTER(C.c_uint64)),
+                ("hover_ref", C.POINTER(C.c_uint64))]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -177,6 +202,14 @@ def _load():
     lib.nolzss_factor_maps_text.argtypes = [vp, sz, C.c_int, C.c_int, rqp, fmp]
     lib.nolzss_factor_maps_fasta.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, rqp, fmp]
     lib.nolzss_factor_maps_records.argtypes = [vp, sz, vp, sz, C.c_int, rqp, fmp]
+    lib.nolzss_dotplot_open_text.argtypes = [vp, sz, C.c_int, C.c_int, vpp]
+    lib.nolzss_dotplot_open_fasta.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, vpp]
+    lib.nolzss_dotplot_open_records.argtypes = [vp, sz, vp, sz, C.c_int, vpp]
+    lib.nolzss_dotplot_info.argtypes = [vp, C.POINTER(DotPlotSummary)]
+    lib.nolzss_dotplot_render.argtypes = [vp, C.POINTER(DotPlotView), C.POINTER(DotPlotRaster)]
+    lib.nolzss_free_dotplot_raster.argtypes = [C.POINTER(DotPlotRaster)]
+    lib.nolzss_free_dotplot_raster.restype = None
+    lib.nolzss_dotplot_close.argtypes = [vp]
     lib.nolzss_debug_position_edges.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, vpp, szp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
@@ -219,6 +252,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_fasta_shuffled_text", "nolzss_factor_lengths", "nolzss_shuffle_dna",
     "nolzss_free_factor_maps", "nolzss_factor_maps_text", "nolzss_factor_maps_fasta", "nolzss_factor_maps_records",
     "nolzss_debug_position_edges",
+    "nolzss_dotplot_open_text", "nolzss_dotplot_open_fasta", "nolzss_dotplot_open_records", "nolzss_dotplot_info",
+    "nolzss_dotplot_render", "nolzss_free_dotplot_raster", "nolzss_dotplot_close",
 ]
 
 

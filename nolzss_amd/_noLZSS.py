@@ -412,20 +412,122 @@ def records_factor_maps(factors, sentinel_factor_indices=(), grid=None, total_le
     array.  C ABI nolzss_factor_maps_records."""
     rq, keep_rq = _map_request(grid, total_length, min_factor_length, length_edges, position_edges, position_min_bins,
                                position_bin_bp)
-    f = np.asarray(factors)
-    if f.dtype != FACTOR_DTYPE:
-        f = np.ascontiguousarray(f, dtype=np.uint64)
-        if f.size and (f.ndim != 2 or f.shape[1] != 3):
-            raise ValueError("factors must be a FACTOR_DTYPE array or an (n, 3) uint64 array")
-        z = f.shape[0] if f.size else 0
-    else:
-        f = np.ascontiguousarray(f)
-        z = f.size
+    f, z = _records_array(factors)
     sent = np.ascontiguousarray(sorted(operator.index(i) for i in sentinel_factor_indices), dtype=np.uint64)
     res = _lib.FactorMaps()
     check(lib.nolzss_factor_maps_records(f.ctypes.data if z else None, z, sent.ctypes.data if sent.size else None,
                                          sent.size, _default_device, C.byref(rq), C.byref(res)))
     return _unpack_factor_maps(res)
+
+
+def _records_array(factors):
+    """-> (contiguous array, z): a FACTOR_DTYPE array (ref carrying RC_MASK) or an (n, 3) uint64 array"""
+    f = np.asarray(factors)
+    if f.dtype != FACTOR_DTYPE:
+        f = np.ascontiguousarray(f, dtype=np.uint64)
+        if f.size and (f.ndim != 2 or f.shape[1] != 3):
+            raise ValueError("factors must be a FACTOR_DTYPE array or an (n, 3) uint64 array")
+        return f, (f.shape[0] if f.size else 0)
+    f = np.ascontiguousarray(f)
+    return f, f.size
+
+
+# ---- self dot-plot rasters from resident factors (genomics/plots.py) --------------------------------------------
+class DotPlot:
+    """Extension: the records of one factorisation kept in device memory (C ABI nolzss_dotplot_*), rendered into
+    per-strand max-length rasters, count rasters and a hover table, any number of times.  A context manager;
+    close() may be called more than once."""
+
+    def __init__(self, handle):
+        self._h = handle
+        info = _lib.DotPlotSummary()
+        try:
+            check(lib.nolzss_dotplot_info(self._h, C.byref(info)))
+        except Exception:
+            self.close()
+            raise
+        self.info = {k: int(getattr(info, k)) for k in ("z", "x_max", "y_max", "min_length", "max_length",
+                                                        "kept_forward", "kept_rc", "device")}
+        n = info.n_sentinel_starts
+        self.info["sentinel_starts"] = (np.ctypeslib.as_array(info.sentinel_starts, shape=(n,)).copy() if n
+                                        else np.zeros(0, dtype=np.uint64))
+
+    @classmethod
+    def _open(cls, call):
+        h = C.c_void_p()
+        check(call(C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_text(cls, data, with_rc: bool = False):
+        """The factors of factorize (or factorize_dna_w_rc with with_rc).  C ABI nolzss_dotplot_open_text."""
+        p, n, keep = _as_buffer(data)
+        return cls._open(lambda h: lib.nolzss_dotplot_open_text(p, n, 1 if with_rc else 0, _default_device, h))
+
+    @classmethod
+    def from_fasta(cls, fasta_path, with_rc: bool = True, sanitize_mode: str = "remove_ambiguous"):
+        """The factors of factorize_fasta_multiple_dna_{w,no}_rc.  C ABI nolzss_dotplot_open_fasta."""
+        path, mode = _str_arg(fasta_path, "fasta_path"), _sanitize_mode(sanitize_mode)
+        return cls._open(lambda h: lib.nolzss_dotplot_open_fasta(path, 1 if with_rc else 0, mode, _default_device, h))
+
+    @classmethod
+    def from_records(cls, factors, sentinel_factor_indices=()):
+        """Host records, uploaded once.  C ABI nolzss_dotplot_open_records."""
+        f, z = _records_array(factors)
+        sent = np.ascontiguousarray(sorted(operator.index(i) for i in sentinel_factor_indices), dtype=np.uint64)
+        return cls._open(lambda h: lib.nolzss_dotplot_open_records(
+            f.ctypes.data if z else None, z, sent.ctypes.data if sent.size else None, sent.size, _default_device, h))
+
+    def render(self, x_range, y_range, width: int = 800, height: int = 800, min_factor_length: int = 1,
+               length_range=None, hover_bins: int = 0, counts: bool = False):
+        """One view -> dict: max_forward, max_rc (and count_forward, count_rc with counts) as uint32 arrays of shape
+        (height, width), row 0 the lowest y; visible_forward, visible_rc; with hover_bins, hover_start, hover_length,
+        hover_ref (uint64, shape (hover_bins,), ref carrying RC_MASK).  length_range = (lo, hi), hi = 0 or None: no
+        upper bound."""
+        if self._h is None:
+            raise ValueError("the dot plot is closed")
+        v = _lib.DotPlotView()
+        bounds = [operator.index(b) for b in (*x_range, *y_range)]
+        lo, hi = (0, 0) if length_range is None else length_range
+        scalars = [operator.index(width), operator.index(height), operator.index(min_factor_length),
+                   operator.index(lo), 0 if hi is None else operator.index(hi), operator.index(hover_bins)]
+        if len(bounds) != 4 or min(bounds) < 0 or min(scalars) < 0:
+            raise ValueError("x_range and y_range are pairs; no bound, size or length may be negative")
+        if max(bounds) >= 1 << 64 or max(scalars[:2] + scalars[5:]) >= 1 << 32 or max(scalars[2:5]) >= 1 << 64:
+            raise ValueError("x_range, y_range, width, height, hover_bins or a length is out of range")
+        v.x_lo, v.x_hi, v.y_lo, v.y_hi = bounds
+        v.width, v.height, v.min_factor_length, v.len_lo, v.len_hi, v.hover_bins = scalars
+        v.want_counts = 1 if counts else 0
+        res = _lib.DotPlotRaster()
+        check(lib.nolzss_dotplot_render(self._h, C.byref(v), C.byref(res)))
+        try:
+            out = {"visible_forward": int(res.visible_forward), "visible_rc": int(res.visible_rc)}
+            for k in ("max_forward", "max_rc", "count_forward", "count_rc"):
+                p = getattr(res, k)
+                out[k] = np.ctypeslib.as_array(p, shape=(res.height, res.width)).copy() if p else None
+            for k in ("hover_start", "hover_length", "hover_ref"):
+                p = getattr(res, k)
+                out[k] = np.ctypeslib.as_array(p, shape=(res.hover_bins,)).copy() if p else None
+        finally:
+            lib.nolzss_free_dotplot_raster(C.byref(res))
+        return out
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            check(lib.nolzss_dotplot_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def debug_position_edges(genome_end: int, min_bins: int = 50, bin_bp: int = 1_000_000) -> np.ndarray:

@@ -13,14 +13,14 @@
 // every part to its cell.  The segment is first clipped to [0, x_max) x [0, y_max) -- the clip points are integers --
 // so every part is inside the grid and the walk has at most x_bins + y_bins + 1 parts.  Widths: x_max, y_max <= 2^33
 // and unit <= 2^24 keep every product below 2^57.
-#include "api_internal.hpp"
+#include "factor_records.hpp"
 
 #include <cmath>
 
 namespace nolzss {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kRecThreads;
 constexpr uint32_t kMaxBins = 4096;                    // per axis of the strand grid: unit <= 2^24
 constexpr uint64_t kMaxExtent = 1ull << 33;            // x_max, y_max
 constexpr size_t kMaxLengthEdges = 4097;               // staged in LDS (32 KB)
@@ -30,82 +30,6 @@ constexpr size_t kMaxHistCells = size_t(1) << 26;
 // LDS a workgroup of these kernels may take: what HIP grants without opting in, and two workgroups per CU of the
 // 160 KB.  The default 50 x 50 grid takes 40 KB of it.
 constexpr size_t kLdsBudget = 64 * 1024;
-constexpr uint64_t kRcMask = 1ull << 63;
-
-struct Rec {
-    uint64_t start, length, ref;
-};
-
-// min_length starts at ~0; the rest at 0
-struct MapStats {
-    unsigned long long x_max, y_max, min_length, max_length, max_start, kept_fwd, kept_rc;
-};
-
-// length >= min_len, or a sentinel factor: key = the factor's index (records source) or its start (sentinel
-// positions of the prepared string), looked up in the ascending list
-struct KeepRule {
-    uint64_t min_len;
-    const uint64_t *sentinels;
-    uint32_t n_sentinels;
-    uint32_t by_index;
-    uint64_t base_index;  // index of the first record of this chunk
-};
-
-__device__ __forceinline__ bool is_kept(const KeepRule &k, uint64_t i, uint64_t start, uint64_t length) {
-    if (length >= k.min_len) return true;
-    const uint64_t key = k.by_index ? k.base_index + i : start;
-    uint32_t lo = 0, hi = k.n_sentinels;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (k.sentinels[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < k.n_sentinels && k.sentinels[lo] == key;
-}
-
-__device__ __forceinline__ uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
-
-// extents, length range, largest start and the kept counts per strand
-__global__ __launch_bounds__(kThreads) void map_stats_kernel(const Rec *__restrict__ recs, uint64_t z, KeepRule keep,
-                                                             MapStats *__restrict__ out) {
-    __shared__ MapStats sh;
-    if (threadIdx.x == 0) sh = MapStats{0, 0, ~0ull, 0, 0, 0, 0};
-    __syncthreads();
-    MapStats m{0, 0, ~0ull, 0, 0, 0, 0};
-    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
-    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < z; i += stride) {
-        const Rec f = recs[i];
-        if (!is_kept(keep, i, f.start, f.length)) continue;
-        const uint64_t r = f.ref & ~kRcMask;
-        const uint64_t xe = sat_add(f.start, f.length), ye = sat_add(r, f.length);
-        m.x_max = xe > m.x_max ? xe : m.x_max;
-        m.y_max = ye > m.y_max ? ye : m.y_max;
-        m.min_length = f.length < m.min_length ? f.length : m.min_length;
-        m.max_length = f.length > m.max_length ? f.length : m.max_length;
-        m.max_start = f.start > m.max_start ? f.start : m.max_start;
-        if (f.ref & kRcMask) ++m.kept_rc;
-        else ++m.kept_fwd;
-    }
-    if (m.kept_fwd | m.kept_rc) {
-        atomicMax(&sh.x_max, m.x_max);
-        atomicMax(&sh.y_max, m.y_max);
-        atomicMin(&sh.min_length, m.min_length);
-        atomicMax(&sh.max_length, m.max_length);
-        atomicMax(&sh.max_start, m.max_start);
-        if (m.kept_fwd) atomicAdd(&sh.kept_fwd, m.kept_fwd);
-        if (m.kept_rc) atomicAdd(&sh.kept_rc, m.kept_rc);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && (sh.kept_fwd | sh.kept_rc)) {
-        atomicMax(&out->x_max, sh.x_max);
-        atomicMax(&out->y_max, sh.y_max);
-        atomicMin(&out->min_length, sh.min_length);
-        atomicMax(&out->max_length, sh.max_length);
-        atomicMax(&out->max_start, sh.max_start);
-        if (sh.kept_fwd) atomicAdd(&out->kept_fwd, sh.kept_fwd);
-        if (sh.kept_rc) atomicAdd(&out->kept_rc, sh.kept_rc);
-    }
-}
 
 struct GridParams {
     uint64_t x_max, y_max;
@@ -250,11 +174,7 @@ __global__ __launch_bounds__(kThreads) void length_position_hist_kernel(const Re
     }
 }
 
-unsigned grid_of(uint64_t items) {
-    uint64_t g = div_up(items, (uint64_t)kThreads);
-    if (g < 1) g = 1;
-    return (unsigned)(g > 1024 ? 1024 : g);
-}
+unsigned grid_of(uint64_t items) { return record_grid(items); }
 
 bool force_global() {  // the form without workgroup-private LDS accumulators, for A/B runs and tests
     const char *e = getenv("NOLZSS_FACTOR_MAPS_GLOBAL");
@@ -468,38 +388,58 @@ void bin_device_records(Context &ctx, const nolzss_factor_map_request &rq, const
 
 // plain mode over the bytes, rc mode over T s0 rc(T) s1 prepared on the device: text_lengths of significance.hip
 // with the records kept (the refusals of nolzss_count_factors / nolzss_count_factors_dna_w_rc)
-void text_maps(const uint8_t *text, size_t n, bool with_rc, int device, const nolzss_factor_map_request &rq,
-               MapsResult &r) {
-    shape_result(rq, r);
+bool check_text_source(const uint8_t *text, size_t n, bool with_rc) {
     if (n && !text) throw std::invalid_argument("text pointer is null");
     if (with_rc) {
-        if (n == 0) return;  // as dna_w_rc_common
+        if (n == 0) return false;  // as dna_w_rc_common
         const size_t m = 2 * n + 2;
         if (m > kMaxText) throw std::invalid_argument("text too long: the device pipeline uses 32-bit indices");
-        if (!rc_guards(m, 0)) return;
-    } else {
-        check_text_args(text, n, 0);
-        if (n == 0) return;
+        return rc_guards(m, 0);
     }
-    Session ses(device, nullptr);
-    Context &ctx = ses.ctx();
+    check_text_args(text, n, 0);
+    return n != 0;
+}
+
+size_t text_records(Context &ctx, const uint8_t *text, size_t n, bool with_rc, size_t extra, void **d_recs) {
     const size_t m = with_rc ? 2 * n + 2 : n;
-    reserve_arena_for(ctx, m, m + n + maps_extra(rq));
+    reserve_arena_for(ctx, m, m + n + extra);
     uint8_t *d_T = ctx.arena.alloc<uint8_t>(n);
     {
         ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream);
         upload_bytes(ctx, d_T, text, n);
     }
-    void *d_recs = nullptr;
-    if (with_rc) {
-        uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
-        const uint32_t bad = prepare_single_rc_on_device(ctx, d_T, (uint32_t)n, d_S);
-        if (bad != 0xffffffffu)
-            throw std::runtime_error("Invalid nucleotide '" + std::string(1, (char)text[bad]) + "' found in sequence 0");
-        r.z = run_rc_pipeline(ctx, d_S, m, 0, &d_recs);
-    } else {
-        r.z = run_plain(ctx, d_T, n, 0, nullptr, nullptr, false, nullptr, &d_recs);
+    if (!with_rc) return run_plain(ctx, d_T, n, 0, nullptr, nullptr, false, nullptr, d_recs);
+    uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
+    const uint32_t bad = prepare_single_rc_on_device(ctx, d_T, (uint32_t)n, d_S);
+    if (bad != 0xffffffffu)
+        throw std::runtime_error("Invalid nucleotide '" + std::string(1, (char)text[bad]) + "' found in sequence 0");
+    return run_rc_pipeline(ctx, d_S, m, 0, d_recs);
+}
+
+size_t fasta_records(Context &ctx, const FastaText &ft, bool with_rc, size_t extra, void **d_recs,
+                     std::vector<uint64_t> &sentinels) {
+    const size_t m = ft.S.size();
+    sentinels.clear();  // ascending: the byte behind every forward record but the end of the string
+    for (const auto &rec : ft.recs)
+        if (rec.second < m) sentinels.push_back(rec.second);
+    reserve_arena_for(ctx, m, m + extra);
+    uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
+    {
+        ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream);
+        upload_bytes(ctx, d_S, ft.S.data(), m);
     }
+    return with_rc ? run_rc_pipeline(ctx, d_S, m, 0, d_recs)
+                   : run_plain(ctx, d_S, m, 0, nullptr, nullptr, false, nullptr, d_recs);
+}
+
+void text_maps(const uint8_t *text, size_t n, bool with_rc, int device, const nolzss_factor_map_request &rq,
+               MapsResult &r) {
+    shape_result(rq, r);
+    if (!check_text_source(text, n, with_rc)) return;
+    Session ses(device, nullptr);
+    Context &ctx = ses.ctx();
+    void *d_recs = nullptr;
+    r.z = text_records(ctx, text, n, with_rc, maps_extra(rq), &d_recs);
     bin_device_records(ctx, rq, {}, d_recs, r);
 }
 
@@ -509,21 +449,11 @@ void fasta_maps(const char *path, bool with_rc, bool strict, int device, const n
     FastaText ft;
     read_fasta_text(path, with_rc, strict, ft);
     if (ft.empty) return;
-    const size_t m = ft.S.size();
-    std::vector<uint64_t> sentinels;  // ascending: the byte behind every forward record but the end of the string
-    for (const auto &rec : ft.recs)
-        if (rec.second < m) sentinels.push_back(rec.second);
+    std::vector<uint64_t> sentinels;
     Session ses(device, nullptr);
     Context &ctx = ses.ctx();
-    reserve_arena_for(ctx, m, m + maps_extra(rq));
-    uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
-    {
-        ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream);
-        upload_bytes(ctx, d_S, ft.S.data(), m);
-    }
     void *d_recs = nullptr;
-    r.z = with_rc ? run_rc_pipeline(ctx, d_S, m, 0, &d_recs)
-                  : run_plain(ctx, d_S, m, 0, nullptr, nullptr, false, nullptr, &d_recs);
+    r.z = fasta_records(ctx, ft, with_rc, maps_extra(rq), &d_recs, sentinels);
     bin_device_records(ctx, rq, sentinels, d_recs, r);
 }
 

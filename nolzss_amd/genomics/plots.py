@@ -6,6 +6,10 @@ Both are binned on the device from the factor records the pipeline leaves there 
 record crosses PCIe and no tuple is built.  The strand grid comes back as exact integers -- nucleotides in units of
 1 / (x_bins * y_bins) -- and the reference's float grids, edges and log2 bias follow from them on the host.
 
+The self dot plot of plot_multiple_seq_self_lz_factor_plot_from_file (:352-900) is served the same way: self_dotplot
+keeps the records of one factorisation on the device and renders any number of views into exact integer rasters (C
+ABI nolzss_dotplot_*).
+
 Drawing is not part of this package (no matplotlib), nor are the CCDF weighting and `sequence_index` of
 plot_space_scale_heatmap or the other plots of the reference's module.
 """
@@ -20,7 +24,7 @@ from .. import _noLZSS as _native
 from ..utils import NoLZSSError, _read_footer, read_binary_file_metadata
 
 __all__ = ["PlotError", "bias_from_grids", "strand_bias_grid", "fasta_strand_bias_grid", "factors_strand_bias_grid",
-           "space_scale_histogram"]
+           "space_scale_histogram", "DotPlot", "self_dotplot"]
 
 RC_MASK = 1 << 63
 _INVALID = "Invalid factor coordinates for strand bias grid"
@@ -237,3 +241,86 @@ def space_scale_histogram(data=None, *, fasta_filepath=None, factors=None, with_
     return {"genome_bins": m["position_edges"], "length_bin_edges": edges, "forward_hist": fwd, "reverse_hist": rev,
             "kept_forward": m["kept_forward"], "kept_rc": m["kept_rc"], "min_length": m["min_length"],
             "max_length": max_length, "max_start": m["max_start"], "z": m["z"], "z_used": m["z_used"]}
+
+
+def sequence_boundaries_from(sentinel_starts, sequence_names, max_pos: Optional[int]):
+    """[(start_pos, end_pos, sequence_name)] as plots.py:522-553 computes them: one sequence between two sentinel
+    factors (the sentinel itself is skipped), names from `sequence_names` or seq_<i>; the last one ends at max_pos, the
+    largest x or y of any factor.  max_pos = None: no factors (the reference's 1000 / the last sentinel + 1)."""
+    names = list(sequence_names) if sequence_names else []
+    positions = [int(p) for p in sentinel_starts]
+    if not positions:
+        return [(0, 1000 if max_pos is None else max_pos, names[0] if names else "sequence")]
+    out, prev_pos = [], 0
+    for i, pos in enumerate(positions):
+        out.append((prev_pos, pos, names[i] if i < len(names) else f"seq_{i}"))
+        prev_pos = pos + 1
+    last_name = names[len(positions)] if len(names) > len(positions) else f"seq_{len(positions)}"
+    out.append((prev_pos, prev_pos if max_pos is None else max_pos, last_name))
+    return out
+
+
+def default_view(x_max: int, y_max: int, width: int, height: int, x_range=None, y_range=None):
+    """-> ((x_lo, x_hi), (y_lo, y_hi)).  A range that is not given is [0, max(x_max, y_max)), the reference's diagonal
+    extent, raised so that it spans at least one base per pixel; a given range is passed on as it is."""
+    extent = max(int(x_max), int(y_max))
+    if x_range is None:
+        x_range = (0, max(extent, int(width)))
+    if y_range is None:
+        y_range = (0, max(extent, int(height)))
+    (x_lo, x_hi), (y_lo, y_hi) = x_range, y_range
+    return (int(x_lo), int(x_hi)), (int(y_lo), int(y_hi))
+
+
+class DotPlot(_native.DotPlot):
+    """What self_dotplot returns: .info (z, x_max, y_max, min_length, max_length, kept_forward, kept_rc, device,
+    sentinel_starts), .sequence_boundaries and .render(); a context manager that frees the device records."""
+
+    _names = None
+    _fasta = None
+
+    @property
+    def sequence_boundaries(self):
+        names = self._names
+        if names is None and self._fasta is not None:
+            path, mode = self._fasta
+            names = self._names = [i.decode("utf-8", "replace") for i, _ in _native.debug_parse_fasta(path, mode)]
+        max_pos = max(self.info["x_max"], self.info["y_max"]) if self.info["z"] else None
+        return sequence_boundaries_from(self.info["sentinel_starts"], names, max_pos)
+
+    def render(self, x_range=None, y_range=None, width: int = 800, height: int = 800, min_factor_length: int = 1,
+               length_range=None, hover_bins: int = 0, counts: bool = False) -> Dict[str, Any]:
+        """The view x_range x y_range (half-open nucleotide windows; default: the square [0, max(x_max, y_max)))
+        as width x height pixels: max_forward, max_rc, count_forward, count_rc (uint32, shape (height, width), row 0
+        the lowest y), visible_forward, visible_rc, hover_start, hover_length, hover_ref, and the x_range / y_range
+        used.  length_range: the reference's slider, inclusive."""
+        x_range, y_range = default_view(self.info["x_max"], self.info["y_max"], width, height, x_range, y_range)
+        out = super().render(x_range, y_range, width=width, height=height, min_factor_length=min_factor_length,
+                             length_range=length_range, hover_bins=hover_bins, counts=counts)
+        out["x_range"], out["y_range"] = x_range, y_range
+        return out
+
+
+def self_dotplot(data=None, *, fasta_filepath=None, factors=None, with_rc: bool = True,
+                 sanitize_mode: str = "remove_ambiguous", sentinel_factor_indices=(), sequence_names=None) -> DotPlot:
+    """The data of the reference's self LZ factor plots (plots.py:352-900) without the download of the records:
+    factorise once -- exactly one of `data` (a sequence), `fasta_filepath` or `factors` (a v2 factor file path, tuples
+    or a record array) --, then render views.  The hover table keeps a factor with a base pair in view, where the
+    reference tests its bounding box against the view padded by 10 %."""
+    if sum(x is not None for x in (data, fasta_filepath, factors)) != 1:
+        raise ValueError("Exactly one of data, fasta_filepath or factors must be provided")
+    if data is not None:
+        dp = DotPlot.from_text(data, with_rc=with_rc)
+    elif fasta_filepath is not None:
+        if not Path(fasta_filepath).exists():
+            raise FileNotFoundError(f"Input file not found: {fasta_filepath}")
+        dp = DotPlot.from_fasta(os.fspath(fasta_filepath), with_rc=with_rc, sanitize_mode=sanitize_mode)
+        dp._fasta = (os.fspath(fasta_filepath), sanitize_mode)
+    else:
+        if isinstance(factors, (str, os.PathLike)) and sequence_names is None:
+            sequence_names = read_binary_file_metadata(Path(factors)).get("sequence_names")
+        recs, _, sent = _records_arg(factors, None, sentinel_factor_indices)
+        dp = DotPlot.from_records(recs, sent)
+    if sequence_names is not None:
+        dp._names = list(sequence_names)
+    return dp
