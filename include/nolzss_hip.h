@@ -461,6 +461,20 @@ int nolzss_profile_report(int device, char *buf, size_t cap);
 /* Any output pointer may be NULL.  sa/isa/lstar: n entries; lcp: n + 1 entries. */
 int nolzss_debug_arrays(const uint8_t *text, size_t n, int device, uint32_t *sa, uint32_t *isa,
                         uint32_t *lcp, uint32_t *lstar);
+/* The factor record (start, length, ref) of EVERY position of the text in plain mode -- what nolzss_factorize would
+ * emit for a factor starting there (a literal has ref = start): n records in out. */
+int nolzss_debug_position_factors(const uint8_t *text, size_t n, int device, nolzss_factor *out);
+/* The reverse-complement pipeline over a prepared string S (nolzss_prepare_multiple_dna_w_rc; same guards as
+ * nolzss_factorize_multiple_dna_w_rc), N = S_len / 2 - 1.  Any output pointer may be NULL.  sa: S_len entries; lcp:
+ * S_len + 1; isa, code, plain, records: N.  code = factor length of the position in bits 0..30, bit 31 set for a
+ * reverse-complement factor, 0 for a literal.  want_plain != 0 runs the form that also computes the plain-mode length
+ * of every position (0 = literal) as a by-product, as nolzss_count_factors_batch_both does.  records: the factor a
+ * cursor at each position would emit.  counters (5 entries): ranks finished from global memory, ranks queued for the
+ * exact forward search by the tile kernel, the same after the far ranks, compact tile output used (0 / 1), tile kernel
+ * relaunched after an undecided LCP entry (0 / 1). */
+int nolzss_debug_rc_arrays(const uint8_t *S, size_t S_len, int device, int want_plain, uint32_t *sa, uint32_t *isa,
+                           uint32_t *lcp, uint32_t *code, uint32_t *plain, nolzss_factor *records,
+                           uint32_t *counters);
 /* Sorts n (key, value) pairs in place on the device by all 64 key bits (stable). */
 int nolzss_debug_sort_pairs(uint64_t *keys, uint32_t *vals, size_t n, int device);
 /* mode 0: exclusive add-scan, mode 1: inclusive max-scan, in place. */

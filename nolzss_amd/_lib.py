@@ -215,6 +215,8 @@ def _load():
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
     lib.nolzss_debug_arrays.argtypes = [vp, sz, C.c_int, vp, vp, vp, vp]
+    lib.nolzss_debug_position_factors.argtypes = [vp, sz, C.c_int, vp]
+    lib.nolzss_debug_rc_arrays.argtypes = [vp, sz, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.nolzss_debug_sort_pairs.argtypes = [vp, vp, sz, C.c_int]
     lib.nolzss_debug_scan.argtypes = [vp, sz, C.c_int, C.c_int]
     lib.nolzss_debug_arena.argtypes = [C.c_int, szp, szp]
@@ -254,6 +256,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_position_edges",
     "nolzss_dotplot_open_text", "nolzss_dotplot_open_fasta", "nolzss_dotplot_open_records", "nolzss_dotplot_info",
     "nolzss_dotplot_render", "nolzss_free_dotplot_raster", "nolzss_dotplot_close",
+    "nolzss_debug_position_factors", "nolzss_debug_rc_arrays",
 ]
 
 

@@ -1079,6 +1079,42 @@ def debug_arrays(data):
     return {"sa": sa, "isa": isa, "lcp": lcp, "lstar": lstar}
 
 
+def debug_position_factors(data) -> np.ndarray:
+    """-> the plain-mode factor record (start, length, ref) of EVERY position of the text, as the device's
+    factor kernel gives it for a factor starting there (a literal has ref = start)."""
+    p, n, keep = _as_buffer(data)
+    out = np.zeros(n, dtype=FACTOR_DTYPE)
+    check(lib.nolzss_debug_position_factors(p, n, _default_device, out.ctypes.data))
+    return out
+
+
+RC_COUNTERS = ("far_ranks", "exact_from_tiles", "exact_total", "compact", "pending_relaunch")
+
+
+def debug_rc_arrays(S, want_plain: bool = False) -> dict:
+    """The reverse-complement pipeline over a prepared string S, N = len(S) // 2 - 1 -> dict(sa (len(S) entries),
+    lcp (len(S) + 1), isa, code, records (N each), plain (N, only with want_plain: the plain-mode length of every
+    position as a by-product, 0 = literal), counters (RC_COUNTERS -> int)).  code: factor length in bits 0..30, bit 31
+    = reverse complement, 0 = literal; records: the factor a cursor at each position would emit."""
+    p, m, keep = _as_buffer(S)
+    N = m // 2 - 1 if m >= 4 else 0
+    sa = np.zeros(m if N else 0, dtype=np.uint32)
+    lcp = np.zeros(m + 1 if N else 0, dtype=np.uint32)
+    isa = np.zeros(N, dtype=np.uint32)
+    code = np.zeros(N, dtype=np.uint32)
+    plain = np.zeros(N, dtype=np.uint32) if want_plain else None
+    records = np.zeros(N, dtype=FACTOR_DTYPE)
+    counters = np.zeros(5, dtype=np.uint32)
+    check(lib.nolzss_debug_rc_arrays(p, m, _default_device, 1 if want_plain else 0, sa.ctypes.data, isa.ctypes.data,
+                                     lcp.ctypes.data, code.ctypes.data, plain.ctypes.data if want_plain else None,
+                                     records.ctypes.data, counters.ctypes.data))
+    res = {"sa": sa, "isa": isa, "lcp": lcp, "code": code, "records": records,
+           "counters": dict(zip(RC_COUNTERS, (int(c) for c in counters)))}
+    if want_plain:
+        res["plain"] = plain
+    return res
+
+
 def debug_sort_pairs(keys, vals):
     keys = np.ascontiguousarray(keys, dtype=np.uint64).copy()
     vals = np.ascontiguousarray(vals, dtype=np.uint32).copy()

@@ -87,6 +87,7 @@ void order_behind_default_stream(Context &ctx);
 
 struct DebugOut {
     uint32_t *sa = nullptr, *isa = nullptr, *lcp = nullptr, *lstar = nullptr;
+    void *records = nullptr;  // n x (start, length, ref): the factor record of every position (position_factors)
 };
 
 // the plain-mode pipeline on a device-resident text / on a host buffer (upload first); returns z

@@ -212,6 +212,13 @@ size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos
         copy_out(ctx, dbg->isa, isa, n);  // (1-based on the device; nolzss_debug_arrays subtracts the one)
         copy_out(ctx, dbg->lcp, lcp, n + 1);
         copy_out(ctx, dbg->lstar, lstar, n);
+        if (dbg->records) {
+            const size_t rmark = arena.mark();
+            const void *recs = position_factors(ctx, (uint32_t)n, lstar, sa, isa, lcp, Psa, Plcp);
+            HIP_CHECK(hipMemcpyAsync(dbg->records, recs, n * sizeof(nolzss_factor), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            arena.rewind(rmark);
+        }
     }
     void *d_recs = nullptr;
     const uint32_t z = resolve_chain(ctx, (uint32_t)n, (uint32_t)start_pos, lstar, sa, isa, lcp, Psa, Plcp,

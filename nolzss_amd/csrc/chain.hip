@@ -533,4 +533,32 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
     return z;
 }
 
+// Debug hooks: every position is a factor start (pipeline.hpp).  With fpos = 0, 1, .., n - 1 the distance to the next
+// start is 1 everywhere, so factor_kernel takes length and flag from lstar[i] at every position.
+void *position_factors(Context &ctx, uint32_t n, const uint32_t *lstar, const uint32_t *sa, const uint32_t *isa,
+                       const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp, uint32_t rcN, const Pyramid *Pmax,
+                       const TermTable *rebase) {
+    if (n == 0) return nullptr;
+    hipStream_t s = ctx.stream;
+    uint32_t *fpos = ctx.arena.alloc<uint32_t>(n);
+    FactorRec *recs = ctx.arena.alloc<FactorRec>(n);
+    std::vector<uint32_t> iota(n);
+    for (uint32_t i = 0; i < n; ++i) iota[i] = i;
+    HIP_CHECK(hipMemcpyAsync(fpos, iota.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // iota is a local vector
+    if (rcN) {
+        if (rebase) throw HipError("position_factors: record-relative output exists in plain mode only");
+        factor_kernel<true, false><<<grid_for(n), kThreads, 0, s>>>(fpos, n, lstar, isa, sa, lcp, Psa, Plcp, *Pmax, rcN, recs,
+                                                                    TermTable{}, n);
+    } else if (rebase) {
+        factor_kernel<false, true><<<grid_for(n), kThreads, 0, s>>>(fpos, n, lstar, isa, sa, lcp, Psa, Plcp, Psa, 0u, recs,
+                                                                    *rebase, n);
+    } else {
+        factor_kernel<false, false><<<grid_for(n), kThreads, 0, s>>>(fpos, n, lstar, isa, sa, lcp, Psa, Plcp, Psa, 0u, recs,
+                                                                     TermTable{}, n);
+    }
+    KERNEL_CHECK();
+    return recs;
+}
+
 }  // namespace nolzss

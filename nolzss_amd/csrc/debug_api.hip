@@ -98,6 +98,61 @@ int nolzss_debug_arrays(const uint8_t *text, size_t n, int device, uint32_t *sa,
     });
 }
 
+int nolzss_debug_position_factors(const uint8_t *text, size_t n, int device, nolzss_factor *out) {
+    return guarded([&] {
+        check_text_args(text, n, 0);
+        if (n == 0) return;
+        if (!out) throw std::invalid_argument("output pointer is null");
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        reserve_arena_for(ctx, n, n + n * (sizeof(nolzss_factor) + sizeof(uint32_t)));  // text, records, their positions
+        uint8_t *d_text = ctx.arena.alloc<uint8_t>(n);
+        upload_bytes(ctx, d_text, text, n);
+        DebugOut dbg;
+        dbg.records = out;
+        run_plain(ctx, d_text, n, 0, nullptr, &dbg);
+    });
+}
+
+int nolzss_debug_rc_arrays(const uint8_t *S, size_t S_len, int device, int want_plain, uint32_t *sa, uint32_t *isa,
+                           uint32_t *lcp, uint32_t *code, uint32_t *plain, nolzss_factor *records, uint32_t *counters) {
+    return guarded([&] {
+        if (S_len && !S) throw std::invalid_argument("text pointer is null");
+        if (S_len > kMaxText) throw std::invalid_argument("text too long: the device pipeline uses 32-bit indices");
+        if (counters) std::fill(counters, counters + 5, 0u);
+        if (!rc_guards(S_len, 0)) return;
+        const size_t m = S_len, N = m / 2 - 1;
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        // the upload path of run_rc_host, with room for the plain by-product (by rank and in text order, as
+        // dna_w_rc_common asks for it) and for the records of every position
+        reserve_arena_for(ctx, m, m + (want_plain ? 4 * m + 4 * N + (size_t(32) << 20) : 0) +
+                                      (records ? N * (sizeof(nolzss_factor) + sizeof(uint32_t)) : 0));
+        uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
+        upload_bytes(ctx, d_S, S, m);
+        RcDebugOut dbg;
+        dbg.sa = sa;
+        dbg.isa = isa;
+        dbg.lcp = lcp;
+        dbg.code = code;
+        dbg.plain = want_plain ? plain : nullptr;
+        dbg.records = records;
+        RcPlainOut plain_out;
+        run_rc_pipeline(ctx, d_S, m, 0, nullptr, want_plain ? &plain_out : nullptr, nullptr, &dbg);
+        HIP_CHECK(hipStreamSynchronize(ctx.stream));
+        ctx.prof.collect();
+        if (isa)
+            for (size_t i = 0; i < N; ++i) isa[i] -= 1u;  // the device array holds rank + 1
+        if (counters) {
+            counters[0] = dbg.far_ranks;
+            counters[1] = dbg.exact_from_tiles;
+            counters[2] = dbg.exact_total;
+            counters[3] = dbg.compact;
+            counters[4] = dbg.pending_relaunch;
+        }
+    });
+}
+
 int nolzss_debug_sort_pairs(uint64_t *keys, uint32_t *vals, size_t n, int device) {
     return guarded([&] {
         if (n == 0) return;

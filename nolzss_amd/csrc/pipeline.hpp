@@ -86,11 +86,20 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
                        void **d_factors_out, uint32_t rcN = 0, const Pyramid *Pmax = nullptr,
                        uint32_t **d_fpos_out = nullptr, const TermTable *rebase = nullptr,
                        const ChainLengthsOut *lengths = nullptr);
+// Debug hooks (debug_api.hip): the record (start, length, ref) of EVERY position i < n, as factor_kernel gives it when
+// each position is a factor start -- the kernel reads the length code itself for a factor of length 1, so the existing
+// instantiations launched with fpos = 0, 1, .., n - 1 do that.  The n records (3 x u64 each) are left in the arena:
+// the caller owns the mark.  Arguments as resolve_chain.
+void *position_factors(Context &ctx, uint32_t n, const uint32_t *lstar, const uint32_t *sa, const uint32_t *isa,
+                       const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp, uint32_t rcN = 0,
+                       const Pyramid *Pmax = nullptr, const TermTable *rebase = nullptr);
 
 // ---- reverse-complement mode (rc.hip): whole pipeline over the prepared string S -------------
 struct RcPlainOut;
+struct RcDebugOut;
 uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m, size_t start_pos, void **d_factors_out,
-                         RcPlainOut *plain = nullptr, const ChainLengthsOut *lengths = nullptr);
+                         RcPlainOut *plain = nullptr, const ChainLengthsOut *lengths = nullptr,
+                         RcDebugOut *dbg = nullptr);
 // plain-mode counts as a by-product of a reverse-complement run: the plain L* of every position i < N comes out of
 // the same candidate kernels (rc.hip) and is chained on its own; z = nolzss_count_factors of the original strand(s),
 // fpos (want_fpos) = its factor starts in the arena, for the per-record split of a merged run
@@ -99,12 +108,28 @@ struct RcPlainOut {
     uint32_t z = 0;
     uint32_t *fpos = nullptr;
 };
+// Debug-out of a reverse-complement run (tests; debug_api.hip, in the spirit of api::DebugOut): HOST pointers, each may
+// be null.  The arrays are copied out behind the far and exact kernels, before their queues are released; N = m / 2 - 1.
+struct RcDebugOut {
+    uint32_t *sa = nullptr;     // m
+    uint32_t *lcp = nullptr;    // m + 1
+    uint32_t *isa = nullptr;    // N entries, rank + 1 as on the device (the compact permutation fills no more)
+    uint32_t *code = nullptr;   // N: length in bits 0..30, bit 31 = reverse complement, 0 = literal
+    uint32_t *plain = nullptr;  // N: the plain-mode by-product; only in a run with RcPlainOut
+    void *records = nullptr;    // N x (start, length, ref) as u64: position_factors over the codes
+    // what the host read back on the way
+    uint32_t far_ranks = 0;         // far queue behind the tile kernel
+    uint32_t exact_from_tiles = 0;  // exact-search queue in front of rc_far_kernel
+    uint32_t exact_total = 0;       // ... and behind it
+    uint32_t compact = 0;           // the tile kernel wrote the compact output
+    uint32_t pending_relaunch = 0;  // an undecided LCP entry sent the tile kernel round a second time
+};
 // the same over a text that has already been packed (merged batch); plain (optional): the plain-mode by-product
 // above; d_fpos_out (optional, with d_factors_out null): the factor starts of the reverse-complement chain
 // lengths (optional, with d_factors_out null): the factor lengths of the reverse-complement chain (ChainLengthsOut)
 uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
                                 RcPlainOut *plain = nullptr, uint32_t **d_fpos_out = nullptr,
-                                const ChainLengthsOut *lengths = nullptr);
+                                const ChainLengthsOut *lengths = nullptr, RcDebugOut *dbg = nullptr);
 // d_S (2n + 2 bytes) = T' sep revcomp(T') sep for the n bytes d_T = upper-case records with separator bytes
 // between them; bytes that are not nucleotides (the separators) are copied to their mirror position.
 void prepare_batch_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t n, uint8_t separator, uint8_t *d_S);

@@ -377,13 +377,14 @@ uint32_t prepare_single_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t 
 }
 
 uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m_sz, size_t start_pos, void **d_factors_out,
-                         RcPlainOut *plain, const ChainLengthsOut *lengths) {
+                         RcPlainOut *plain, const ChainLengthsOut *lengths, RcDebugOut *dbg) {
     const PackedText text = pack_text(ctx, d_S, m_sz);  // segmented 2-bit packing is detected there
-    return run_rc_pipeline_packed(ctx, text, start_pos, d_factors_out, plain, nullptr, lengths);
+    return run_rc_pipeline_packed(ctx, text, start_pos, d_factors_out, plain, nullptr, lengths, dbg);
 }
 
 uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
-                                RcPlainOut *plain_out, uint32_t **d_fpos_out, const ChainLengthsOut *lengths) {
+                                RcPlainOut *plain_out, uint32_t **d_fpos_out, const ChainLengthsOut *lengths,
+                                RcDebugOut *dbg) {
     const uint32_t m = text.n;
     const uint32_t N = m / 2 - 1;
     hipStream_t s = ctx.stream;
@@ -483,6 +484,7 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
             if (pending) {
                 // safety net (build_lcp_pyramid): an undecided LCP entry is compared in the text, the pyramids are
                 // built again and the candidates computed once more from the repaired array
+                if (dbg) dbg->pending_relaunch = 1;
                 finish_pending_lcp(ctx, text, sa, lcp);
                 fill_pyramid(Pmin, 1, false, s);
                 fill_pyramid(Pmax, 1, true, s);
@@ -513,6 +515,11 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
         }
         uint32_t h[2] = {0, 0};
         read_totals(h);
+        if (dbg) {
+            dbg->compact = compact ? 1u : 0u;
+            dbg->far_ranks = h[1];
+            dbg->exact_from_tiles = h[0];
+        }
         if (h[1] > 0) {
             ProfScope ps(ctx.profiler(), "rc_far", s);
             const unsigned gy = (unsigned)std::min<size_t>(64, std::max<size_t>(1, div_up(h[1], (size_t)kQShards * kThreads)));
@@ -534,6 +541,25 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
                 rc_fallback_kernel<false><<<dim3(kQShards, gy), kThreads, 0, s>>>(exact_q, m, isa, lcp, Pmin, Plcp, code, nullptr);
             KERNEL_CHECK();
         }
+        if (dbg) {
+            dbg->exact_total = h[0];
+            auto copy_out = [&](uint32_t *host, const uint32_t *dev, size_t count) {
+                if (host && count) HIP_CHECK(hipMemcpyAsync(host, dev, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            };
+            copy_out(dbg->sa, sa, m);
+            copy_out(dbg->lcp, lcp, (size_t)m + 1);
+            copy_out(dbg->isa, isa, N);  // (1-based on the device; nolzss_debug_rc_arrays subtracts the one)
+            copy_out(dbg->code, code, N);
+            if (plain) copy_out(dbg->plain, plain, N);
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+        arena.rewind(mark);
+    }
+    if (dbg && dbg->records) {
+        const size_t mark = arena.mark();
+        const void *recs = position_factors(ctx, N, code, sa, isa, lcp, Pmin, Plcp, N, &Pmax);
+        HIP_CHECK(hipMemcpyAsync(dbg->records, recs, (size_t)N * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
         arena.rewind(mark);
     }
     const uint32_t z = resolve_chain(ctx, N, (uint32_t)start_pos, code, sa, isa, lcp, Pmin, Plcp, d_factors_out, N, &Pmax,

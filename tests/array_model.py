@@ -121,7 +121,7 @@ def factor_rc(sa, isa, lcp, m, N, i):
 
 
 def factor_rc_fastpath(sa, isa, lcp, m, N, i):
-    """Same result as factor_rc, organised the way rc_candidates_kernel / rc_fallback_kernel are:
+    """Same result as factor_rc, organised the way rc_tile_kernel / rc_fallback_kernel are:
     when a best forward neighbour does not overlap position i the forward length is final and no
     explicit-node bookkeeping is needed; reverse-complement candidates shorter than what the
     forward side already has are pruned."""

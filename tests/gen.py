@@ -36,6 +36,36 @@ def repeat_dna(n: int, seed: int = 0x5EED0003, p_copy: float = 0.4, lo: int = 64
     return out
 
 
+def far_copy(n: int, seed: int) -> bytes:
+    """random DNA whose second half repeats blocks from far back (beyond the LDS reach of the tile kernels)"""
+    rng = np.random.default_rng(seed)
+    a = random_dna(n, seed)
+    for _ in range(8):
+        ln = int(rng.integers(2000, 20000))
+        dst = int(rng.integers(n // 2, n - ln))
+        src = int(rng.integers(0, n // 4))
+        a[dst:dst + ln] = a[src:src + ln]
+    return a.tobytes()
+
+
+_COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def mixed_dna(rng, n: int, p_copy: float = 0.5, maxlen: int = 40) -> str:
+    """single bases and copies of earlier stretches, half of them reverse-complemented (rng: random.Random)"""
+    s = ""
+    while len(s) < n:
+        if s and rng.random() < p_copy:
+            a = rng.randrange(len(s))
+            seg = s[a:a + rng.randint(1, maxlen)]
+            if rng.random() < 0.5:
+                seg = seg[::-1].translate(_COMPLEMENT)
+            s += seg
+        else:
+            s += rng.choice("ACGT")
+    return s[:n]
+
+
 def fasta_records(m: int, length: int, seed0: int = 0x4000):
     """Config 4: m records of `length` random bases, ids seq{k}, seeds seed0 + k."""
     return [(f"seq{k}", random_dna(length, seed0 + k)) for k in range(m)]

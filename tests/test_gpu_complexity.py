@@ -78,16 +78,7 @@ def test_kats_and_atgcat(native):
         assert native.count_factors_batch_both([t]) == ([oracle_pair(t)[0]], [oracle_pair(t)[1]])
 
 
-def _far_copy(n, seed):
-    """random DNA whose second half repeats blocks from far back (beyond the LDS reach of the tile kernels)"""
-    rng = np.random.default_rng(seed)
-    a = gen.random_dna(n, seed)
-    for _ in range(8):
-        ln = int(rng.integers(2000, 20000))
-        dst = int(rng.integers(n // 2, n - ln))
-        src = int(rng.integers(0, n // 4))
-        a[dst:dst + ln] = a[src:src + ln]
-    return a.tobytes()
+_far_copy = gen.far_copy
 
 
 @pytest.fixture(scope="module")

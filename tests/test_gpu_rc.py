@@ -41,18 +41,7 @@ def test_doc_example_follows_the_code(native):
     assert native.factorize_dna_w_rc(v["input"].encode()) == [tuple(f) for f in v["code_trace"]]
 
 
-def _mixed(rng, n, p_copy=0.5, maxlen=40):
-    s = ""
-    while len(s) < n:
-        if s and rng.random() < p_copy:
-            a = rng.randrange(len(s))
-            seg = s[a:a + rng.randint(1, maxlen)]
-            if rng.random() < 0.5:
-                seg = bf.revcomp(seg)
-            s += seg
-        else:
-            s += rng.choice("ACGT")
-    return s[:n]
+_mixed = gen.mixed_dna
 
 
 def _cases():
