@@ -4,6 +4,12 @@
 
 namespace nolzss {
 
+void Context::read_back(const uint32_t *d_src, uint32_t *dst, int count) {
+    HIP_CHECK(hipMemcpyAsync(h_pinned, d_src, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (int k = 0; k < count; ++k) dst[k] = h_pinned[k];
+}
+
 namespace api {
 
 thread_local std::string g_error;

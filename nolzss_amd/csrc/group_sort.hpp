@@ -1,4 +1,4 @@
-// group_sort.hpp -- the SECOND direct round of the suffix-array construction (included by suffix_array.hip
+// group_sort.hpp -- the SECOND direct round of the suffix-array construction (included by sa_direct.hip
 // inside its anonymous namespace, behind the first direct round's kernel).
 //
 // The first direct round (group_refine_kernel) finishes groups of up to 64 suffixes by comparing pairs,

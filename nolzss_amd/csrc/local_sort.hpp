@@ -127,13 +127,13 @@ __device__ __forceinline__ void local_store(const uint32_t *s_stage, uint32_t *_
 }
 
 // ---- the regroup of round 0 inside local_sort_kernel ---------------------------------------------------------
-// After its last digit a sub-bucket lies sorted in LDS: everything regroup_kernel<true, 3> (suffix_array.hip) would read
+// After its last digit a sub-bucket lies sorted in LDS: everything regroup_kernel<true, 3> (sa_regroup.hip) would read
 // back from HBM is at hand.  Groups never span two sub-buckets (their members differ in the first eight bases), so a
 // workgroup finds the group heads, the LCP of every boundary the keys decide and the elements that stay tied by itself;
 // what it needs from the others is the number of tied elements in front (a decoupled look-back over one descriptor per
 // non-empty sub-bucket, lookback.hpp) and, for the LCP of its first boundary, the last key of the sub-bucket in front.
 // The keys are not written at all: 4 bytes per suffix less out, 4 less in, and a kernel less.
-constexpr uint32_t kLcpPendingCode = 0xffffffffu;  // (suffix_array.hip: kLcpPending)
+constexpr uint32_t kLcpPendingCode = 0xffffffffu;  // (sa_internal.hpp: kLcpPending)
 // The sub-buckets are dealt out statically (that is what lets a workgroup ask for the next one's keys a turn ahead), so a
 // look-back can wait for a workgroup that is not resident -- if another process or stream holds CUs with a kernel of its
 // own that waits the same way, for as long as it likes.  The walk therefore gives up after ~0.2 s (2^17 polls of a

@@ -1,5 +1,5 @@
 // lookback.hpp -- decoupled look-back over per-tile descriptors in HBM: [status : value] in one 64-bit word, status 1 =
-// the tile's own aggregate, 2 = inclusive prefix.  Shared by the regroup kernel (suffix_array.hip) and the sub-bucket
+// the tile's own aggregate, 2 = inclusive prefix.  Shared by the regroup kernel (sa_regroup.hip) and the sub-bucket
 // sort that does the regroup of round 0 on the way (radix_sort.hip: local_sort_kernel).
 #pragma once
 #include "common.hpp"

@@ -62,7 +62,7 @@ struct Pyramid;
 uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_t *isa, const uint32_t *lcp,
                      const Pyramid &Psa, const Pyramid &Plcp, uint32_t *lstar, uint32_t *isa_fill = nullptr,
                      const PackedText *fill_pyramids = nullptr);
-// pieces of build_lcp_pyramid for that form (suffix_array.hip): the code above which an LCP entry counts as
+// pieces of build_lcp_pyramid for that form (sa_regroup.hip): the code above which an LCP entry counts as
 // undecided, the comparison of the suffixes around every undecided entry, and the test hook that leaves one undecided
 uint32_t pending_threshold();
 void finish_pending_lcp(Context &ctx, const PackedText &text, const uint32_t *sa, uint32_t *lcp);

@@ -103,7 +103,7 @@ void radix_sort_dna_keys(const PackedText &text, uint32_t *keys32[2], uint32_t *
 // (also segmented texts with a terminator table of at most kTermFew entries and segments of at least 16 symbols -- a
 // prepared reverse-complement string --: key16_applicable says whether a text takes this sort)
 bool key16_applicable(const PackedText &text);
-// What the regroup kernel of round 0 produces from the sorted keys (suffix_array.hip: regroup_kernel<true, 3>), asked of the
+// What the regroup kernel of round 0 produces from the sorted keys (sa_regroup.hip: regroup_kernel<true, 3>), asked of the
 // sort itself: where the sub-buckets are finished in LDS the sorted keys are at hand -- LCP of every boundary the keys
 // decide (0xffffffff = pending elsewhere), the elements that stay tied (slot and slot of their group's head, in slot
 // order) and their number.  `done` says whether the sort did it (the keys are then NOT written).

@@ -211,7 +211,7 @@ print("ok", len(cases))
 
 def test_pair_runs_on_long_exact_repeats():
     """Long exact repeats leave pairs of suffixes tied beyond the cap of the direct round; along runs of
-    text positions they are finished arithmetically (suffix_array.hip, pair_delta_kernel ...).  One child
+    text positions they are finished arithmetically (sa_repeats.hip, pair_delta_kernel ...).  One child
     process with a tiny cap (NOLZSS_REFINE_WORDS=1: 49 symbols) and NOLZSS_PAIR_RUNS_MIN=1 sends every
     repeat longer than that through this path: two and three copies, copies with substitutions, nested and
     overlapping repeats, repeats that end at the end of the text, other alphabets, reverse complement."""
@@ -289,7 +289,7 @@ def test_collections_of_similar_genomes(native, copies, base_len):
     to thousands of symbols.  Groups of up to 64 members go through the pair comparisons of the direct round, what
     it leaves and every larger group through the doubling rounds -- groups of 65 .. 1024 members sorted in LDS
     (mid_sort_kernel), larger ones by the radix sort; with 20 and 24 copies a part of the groups does not fit the
-    pair list of the direct round and goes through the equalising round first (suffix_array.hip).  Factors, suffix
+    pair list of the direct round and goes through the equalising round first (sa_direct.hip).  Factors, suffix
     array, LCP and inverse against the oracle."""
     rng = np.random.default_rng(1000 + copies)
     base = gen.random_dna(base_len, 500 + copies)
@@ -387,7 +387,7 @@ print("ok", len(texts))
 
 def test_periodic_runs_pass():
     """Runs of a short period tie the suffixes of a run in groups that only log2(run length) doubling
-    rounds would resolve; the periodic-run pass orders them arithmetically (suffix_array.hip, "Periodic
+    rounds would resolve; the periodic-run pass orders them arithmetically (sa_repeats.hip, "Periodic
     runs").  One child process with a tiny direct-round cap (NOLZSS_REFINE_WORDS=1: 49 symbols) and
     NOLZSS_PAIR_RUNS_MIN=1 sends every run longer than that through the pass: single runs, several runs of
     the same and of different periods, runs that break upwards / downwards / at the end of the text, runs
@@ -448,3 +448,76 @@ print("ok", len(texts))
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     done = [int(line.split("periodic runs")[1].split(":")[1].split()[0]) for line in r.stderr.splitlines() if "periodic runs" in line]
     assert len(done) >= 20 and sum(done) > 50000, done  # the pass ran and finished suffixes
+
+
+_SWITCH_ENVS = [("NO_PERIODIC",), ("NO_PERIODIC", "NO_SEG_LARGE"), ("NO_PERIODIC", "NO_MID_SORT"), ("NO_DIRECT2",),
+                ("NO_EQUALISE",), ("NO_PIVOT",), ("NO_DEFER_ISA",), ("DNA_FAST_MIN", "NO_KEY16")]
+
+
+@pytest.mark.parametrize("switches", _SWITCH_ENVS, ids=["-".join(s).lower() for s in _SWITCH_ENVS])
+def test_ab_switches_of_the_suffix_array_driver(switches):
+    """The A/B switches of the suffix-array driver (suffix_array.hip, sa_direct.hip, sa_repeats.hip) take the branch
+    that is not the default: no periodic pass (whole runs reach the doubling rounds, whose large groups go through the
+    segmented sort, the global sort, or -- without mid_sort_kernel -- both for every group of more than 64 members),
+    no second direct round, no equalising round, no pivot rounds, rank[] scattered although the direct rounds finish,
+    the 40-bit key of the bucketed sort.  One child process per set of switches, with the cap of the first direct
+    round lowered to 49 symbols (NOLZSS_REFINE_WORDS=1): runs, a Fibonacci word, collections of 20 / 130 / 1100
+    similar sequences, repeats, an 8-bit and a 4-bit text, one prepared reverse-complement string.  Factors, suffix
+    array, LCP and inverse suffix array against the oracle for every text.  (The texts were meant to stay under
+    100 000 symbols; the collection of 1100 x 150 bases, which is there for its groups of more than 1024 members, has
+    165 000, and the size check in the child says so.)"""
+    import os
+    import subprocess
+    import sys
+    code = r'''
+import sys
+sys.path.insert(0, "tests")
+import numpy as np
+import gen, oracle_lib as oracle
+from nolzss_amd import _noLZSS as native
+def rnd(n, seed): return gen.random_dna(n, seed)
+def mutate(x, k, seed):
+    y = x.copy(); r = np.random.default_rng(seed)
+    idx = r.integers(0, len(y), size=k); y[idx] = np.frombuffer(b"ACGT", dtype=np.uint8)[r.integers(0, 4, size=k)]
+    return y
+def collection(copies, base_len, seed):
+    base = rnd(base_len, seed)
+    return np.concatenate([base] + [mutate(base, max(1, base_len // 100), seed * 100 + k) for k in range(copies - 1)])
+def fib(k):
+    a, b = b"A", b"AC"
+    while len(b) < k: a, b = b, b + a
+    return b[:k]
+S, orig, sent = native.prepare_multiple_dna_sequences_w_rc_bytes([bytes(rnd(3000, 1)), bytes(rnd(2000, 2)), bytes(rnd(3000, 1))])
+texts = [
+    b"A" * 5000, b"AC" * 3000, b"A" * 3000 + b"C" + b"A" * 2000, fib(20000), bytes(np.tile(rnd(300, 3), 40)),
+    bytes(collection(20, 1000, 11)), bytes(collection(130, 500, 12)), bytes(collection(1100, 150, 13)),
+    gen.repeat_dna(70_000, 5, lo=16, hi=4096).tobytes(),
+    b"abracadabra, " * 300,                                                                                               # 8-bit
+    bytes(np.concatenate([np.frombuffer(b"ACGTNRYK", dtype=np.uint8)[np.random.default_rng(5).integers(0, 8, 3000)]] * 12)),  # 4-bit
+    bytes(S),
+]
+assert all(len(t) <= 165_000 for t in texts)   # (the largest: 1100 copies x 150 bases)
+checked = 0
+for t in texts:
+    got = native.factorize_array(t)
+    exp = oracle.factors_array(t)
+    assert len(got) == len(exp), (len(t), len(got), len(exp))
+    for k in ("start", "length", "ref"):
+        assert np.array_equal(got[k], exp[k]), (len(t), k)
+    d = native.debug_arrays(t)
+    sa = oracle.suffix_array(t)
+    assert np.array_equal(d["sa"].astype(np.int64), sa.astype(np.int64)), ("sa", len(t))
+    assert np.array_equal(d["lcp"][:len(t)].astype(np.int64), oracle.lcp_array(t, sa).astype(np.int64)), ("lcp", len(t))
+    isa = np.empty(len(t), dtype=np.int64); isa[sa] = np.arange(len(t))
+    assert np.array_equal(d["isa"].astype(np.int64), isa), ("isa", len(t))
+    checked += 1
+assert native.factorize_multiple_dna_w_rc(S) == oracle.factorize_multiple_dna_w_rc(S)
+print("ok", checked, "of", len(texts))
+'''
+    env = dict(os.environ, NOLZSS_REFINE_WORDS="1", NOLZSS_TRACE="1", **{"NOLZSS_" + k: "1" for k in switches})
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ok 12 of 12" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]  # no text skipped
+    if "NO_PERIODIC" in switches:
+        large = [int(line.split(":")[1].split()[0]) for line in r.stderr.splitlines() if "doubling round h=" in line]
+        assert any(x > 0 for x in large), large  # the large-group branches of the doubling rounds ran
