@@ -30,7 +30,7 @@
 #include "host_util.hpp"
 #include "pipeline.hpp"
 #include "pyramid.hpp"
-#include "radix_sort.hpp"
+#include "text_order.hpp"
 #include "scan.hpp"
 
 namespace nolzss {

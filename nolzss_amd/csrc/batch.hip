@@ -17,7 +17,7 @@ namespace api {
 constexpr uint8_t kBatchSeparator = 0x01;
 
 // Runs of long records: for the duration of the run the context carries the plan that keeps the two permutation
-// scatters of the pipeline inside the records (radix_sort.hpp; NOLZSS_NO_RECORD_SCATTER=1 switches it off)
+// scatters of the pipeline inside the records (text_order.hpp; NOLZSS_NO_RECORD_SCATTER=1 switches it off)
 struct RecordPlanScope {
     Context &ctx;
     RecordScatterPlan plan;

@@ -1,12 +1,16 @@
 // local_sort.hpp -- the sub-buckets of two most-significant-digit passes sorted in LDS (local_sort_kernel), with the
-// regroup of round 0 on the way where it pays, and the host side of it (local_sort_sub_buckets).  A part of radix_sort.hip:
-// included there, inside namespace nolzss, behind the radix kernels it builds on (rs_hist_kernel, rs_scatter_kernel, the
-// segment-list kernels).
+// regroup of round 0 on the way where it pays, and the host side of it (local_sort_sub_buckets), the segmented passes
+// over the sub-buckets too large for a workgroup included (seg_desc_list_kernel, seg_table_shift_kernel,
+// seg_copy_kernel).  Internal to radix_sort.hip, like radix_pass.hpp, whose kernels it builds on.
 #pragma once
-#ifndef NOLZSS_RADIX_SORT_HIP
-#error "local_sort.hpp is a part of radix_sort.hip"
-#endif
+#include "lookback.hpp"
+#include "radix_pass.hpp"
 
+#include <algorithm>
+#include <atomic>
+#include <vector>
+
+namespace nolzss {
 namespace {
 
 // ---- sub-buckets sorted in LDS (round 4) -----------------------------------------------------------------
@@ -545,6 +549,66 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
     if (!order_ok) atomicOr(&ctl[2], 1u);
 }
 
+// one descriptor per tile (radix_sort.hpp, SegView) of segments given by a first and an end element each: the large
+// sub-buckets of local_sort_kernel
+__global__ __launch_bounds__(kThreads) void seg_desc_list_kernel(const uint32_t *__restrict__ first_of,
+                                                                 const uint32_t *__restrict__ end_of,
+                                                                 const uint32_t *__restrict__ tile0, uint32_t num_tiles,
+                                                                 uint32_t *__restrict__ desc, uint32_t num_segs) {
+    const uint32_t tile = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tile >= num_tiles) return;
+    uint32_t lo = 0, hi = num_segs;  // the segment of the tile (segments of the list are never empty)
+    while (lo + 1 < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tile0[mid] <= tile)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const uint32_t t0 = tile0[lo], local = tile - t0;
+    const uint32_t first = first_of[lo] + local * (uint32_t)kTile, end = end_of[lo];
+    uint32_t *d = desc + (size_t)tile * kSegDescWords;
+    d[0] = first;
+    d[1] = end - first < (uint32_t)kTile ? end - first : (uint32_t)kTile;
+    d[2] = lo;
+    d[3] = t0 * (uint32_t)kBins + local;
+    d[4] = tile0[lo + 1] - t0;
+    d[5] = first_of[lo];
+    d[6] = end;
+    d[7] = lo ? lo - 1 : 0xffffffffu;
+    d[8] = lo + 1 < num_segs ? lo + 1 : 0xffffffffu;
+    d[9] = d[10] = d[11] = 0;
+}
+
+// The scanned table of a pass over such a list counts from the first segment of the LIST: every entry of segment k
+// is moved by shift[k] = (first element of the segment) - (elements of the list in front of it).  The entries of
+// segment k are [tile0[k] * 256, tile0[k + 1] * 256): one workgroup per 256 of them, all in one segment.
+// (one workgroup per SEGMENT walked 16.7 M entries alone when a text is one run of A's: +19 ms)
+__global__ __launch_bounds__(kBins) void seg_table_shift_kernel(uint32_t *__restrict__ table, const uint32_t *__restrict__ tile0,
+                                                               const uint32_t *__restrict__ shift, uint32_t num_segs) {
+    const uint32_t q = blockIdx.x;  // < tile0[num_segs]
+    uint32_t lo = 0, hi = num_segs;  // the segment with tile0[lo] <= q < tile0[lo + 1] (segments of the list are never empty)
+    while (lo + 1 < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tile0[mid] <= q)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    table[(size_t)q * kBins + threadIdx.x] += shift[lo];
+}
+
+// the elements of the tiles of a SegView copied from one pair of arrays to another
+__global__ __launch_bounds__(kThreads) void seg_copy_kernel(const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
+                                                            uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
+                                                            SegView seg) {
+    const TileExtent ext = tile_extent(blockIdx.x, 0, seg.num_tiles, seg);
+    for (uint32_t p = threadIdx.x; p < ext.count; p += kThreads) {
+        keys_out[ext.first + p] = keys_in[ext.first + p];
+        vals_out[ext.first + p] = vals_in[ext.first + p];
+    }
+}
+
 std::atomic<bool> local_sort_off{false};  // a lane-order check of local_sort_kernel failed on this machine
 
 // The buckets of a bucketed view (first elements bstart[0 .. num_buckets], first tiles tile0[]) have just been partitioned
@@ -569,8 +633,6 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
 #ifdef NOLZSS_LOCAL_TIMED
     d_ph = arena.alloc<unsigned long long>(32);
     HIP_CHECK(hipMemsetAsync(d_ph, 0, 32 * sizeof(unsigned long long), stream));
-#endif
-#ifdef NOLZSS_LOCAL_TIMED
     auto print_phases = [&] {
         unsigned long long h[32];
         HIP_CHECK(hipMemcpyAsync(h, d_ph, sizeof(h), hipMemcpyDeviceToHost, stream));
@@ -586,13 +648,12 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
         fprintf(stderr, " hand-over %.0f\n", h[30] / wn);
     };
 #endif
-    static const bool fail_order = getenv("NOLZSS_TEST_LOCAL_ORDER_FAILS") != nullptr;  // (test hook: the redo path)
-    static const bool no_fuse = getenv("NOLZSS_NO_LOCAL_REGROUP") != nullptr;            // (A/B switch)
+    const SortKnobs &knobs = sort_knobs();
+    const bool fail_order = knobs.test_local_order_fails;  // (test hook: the redo path)
     // (it pays where the regroup kernel is expensive -- many tied elements -- and the turns are long: 2^30 bases of the
     // benchmark text 21.7 -> 20.0 ms for sort + regroup, but random DNA of 2^29 bases 10.7 -> 11.2 and of 2^28 bases 6.3 -> 7.5:
     // the look-back and the two loops are a fixed cost per sub-bucket.  NOLZSS_LOCAL_REGROUP_MIN = smallest text that takes it.)
-    static const size_t fuse_min = getenv("NOLZSS_LOCAL_REGROUP_MIN") ? (size_t)atoll(getenv("NOLZSS_LOCAL_REGROUP_MIN")) : (size_t(3) << 28);
-    if (rg && !no_fuse && !fail_order && npass == 2 && num_sub % 1024u == 0 && n >= fuse_min) {
+    if (rg && !knobs.no_local_regroup && !fail_order && npass == 2 && num_sub % 1024u == 0 && n >= knobs.local_regroup_min) {
         // the regroup of round 0 on the way -- if no sub-bucket overflows a workgroup (the segmented passes that finish
         // those come after the kernel) and the kernel's checks hold; otherwise the plain form below runs from the same input
         uint32_t *dense = arena.alloc<uint32_t>(num_sub), *prev_sub = arena.alloc<uint32_t>(num_sub), *info = arena.alloc<uint32_t>(2);
@@ -608,7 +669,7 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
             uint64_t *dd = arena.alloc<uint64_t>(2 * (size_t)F.nq);
             HIP_CHECK(hipMemsetAsync(dd, 0, 2 * (size_t)F.nq * sizeof(uint64_t), stream));
             HIP_CHECK(hipMemsetAsync(rg->d_total, 0, 2 * sizeof(uint32_t), stream));
-            static const bool fail_lookback = getenv("NOLZSS_TEST_LOCAL_LOOKBACK_FAILS") != nullptr;  // (test hook: the way back)
+            const bool fail_lookback = knobs.test_local_lookback_fails;  // (test hook: the way back)
             if (fail_lookback) HIP_CHECK(hipMemsetAsync(rg->d_total + 1, 1, 1, stream));  // (the flag a look-back sets when it gives up)
             F.desc = dd; F.lastkey = dd + F.nq; F.dense = dense; F.prev_sub = prev_sub;
             {
@@ -715,3 +776,4 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
     }
 }
 }  // namespace
+}  // namespace nolzss

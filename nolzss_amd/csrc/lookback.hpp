@@ -1,6 +1,6 @@
 // lookback.hpp -- decoupled look-back over per-tile descriptors in HBM: [status : value] in one 64-bit word, status 1 =
 // the tile's own aggregate, 2 = inclusive prefix.  Shared by the regroup kernel (sa_regroup.hip) and the sub-bucket
-// sort that does the regroup of round 0 on the way (radix_sort.hip: local_sort_kernel).
+// sort that does the regroup of round 0 on the way (local_sort.hpp: local_sort_kernel).
 #pragma once
 #include "common.hpp"
 

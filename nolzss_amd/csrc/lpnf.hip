@@ -20,7 +20,7 @@
 #include <cstdlib>
 #include "nearest_lds.hpp"
 #include "queues.hpp"
-#include "radix_sort.hpp"
+#include "text_order.hpp"
 #include "scan.hpp"
 
 namespace nolzss {
@@ -295,7 +295,7 @@ uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_
     uint32_t *by_rank = ctx.arena.alloc<uint32_t>(n);
     uint32_t *far_aux = ctx.arena.alloc<uint32_t>(n);
     uint32_t *scratch_idx = ctx.arena.alloc<uint32_t>(n);
-    uint32_t *scratch_val = ctx.arena.alloc<uint32_t>(isa_fill ? 2 * (size_t)n : (size_t)n);  // (two values per pair: radix_sort.hpp)
+    uint32_t *scratch_val = ctx.arena.alloc<uint32_t>(isa_fill ? 2 * (size_t)n : (size_t)n);  // (two values per pair: text_order.hpp)
     HIP_CHECK(hipMemsetAsync(qcounts, 0, kQShards * kQPad * sizeof(uint32_t), s));
     const uint32_t *h_ptrs[1] = {exact_q.counts};
     HIP_CHECK(hipMemcpyAsync(count_ptrs, h_ptrs, sizeof h_ptrs, hipMemcpyHostToDevice, s));

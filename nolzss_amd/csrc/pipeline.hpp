@@ -17,7 +17,7 @@ struct Context {
     uint8_t *h_stage = nullptr;    // pinned host staging for uploads (grow-only, merged batch)
     size_t h_stage_cap = 0;
     // merged batch of long records (set for the duration of one run): the two permutation scatters of the
-    // pipeline -- rank[sa[r]] and L*[sa[r]] -- stay inside the records (radix_sort.hpp, RecordScatterPlan)
+    // pipeline -- rank[sa[r]] and L*[sa[r]] -- stay inside the records (text_order.hpp, RecordScatterPlan)
     const struct RecordScatterPlan *rec_plan = nullptr;
 
     Profiler *profiler() { return prof.enabled() ? &prof : nullptr; }
@@ -44,7 +44,7 @@ bool pack_independent_text(Context &ctx, const uint8_t *d_text, size_t n, const 
 // isa_deferred (optional): the caller can do without isa[] until the factor-length codes have been brought into
 // text order -- if the direct rounds finish the suffix array (no doubling round needs rank[]), isa[] is then NOT
 // written here and *isa_deferred = true: the caller hands isa to the permutation of the codes, which delivers it
-// as a second value (build_lstar's isa_fill; radix_sort.hpp, bucketed_scatter with out2).
+// as a second value (build_lstar's isa_fill; text_order.hpp, bucketed_scatter with out2).
 int build_suffix_array(Context &ctx, const PackedText &text, uint32_t *sa, uint32_t *isa, uint32_t *lcp,
                        bool *isa_deferred = nullptr);
 // The range-minimum pyramid over lcp[0..n]; checks on the way that the construction left no boundary

@@ -1,4 +1,6 @@
-// radix_sort.hpp -- LSD radix sort of (u64 or u32 key, u32 value) pairs, 8-bit digits.
+// radix_sort.hpp -- LSD radix sort of (u64 or u32 key, u32 value) pairs, 8-bit digits: the bucketed view of segmented
+// passes (SegView), the sorts of radix_sort.hip and their knobs.  (One pass and its kernels: radix_pass.hpp, internal;
+// the permutation into text order, built on the same pass: text_order.hpp.)
 #pragma once
 #include "common.hpp"
 #include "text.hpp"
@@ -67,6 +69,28 @@ __device__ __forceinline__ TileExtent tile_extent(uint32_t tile, size_t n, uint3
     return e;
 }
 
+// ---- knobs: every NOLZSS_* environment variable of radix_sort.hip, local_sort.hpp and text_order.hip, read once at
+// first use and frozen (as SaKnobs, sa_internal.hpp; the tests and tools set them on child processes only)
+struct SortKnobs {
+    SortKnobs();
+    bool trace;                // NOLZSS_TRACE: what the text-order permutation did, to stderr
+    bool scatter_phases;       // NOLZSS_SCATTER_PHASES: (diagnostics) cycles per phase of rs_scatter_kernel, large array passes
+    bool no_local_sort;        // NOLZSS_NO_LOCAL_SORT: A/B switch, segmented passes instead of local_sort_kernel
+    bool local_sort_min_set;   // NOLZSS_LOCAL_SORT_MIN: smallest text / average record whose sub-buckets are sorted in LDS;
+    size_t local_sort_min;     // not set: the two defaults below
+    static constexpr size_t kLocalSortMinText = size_t(1) << 28;
+    static constexpr size_t kLocalSortMinRecord = size_t(1) << 20;
+    size_t local_min(size_t dflt) const { return local_sort_min_set ? local_sort_min : dflt; }
+    bool no_local_regroup;     // NOLZSS_NO_LOCAL_REGROUP: A/B switch, local_sort_kernel without the regroup of round 0 on the way
+    size_t local_regroup_min;  // NOLZSS_LOCAL_REGROUP_MIN: smallest text that takes the regroup on the way
+    bool test_local_order_fails;     // NOLZSS_TEST_LOCAL_ORDER_FAILS: (test hook) the redo path of a failed lane-order check
+    bool test_local_lookback_fails;  // NOLZSS_TEST_LOCAL_LOOKBACK_FAILS: (test hook) the look-back's flag is up before the kernel starts
+    uint64_t rec_bucket_min;   // NOLZSS_REC_BUCKET_MIN: smallest average record for the record sort and scatter plan (tiles cost 4096 / that)
+    bool text_order_hist;      // NOLZSS_TEXT_ORDER_HIST: A/B switch (and tests), the two-value permutation with histograms
+    long long text_order_esc;  // NOLZSS_TEXT_ORDER_ESC: (tests) lower escape threshold of the packed form (-1: not set)
+};
+const SortKnobs &sort_knobs();
+
 // Sorts n pairs by the key digits at the given bit offsets (least significant first;
 // each digit is kRadixBits wide).  keys[0]/vals[0] hold the input; the two buffers
 // ping-pong.  Returns the index (0 or 1) of the buffer pair that holds the sorted output.
@@ -76,6 +100,11 @@ int radix_sort_pairs(uint64_t *keys[2], uint32_t *vals[2], size_t n, const int *
                      int npasses, Arena &arena, hipStream_t stream, Profiler *prof = nullptr);
 int radix_sort_pairs(uint32_t *keys[2], uint32_t *vals[2], size_t n, const int *shifts,
                      int npasses, Arena &arena, hipStream_t stream, Profiler *prof = nullptr);
+
+// ONE pass by the digit at `shift` that keeps only the low 16 bits of every key: the last pass of a window permutation
+// (text_order.hip).  It lives with the sorts because its histogram kernel is the one every u32 sort uses.
+void radix_pass_low16(const uint32_t *keys, const uint32_t *vals, uint16_t *keys16_out, uint32_t *vals_out, size_t n, int shift,
+                      Arena &arena, hipStream_t stream, Profiler *prof = nullptr);
 
 // The round-0 sort of the suffix array: pairs (initial_key(i), i) for i < text.n, sorted by the given
 // digits.  The first pass computes the keys from the packed text on the fly (histogram and scatter
@@ -139,50 +168,5 @@ void radix_sort_record_keys(const PackedText &text, const std::vector<uint32_t> 
 // index of the buffer pair that holds the result.
 int radix_sort_segments_u32(uint32_t *keys[2], uint32_t *vals[2], size_t n, const std::vector<uint32_t> &h_start, int npasses,
                             Arena &arena, hipStream_t stream, Profiler *prof = nullptr);
-
-// out[idx[k]] = val[k] for k < count, idx[k] < n_out (entries with idx >= n_out are dropped).
-// A random 4-byte scatter over an array much larger than the caches costs a read-modify-write
-// of a whole line per element at HBM.  For large targets the pairs are therefore first
-// partitioned by the top 8 bits of idx (one radix pass, coalesced), then written bucket by
-// bucket so that all writes in flight fall into a window of n_out/256 entries that L2 /
-// Infinity Cache can merge into full lines (a permutation of the whole target is assembled
-// window by window in LDS instead).  idx[0]/val[0] hold the input, idx[1]/val[1] are scratch of
-// the same size.  With keep_input the input arrays survive (a third pair of buffers is taken
-// from the arena); otherwise they are used as scratch too.  The pointer arrays may be updated.
-// keep_val = false (with keep_input): only idx[0] survives, val[0] is used as a ping-pong buffer too.
-//
-// plan (optional): the target is a text of independent RECORDS and the pairs are (position, value) in suffix-
-// array order of such a text -- a block-diagonal permutation: the ranks of a record hold the positions of that
-// record (record_scatter_plan).  Then ONE segmented radix pass (the record is the bucket, the digit the window
-// inside the record) and the window scatter do it, 28 instead of 48 bytes per pair; idx[0] / val[0] survive,
-// idx[1] / val[1] are the only scratch.
-struct RecordScatterPlan {
-    SegView seg;                    // the base positions of every record as one bucket (ranks = positions)
-    const uint32_t *win = nullptr;  // per window: first list element, first target element, elements
-    uint32_t num_windows = 0;
-    const uint32_t *sep = nullptr;  // per separator: its rank (the first of its record) and its position
-    uint32_t num_seps = 0;
-    uint32_t n = 0;
-    int window_bits = 0;
-};
-// out2 (optional): a second target, out2[idx[k]] = k + 1 -- for the pairs (sa[r], code[r]) of the pipeline that is
-// the inverse suffix array in its 1-based form, delivered by the same permutation.  val[1] must then hold
-// 2 * count words (the pairs travel with 64-bit values).  A permutation of up to 2^30 targets then goes without
-// histograms, each pair in ONE 8-byte word whose code field holds 72 - 2 * nb bits or more; larger codes take an
-// exception list (and, should it overflow, the histogram form runs after all).  short_codes = false keeps the
-// histogram form: codes that are mostly large (a flag in bit 31) would only overflow the list.
-void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out,
-                      Arena &arena, hipStream_t stream, Profiler *prof, bool keep_input, bool keep_val = true,
-                      const RecordScatterPlan *plan = nullptr, uint32_t *out2 = nullptr, bool short_codes = true);
-// The same permutation for pairs that already carry both values in one 64-bit word (low half -> out, high half ->
-// out2) and are a permutation of [0, count): out[idx[k]] = (uint32_t)packed[k], out2[idx[k]] = packed[k] >> 32.
-// Both inputs are overwritten (they serve as buffers of the later passes).
-void permute_packed(uint32_t *idx, uint64_t *packed, size_t count, uint32_t *out, uint32_t *out2, Arena &arena,
-                    hipStream_t stream, Profiler *prof);
-// The plan for a text of n symbols whose records end at h_terms[k] (separator positions, the last entry = n);
-// false when the shape does not allow it (a record longer than 2^22 bases, or too many short ones).  The
-// tables live in the arena (not released here).
-bool record_scatter_plan(const std::vector<uint32_t> &h_terms, uint32_t n, Arena &arena, hipStream_t stream,
-                         RecordScatterPlan &plan);
 
 }  // namespace nolzss

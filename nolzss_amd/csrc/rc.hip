@@ -21,7 +21,7 @@
 #include "nearest_lds.hpp"
 #include "pipeline.hpp"
 #include "queues.hpp"
-#include "radix_sort.hpp"
+#include "text_order.hpp"
 #include "scan.hpp"
 
 namespace nolzss {
@@ -439,7 +439,7 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
             scan_exclusive_add_u32(tile_cnt, tile_off, tiles, nullptr, arena, s);
         } else {
             scratch_idx = arena.alloc<uint32_t>(m);
-            scratch_val = arena.alloc<uint32_t>(isa_deferred ? 2 * (size_t)m : (size_t)m);  // (two values per pair: radix_sort.hpp)
+            scratch_val = arena.alloc<uint32_t>(isa_deferred ? 2 * (size_t)m : (size_t)m);  // (two values per pair: text_order.hpp)
         }
         // the plain values by rank: in by_rank itself when the output is compact (by_rank then holds only the masks of
         // the far ranks, whose plain values come from rc_far_kernel), beside it otherwise (by_rank holds the codes)

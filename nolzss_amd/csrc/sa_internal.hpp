@@ -5,6 +5,7 @@
 #pragma once
 #include "pipeline.hpp"
 #include "radix_sort.hpp"
+#include "text_order.hpp"
 
 #include <type_traits>
 
@@ -53,13 +54,13 @@ template <class F> inline void dispatch_bits(int bits, F &&f) {
 // ---- knobs: every NOLZSS_* environment variable of the construction, read once at first use ------------------------
 // (ALL of them are frozen by the first reader, whichever file it is in -- on some paths inject_pending_for_test, called
 // from lpnf.hip and rc.hip: a variable set in the process after its first factorization is not seen.  The tests and
-// tools set them on child processes only.)
+// tools set them on child processes only.  The knobs of the sorts and of the text-order permutation, NOLZSS_REC_BUCKET_MIN
+// among them: SortKnobs, radix_sort.hpp.)
 struct SaKnobs {
     SaKnobs();
     bool trace;               // NOLZSS_TRACE: active-list sizes to stderr
     uint32_t dna_fast_min;    // NOLZSS_DNA_FAST_MIN: smallest text that takes the bucketed sort; the tests lower it
     bool no_key16;            // NOLZSS_NO_KEY16: A/B switch back to the 40-bit key [17 bases][6-bit tag]
-    uint64_t rec_bucket_min;  // NOLZSS_REC_BUCKET_MIN: smallest average record that takes the record sort; partial tiles cost 4096 / that
     bool no_defer;            // NOLZSS_NO_DEFER_ISA: A/B switch, rank[] is scattered although the direct rounds finish
     bool fused_sort;          // NOLZSS_FUSED_SORT: the 16-base key sort on fused 64-bit records, radix_sort.hip -- A/B switch
     bool regroup_phases;      // NOLZSS_REGROUP_PHASES: (diagnostics) cycles per phase of regroup_kernel

@@ -234,7 +234,6 @@ SaKnobs::SaKnobs() {
     trace = set("NOLZSS_TRACE");
     dna_fast_min = (uint32_t)i64("NOLZSS_DNA_FAST_MIN", 1ll << 20);
     no_key16 = set("NOLZSS_NO_KEY16");
-    rec_bucket_min = (uint64_t)i64("NOLZSS_REC_BUCKET_MIN", 1ll << 16);
     no_defer = set("NOLZSS_NO_DEFER_ISA");
     fused_sort = u32("NOLZSS_FUSED_SORT", 0u) != 0;
     regroup_phases = set("NOLZSS_REGROUP_PHASES");
@@ -284,8 +283,8 @@ KeyPlan plan_keys(const PackedText &text) {
     // (segmented texts with a short terminator table take it too: the reverse-complement string of one sequence)
     const bool key16 = dna_fast && !knobs.no_key16 && key16_applicable(text);
     // independent LONG records (text.hpp, kRecSyms): the records are the buckets of the segmented sort
-    const bool rec_fast = independent && !text.terms.mirror && n >= knobs.dna_fast_min && knobs.rec_bucket_min > 0 &&
-                          (uint64_t)text.terms.count * knobs.rec_bucket_min <= (uint64_t)n;
+    const bool rec_fast = independent && !text.terms.mirror && n >= knobs.dna_fast_min && sort_knobs().rec_bucket_min > 0 &&
+                          (uint64_t)text.terms.count * sort_knobs().rec_bucket_min <= (uint64_t)n;
     const bool fused = key16 && knobs.fused_sort && !text.segmented;
     p.choice = fused ? KeyPlan::kFused : key16 ? KeyPlan::kKey16 : dna_fast ? KeyPlan::kDnaFast : rec_fast ? KeyPlan::kRecFast
                : independent ? KeyPlan::kIndependent : text.segmented ? KeyPlan::kSegmented : KeyPlan::kGeneral;

@@ -451,7 +451,7 @@ print("ok", len(texts))
 
 
 _SWITCH_ENVS = [("NO_PERIODIC",), ("NO_PERIODIC", "NO_SEG_LARGE"), ("NO_PERIODIC", "NO_MID_SORT"), ("NO_DIRECT2",),
-                ("NO_EQUALISE",), ("NO_PIVOT",), ("NO_DEFER_ISA",), ("DNA_FAST_MIN", "NO_KEY16")]
+                ("NO_EQUALISE",), ("NO_PIVOT",), ("NO_DEFER_ISA",), ("DNA_FAST_MIN", "NO_KEY16"), ("DNA_FAST_MIN", "FUSED_SORT")]
 
 
 @pytest.mark.parametrize("switches", _SWITCH_ENVS, ids=["-".join(s).lower() for s in _SWITCH_ENVS])
@@ -460,7 +460,8 @@ def test_ab_switches_of_the_suffix_array_driver(switches):
     that is not the default: no periodic pass (whole runs reach the doubling rounds, whose large groups go through the
     segmented sort, the global sort, or -- without mid_sort_kernel -- both for every group of more than 64 members),
     no second direct round, no equalising round, no pivot rounds, rank[] scattered although the direct rounds finish,
-    the 40-bit key of the bucketed sort.  One child process per set of switches, with the cap of the first direct
+    the 40-bit key of the bucketed sort, the 16-base key sort on fused 64-bit records (radix_sort.hip,
+    radix_sort_dna_keys16_fused).  One child process per set of switches, with the cap of the first direct
     round lowered to 49 symbols (NOLZSS_REFINE_WORDS=1): runs, a Fibonacci word, collections of 20 / 130 / 1100
     similar sequences, repeats, an 8-bit and a 4-bit text, one prepared reverse-complement string.  Factors, suffix
     array, LCP and inverse suffix array against the oracle for every text.  (The texts were meant to stay under
@@ -513,11 +514,17 @@ for t in texts:
     checked += 1
 assert native.factorize_multiple_dna_w_rc(S) == oracle.factorize_multiple_dna_w_rc(S)
 print("ok", checked, "of", len(texts))
+native.profile_enable(True)
+native.profile_reset()
+native.factorize_array(texts[8])
+print("stages", " ".join(sorted(native.profile_report())))
 '''
     env = dict(os.environ, NOLZSS_REFINE_WORDS="1", NOLZSS_TRACE="1", **{"NOLZSS_" + k: "1" for k in switches})
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ok 12 of 12" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]  # no text skipped
+    if "FUSED_SORT" in switches:  # the fused-record passes ran (their profiler class) on the plain DNA text
+        assert "rs_scatter.rec" in r.stdout.splitlines()[-1].split(), r.stdout[-2000:]
     if "NO_PERIODIC" in switches:
         large = [int(line.split(":")[1].split()[0]) for line in r.stderr.splitlines() if "doubling round h=" in line]
         assert any(x > 0 for x in large), large  # the large-group branches of the doubling rounds ran

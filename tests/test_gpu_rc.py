@@ -159,7 +159,7 @@ def test_rc_six_million_bases_every_factor(native):
     """6 M bases with copied blocks (and their reverse complements, which RC mode finds): above 2^22 bases the
     candidate kernel hands only the ranks of the original strand to the permutation that brings codes and ranks
     into text order, and that permutation takes its two partition passes and the LDS windows (rc.hip,
-    radix_sort.hip: permute_packed) -- the path of BASELINE config 5, here at a size the oracle finishes in seconds."""
+    text_order.hip: permute_packed) -- the path of BASELINE config 5, here at a size the oracle finishes in seconds."""
     t = gen.repeat_dna(6_000_000, seed=0x5EED0005 + 17)
     got = native.factorize_dna_w_rc_array(t)
     S, _, _ = oracle.prepare_multiple_dna_w_rc([t.tobytes()])

@@ -8,7 +8,7 @@
 //
 // This program measures that mechanism alone at the scatter kernel's own tile rate: 2^18 tiles of 256 threads
 // (thread = bin), the scatter kernel's LDS footprint (so the same 3 workgroups per CU are resident), the XCD chunk
-// mapping of radix_sort.hip, and in place of the loads / ranking / writes of a tile two timed waits that make the
+// mapping of radix_pass.hpp, and in place of the loads / ranking / writes of a tile two timed waits that make the
 // launch WITHOUT look-back as long as the real kernel.  Reported: launch time without and with the look-back, rows
 // read per tile and bin, the longest walk.  Every spin is bounded: a walk that waits too long sets an error flag and
 // the tile leaves (no launch can hang).
