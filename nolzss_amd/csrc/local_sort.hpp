@@ -56,7 +56,9 @@ __global__ __launch_bounds__(kBins) void sub_starts_kernel(const uint32_t *__res
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // block_scan_exclusive (common.hpp) on lds_barrier(); w / lane: the caller's wave number and lane
-template <int NW>
+// (kFreshCompares: the comparisons with the wave number are made anew as well -- hoisted they are twelve lane masks, which
+// the form of the kernel with 1024-bin digits has no scalar registers for)
+template <int NW, bool kFreshCompares = false>
 __device__ __forceinline__ uint32_t block_scan_exclusive_add_lds(uint32_t v, uint32_t *lds, int w, int lane) {
     const uint32_t inc = wave_scan_inclusive_dpp(v, 0u, OpAdd<uint32_t>());
     // (the address is made anew every time: hoisted out of the loop over the sub-buckets it was spilled, and the reload from
@@ -69,7 +71,7 @@ __device__ __forceinline__ uint32_t block_scan_exclusive_add_lds(uint32_t v, uin
 #pragma unroll
     for (int k = 0; k < NW; ++k) {
         const uint32_t t = lds[k];
-        if (k < w) prefix += t;
+        if (k < (kFreshCompares ? ww : w)) prefix += t;
     }
     lds_barrier();
     return prefix + inc - v;
@@ -222,8 +224,26 @@ __device__ __forceinline__ void local_zero4(uint4 *p) {
     asm volatile("v_mov_b32 %0, 0" : "=v"(z));
     *p = make_uint4(z, z, z, z);
 }
+// ... to kQuads quads 64 quads apart (a wave's counters, one quad per lane and store), out of the same four registers
+template <int kQuads> __device__ __forceinline__ void local_zero4s(uint4 *p) {
+    if constexpr (kQuads == 1) {
+        local_zero4(p);
+    } else {
+        uint32_t z;
+        asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+        const uint4 z4 = make_uint4(z, z, z, z);
+#pragma unroll
+        for (int j = 0; j < kQuads; ++j) p[j * 64] = z4;
+    }
+}
 
-template <int NPASS, bool kFuse = false>
+// digit of `bits` bits (a compile-time constant where it is called) at a bit offset
+__device__ __forceinline__ uint32_t local_digit(uint32_t k, int shift, int bits) { return (k >> shift) & ((1u << bits) - 1u); }
+
+// kKey35: the stored word is [27 key bits][5-bit tag] (text.hpp, kP35Syms) and the 19 bits between the tag and the
+// sub-bucket's byte are ranked as TWO digits of kP35Digit0 and kP35Digit1 bits -- in LDS a digit of 1024 bins costs
+// counters (48 KiB for the twelve waves) and a wider offset phase, not a pass.  Otherwise every digit has 8 bits.
+template <int NPASS, bool kFuse = false, bool kKey35 = false>
 __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
     const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, uint32_t *__restrict__ keys_out,
     uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ sub_start, uint32_t num_sub, int shift0,
@@ -241,7 +261,12 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
 #define LOCAL_CK(slot)
 #endif
     __shared__ __align__(16) uint32_t s_stage[kLocalCap + 4];  // keys, then values, take turns
-    __shared__ __align__(16) uint32_t s_whist[kLocalWaves * kBins];
+    static_assert(!kKey35 || NPASS == 2, "the 35-bit key has two digits below the sub-bucket");
+    constexpr int kW0 = kKey35 ? kP35Digit0 : kRadixBits, kW1 = kKey35 ? kP35Digit1 : kRadixBits;
+    constexpr int kMaxBins = 1 << (kW0 > kW1 ? kW0 : kW1);  // counters per wave
+    constexpr uint32_t kTagMask = kKey35 ? (1u << kP35TagBits) - 1u : 0xffu, kShortTag = kKey35 ? (uint32_t)kP35Syms : (uint32_t)kP16Syms;
+    constexpr int kTagBits = kKey35 ? kP35TagBits : kP16TagBits;
+    __shared__ __align__(16) uint32_t s_whist[kLocalWaves * kMaxBins];
     __shared__ uint32_t s_scan[kLocalWaves];
     // (kFuse) per 64 places in place order: tied elements, place of the last head + 1 (then their exclusive prefixes);
     // first key, last key, tied elements in front of the sub-bucket
@@ -251,9 +276,9 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
     const int tid = threadIdx.x;
     const int w = tid >> 6;
     const int lane = tid & 63;
-    uint32_t *wcount = s_whist + w * kBins;  // this wave's counters: zeroed by the wave itself after every use
-    local_zero4(reinterpret_cast<uint4 *>(wcount) + lane);
-    static_assert(kBins == 256, "four counters per lane");
+    uint32_t *wcount = s_whist + w * kMaxBins;  // this wave's counters: zeroed by the wave itself after every use
+    static_assert(kMaxBins % 256 == 0, "four counters per lane and store");
+    local_zero4s<kMaxBins / 256>(reinterpret_cast<uint4 *>(wcount) + lane);
 
     uint32_t sub = blockIdx.x, first, count, cur_sub;
     local_next(sub_start, num_sub, sub, first, count, ctl, large_list, tid, cur_sub);
@@ -261,7 +286,13 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
     local_load(keys_in, first, count, (int)((count + kLocalThreads - 1) / kLocalThreads), key, tid);
     bool order_ok = true;
     bool preset_failure = false;  // (test hook NOLZSS_TEST_LOCAL_LOOKBACK_FAILS: the flag is up before the kernel starts)
-    if constexpr (kFuse) preset_failure = __hip_atomic_load(F.d_total + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+    if constexpr (kFuse) {
+        const uint32_t flag = __hip_atomic_load(F.d_total + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (kKey35)  // (one value for everybody: a scalar register, where this form has no vector register left)
+            preset_failure = __builtin_amdgcn_readfirstlane((int)flag) != 0;
+        else
+            preset_failure = flag != 0u;
+    }
     while (count) {  // (uniform)
         // this sub-bucket's values (wanted when its keys have been ranked once) and the NEXT one's keys are asked for
         // before anything else (the values of the next one, too, took the registers over the edge: a prefetched value
@@ -284,7 +315,9 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
         uint32_t lrank[kLocalRows];
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
-            const int shift = shift0 + pass * kRadixBits;
+            // (constants once the loop is unrolled)
+            const int bits = pass == 0 ? kW0 : (pass == 1 ? kW1 : kRadixBits);
+            const int shift = shift0 + (pass == 0 ? 0 : (pass == 1 ? kW0 : kW0 + kW1));
             // (keys of all ones behind the end of the sub-bucket: last in input order and in the last bin of every digit,
             // they stay behind its pairs through every stable pass -- no masks)
             if (pass == 0) {
@@ -294,7 +327,7 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
             }
 #pragma unroll
             for (int r = 0; r < kLocalRows; ++r)
-                if (r < rows) lrank[r] = atomicAdd(&wcount[digit_of(key[r], shift)], 1u);
+                if (r < rows) lrank[r] = atomicAdd(&wcount[local_digit(key[r], shift, bits)], 1u);
             if (pass == 0 && !kFuse) {
                 // This sub-bucket's values and the next one's keys are asked for HERE, behind the first ranking's atomics:
                 // finding the next sub-bucket (two scalar loads) and issuing 48 loads took 8 k cycles at the start of
@@ -306,10 +339,11 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
                 LOCAL_CK(1)  // its keys asked for
             }
             {  // the lane-order check on row 0 (its counters started at zero)
-                const uint32_t d = digit_of(key[0], shift);
+                const uint32_t d = local_digit(key[0], shift, bits);
                 uint32_t diff_lo = 0, diff_hi = 0;
 #pragma unroll
-                for (int b = 0; b < kRadixBits; ++b) {
+                for (int b = 0; b < (kW0 > kW1 ? kW0 : kW1); ++b) {  // (every bit of the digit)
+                    if (b >= bits) break;
                     const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)d, (unsigned)b, 1u);
                     const uint64_t bal = __ballot((int)m < 0);
                     diff_lo = __builtin_amdgcn_bitop3_b32(m, diff_lo, (uint32_t)bal, 0xde);
@@ -321,7 +355,47 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
             LOCAL_CK(2 + 8 * pass)  // ranked (wave 0)
             lds_barrier();
             LOCAL_CK(3 + 8 * pass)  // ... everybody
-            {  // thread = bin (the first kBins threads): per-wave counts -> start positions in the sub-bucket
+            if constexpr (kKey35) {
+                // per-wave counts -> start positions in the sub-bucket, 512 or 1024 bins on kLocalThreads threads: the first
+                // (bins - threads) threads own two neighbouring bins each, the others one (bins in thread order: one scan).
+                // The counts are read again where the positions are written: no array of them in registers.
+                const int bins = 1 << bits;
+                const int extra = bins > kLocalThreads ? bins - kLocalThreads : 0;
+                // (made anew every time, as the address in block_scan_exclusive_add_lds: what depends on the thread alone is
+                // hoisted out of the loop over the sub-buckets, and this kernel has no register to keep it in)
+                int tt = tid;
+                asm volatile("" : "+v"(tt));
+                const int d0 = tt < extra ? 2 * tt : tt + extra;
+                const bool own0 = d0 < bins, own1 = tt < extra;
+                uint32_t t0 = 0, t1 = 0;
+#pragma unroll
+                for (int k = 0; k < kLocalWaves; ++k) t0 += own0 ? s_whist[k * kMaxBins + d0] : 0u;
+                if (extra) {
+                    // (the second dozen of reads behind the first: two dozen at once are a dozen registers this kernel does not have)
+                    asm volatile("" : "+v"(t0) : : "memory");
+#pragma unroll
+                    for (int k = 0; k < kLocalWaves; ++k) t1 += own1 ? s_whist[k * kMaxBins + d0 + 1] : 0u;
+                }
+                const uint32_t bin_start = block_scan_exclusive_add_lds<kLocalWaves, true>(t0 + t1, s_scan, w, lane);
+                if (own0) {
+                    uint32_t run = bin_start;
+#pragma unroll
+                    for (int k = 0; k < kLocalWaves; ++k) {
+                        const uint32_t c = s_whist[k * kMaxBins + d0];
+                        s_whist[k * kMaxBins + d0] = run;
+                        run += c;
+                    }
+                }
+                if (extra && own1) {
+                    uint32_t run = bin_start + t0;
+#pragma unroll
+                    for (int k = 0; k < kLocalWaves; ++k) {
+                        const uint32_t c = s_whist[k * kMaxBins + d0 + 1];
+                        s_whist[k * kMaxBins + d0 + 1] = run;
+                        run += c;
+                    }
+                }
+            } else {  // thread = bin (the first kBins threads): per-wave counts -> start positions in the sub-bucket
                 const int d = tid & (kBins - 1);
                 const bool owner = tid < kBins;
                 uint32_t c[kLocalWaves], total = 0;
@@ -344,8 +418,14 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
             LOCAL_CK(4 + 8 * pass)  // offsets
 #pragma unroll
             for (int r = 0; r < kLocalRows; ++r)
-                if (r < rows) lrank[r] += wcount[digit_of(key[r], shift)];
-            local_zero4(reinterpret_cast<uint4 *>(wcount) + lane);  // (after the wave's own reads, before its next atomics)
+                if (r < rows) lrank[r] += wcount[local_digit(key[r], shift, bits)];
+            // (after the wave's own reads, before its next atomics: the counters this pass has used)
+            if (bits == kRadixBits)
+                local_zero4s<1>(reinterpret_cast<uint4 *>(wcount) + lane);
+            else if (bits == 9)
+                local_zero4s<2>(reinterpret_cast<uint4 *>(wcount) + lane);
+            else
+                local_zero4s<4>(reinterpret_cast<uint4 *>(wcount) + lane);
             if constexpr (kFuse) {
                 if (pass + 1 == NPASS) {
                     // The last digit with the regroup of round 0 on the way.  The VALUES go first: their stores are
@@ -389,16 +469,17 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
                             const bool valid = pl < count;
                             const uint32_t pk = (uint32_t)__builtin_amdgcn_update_dpp((int)edge[u], (int)k[u], 0x138, 0xf, 0xf, false);  // wave_shr:1
                             const uint32_t nk = (uint32_t)__builtin_amdgcn_update_dpp((int)edge[u], (int)k[u], 0x130, 0xf, 0xf, false);  // wave_shl:1
-                            // (a suffix that ends inside the key window -- tag < 16 -- ties with nobody: a head, and so is
+                            // (a suffix that ends inside the key window -- tag < 16, or < 17 with the 35-bit key -- ties with nobody: a head, and so is
                             // whoever follows it; the first place of a sub-bucket is a head, and so is the one behind its last.
                             // Bitwise & and | on purpose: with && and || every condition became a branch on the lane mask,
                             // a hundred instructions per row of places.)
-                            const bool head = valid & ((pl == 0u) | (k[u] != pk) | ((k[u] & 0xffu) < (uint32_t)kP16Syms));
-                            const bool nhead = (pl + 1u >= count) | (nk != k[u]) | ((nk & 0xffu) < (uint32_t)kP16Syms);
+                            const bool head = valid & ((pl == 0u) | (k[u] != pk) | ((k[u] & kTagMask) < kShortTag));
+                            const bool nhead = (pl + 1u >= count) | (nk != k[u]) | ((nk & kTagMask) < kShortTag);
                             const bool keep = valid & !(head & nhead);
                             {  // (place 0: below, with the last key of the sub-bucket in front)
-                                const uint32_t y = (k[u] ^ pk) >> kP16TagBits, ta = k[u] & 0xffu, tb = pk & 0xffu;
-                                uint32_t ls = (uint32_t)__clz((int)y) >> 1;  // (y = 0: 16, and no tag is larger)
+                                const uint32_t y = (k[u] ^ pk) >> kTagBits, ta = k[u] & kTagMask, tb = pk & kTagMask;
+                                // (four bases of the bucket in front of the 24 or 27 stored key bits; y = 0: 16 or 17, and no tag is larger)
+                                uint32_t ls = kKey35 ? ((uint32_t)__clz((int)y) + 3u) >> 1 : (uint32_t)__clz((int)y) >> 1;
                                 ls = ls < ta ? ls : ta;
                                 ls = ls < tb ? ls : tb;
                                 const uint32_t l = head ? ls : kLcpPendingCode;
@@ -470,9 +551,15 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
                                     __builtin_amdgcn_s_sleep(1);
                                 }
                                 const uint32_t pk = (uint32_t)d, k = s_edge[0];
-                                const uint32_t y = ((bucket ^ (F.prev_sub[cur_sub] >> 8)) << 24) | ((k ^ pk) >> kP16TagBits);
-                                const uint32_t ta = k & 0xffu, tb = pk & 0xffu;
-                                uint32_t ls = y ? (uint32_t)__builtin_clz(y) >> 1 : 0xffffffffu;
+                                uint32_t ls;
+                                if constexpr (kKey35) {  // (8 + 27 key bits)
+                                    const uint64_t y = ((uint64_t)(bucket ^ (F.prev_sub[cur_sub] >> 8)) << (32 - kTagBits)) | (uint64_t)((k ^ pk) >> kTagBits);
+                                    ls = y ? (uint32_t)(__builtin_clzll(y) - (64 - kP35KeyBits)) >> 1 : 0xffffffffu;
+                                } else {
+                                    const uint32_t y = ((bucket ^ (F.prev_sub[cur_sub] >> 8)) << 24) | ((k ^ pk) >> kTagBits);
+                                    ls = y ? (uint32_t)__builtin_clz(y) >> 1 : 0xffffffffu;
+                                }
+                                const uint32_t ta = k & kTagMask, tb = pk & kTagMask;
                                 ls = ls < ta ? ls : ta;
                                 l0 = ls < tb ? ls : tb;
                             }
@@ -617,7 +704,11 @@ std::atomic<bool> local_sort_off{false};  // a lane-order check of local_sort_ke
 // a workgroup's capacity go through segmented passes.  keys_in / vals_in are scratch afterwards.
 void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out, const uint32_t *scanned,
                             const uint32_t *tile0, const uint32_t *bstart, uint32_t num_buckets, int shift0, int npass, size_t n,
-                            Arena &arena, hipStream_t stream, Profiler *prof, Round0Regroup *rg = nullptr) {
+                            Arena &arena, hipStream_t stream, Profiler *prof, Round0Regroup *rg = nullptr, bool key35 = false) {
+    if (key35 && (npass != 2 || shift0 != kP35TagBits)) throw HipError("local_sort_sub_buckets: the 35-bit key has two digits above its tag");
+    // (segmented passes have 8-bit digits: the 19 bits of the 35-bit key take three, the top one reading five bits that are
+    // constant inside a sub-bucket)
+    const int seg_passes = key35 ? 3 : npass;
     const uint32_t num_sub = num_buckets * (uint32_t)kBins;
     uint32_t *sub_start = arena.alloc<uint32_t>((size_t)num_sub + 1);
     uint32_t *large_list = arena.alloc<uint32_t>(num_sub);
@@ -674,8 +765,12 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
             F.desc = dd; F.lastkey = dd + F.nq; F.dense = dense; F.prev_sub = prev_sub;
             {
                 ProfScope ps(prof, "rs_local_sort", stream, 16.0 * (double)n);  // (pairs in; suffixes and LCP out; the tied elements come on top)
-                local_sort_kernel<2, true><<<grid, kLocalThreads, 0, stream>>>(keys_in, vals_in, keys_out, vals_out, sub_start, num_sub, shift0,
-                                                                               ctl, large_list, d_ph, F);
+                if (key35)
+                    local_sort_kernel<2, true, true><<<grid, kLocalThreads, 0, stream>>>(keys_in, vals_in, keys_out, vals_out, sub_start, num_sub,
+                                                                                         shift0, ctl, large_list, d_ph, F);
+                else
+                    local_sort_kernel<2, true><<<grid, kLocalThreads, 0, stream>>>(keys_in, vals_in, keys_out, vals_out, sub_start, num_sub, shift0,
+                                                                                   ctl, large_list, d_ph, F);
                 KERNEL_CHECK();
             }
             uint32_t h_c[4], h_t[2];
@@ -696,7 +791,10 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
     }
     {
         ProfScope ps(prof, "rs_local_sort", stream, 16.0 * (double)n);
-        if (npass == 2)
+        if (key35)
+            local_sort_kernel<2, false, true><<<grid, kLocalThreads, 0, stream>>>(keys_in, vals_in, keys_out, vals_out, sub_start, num_sub, shift0,
+                                                                                  ctl, large_list, d_ph);
+        else if (npass == 2)
             local_sort_kernel<2><<<grid, kLocalThreads, 0, stream>>>(keys_in, vals_in, keys_out, vals_out, sub_start, num_sub, shift0, ctl,
                                                                      large_list, d_ph);
         else if (npass == 3)
@@ -758,7 +856,7 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
     big.desc = big_mem;
     uint32_t *big_hist = arena.alloc<uint32_t>((size_t)kBins * big.num_tiles);
     uint32_t *kbuf[2] = {keys_in, keys_out}, *vbuf[2] = {vals_in, vals_out};
-    for (int p = 0; p < npass; ++p) {
+    for (int p = 0; p < seg_passes; ++p) {
         const ArraySrc<uint32_t> src{kbuf[p & 1], vbuf[p & 1]};
         const int shift = shift0 + 8 * p;
         rs_hist_kernel<uint32_t, ArraySrc<uint32_t>><<<xcd_grid(big.num_tiles), kThreads, 0, stream>>>(src, n, shift, big_hist, big.num_tiles, big);
@@ -770,7 +868,7 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
             src, kbuf[(p & 1) ^ 1], vbuf[(p & 1) ^ 1], n, shift, big_hist, big.num_tiles, big);
         KERNEL_CHECK();
     }
-    if ((npass & 1) == 0) {
+    if ((seg_passes & 1) == 0) {
         seg_copy_kernel<<<big.num_tiles, kThreads, 0, stream>>>(keys_in, vals_in, keys_out, vals_out, big);
         KERNEL_CHECK();
     }

@@ -2,7 +2,7 @@
 // digits, (u64 or u32 key, u32 value) pairs), for gfx950:
 //   * radix_sort_pairs, and radix_pass_low16 for the window permutation of text_order.hip;
 //   * the round-0 key sorts of the suffix array, whose first pass computes its pairs from the packed text (TextSrc,
-//     Text16Src, Text16SegSrc, RecordTextSrc): radix_sort_initial_keys, radix_sort_dna_keys, radix_sort_dna_keys16 (and
+//     Text16Src, Text35Src, Text16SegSrc, RecordTextSrc): radix_sort_initial_keys, radix_sort_dna_keys, radix_sort_dna_keys16 (and
 //     its fused-record A/B variant, rs_scatter_rec_kernel), radix_sort_record_keys;
 //   * radix_sort_segments_u32.
 // The bucketed sorts run SEGMENTED passes -- tiles that never straddle the buckets of an earlier most-significant-digit
@@ -27,6 +27,7 @@ SortKnobs::SortKnobs() {
     local_sort_min_set = set("NOLZSS_LOCAL_SORT_MIN");
     local_sort_min = (size_t)i64("NOLZSS_LOCAL_SORT_MIN", 0);
     no_local_regroup = set("NOLZSS_NO_LOCAL_REGROUP");
+    no_key35 = set("NOLZSS_NO_KEY35");
     local_regroup_min = (size_t)i64("NOLZSS_LOCAL_REGROUP_MIN", 3ll << 28);
     test_local_order_fails = set("NOLZSS_TEST_LOCAL_ORDER_FAILS");
     test_local_lookback_fails = set("NOLZSS_TEST_LOCAL_LOOKBACK_FAILS");
@@ -108,6 +109,17 @@ struct Text16Src {
     __device__ __forceinline__ uint32_t window_digit(uint64_t w, int j, size_t idx0) const {
         const int jj = idx0 == 0 ? 15 - j : j;
         return (uint32_t)((w >> (64 - kRadixBits - 2 * jj)) & (uint64_t)(kBins - 1));
+    }
+};
+// The same pass with the 35-bit key of text.hpp (kP35Syms): the value handed to the kernels is [35 key bits][5-bit tag],
+// its digit (shift 32) the first four bases as before, the stored low 32 bits [27 key bits][tag].  The elements and their
+// order are Text16Src's: the suffixes that are short here (tag < 17) are the 16 it takes first.
+struct Text35Src : Text16Src {
+    __device__ __forceinline__ uint64_t key_of(const Raw &raw, size_t idx, const TileExtent &) const {
+        const uint32_t s = suffix_of(idx);
+        const uint32_t lim = n - s;
+        const uint32_t tag = lim < (uint32_t)kP35Syms ? lim : (uint32_t)kP35Syms;
+        return ((sym_word_of<2>(raw, s) >> (64 - kP35KeyBits)) << kP35TagBits) | tag;
     }
 };
 // The same pass for a SEGMENTED text with a short terminator table (at most kTermFew entries: a prepared reverse-
@@ -555,6 +567,19 @@ bool key16_applicable(const PackedText &text) {
 }
 
 namespace {
+// does radix_sort_dna_keys16 finish the sub-buckets of this text in LDS?
+bool local_sort_applies(size_t n) {
+    const SortKnobs &knobs = sort_knobs();
+    return !knobs.no_local_sort && !local_sort_off.load() && n >= knobs.local_min(SortKnobs::kLocalSortMinText) &&
+           n <= (size_t)kBins * kBins * kLocalCap / 16 * 15;
+}
+}  // namespace
+
+bool key35_applicable(const PackedText &text) {
+    return !sort_knobs().no_key35 && key16_applicable(text) && !text.segmented && local_sort_applies(text.n);
+}
+
+namespace {
 Text16SegSrc make_text16_seg(const PackedText &text) {
     Text16SegSrc src{};
     src.words = text.words;
@@ -570,7 +595,7 @@ Text16SegSrc make_text16_seg(const PackedText &text) {
 }  // namespace
 
 void radix_sort_dna_keys16(const PackedText &text, uint32_t *keys32[2], uint32_t *vals[2], uint32_t *seg_mem,
-                           SegView &seg_out, Arena &arena, hipStream_t stream, Profiler *prof, Round0Regroup *regroup) {
+                           SegView &seg_out, Arena &arena, hipStream_t stream, Profiler *prof, Round0Regroup *regroup, bool key35) {
     if (regroup) regroup->done = false;
     const size_t n = text.n;
     if (!key16_applicable(text)) throw HipError("radix_sort_dna_keys16: plain 2-bit texts, or segmented ones with a short terminator table");
@@ -583,21 +608,27 @@ void radix_sort_dna_keys16(const PackedText &text, uint32_t *keys32[2], uint32_t
     // Two ways from here (both end in keys32[0] / vals[0]): three bucket-segmented passes, or ONE and the sub-buckets it
     // makes sorted in LDS (local_sort_kernel) -- for texts whose 65 536 sub-buckets are large enough to pay for a
     // workgroup each and small enough to fit one (NOLZSS_NO_LOCAL_SORT, NOLZSS_LOCAL_SORT_MIN = smallest such text).
-    const SortKnobs &knobs = sort_knobs();
-    const bool local = !knobs.no_local_sort && !local_sort_off.load() && n >= knobs.local_min(SortKnobs::kLocalSortMinText) && n <= (size_t)kBins * kBins * kLocalCap / 16 * 15;
+    // (the 35-bit key exists on the second way only, and the caller's plan has chosen it: key35_applicable)
+    if (key35 && text.segmented) throw HipError("radix_sort_dna_keys16: the 35-bit key is for plain texts");
+    const bool local = key35 || local_sort_applies(n);
     const int msd_to = local ? 0 : 1;
     // most significant digit first: the first four bases (bits 32..39 of [32 key bits][8-bit tag])
     if (text.segmented)
         radix_pass<uint64_t, uint32_t>(make_text16_seg(text), keys32[msd_to], vals[msd_to], n, 32, hist, tiles0, text_bytes,
+                                       text_bytes + 8.0 * (double)n, arena, stream, prof);
+    else if (key35)
+        radix_pass<uint64_t, uint32_t>(Text35Src{{text.words, (uint32_t)n}}, keys32[msd_to], vals[msd_to], n, 32, hist, tiles0, text_bytes,
                                        text_bytes + 8.0 * (double)n, arena, stream, prof);
     else
         radix_pass<uint64_t, uint32_t>(Text16Src{text.words, (uint32_t)n}, keys32[msd_to], vals[msd_to], n, 32, hist, tiles0, text_bytes,
                                        text_bytes + 8.0 * (double)n, arena, stream, prof);
     seg_out = seg_view_of_msd_pass(hist, tiles0, n, tabs, seg_mem, arena, stream);
     if (local) {
-        // the digit below the bucket's (four more bases) first, then every sub-bucket by the 16 bits between it and the tag
-        segmented_lsd_passes(keys32, vals, 0, n, kP16TagBits + 16, 1, hist, seg_out, arena, stream, prof);
-        local_sort_sub_buckets(keys32[1], vals[1], keys32[0], vals[0], hist, tile0, bstart, (uint32_t)kBins, kP16TagBits, 2, n, arena, stream, prof, regroup);
+        // the digit below the bucket's (four more bases: the top byte of the stored word in both layouts) first, then
+        // every sub-bucket by the 16 or 19 bits between it and the tag
+        segmented_lsd_passes(keys32, vals, 0, n, 24, 1, hist, seg_out, arena, stream, prof);
+        local_sort_sub_buckets(keys32[1], vals[1], keys32[0], vals[0], hist, tile0, bstart, (uint32_t)kBins, key35 ? kP35TagBits : kP16TagBits, 2, n,
+                               arena, stream, prof, regroup, key35);
         arena.rewind(m);
         return;
     }

@@ -83,6 +83,7 @@ struct SortKnobs {
     size_t local_min(size_t dflt) const { return local_sort_min_set ? local_sort_min : dflt; }
     bool no_local_regroup;     // NOLZSS_NO_LOCAL_REGROUP: A/B switch, local_sort_kernel without the regroup of round 0 on the way
     size_t local_regroup_min;  // NOLZSS_LOCAL_REGROUP_MIN: smallest text that takes the regroup on the way
+    bool no_key35;             // NOLZSS_NO_KEY35: A/B switch, the 16-base key where the 35-bit key would be taken
     bool test_local_order_fails;     // NOLZSS_TEST_LOCAL_ORDER_FAILS: (test hook) the redo path of a failed lane-order check
     bool test_local_lookback_fails;  // NOLZSS_TEST_LOCAL_LOOKBACK_FAILS: (test hook) the look-back's flag is up before the kernel starts
     uint64_t rec_bucket_min;   // NOLZSS_REC_BUCKET_MIN: smallest average record for the record sort and scatter plan (tiles cost 4096 / that)
@@ -136,6 +137,7 @@ bool key16_applicable(const PackedText &text);
 // sort itself: where the sub-buckets are finished in LDS the sorted keys are at hand -- LCP of every boundary the keys
 // decide (0xffffffff = pending elsewhere), the elements that stay tied (slot and slot of their group's head, in slot
 // order) and their number.  `done` says whether the sort did it (the keys are then NOT written).
+// (with the 35-bit key, key35 below, its layout is 4)
 struct Round0Regroup {
     uint32_t *lcp = nullptr;
     uint32_t *new_slot = nullptr, *new_grp = nullptr;
@@ -144,7 +146,12 @@ struct Round0Regroup {
 };
 void radix_sort_dna_keys16(const PackedText &text, uint32_t *keys32[2], uint32_t *vals[2], uint32_t *seg_mem,
                            SegView &seg_out, Arena &arena, hipStream_t stream, Profiler *prof = nullptr,
-                           Round0Regroup *regroup = nullptr);
+                           Round0Regroup *regroup = nullptr, bool key35 = false);
+// The 35-bit key (text.hpp, kP35Syms; stored word [27 key bits][5-bit tag]): taken by plain one-segment texts exactly
+// where radix_sort_dna_keys16 finishes the sub-buckets in LDS, whose two digits then have 10 and 9 bits -- the same
+// passes and records, 17 1/2 bases sorted instead of 16 (NOLZSS_NO_KEY35 keeps the 16-base key).  The caller asks here
+// and passes the answer on as key35: the regroup and the direct round behind the sort must know the layout.
+bool key35_applicable(const PackedText &text);
 
 // The same sort on FUSED records [stored key word : 32 | suffix : 32] (round 4, A/B: NOLZSS_FUSED_SORT): rec[0] and rec[1]
 // hold n 64-bit words each; the last pass writes the suffixes to sa_out and the key words to rec[0] (as 32-bit words).

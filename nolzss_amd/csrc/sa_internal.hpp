@@ -89,8 +89,8 @@ const SaKnobs &sa_knobs();
 
 // ---- round 0: one plan for the key sort and the regroup behind it ---------------------------------------------------
 struct KeyPlan {
-    // fused / key16 / dna_fast / rec_fast name their sort in radix_sort.hpp; the other three take the general sort
-    enum Choice { kFused, kKey16, kDnaFast, kRecFast, kIndependent, kSegmented, kGeneral } choice = kGeneral;
+    // fused / key16 / key35 / dna_fast / rec_fast name their sort in radix_sort.hpp; the other three take the general sort
+    enum Choice { kFused, kKey16, kKey35, kDnaFast, kRecFast, kIndependent, kSegmented, kGeneral } choice = kGeneral;
     int seq_bits = 0;                            // independent sequences: bits of the sequence number above the key
     int key_bits = 0, key_passes = 0;            // populated low bits of the key, radix passes over them
     int cur = 0;                                 // the buffer the sorted keys end in (the suffixes end in sa)

@@ -162,16 +162,17 @@ __device__ __forceinline__ uint32_t lane_next(uint32_t v, uint32_t edge) {
 // shifts and masks of every item (the kernel is bound by VALU issue: ~1300 instructions per wavefront and 512
 // suffixes).  1 = plain DNA: 34 symbol bits, 6-bit tag, no low bits, no sequence numbers, short suffixes flagged;
 // 2 = long independent records, bucket = record: 28 symbol bits, 4-bit tag, the record number above bit 32;
-// 3 = plain DNA with the 16-base key: 32 symbol bits (bucket + 24 stored bits), the tag in the low byte of the stored word.
+// 3 = plain DNA with the 16-base key: 32 symbol bits (bucket + 24 stored bits), the tag in the low byte of the stored word;
+// 4 = plain DNA with the 35-bit key: 35 "symbol" bits (bucket + 27 stored bits, 17 1/2 bases), a 5-bit tag, short below 17.
 template <bool kRound0, int kLayout>
 __global__ __launch_bounds__(kFuseThreads) void regroup_kernel(RegroupArgs A) {
     constexpr bool kDnaFast = kLayout != 0;  // (bucketed, compile-time layout)
     const int low_bits = kDnaFast ? 0 : A.low_bits;
-    const int tag_bits = kLayout == 1 ? KeyLayout<2>::kTagBits : (kLayout == 2 ? kRecTagBits : (kLayout == 3 ? kP16TagBits : A.tag_bits));
-    const int sym_bits = kLayout == 1 ? 2 * KeyLayout<2>::kSyms : (kLayout == 2 ? 2 * kRecSyms : (kLayout == 3 ? 2 * kP16Syms : A.sym_bits));
+    const int tag_bits = kLayout == 1 ? KeyLayout<2>::kTagBits : (kLayout == 2 ? kRecTagBits : (kLayout == 3 ? kP16TagBits : (kLayout == 4 ? kP35TagBits : A.tag_bits)));
+    const int sym_bits = kLayout == 1 ? 2 * KeyLayout<2>::kSyms : (kLayout == 2 ? 2 * kRecSyms : (kLayout == 3 ? 2 * kP16Syms : (kLayout == 4 ? kP35KeyBits : A.sym_bits)));
     const int bits_shift = kDnaFast ? 1 : A.bits_shift;
-    const uint32_t short_tag = kLayout == 1 ? (uint32_t)KeyLayout<2>::kSyms : (kLayout == 2 ? 0u : (kLayout == 3 ? (uint32_t)kP16Syms : A.short_tag));
-    const uint32_t seq_shift = (kLayout == 1 || kLayout == 3) ? 0u : (kLayout == 2 ? 32u : A.seq_shift);
+    const uint32_t short_tag = kLayout == 1 ? (uint32_t)KeyLayout<2>::kSyms : (kLayout == 2 ? 0u : (kLayout == 3 ? (uint32_t)kP16Syms : (kLayout == 4 ? (uint32_t)kP35Syms : A.short_tag)));
+    const uint32_t seq_shift = (kLayout == 1 || kLayout == 3 || kLayout == 4) ? 0u : (kLayout == 2 ? 32u : A.seq_shift);
     constexpr int kWaves = kFuseThreads / 64;
     constexpr int kSegs = kFuseItems * kWaves;  // 64-element segments of the tile, in element order
     __shared__ uint32_t s_tile;
@@ -491,10 +492,14 @@ template <bool kRound0> void regroup(SaBuild &b, const RegroupIn &in) {
                                 in.seq_shift == 32 && in.short_tag == 0;
         const bool p16_layout = two_bit_buckets && in.tag_bits == kP16TagBits && in.sym_bits == 2 * kP16Syms &&
                                 in.seq_shift == 0 && in.short_tag == (uint32_t)kP16Syms;
+        const bool p35_layout = two_bit_buckets && in.tag_bits == kP35TagBits && in.sym_bits == kP35KeyBits &&
+                                in.seq_shift == 0 && in.short_tag == (uint32_t)kP35Syms;
         if (fast_layout)
             regroup_kernel<kRound0, kRound0 ? 1 : 0><<<(unsigned)tiles, kFuseThreads, 0, s>>>(A);  // (layouts only exist for round 0)
         else if (p16_layout)
             regroup_kernel<kRound0, kRound0 ? 3 : 0><<<(unsigned)tiles, kFuseThreads, 0, s>>>(A);
+        else if (p35_layout)
+            regroup_kernel<kRound0, kRound0 ? 4 : 0><<<(unsigned)tiles, kFuseThreads, 0, s>>>(A);
         else if (rec_layout)
             regroup_kernel<kRound0, kRound0 ? 2 : 0><<<(unsigned)tiles, kFuseThreads, 0, s>>>(A);
         else

@@ -286,12 +286,17 @@ KeyPlan plan_keys(const PackedText &text) {
     const bool rec_fast = independent && !text.terms.mirror && n >= knobs.dna_fast_min && sort_knobs().rec_bucket_min > 0 &&
                           (uint64_t)text.terms.count * sort_knobs().rec_bucket_min <= (uint64_t)n;
     const bool fused = key16 && knobs.fused_sort && !text.segmented;
-    p.choice = fused ? KeyPlan::kFused : key16 ? KeyPlan::kKey16 : dna_fast ? KeyPlan::kDnaFast : rec_fast ? KeyPlan::kRecFast
+    // ... and the 35-bit key where that sort ranks its low digits in LDS (radix_sort.hpp: key35_applicable)
+    const bool key35 = key16 && !fused && key35_applicable(text);
+    p.choice = fused ? KeyPlan::kFused : key35 ? KeyPlan::kKey35 : key16 ? KeyPlan::kKey16 : dna_fast ? KeyPlan::kDnaFast : rec_fast ? KeyPlan::kRecFast
                : independent ? KeyPlan::kIndependent : text.segmented ? KeyPlan::kSegmented : KeyPlan::kGeneral;
     switch (p.choice) {
     case KeyPlan::kFused:
     case KeyPlan::kKey16:  // bucket = first four bases, stored word [24 key bits][8-bit tag]
         p.k_syms = kP16Syms, p.tag_bits = kP16TagBits, p.key_bits = kP16Syms * 2;
+        break;
+    case KeyPlan::kKey35:  // bucket = first four bases, stored word [27 key bits][5-bit tag]: 17 1/2 bases
+        p.k_syms = kP35Syms, p.tag_bits = kP35TagBits, p.key_bits = kP35KeyBits;
         break;
     case KeyPlan::kRecFast:  // bucket = record, [kRecSyms bases][4-bit tag]
         p.k_syms = kRecSyms, p.tag_bits = kRecTagBits, p.key_bits = kRecSyms * 2 + kRecTagBits;
@@ -311,6 +316,7 @@ KeyPlan plan_keys(const PackedText &text) {
         break;
     }
     p.key_passes = std::min(8, (p.key_bits + kRadixBits - 1) / kRadixBits);
+    if (p.choice == KeyPlan::kKey35) p.key_passes = 4;  // (as kKey16: the two digits ranked in LDS are wider, not more)
     // (the bucketed sorts name the buffer their keys end in, radix_sort.hpp; the general sort alternates)
     p.cur = p.choice == KeyPlan::kDnaFast ? 1 : p.choice <= KeyPlan::kRecFast ? 0 : (p.key_passes & 1);
     p.bucketed = dna_fast || rec_fast;
@@ -359,13 +365,15 @@ void key_sort_round0(SaBuild &b, const KeyPlan &plan) {
             radix_sort_dna_keys16_fused(text, keys, b.sa, seg_mem, seg, arena, s, ctx.profiler());
             break;
         case KeyPlan::kKey16:
+        case KeyPlan::kKey35:
             // (where the sort finishes its sub-buckets in LDS it does the regroup of round 0 on the way, if nobody needs
             // the ranks it would store: the sorted keys are then never written)
             round0.lcp = b.lcp;
             round0.new_slot = b.next_slot();
             round0.new_grp = b.next_grp();
             round0.d_total = b.d_total;
-            radix_sort_dna_keys16(text, keys32, vals, seg_mem, seg, arena, s, ctx.profiler(), b.store_ranks ? nullptr : &round0);
+            radix_sort_dna_keys16(text, keys32, vals, seg_mem, seg, arena, s, ctx.profiler(), b.store_ranks ? nullptr : &round0,
+                                  plan.choice == KeyPlan::kKey35);
             break;
         case KeyPlan::kDnaFast:
             // plain DNA: partition by the first four bases, then sort the buckets on 8-byte records
@@ -399,7 +407,7 @@ void key_sort_round0(SaBuild &b, const KeyPlan &plan) {
             in.keys32 = keys32[plan.cur];
             in.seg = &seg;
         }
-        in.sym_bits = plan.k_syms * text.bits;
+        in.sym_bits = plan.choice == KeyPlan::kKey35 ? plan.key_bits : plan.k_syms * text.bits;
         in.tag_bits = plan.tag_bits;
         in.bits = text.bits;
         in.low_bits = plan.low_bits;
@@ -600,7 +608,12 @@ int build_suffix_array(Context &ctx, const PackedText &text, uint32_t *sa, uint3
     b.a_cur = 1;  // (round 0 fills list 0)
     key_sort_round0(b, plan);
     b.h = (uint64_t)plan.k_syms;
-    if (knobs.trace) fprintf(stderr, "[nolzss] n=%u: %u suffixes tied after the %d-symbol key sort\n", n, b.m, plan.k_syms);
+    if (knobs.trace) {
+        if (plan.choice == KeyPlan::kKey35)
+            fprintf(stderr, "[nolzss] n=%u: %u suffixes tied after the %d-bit key sort\n", n, b.m, plan.key_bits);
+        else
+            fprintf(stderr, "[nolzss] n=%u: %u suffixes tied after the %d-symbol key sort\n", n, b.m, plan.k_syms);
+    }
     if (b.m > 0 && b.h < n) direct_round(b, plan.k_syms);
     group_sort_passes(b);
 

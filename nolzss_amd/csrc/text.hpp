@@ -127,6 +127,21 @@ template <> struct KeyLayout<8> { static constexpr int kSyms = 7, kTagBits = 8; 
 // zero-padded key -- comes from the stability of the sort: the first pass takes the last 16 suffixes of
 // the text first, shortest first (element e < 16 is suffix n - 1 - e, element e >= 16 is suffix e - 16).
 constexpr int kP16Syms = 16, kP16TagBits = 8;
+// The same sort where the digits below the second most-significant-digit pass are ranked in LDS (local_sort.hpp; texts
+// of 2^28 bases and more): a digit may be wider than 8 bits there, and the tag only ever holds 0 .. 17, so the stored
+// word is [27 key bits][5-bit tag] -- with the bucket 35 key bits = 17 1/2 bases, on the same records and the same
+// number of passes.  Any bit prefix of the big-endian packed text orders like the text, so the half base is sound: equal
+// keys agree on 17 whole bases (the direct round starts there and reads base 17 again from the text), and the LCP of two
+// words that differ is (common key bits) / 2.  Short (a group of its own): tag < 17, the last 16 suffixes of the text --
+// exactly the 16 elements the first pass takes first, shortest first, so the stability argument above carries over.
+// The suffix of 17 bases is a full-length member whose 35th bit is padding; the direct round orders it by its length.
+constexpr int kP35Syms = 17, kP35TagBits = 5, kP35KeyBits = 35;
+// the 19 stored key bits below the sub-bucket's byte: two LDS digits, least significant first
+#ifndef NOLZSS_K35_DIGIT0
+#define NOLZSS_K35_DIGIT0 10
+#endif
+constexpr int kP35Digit0 = NOLZSS_K35_DIGIT0, kP35Digit1 = 32 - 8 - kP35TagBits - kP35Digit0;
+static_assert(kP35Digit0 >= 8 && kP35Digit0 <= 10 && kP35Digit1 >= 8 && kP35Digit1 <= 10, "two LDS digits of at most 1024 bins");
 
 // 64 bits of text starting at symbol `pos` (zero padded past the end).
 template <int BITS>
