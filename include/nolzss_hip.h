@@ -449,6 +449,58 @@ void nolzss_free_dotplot_raster(nolzss_dotplot_raster *out);
  * on that handle: it frees the records at once.  The calling thread's current device is left as it was. */
 int nolzss_dotplot_close(nolzss_dotplot *h);
 
+/* ---- relative LZ: many targets against one reference from one suffix sort ----------------------- */
+/* Extension (the reference has no such mode); it sits next to the reference/target entry points
+ * factorize_dna_w_reference_seq (factorizer.cpp:825-842) and factorize_dna_rc_w_ref_fasta_files
+ * (fasta_processor.cpp:240-287, 362-378), which let target j copy from targets 1..j-1 and from itself.  Here every
+ * target is parsed on its own against the reference block and nothing else ("Relative LZ against a
+ * reference block"):
+ *   Rblk = the m reference records joined by one separator each, B = |Rblk|; separators match nothing.
+ *   At position p of target T: Lf = the largest L with T[p:p+L] in Rblk, Lr = the largest L with revcomp(T[p:p+L]) in
+ *   Rblk (0 without with_rc).  max(Lf, Lr) = 0: a literal of length 1.  Lf >= Lr: a forward factor of length Lf whose
+ *   ref is the leftmost occurrence in Rblk.  Otherwise a reverse-complement factor of length Lr whose ref is the
+ *   leftmost occurrence of the reverse complement in Rblk, with NOLZSS_RC_MASK.  The next factor starts at p + length.
+ * Prepared string: S = Rblk s T1 s .. Tk s [pad] rc-block s, every s a fresh sentinel (the sequence of
+ * factorizer.cpp:110-125), rc-block = rc(Rm) s .. s rc(R1) at rc_block_start = E (with_rc only), pad = one more
+ * sentinel when B - 1 + E would be odd; rcN = (B - 1 + E) / 2.  Without with_rc S ends behind the sentinel of Tk,
+ * rc_block_start = S_len and rcN = 0.
+ * Refusals: m == 0 or no reference base, more than 250 sentinels (with_rc: 2m + k + 1 > 250, else m + k > 250), S longer
+ * than the 32-bit pipeline takes: NOLZSS_ERR_INVALID_ARGUMENT; "Invalid nucleotide 'x' found in sequence j" (j counts
+ * the references first, then the targets): NOLZSS_ERR_RUNTIME.  Lower case is upper-cased (factorizer.cpp:86-95). */
+/* Host only.  S, target_offsets (k entries: the first position of each target in S): malloc'ed, nolzss_free(). */
+int nolzss_rlz_prepare(const char *const *refs, const size_t *ref_lens, size_t m, const char *const *targets,
+                       const size_t *target_lens, size_t k, int with_rc, uint8_t **S, size_t *S_len,
+                       uint64_t **target_offsets, size_t *block_length, size_t *rc_block_start, size_t *rcN);
+typedef struct nolzss_rlz_result {
+    size_t num_targets;
+    uint64_t block_length;      /* B */
+    uint64_t *target_offsets;   /* [num_targets] first position of each target in S */
+    uint64_t *target_lengths;   /* [num_targets] */
+    size_t *counts;             /* [num_targets] factors per target */
+    nolzss_factor **factors;    /* [num_targets] pointers into block, or NULL without want_factors */
+    nolzss_factor *block;       /* owns every record */
+    /* nolzss_rlz_factorize_fasta only: NUL-terminated ids back to back */
+    char *reference_ids;
+    size_t reference_ids_bytes, num_references;
+    char *target_ids;
+    size_t target_ids_bytes;
+} nolzss_rlz_result;
+/* Records are in coordinates of S, like nolzss_factorize_w_reference: start is absolute, a match has ref < block_length
+ * (plus NOLZSS_RC_MASK for a reverse-complement factor), a literal has ref = start.  k == 0 gives an empty result
+ * without touching the device; with want_factors == 0 only the k counts leave the device. */
+int nolzss_rlz_factorize(const char *const *refs, const size_t *ref_lens, size_t m, const char *const *targets,
+                         const size_t *target_lens, size_t k, int with_rc, int want_factors, int device,
+                         nolzss_rlz_result *out);
+/* Reader, sanitize modes and error texts of nolzss_factorize_dna_rc_w_ref_fasta_files; fills the two id lists. */
+int nolzss_rlz_factorize_fasta(const char *reference_fasta_path, const char *target_fasta_path, int with_rc,
+                               int sanitize_mode, int want_factors, int device, nolzss_rlz_result *out);
+void nolzss_free_rlz_result(nolzss_rlz_result *r);
+/* The code (length in bits 0..30, bit 31 = reverse complement, 0 = literal) of every position of S below the sentinel
+ * behind the last target: target_offsets[k - 1] + target_lens[k - 1] entries (nolzss_rlz_prepare), caller-allocated.
+ * Only target positions are specified. */
+int nolzss_debug_rlz_codes(const char *const *refs, const size_t *ref_lens, size_t m, const char *const *targets,
+                           const size_t *target_lens, size_t k, int with_rc, int device, uint32_t *code);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

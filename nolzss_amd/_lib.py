@@ -87,6 +87,15 @@ class DotPlotRaster(C.Structure):
                 ("hover_ref", C.POINTER(C.c_uint64))]
 
 
+class RlzResult(C.Structure):
+    """Mirror of nolzss_rlz_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_targets", C.c_size_t), ("block_length", C.c_uint64),
+                ("target_offsets", C.POINTER(C.c_uint64)), ("target_lengths", C.POINTER(C.c_uint64)),
+                ("counts", C.POINTER(C.c_size_t)), ("factors", C.POINTER(C.c_void_p)), ("block", C.c_void_p),
+                ("reference_ids", C.c_void_p), ("reference_ids_bytes", C.c_size_t), ("num_references", C.c_size_t),
+                ("target_ids", C.c_void_p), ("target_ids_bytes", C.c_size_t)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -211,6 +220,14 @@ def _load():
     lib.nolzss_free_dotplot_raster.restype = None
     lib.nolzss_dotplot_close.argtypes = [vp]
     lib.nolzss_debug_position_edges.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, vpp, szp]
+    seqs = [C.POINTER(C.c_char_p), szp, sz, C.POINTER(C.c_char_p), szp, sz]  # references, then targets
+    lib.nolzss_rlz_prepare.argtypes = seqs + [C.c_int, vpp, szp, vpp, szp, szp, szp]
+    lib.nolzss_rlz_factorize.argtypes = seqs + [C.c_int, C.c_int, C.c_int, C.POINTER(RlzResult)]
+    lib.nolzss_rlz_factorize_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(RlzResult)]
+    lib.nolzss_free_rlz_result.argtypes = [C.POINTER(RlzResult)]
+    lib.nolzss_free_rlz_result.restype = None
+    lib.nolzss_debug_rlz_codes.argtypes = seqs + [C.c_int, C.c_int, vp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -257,6 +274,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_dotplot_open_text", "nolzss_dotplot_open_fasta", "nolzss_dotplot_open_records", "nolzss_dotplot_info",
     "nolzss_dotplot_render", "nolzss_free_dotplot_raster", "nolzss_dotplot_close",
     "nolzss_debug_position_factors", "nolzss_debug_rc_arrays",
+    "nolzss_rlz_prepare", "nolzss_rlz_factorize", "nolzss_rlz_factorize_fasta", "nolzss_free_rlz_result",
+    "nolzss_debug_rlz_codes",
 ]
 
 

@@ -1039,6 +1039,95 @@ def parallel_write_factors_binary_file_fasta_multiple_dna_no_rc(fasta_path, out_
     return _write_fasta_multiple(fasta_path, out_path, sanitize_mode, False)
 
 
+# ---- relative LZ: many targets against one reference block (extension) -----------
+def _seq_args(sequences, name):
+    seqs = [_str_arg(s, name) for s in sequences]
+    n = len(seqs)
+    return (C.c_char_p * max(n, 1))(*seqs), (C.c_size_t * max(n, 1))(*[len(s) for s in seqs]), n
+
+
+def _rlz_inputs(reference, targets):
+    if isinstance(reference, (str, bytes, bytearray)):
+        reference = [reference]
+    return _seq_args(reference, "reference") + _seq_args(targets, "target")
+
+
+def rlz_prepare(reference, targets, with_rc: bool = True) -> dict:
+    """Host only: the prepared string of a relative-LZ run, S = Rblk s T1 s .. Tk s [pad] rc-block s ->
+    dict(S: bytes, target_offsets: list, block_length, rc_block_start, rcN)."""
+    args = _rlz_inputs(reference, targets)
+    S, off = C.c_void_p(), C.c_void_p()
+    S_len, B, E, rcN = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    check(lib.nolzss_rlz_prepare(*args, 1 if with_rc else 0, C.byref(S), C.byref(S_len), C.byref(off), C.byref(B),
+                                 C.byref(E), C.byref(rcN)))
+    try:
+        k = args[5]
+        offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(k,)).tolist() if k else []
+        data = C.string_at(S, S_len.value)
+    finally:
+        lib.nolzss_free(S)
+        lib.nolzss_free(off)
+    return {"S": data, "target_offsets": offsets, "block_length": B.value, "rc_block_start": E.value, "rcN": rcN.value}
+
+
+def _unpack_rlz_result(res, want_factors):
+    try:
+        k = res.num_targets
+        out = {"block_length": int(res.block_length),
+               "target_offsets": [int(res.target_offsets[j]) for j in range(k)],
+               "target_lengths": [int(res.target_lengths[j]) for j in range(k)],
+               "counts": [int(res.counts[j]) for j in range(k)], "factors": None}
+        if want_factors:
+            out["factors"] = []
+            for j in range(k):
+                z = out["counts"][j]
+                if z:
+                    raw = np.ctypeslib.as_array(C.cast(res.factors[j], C.POINTER(C.c_uint64)), shape=(z * 3,)).copy()
+                    out["factors"].append(raw.view(FACTOR_DTYPE))
+                else:
+                    out["factors"].append(np.zeros(0, dtype=FACTOR_DTYPE))
+        if res.reference_ids:
+            blob = C.string_at(res.reference_ids, res.reference_ids_bytes)
+            out["reference_ids"] = [x.decode("utf-8") for x in blob.split(b"\x00")[:res.num_references]]
+            blob = C.string_at(res.target_ids, res.target_ids_bytes)
+            out["target_ids"] = [x.decode("utf-8") for x in blob.split(b"\x00")[:k]]
+    finally:
+        lib.nolzss_free_rlz_result(C.byref(res))
+    return out
+
+
+def rlz_factorize_arrays(reference, targets, with_rc: bool = True, want_factors: bool = True) -> dict:
+    """Every target factorized against the reference block only -> dict(block_length, target_offsets, target_lengths,
+    counts, factors: one (start, length, ref) array per target in coordinates of the prepared string -- start absolute,
+    a match has ref < block_length (plus RC_MASK), a literal ref = start -- or None without want_factors)."""
+    args = _rlz_inputs(reference, targets)
+    res = _lib.RlzResult()
+    check(lib.nolzss_rlz_factorize(*args, 1 if with_rc else 0, 1 if want_factors else 0, _default_device, C.byref(res)))
+    return _unpack_rlz_result(res, want_factors)
+
+
+def rlz_factorize_fasta_arrays(reference_fasta_path, target_fasta_path, with_rc: bool = True,
+                               sanitize_mode: str = "remove_ambiguous", want_factors: bool = True) -> dict:
+    """rlz_factorize_arrays over the records of two FASTA files, plus reference_ids and target_ids."""
+    res = _lib.RlzResult()
+    check(lib.nolzss_rlz_factorize_fasta(_str_arg(reference_fasta_path, "reference_fasta_path"),
+                                         _str_arg(target_fasta_path, "target_fasta_path"), 1 if with_rc else 0,
+                                         _sanitize_mode(sanitize_mode), 1 if want_factors else 0, _default_device,
+                                         C.byref(res)))
+    return _unpack_rlz_result(res, want_factors)
+
+
+def debug_rlz_codes(reference, targets, with_rc: bool = True) -> np.ndarray:
+    """The relative-LZ code (length, bit 31 = reverse complement, 0 = literal) of every position of the prepared
+    string below the sentinel behind the last target; only target positions are specified."""
+    args = _rlz_inputs(reference, targets)
+    prep = rlz_prepare(reference, targets, with_rc)
+    n = prep["target_offsets"][-1] + args[4][args[5] - 1] if args[5] else 0
+    code = np.zeros(n, dtype=np.uint32)
+    check(lib.nolzss_debug_rlz_codes(*args, 1 if with_rc else 0, _default_device, code.ctypes.data))
+    return code
+
+
 # ---- measurement hooks ----------------------------------------------------------------------
 def profile_enable(on: bool = True) -> None:
     check(lib.nolzss_profile_enable(_default_device, 1 if on else 0))

@@ -137,4 +137,29 @@ void prepare_batch_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t n, ui
 // invalid nucleotide or 0xffffffff.
 uint32_t prepare_single_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t n, uint8_t *d_S);
 
+// ---- relative LZ (rlz.hip): every target against the reference block only -----------------------
+// The prepared string S = Rblk s T1 s .. Tk s [pad] rc-block s (rlz_api.hip builds it).  Without reverse complement S
+// ends behind the sentinel of Tk, rc_block_start = total and rcN = 0.
+struct RlzLayout {
+    uint32_t total = 0;           // |S|
+    uint32_t block_length = 0;    // B = |Rblk|; the chain starts at B + 1
+    uint32_t rc_block_start = 0;  // E
+    uint32_t chain_end = 0;       // position of the sentinel behind Tk
+    uint32_t rcN = 0;             // (B - 1 + E) / 2
+    bool with_rc = false;
+};
+// by_rank[r] = the code (length, bit 31 = reverse complement, 0 = no match) of the suffix of rank r against the
+// suffixes that start below B (forward) or at E and beyond (reverse complement); m ranks, lcp as build_suffix_array
+// leaves it once build_lcp_pyramid has decided every entry.  E is not read without with_rc.
+void rlz_candidates(Context &ctx, const uint32_t *sa, const uint32_t *lcp, uint32_t m, uint32_t B, uint32_t E, bool with_rc,
+                    uint32_t *by_rank);
+// The whole pipeline over the device-resident S; outputs as resolve_chain (records and / or factor starts in the arena,
+// the caller owns the mark; the sentinels between the targets come out as literals).  h_codes (optional, host): the
+// code of every position below chain_end.
+uint32_t run_rlz_pipeline(Context &ctx, const uint8_t *d_S, const RlzLayout &lay, void **d_factors_out,
+                          uint32_t **d_fpos_out = nullptr, uint32_t *h_codes = nullptr);
+// counts[j] = entries of the ascending list d_fpos inside [bounds[2j], bounds[2j + 1]) (all device pointers)
+void rlz_count_per_target(Context &ctx, const uint32_t *d_fpos, uint32_t z, const uint32_t *d_bounds, uint32_t k,
+                          uint32_t *d_counts);
+
 }  // namespace nolzss
