@@ -501,6 +501,59 @@ void nolzss_free_rlz_result(nolzss_rlz_result *r);
 int nolzss_debug_rlz_codes(const char *const *refs, const size_t *ref_lens, size_t m, const char *const *targets,
                            const size_t *target_lens, size_t k, int with_rc, int device, uint32_t *code);
 
+/* ---- decoding: factors and literals back to text ------------------------------------------------ */
+/* Extension (the reference has no decoder).  A factor record does not carry the symbol of a literal, so a
+ * factorization is the z records plus the literal symbols in record order ("Decoding: factors and
+ * literals back to text").  One contract serves every mode the library emits:
+ *   Inputs: z records (start, length, ref), ref carrying NOLZSS_RC_MASK; n_literals bytes; a known prefix of
+ *     prefix_len bytes (may be empty).
+ *   Output: text[0 : n), n = prefix_len when z == 0, else start[z - 1] + length[z - 1]; text[0 : prefix_len) is the prefix.
+ *   Tiling: start[0] == prefix_len, start[k + 1] == start[k] + length[k], length >= 1.
+ *   Literal: ref == start (no mask).  It has length 1 and takes the next byte of `literals`, in record order; the
+ *     number of literal records must equal n_literals.
+ *   Copy: r = ref & ~NOLZSS_RC_MASK, r + length <= start (what every mode emits: sources end before the factor starts).
+ *     Forward: text[start + t] = text[r + t].  Reverse complement (mask set): text[start + t] =
+ *     comp(text[r + length - 1 - t]), comp = A<->T, C<->G on upper-case bytes.  A position whose chain of copies
+ *     carries an odd number of complements and ends in any other byte is an error; an even number is the identity
+ *     for every byte value, so plain-mode texts over all 256 values decode.
+ *   Errors: every violation is NOLZSS_ERR_INVALID_ARGUMENT, the message names the first offending record index and
+ *     the rule (tiling, literal length, source range, literal count, complement of a non-nucleotide); nothing is
+ *     returned.  n beyond the 32-bit pipeline is refused up front.  z == 0 returns a copy of the prefix without
+ *     touching a device.
+ *   Per mode: nolzss_factorize, nolzss_factorize_dna_w_rc, nolzss_factorize_multiple_dna_w_rc and the concatenated
+ *     FASTA forms: empty prefix (the result is S[:n], the sentinel literals come from the literal stream);
+ *     nolzss_factorize_w_reference, nolzss_factorize_dna_w_reference_seq: prefix S[:start_pos]; relative LZ: prefix =
+ *     the reference block, the targets laid end to end behind it (nolzss_amd.genomics.rlz.rlz_decode rebases). */
+typedef struct nolzss_decode_info {
+    uint64_t n, z, n_literals;
+    uint64_t resolved_at_expand;   /* of the n - prefix_len decoded positions: resolved before the first jump round */
+    uint64_t rounds;               /* jump launches */
+    uint64_t max_active;           /* unresolved positions entering the first jump round */
+} nolzss_decode_info;
+/* Host only: literals[j] = text[start of the j-th literal record]; a literal record with start >= n is refused.
+ * *literals: malloc'ed, nolzss_free. */
+int nolzss_literal_symbols(const uint8_t *text, size_t n, const nolzss_factor *factors, size_t z,
+                           uint8_t **literals, size_t *n_literals);
+/* *text: malloc'ed, nolzss_free; info may be NULL. */
+int nolzss_decode(const nolzss_factor *factors, size_t z, const uint8_t *literals, size_t n_literals,
+                  const uint8_t *prefix, size_t prefix_len, int device, uint8_t **text, size_t *n,
+                  nolzss_decode_info *info);
+/* Factorize (with_rc: as nolzss_factorize_dna_w_rc, with its refusals; else as nolzss_factorize), keep the records in
+ * device memory, gather the literals, decode and compare with the input, all on the device: only the numbers below
+ * come back (with_rc: the comparison is with the upper-cased input, the strand the records describe).
+ * first_mismatch = UINT64_MAX when there is none.  An empty text gives z = 0 and no mismatch.  If the
+ * device arena cannot hold the records plus the decode state behind the factorization the call fails with
+ * NOLZSS_ERR_NOMEM; there is no fallback. */
+int nolzss_roundtrip(const uint8_t *text, size_t n, int with_rc, int device, size_t *z,
+                     uint64_t *mismatches, uint64_t *first_mismatch, nolzss_decode_info *info);
+/* The same with the text resident in device memory (`stream` as nolzss_factorize_device). */
+int nolzss_roundtrip_device(const void *d_text, size_t n, int with_rc, int device, void *stream, size_t *z,
+                            uint64_t *mismatches, uint64_t *first_mismatch, nolzss_decode_info *info);
+/* Debug hook of the comparison kernel: host arrays up, the number of differing positions and the first one
+ * (UINT64_MAX if none) back. */
+int nolzss_debug_count_mismatches(const uint8_t *a, const uint8_t *b, size_t n, int device,
+                                  uint64_t *count, uint64_t *first);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

@@ -7,13 +7,13 @@ by hand-written HIP kernels for gfx950 behind a C ABI (include/nolzss_hip.h).
 """
 from ._noLZSS import __version__
 from .core import (factorize, factorize_file, count_factors, count_factors_file, write_factors_binary_file,
-                   factorize_w_reference, factorize_w_reference_file)
+                   factorize_w_reference, factorize_w_reference_file, decode, literal_symbols)
 from .utils import (NoLZSSError, InvalidInputError, validate_input, read_factors_binary_file,
                     read_binary_file_metadata, read_factors_binary_file_with_metadata)
 
 __all__ = [
     "factorize", "factorize_file", "count_factors", "count_factors_file", "write_factors_binary_file",
-    "factorize_w_reference", "factorize_w_reference_file",
+    "factorize_w_reference", "factorize_w_reference_file", "decode", "literal_symbols",
     "NoLZSSError", "InvalidInputError", "validate_input", "read_factors_binary_file",
     "read_binary_file_metadata", "read_factors_binary_file_with_metadata", "__version__",
 ]

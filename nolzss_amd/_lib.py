@@ -96,6 +96,12 @@ class RlzResult(C.Structure):
                 ("target_ids", C.c_void_p), ("target_ids_bytes", C.c_size_t)]
 
 
+class DecodeInfo(C.Structure):
+    """Mirror of nolzss_decode_info (include/nolzss_hip.h)."""
+    _fields_ = [("n", C.c_uint64), ("z", C.c_uint64), ("n_literals", C.c_uint64), ("resolved_at_expand", C.c_uint64),
+                ("rounds", C.c_uint64), ("max_active", C.c_uint64)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -228,6 +234,12 @@ def _load():
     lib.nolzss_free_rlz_result.argtypes = [C.POINTER(RlzResult)]
     lib.nolzss_free_rlz_result.restype = None
     lib.nolzss_debug_rlz_codes.argtypes = seqs + [C.c_int, C.c_int, vp]
+    u64p, dip = C.POINTER(C.c_uint64), C.POINTER(DecodeInfo)
+    lib.nolzss_literal_symbols.argtypes = [vp, sz, vp, sz, vpp, szp]
+    lib.nolzss_decode.argtypes = [vp, sz, vp, sz, vp, sz, C.c_int, vpp, szp, dip]
+    lib.nolzss_roundtrip.argtypes = [vp, sz, C.c_int, C.c_int, szp, u64p, u64p, dip]
+    lib.nolzss_roundtrip_device.argtypes = [vp, sz, C.c_int, C.c_int, vp, szp, u64p, u64p, dip]
+    lib.nolzss_debug_count_mismatches.argtypes = [vp, vp, sz, C.c_int, u64p, u64p]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -276,6 +288,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_position_factors", "nolzss_debug_rc_arrays",
     "nolzss_rlz_prepare", "nolzss_rlz_factorize", "nolzss_rlz_factorize_fasta", "nolzss_free_rlz_result",
     "nolzss_debug_rlz_codes",
+    "nolzss_literal_symbols", "nolzss_decode", "nolzss_roundtrip", "nolzss_roundtrip_device",
+    "nolzss_debug_count_mismatches",
 ]
 
 

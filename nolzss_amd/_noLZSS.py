@@ -1128,6 +1128,100 @@ def debug_rlz_codes(reference, targets, with_rc: bool = True) -> np.ndarray:
     return code
 
 
+# ---- decoding: factors and literals back to text (extension) ----------------------
+def _decode_records(factors):
+    """-> contiguous FACTOR_DTYPE array: a FACTOR_DTYPE array (ref carrying RC_MASK), or a sequence of
+    (start, length, ref) or (start, length, ref, is_rc) tuples -- with four fields is_rc sets the mask"""
+    if isinstance(factors, np.ndarray) and factors.dtype == FACTOR_DTYPE:
+        return np.ascontiguousarray(factors)
+    rows = list(factors)
+    out = np.zeros(len(rows), dtype=FACTOR_DTYPE)
+    for k, row in enumerate(rows):
+        row = tuple(row)
+        if len(row) not in (3, 4):
+            raise ValueError("factors must be a FACTOR_DTYPE array or tuples of 3 or 4 fields")
+        ref = operator.index(row[2])
+        if len(row) == 4 and row[3]:
+            ref |= RC_MASK
+        out[k] = (operator.index(row[0]), operator.index(row[1]), ref)
+    return out
+
+
+def _info_dict(info):
+    return {name: int(getattr(info, name)) for name, _ in _lib.DecodeInfo._fields_}
+
+
+def literal_symbols(data, factors) -> bytes:
+    """Extension: the symbols of the literal records (ref == start) of `factors` in record order, read from `data`:
+    with the records, all a decoder needs.  Host only.  C ABI nolzss_literal_symbols."""
+    p, n, keep = _as_buffer(data)
+    f = _decode_records(factors)
+    out, count = C.c_void_p(), C.c_size_t()
+    check(lib.nolzss_literal_symbols(p, n, f.ctypes.data if f.size else None, f.size, C.byref(out), C.byref(count)))
+    try:
+        return C.string_at(out, count.value)
+    finally:
+        lib.nolzss_free(out)
+
+
+def decode_array(factors, literals, prefix=b""):
+    """Extension: the text of a factorization -> (np.uint8 array of n bytes, info dict).  `literals`: the literal
+    symbols in record order (literal_symbols); `prefix`: the known bytes in front of the first record (the reference of
+    factorize_w_reference plus its separator, the reference block of relative LZ).  Pointer jumping on the GPU; no
+    records: a copy of the prefix, without a device.  C ABI nolzss_decode (its header states the rules)."""
+    f = _decode_records(factors)
+    lp, ln, keep_l = _as_buffer(literals)
+    pp, pn, keep_p = _as_buffer(prefix)
+    out, n, info = C.c_void_p(), C.c_size_t(), _lib.DecodeInfo()
+    check(lib.nolzss_decode(f.ctypes.data if f.size else None, f.size, lp if ln else None, ln, pp if pn else None, pn,
+                            _default_device, C.byref(out), C.byref(n), C.byref(info)))
+    owner = _Owned(out)
+    if n.value == 0:
+        return np.zeros(0, dtype=np.uint8), _info_dict(info)
+    raw = (C.c_uint8 * n.value).from_address(out.value)
+    raw._owner = owner
+    return np.frombuffer(raw, dtype=np.uint8), _info_dict(info)
+
+
+def _roundtrip_result(z, mismatches, first, info):
+    res = {"z": z.value, "mismatches": mismatches.value,
+           "first_mismatch": None if first.value == (1 << 64) - 1 else first.value}
+    res.update({k: v for k, v in _info_dict(info).items() if k != "z"})
+    return res
+
+
+def roundtrip_check(data, with_rc: bool = False) -> dict:
+    """Extension: factorize (with_rc: as factorize_dna_w_rc), gather the literals, decode and compare with `data`, the
+    records never leaving the device -> dict(z, mismatches, first_mismatch (None: no mismatch), n, n_literals,
+    resolved_at_expand, rounds, max_active).  C ABI nolzss_roundtrip."""
+    p, n, keep = _as_buffer(data)
+    z, mism, first, info = C.c_size_t(), C.c_uint64(), C.c_uint64(), _lib.DecodeInfo()
+    check(lib.nolzss_roundtrip(p, n, 1 if with_rc else 0, _default_device, C.byref(z), C.byref(mism), C.byref(first),
+                               C.byref(info)))
+    return _roundtrip_result(z, mism, first, info)
+
+
+def roundtrip_device(data_ptr: int, n: int, with_rc: bool = False, stream: int = 0) -> dict:
+    """roundtrip_check over n bytes resident in device memory (C ABI nolzss_roundtrip_device)."""
+    z, mism, first, info = C.c_size_t(), C.c_uint64(), C.c_uint64(), _lib.DecodeInfo()
+    check(lib.nolzss_roundtrip_device(C.c_void_p(data_ptr), n, 1 if with_rc else 0, _default_device,
+                                      C.c_void_p(stream) if stream else None, C.byref(z), C.byref(mism), C.byref(first),
+                                      C.byref(info)))
+    return _roundtrip_result(z, mism, first, info)
+
+
+def debug_count_mismatches(a, b):
+    """Debug hook of the round trip's comparison kernel -> (differing positions, the first one or None)."""
+    pa, na, keep_a = _as_buffer(a)
+    pb, nb, keep_b = _as_buffer(b)
+    if na != nb:
+        raise ValueError("arrays of different lengths")
+    count, first = C.c_uint64(), C.c_uint64()
+    check(lib.nolzss_debug_count_mismatches(pa if na else None, pb if nb else None, na, _default_device, C.byref(count),
+                                            C.byref(first)))
+    return count.value, (None if first.value == (1 << 64) - 1 else first.value)
+
+
 # ---- measurement hooks ----------------------------------------------------------------------
 def profile_enable(on: bool = True) -> None:
     check(lib.nolzss_profile_enable(_default_device, 1 if on else 0))

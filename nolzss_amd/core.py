@@ -1,7 +1,8 @@
 """The user-facing factorize API of the hot path, written once for both import names.
 
 `bind(native)` builds the seven functions of the reference's `noLZSS.core` (reference:
-src/noLZSS/core.py:25-257 -- names, argument meaning, error behaviour) over a native module:
+src/noLZSS/core.py:25-257 -- names, argument meaning, error behaviour) and the two of the decoder (extension:
+`decode`, `literal_symbols`) over a native module:
 `nolzss_amd.core` binds them to the ctypes mirror `nolzss_amd._noLZSS`, `noLZSS.core` to the compiled
 pybind11 module `noLZSS._noLZSS`.  Both native modules call the same C ABI (include/nolzss_hip.h).
 """
@@ -11,7 +12,7 @@ from typing import List, Tuple, Union
 from .utils import validate_input
 
 __all__ = ["factorize", "factorize_file", "count_factors", "count_factors_file", "write_factors_binary_file",
-           "factorize_w_reference", "factorize_w_reference_file"]
+           "factorize_w_reference", "factorize_w_reference_file", "decode", "literal_symbols"]
 
 Factors = List[Tuple[int, int, int]]
 Text = Union[str, bytes]
@@ -75,6 +76,20 @@ def bind(native) -> dict:
         """the same into a v2 binary factor file; returns the number of factors (reference: core.py:210-257)"""
         return native.factorize_w_reference_file(as_ascii_str(checked(reference_seq, validate)),
                                                  as_ascii_str(checked(target_seq, validate)), _writable(output_path))
+
+    def as_bytes(data: Text) -> bytes:
+        return data.encode("ascii") if isinstance(data, str) else data
+
+    def literal_symbols(data: Text, factors) -> bytes:
+        """Extension: the symbols of the literal factors (ref == start) of `factors` in factor order, read from
+        `data` -- a factor record does not carry them, and `decode` needs them."""
+        return native.literal_symbols(as_bytes(data), factors)
+
+    def decode(factors, literals: Text, prefix: Text = b"") -> bytes:
+        """Extension: the text of a factorization.  `factors`: what `factorize` (3-tuples) or the reverse-complement
+        forms (4-tuples with is_rc) return, or a structured array; `literals`: `literal_symbols` of the text;
+        `prefix`: the known bytes in front of the first factor (for `factorize_w_reference`: reference + '\x01')."""
+        return native.decode_array(factors, as_bytes(literals), as_bytes(prefix))[0].tobytes()
 
     fns = locals()
     return {name: fns[name] for name in __all__}

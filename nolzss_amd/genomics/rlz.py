@@ -84,5 +84,71 @@ def rlz_summary(result):
     return out
 
 
+SEPARATOR = b"\x01"  # between the records of the reference block that rlz_decode builds: any byte but A/C/G/T
+
+
+def _upper_bytes(seq):
+    return (seq.encode("ascii") if isinstance(seq, str) else bytes(seq)).upper()
+
+
+def rlz_literals(targets, factors):
+    """targets, and what rlz_factorize returned for them -> per target the symbols of its literal factors in factor
+    order (upper case, as the factorization reads the targets).  With `factors`, all rlz_decode needs."""
+    out = []
+    for t, f in zip(targets, factors):
+        f = np.asarray(f, dtype=RLZ_DTYPE)
+        sym = np.frombuffer(_upper_bytes(t), dtype=np.uint8)
+        out.append(sym[f["start"][f["is_literal"]].astype(np.int64)].tobytes())
+    return out
+
+
+def absolute_records(reference, factors):
+    """The reference block, and the per-target RLZ_DTYPE arrays laid end to end behind it as ONE array of absolute
+    (start, length, ref with RC_MASK) records -> (block bytes, records, target lengths).  Raises ValueError if a copy
+    factor's [ref, ref + length) touches a separator or leaves the block.  Pure numpy, no device."""
+    if isinstance(reference, (str, bytes, bytearray)):
+        reference = [reference]
+    refs = [_upper_bytes(r) for r in reference]
+    block = SEPARATOR.join(refs)
+    separators = np.cumsum([len(r) + 1 for r in refs[:-1]], dtype=np.int64) - 1  # ascending positions in the block
+    parts, lengths = [], []
+    at = len(block)
+    for j, f in enumerate(factors):
+        f = np.asarray(f, dtype=RLZ_DTYPE)
+        rec = np.zeros(len(f), dtype=_native.FACTOR_DTYPE)
+        start = f["start"] + np.uint64(at)
+        copy = ~f["is_literal"]
+        ref, length = f["ref"].astype(np.int64), f["length"].astype(np.int64)
+        nxt = np.searchsorted(separators, ref, side="left")  # the first separator at or behind ref
+        nxt_pos = np.append(separators, len(block))[nxt]
+        bad = copy & ((ref + length > len(block)) | (nxt_pos < ref + length))
+        if bad.any():
+            k = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"target {j}, factor {k}: [ref, ref + length) = [{int(ref[k])}, {int(ref[k] + length[k])}) "
+                             f"touches a separator or leaves the reference block of {len(block)} bytes")
+        rec["start"], rec["length"] = start, f["length"]
+        rec["ref"] = np.where(copy, f["ref"] | np.where(f["is_rc"], np.uint64(_native.RC_MASK), np.uint64(0)), start)
+        parts.append(rec)
+        n = int(f["start"][-1] + f["length"][-1]) if len(f) else 0
+        lengths.append(n)
+        at += n
+    records = np.concatenate(parts) if parts else np.zeros(0, dtype=_native.FACTOR_DTYPE)
+    return block, records, lengths
+
+
+def rlz_decode(reference, factors, literals, return_info: bool = False):
+    """The targets back from their relative-LZ factors: `reference` as given to rlz_factorize, `factors` the list it
+    returned, `literals` the list rlz_literals returned -> one bytes object per target (b"" for an empty one).  ONE
+    decode on the GPU for all targets: the reference block is the known prefix and every copy resolves in one hop.
+    return_info: also the info dict of that call."""
+    block, records, lengths = absolute_records(reference, factors)
+    text, info = _native.decode_array(records, b"".join(bytes(x) for x in literals), prefix=block)
+    out, at = [], len(block)
+    for n in lengths:
+        out.append(text[at:at + n].tobytes())
+        at += n
+    return (out, info) if return_info else out
+
+
 __all__ = ["RLZ_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
-           "rlz_summary"]
+           "rlz_summary", "rlz_literals", "rlz_decode"]
