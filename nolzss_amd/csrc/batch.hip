@@ -190,7 +190,7 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
         build_suffix_array(ctx, text, sa, isa, lcp, &isa_deferred);
         // (pyramids: allocated here, filled by build_lstar -- first level from the candidate kernel)
         const Pyramid Psa = alloc_pyramid(sa, (uint32_t)n, arena), Plcp = alloc_pyramid(lcp, (uint32_t)n + 1, arena);
-        uint32_t *lstar = arena.alloc<uint32_t>(n);
+        LstarCodes lstar = LstarCodes::of(arena.alloc<uint32_t>(n));  // (merged batch: 32-bit codes)
         build_lstar(ctx, (uint32_t)n, sa, isa, lcp, Psa, Plcp, lstar, isa_deferred ? isa : nullptr, &text);
         // counts come from the factor starts; records are built only when the caller wants them, and leave
         // the factor kernel in record coordinates
@@ -338,7 +338,7 @@ bool run_merged_chunk_device(Context &ctx, const void *const *d_texts, const siz
     build_suffix_array(ctx, text, sa, isa, lcp, &isa_deferred);
     // (pyramids: allocated here, filled by build_lstar -- first level from the candidate kernel)
     const Pyramid Psa = alloc_pyramid(sa, (uint32_t)n, arena), Plcp = alloc_pyramid(lcp, (uint32_t)n + 1, arena);
-    uint32_t *lstar = arena.alloc<uint32_t>(n);
+    LstarCodes lstar = LstarCodes::of(arena.alloc<uint32_t>(n));  // (merged batch: 32-bit codes)
     build_lstar(ctx, (uint32_t)n, sa, isa, lcp, Psa, Plcp, lstar, isa_deferred ? isa : nullptr, &text);
     void *d_recs = nullptr;
     uint32_t *d_fpos = nullptr;

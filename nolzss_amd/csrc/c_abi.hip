@@ -211,20 +211,23 @@ size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos
     // (the pyramids are only allocated here: the candidate kernel writes their first level from the blocks it holds
     // in LDS anyway, build_lstar fills the rest)
     const Pyramid Psa = alloc_pyramid(sa, (uint32_t)n, arena), Plcp = alloc_pyramid(lcp, (uint32_t)n + 1, arena);
-    uint32_t *lstar = arena.alloc<uint32_t>(n);
+    // (16-bit codes where the stage can write them; the length histograms read 32-bit codes)
+    LstarCodes lstar = alloc_lstar(ctx, (uint32_t)n, isa_deferred && !lengths);
     build_lstar(ctx, (uint32_t)n, sa, isa, lcp, Psa, Plcp, lstar, isa_deferred ? isa : nullptr, &text);
     if (dbg) {
+        // the exports are 32-bit: 16-bit codes are widened once, for here only -- the cursor below still reads them
+        const size_t dmark = arena.mark();
+        const uint32_t *lstar32 = lstar.width == 32 ? lstar.wide : widened_lstar(ctx, lstar, (uint32_t)n, 0);
         copy_out(ctx, dbg->sa, sa, n);
         copy_out(ctx, dbg->isa, isa, n);  // (1-based on the device; nolzss_debug_arrays subtracts the one)
         copy_out(ctx, dbg->lcp, lcp, n + 1);
-        copy_out(ctx, dbg->lstar, lstar, n);
+        copy_out(ctx, dbg->lstar, lstar32, n);
         if (dbg->records) {
-            const size_t rmark = arena.mark();
-            const void *recs = position_factors(ctx, (uint32_t)n, lstar, sa, isa, lcp, Psa, Plcp);
+            const void *recs = position_factors(ctx, (uint32_t)n, lstar32, sa, isa, lcp, Psa, Plcp);
             HIP_CHECK(hipMemcpyAsync(dbg->records, recs, n * sizeof(nolzss_factor), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            arena.rewind(rmark);
         }
+        HIP_CHECK(hipStreamSynchronize(s));
+        arena.rewind(dmark);
     }
     void *d_recs = nullptr;
     const uint32_t z = resolve_chain(ctx, (uint32_t)n, (uint32_t)start_pos, lstar, sa, isa, lcp, Psa, Plcp,

@@ -41,49 +41,96 @@ __device__ __forceinline__ uint32_t next_pos(uint32_t p, uint32_t code, uint32_t
     return nx > n ? n : (uint32_t)nx;
 }
 
-__global__ __launch_bounds__(kThreads) void chain_exit_kernel(const uint32_t *__restrict__ lstar, uint32_t n,
-                                                              uint32_t start_pos,
-                                                              uint32_t *__restrict__ exit0,
+// CodeT = uint16_t (code16.hpp; the array is padded to an even count): two codes per load and lane, and the exit
+// leaves as uint16_t too, exit0[p] = exit - tile_end.  That needs no escape: this form only runs when every code is
+// below 0xffff, so a position of the tile jumps to less than tile_end + 0xffff (or to n).
+template <typename CodeT>
+__global__ __launch_bounds__(kThreads) void chain_exit_kernel(const CodeT *__restrict__ lstar, uint32_t n,
+                                                              uint32_t start_pos, CodeT *__restrict__ exit0,
                                                               uint32_t *__restrict__ target_bits) {
-    __shared__ uint32_t jump[kTile];
+    constexpr bool kNarrow = sizeof(CodeT) == 2;
+    __shared__ __align__(8) uint32_t jump[kTile];
     const uint32_t base = blockIdx.x * (uint32_t)kTile;
     const uint32_t tile_end = (n - base < (uint32_t)kTile) ? n : base + kTile;
     const int tid = threadIdx.x;
-    uint32_t ls[kPerThread];  // all loads of the tile in flight together
+    if constexpr (kNarrow) {
+        const uint32_t *__restrict__ pairs = reinterpret_cast<const uint32_t *>(lstar);
+        const uint32_t last_pair = (n - 1u) >> 1;
+        uint32_t ls[kPerThread / 2];  // all loads of the tile in flight together
 #pragma unroll
-    for (int j = 0; j < kPerThread; ++j) {
-        const uint32_t p = base + j * kThreads + tid;
-        ls[j] = lstar[p < n ? p : n - 1u];  // (no branch around the load: guarded, each one was waited for on its own)
-    }
+        for (int j = 0; j < kPerThread / 2; ++j) {
+            const uint32_t pr = (base >> 1) + j * kThreads + tid;
+            ls[j] = pairs[pr < last_pair ? pr : last_pair];  // (no branch around the load)
+        }
 #pragma unroll
-    for (int j = 0; j < kPerThread; ++j) {
-        const uint32_t lp = j * kThreads + tid;
-        const uint32_t p = base + lp;
-        jump[lp] = (p < n) ? next_pos(p, ls[j], n) : n;
+        for (int j = 0; j < kPerThread / 2; ++j) {
+            const uint32_t lp = 2u * (j * kThreads + tid);
+            const uint32_t p = base + lp;
+            uint2 v;
+            v.x = (p < n) ? next_pos(p, ls[j] & 0xffffu, n) : n;
+            v.y = (p + 1u < n) ? next_pos(p + 1u, ls[j] >> 16, n) : n;
+            *reinterpret_cast<uint2 *>(&jump[lp]) = v;
+        }
+    } else {
+        uint32_t ls[kPerThread];  // all loads of the tile in flight together
+#pragma unroll
+        for (int j = 0; j < kPerThread; ++j) {
+            const uint32_t p = base + j * kThreads + tid;
+            ls[j] = lstar[p < n ? p : n - 1u];  // (no branch around the load: guarded, each one was waited for on its own)
+        }
+#pragma unroll
+        for (int j = 0; j < kPerThread; ++j) {
+            const uint32_t lp = j * kThreads + tid;
+            const uint32_t p = base + lp;
+            jump[lp] = (p < n) ? next_pos(p, ls[j], n) : n;
+        }
     }
     __syncthreads();
+    // the thread's own pointers stay in registers through the rounds: a position that has left the tile costs no LDS
+    // access any more, one that has not costs a read and a write instead of two reads and a write
+    uint32_t own[kPerThread];
+#pragma unroll
+    for (int j = 0; j < kPerThread; ++j) own[j] = jump[j * kThreads + tid];
     for (int round = 0; round < 13; ++round) {
         int changed = 0;
 #pragma unroll
         for (int j = 0; j < kPerThread; ++j) {
-            const uint32_t lp = j * kThreads + tid;
-            const uint32_t t = jump[lp];
-            if (t < tile_end) {  // still inside the tile: hop through
-                jump[lp] = jump[t - base];
+            if (own[j] < tile_end) {  // still inside the tile: hop through
+                own[j] = jump[own[j] - base];
+                jump[j * kThreads + tid] = own[j];
                 changed = 1;
             }
         }
         if (!__syncthreads_or(changed)) break;
     }
+    if constexpr (kNarrow) {
+        uint32_t *__restrict__ exit_pairs = reinterpret_cast<uint32_t *>(exit0);  // (padded to an even count as well)
 #pragma unroll
-    for (int j = 0; j < kPerThread; ++j) {
-        const uint32_t lp = j * kThreads + tid;
-        const uint32_t p = base + lp;
-        if (p < n) {
-            const uint32_t e = jump[lp];
-            exit0[p] = e;
-            const bool last = (lp + 1 == (uint32_t)kTile) || (p + 1 >= n);
-            if (e < n && (last || jump[lp + 1] != e)) atomicOr(&target_bits[e >> 5], 1u << (e & 31));
+        for (int j = 0; j < kPerThread / 2; ++j) {
+            const uint32_t lp = 2u * (j * kThreads + tid);
+            const uint32_t p = base + lp;
+            if (p < n) {
+                const uint2 e = *reinterpret_cast<const uint2 *>(&jump[lp]);
+                const bool second = p + 1u < n;
+                exit_pairs[p >> 1] = ((e.x - tile_end) & 0xffffu) | (second ? (e.y - tile_end) << 16 : 0u);
+                if (e.x < n && (!second || e.y != e.x)) atomicOr(&target_bits[e.x >> 5], 1u << (e.x & 31));
+                if (second) {
+                    const bool last = (lp + 2u == (uint32_t)kTile) || (p + 2u >= n);
+                    if (e.y < n && (last || jump[lp + 2] != e.y)) atomicOr(&target_bits[e.y >> 5], 1u << (e.y & 31));
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPerThread; ++j) {
+            const uint32_t lp = j * kThreads + tid;
+            const uint32_t p = base + lp;
+            if (p < n) {
+                const uint32_t e = jump[lp];
+                exit0[p] = e;
+                const bool last = (lp + 1 == (uint32_t)kTile) || (p + 1 >= n);
+                if (e < n && (last || jump[lp + 1] != e)) atomicOr(&target_bits[e >> 5], 1u << (e & 31));
+            }
         }
     }
     if (blockIdx.x == 0 && tid == 0 && start_pos < n) atomicOr(&target_bits[start_pos >> 5], 1u << (start_pos & 31));
@@ -116,8 +163,10 @@ __device__ __forceinline__ uint32_t node_id(const uint32_t *bits, const uint32_t
 }
 
 // nxt[k] = node reached by one exit0 hop; K = terminal.  reach[] initialised to "start node only".
+// (ExitT = uint16_t: the exit counts from the end of the node's tile, chain_exit_kernel)
+template <typename ExitT>
 __global__ __launch_bounds__(kThreads) void node_edges_kernel(const uint32_t *__restrict__ node_pos, uint32_t K,
-                                                              const uint32_t *__restrict__ exit0, uint32_t n,
+                                                              const ExitT *__restrict__ exit0, uint32_t n,
                                                               const uint32_t *__restrict__ bits,
                                                               const uint32_t *__restrict__ prefix,
                                                               uint32_t start_pos, uint32_t *__restrict__ nxt,
@@ -130,7 +179,11 @@ __global__ __launch_bounds__(kThreads) void node_edges_kernel(const uint32_t *__
             continue;
         }
         const uint32_t p = node_pos[k];
-        const uint32_t e = exit0[p];
+        uint32_t e = exit0[p];
+        if constexpr (sizeof(ExitT) == 2) {
+            const uint32_t tbase = p / (uint32_t)kTile * (uint32_t)kTile;
+            e += (n - tbase < (uint32_t)kTile) ? n : tbase + kTile;
+        }
         nxt[k] = (e >= n) ? K : node_id(bits, prefix, e);
         reach[k] = (p == start_pos) ? 1u : 0u;
     }
@@ -167,11 +220,12 @@ __global__ __launch_bounds__(kThreads) void tile_entries_kernel(const uint32_t *
 // kTile / (mean factor length) factor starts, i.e. a few hundred dependent LDS reads, far cheaper
 // than the log2(kTile) rounds of pointer doubling over all 4096 positions this replaced (3.9 ->
 // 2.6 ms at 2^30 bases); many such single-wave workgroups share a CU.
-__global__ __launch_bounds__(64) void chain_mark_kernel(const uint32_t *__restrict__ lstar, uint32_t n,
+template <typename CodeT>
+__global__ __launch_bounds__(64) void chain_mark_kernel(const CodeT *__restrict__ lstar, uint32_t n,
                                                         const uint32_t *__restrict__ entry,
                                                         unsigned long long *__restrict__ chain_bits,
                                                         uint32_t *__restrict__ tile_count) {
-    __shared__ uint16_t jmp[kTile];
+    __shared__ __align__(4) uint16_t jmp[kTile];
     __shared__ unsigned long long bits[kTile / 64];
     const uint32_t base = blockIdx.x * (uint32_t)kTile;
     const uint32_t tile_end = (n - base < (uint32_t)kTile) ? n : base + kTile;
@@ -184,23 +238,41 @@ __global__ __launch_bounds__(64) void chain_mark_kernel(const uint32_t *__restri
         return;
     }
     constexpr int kBatch = 16;
-    for (int j0 = 0; j0 < kTile / 64; j0 += kBatch) {
-        uint32_t ls[kBatch];
+    auto local_next = [&](uint32_t p, uint32_t code) -> uint32_t {  // kTile: leaves the tile
+        if (p >= n) return (uint32_t)kTile;
+        const uint32_t nx = next_pos(p, code, n);
+        return nx < tile_end ? nx - base : (uint32_t)kTile;
+    };
+    if constexpr (sizeof(CodeT) == 2) {  // two codes per load and lane (the array is padded to an even count)
+        const uint32_t *__restrict__ pairs = reinterpret_cast<const uint32_t *>(lstar);
+        const uint32_t last_pair = (n - 1u) >> 1;
+        for (int j0 = 0; j0 < kTile / 128; j0 += kBatch) {
+            uint32_t ls[kBatch];
 #pragma unroll
-        for (int j = 0; j < kBatch; ++j) {
-            const uint32_t p = base + (uint32_t)(j0 + j) * 64u + lane;
-            ls[j] = lstar[p < n ? p : n - 1u];
-        }
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) {
-            const uint32_t lp = (uint32_t)(j0 + j) * 64u + lane;
-            const uint32_t p = base + lp;
-            uint32_t nl = kTile;
-            if (p < n) {
-                const uint32_t nx = next_pos(p, ls[j], n);
-                if (nx < tile_end) nl = nx - base;
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t pr = (base >> 1) + (uint32_t)(j0 + j) * 64u + lane;
+                ls[j] = pairs[pr < last_pair ? pr : last_pair];
             }
-            jmp[lp] = (uint16_t)nl;
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t lp = 2u * ((uint32_t)(j0 + j) * 64u + lane);
+                const uint32_t p = base + lp;
+                *reinterpret_cast<uint32_t *>(&jmp[lp]) = local_next(p, ls[j] & 0xffffu) | (local_next(p + 1u, ls[j] >> 16) << 16);
+            }
+        }
+    } else {
+        for (int j0 = 0; j0 < kTile / 64; j0 += kBatch) {
+            uint32_t ls[kBatch];
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t p = base + (uint32_t)(j0 + j) * 64u + lane;
+                ls[j] = lstar[p < n ? p : n - 1u];
+            }
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t lp = (uint32_t)(j0 + j) * 64u + lane;
+                jmp[lp] = (uint16_t)local_next(base + lp, ls[j]);
+            }
         }
     }
     bits[lane] = 0ull;
@@ -303,9 +375,10 @@ struct FactorRec {
 //     294-296), i.e. the LARGEST SA value in I(L); ref = RC_MASK | (end - L + 1)  (:362-364).
 // kRebase (merged batch, plain mode): start and ref leave relative to the first position of the factor's
 // record (a separate pass over the records cost 2.3 ms per 7*10^7 factors).
-template <bool kRC, bool kRebase>
+// CodeT = uint16_t: the 16-bit codes of plain mode (code16.hpp; no flag, and every code below the saturation value).
+template <bool kRC, bool kRebase, typename CodeT = uint32_t>
 __global__ __launch_bounds__(kThreads) void factor_kernel(const uint32_t *__restrict__ fpos, uint32_t z,
-                                                          const uint32_t *__restrict__ lstar,
+                                                          const CodeT *__restrict__ lstar,
                                                           const uint32_t *__restrict__ isa,
                                                           const uint32_t *__restrict__ sa,
                                                           const uint32_t *__restrict__ lcp, Pyramid Psa,
@@ -399,7 +472,7 @@ inline unsigned grid_for(size_t items, unsigned cap = 256u * 16u) {
 // independent records; start and ref of every factor are then relative to its record.
 // Plain mode: rcN = 0, Pmax unused.  RC mode: n = N (factorized prefix of S), rcN = N and Pmax
 // is the max pyramid over SA.
-uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint32_t *lstar, const uint32_t *sa,
+uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes, const uint32_t *sa,
                        const uint32_t *isa, const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp,
                        void **d_factors_out, uint32_t rcN, const Pyramid *Pmax, uint32_t **d_fpos_out,
                        const TermTable *rebase, const ChainLengthsOut *lengths) {
@@ -408,6 +481,10 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
     if (d_factors_out) *d_factors_out = nullptr;
     if (d_fpos_out) *d_fpos_out = nullptr;
     if (start_pos >= n) return 0;
+    const bool narrow = codes.width == 16;
+    if (narrow && (rcN || rebase || lengths)) throw HipError("resolve_chain: 16-bit codes are for plain records and counts only");
+    const uint32_t *lstar = codes.wide;       // !narrow
+    const uint16_t *lstar16 = codes.narrow;  // narrow
 
     const uint32_t num_tiles = (uint32_t)div_up(n, kTile);
     const uint32_t tbits_words = (uint32_t)div_up((size_t)n + 1, 32);
@@ -415,14 +492,18 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
     // persistent across the call: factor records (if requested) live below `mark`
     uint32_t *fpos = nullptr;
     const size_t mark = arena.mark();
-    uint32_t *exit0 = arena.alloc<uint32_t>(n);
+    uint32_t *exit0 = narrow ? nullptr : arena.alloc<uint32_t>(n);
+    uint16_t *exit16 = narrow ? arena.alloc<uint16_t>((size_t)n + 2) : nullptr;
     uint32_t *tbits = arena.alloc<uint32_t>(tbits_words);
     uint32_t *tprefix = arena.alloc<uint32_t>(tbits_words);
     uint32_t *d_total = arena.alloc<uint32_t>(2);
     HIP_CHECK(hipMemsetAsync(tbits, 0, sizeof(uint32_t) * tbits_words, s));
     {
-        ProfScope ps(ctx.profiler(), "chain_exit", s);
-        chain_exit_kernel<<<num_tiles, kThreads, 0, s>>>(lstar, n, start_pos, exit0, tbits);
+        ProfScope ps(ctx.profiler(), "chain_exit", s, (narrow ? 4.0 : 8.0) * (double)n);
+        if (narrow)
+            chain_exit_kernel<uint16_t><<<num_tiles, kThreads, 0, s>>>(lstar16, n, start_pos, exit16, tbits);
+        else
+            chain_exit_kernel<uint32_t><<<num_tiles, kThreads, 0, s>>>(lstar, n, start_pos, exit0, tbits);
         KERNEL_CHECK();
     }
     {
@@ -442,8 +523,12 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
         ProfScope ps(ctx.profiler(), "chain_nodes", s);
         node_fill_kernel<<<grid_for(tbits_words), kThreads, 0, s>>>(tbits, tprefix, tbits_words, node_pos);
         KERNEL_CHECK();
-        node_edges_kernel<<<grid_for((size_t)K + 1), kThreads, 0, s>>>(node_pos, K, exit0, n, tbits, tprefix,
-                                                                       start_pos, nxt[0], reach);
+        if (narrow)
+            node_edges_kernel<uint16_t><<<grid_for((size_t)K + 1), kThreads, 0, s>>>(node_pos, K, exit16, n, tbits, tprefix,
+                                                                                     start_pos, nxt[0], reach);
+        else
+            node_edges_kernel<uint32_t><<<grid_for((size_t)K + 1), kThreads, 0, s>>>(node_pos, K, exit0, n, tbits, tprefix,
+                                                                                     start_pos, nxt[0], reach);
         KERNEL_CHECK();
     }
     {
@@ -463,8 +548,11 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
     unsigned long long *cbits = arena.alloc<unsigned long long>((size_t)num_tiles * (kTile / 64));
     uint32_t *tile_count = arena.alloc<uint32_t>(num_tiles);
     {
-        ProfScope ps(ctx.profiler(), "chain_mark", s);
-        chain_mark_kernel<<<num_tiles, 64, 0, s>>>(lstar, n, entry, cbits, tile_count);
+        ProfScope ps(ctx.profiler(), "chain_mark", s, (narrow ? 2.0 : 4.0) * (double)n);
+        if (narrow)
+            chain_mark_kernel<uint16_t><<<num_tiles, 64, 0, s>>>(lstar16, n, entry, cbits, tile_count);
+        else
+            chain_mark_kernel<uint32_t><<<num_tiles, 64, 0, s>>>(lstar, n, entry, cbits, tile_count);
         KERNEL_CHECK();
         scan_exclusive_add_u32(tile_count, tile_count, num_tiles, d_total + 1, arena, s);
     }
@@ -521,6 +609,9 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint3
         } else if (rebase) {
             factor_kernel<false, true><<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar, isa, sa, lcp, Psa, Plcp, Psa,
                                                                         0u, recs_tmp, *rebase, n);
+        } else if (narrow) {
+            factor_kernel<false, false, uint16_t><<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar16, isa, sa, lcp, Psa, Plcp,
+                                                                                   Psa, 0u, recs_tmp, TermTable{}, n);
         } else {
             factor_kernel<false, false><<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar, isa, sa, lcp, Psa, Plcp, Psa,
                                                                          0u, recs_tmp, TermTable{}, n);

@@ -17,6 +17,7 @@
 //      predicate, using the LCP pyramid for I(d) and the SA pyramid for the range minimum.
 #include "pipeline.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 #include "nearest_lds.hpp"
 #include "queues.hpp"
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void lpf_far_kernel(const uint32_t *__res
                                                            Pyramid Psa, Pyramid Plcp,
                                                            const uint32_t *__restrict__ by_rank,
                                                            const uint32_t *__restrict__ far_aux, bool bounded,
-                                                           uint32_t *__restrict__ lstar, uint32_t *__restrict__ far_exact) {
+                                                           LstarCodes lstar, uint32_t *__restrict__ far_exact) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < far_count; k += stride) {
         const uint32_t r = far_list[k];
@@ -229,7 +230,9 @@ __global__ __launch_bounds__(kThreads) void lpf_far_kernel(const uint32_t *__res
             jp = (aux & 0x7fffffffu) == 0x7fffffffu ? kNoPos : (aux & 0x7fffffffu);
             far_down<false>(sa, n, Psa, Plcp, r, i, lp, ls, js);
         }
-        far_exact[k] = lpf_decide(i, lp, jp, ls, js, lstar + i) ? i : kNoPos;
+        uint32_t code;
+        far_exact[k] = lpf_decide(i, lp, jp, ls, js, &code) ? i : kNoPos;
+        store_code(lstar, i, code);
     }
 }
 
@@ -237,37 +240,104 @@ __global__ __launch_bounds__(kThreads) void lpf_far_kernel(const uint32_t *__res
 __global__ __launch_bounds__(kThreads) void lpnf_fallback_list_kernel(const uint32_t *__restrict__ far_exact,
                                                                       uint32_t far_count, uint32_t n,
                                                                       const uint32_t *__restrict__ isa, Pyramid Psa,
-                                                                      Pyramid Plcp, uint32_t *__restrict__ lstar) {
+                                                                      Pyramid Plcp, LstarCodes lstar) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < far_count; k += stride) {
         const uint32_t i = far_exact[k];
         if (i == kNoPos) continue;
         const uint32_t cap = (n - i) < i ? (n - i) : i;  // L* <= i - j <= i and L* <= n - i
-        lstar[i] = lpnf_search(Psa, Plcp, isa[i] - 1u, i, lstar[i], cap);  // P(lstar[i]) holds on entry
+        store_code(lstar, i, lpnf_search(Psa, Plcp, isa[i] - 1u, i, load_code_bound(lstar, i), cap));  // P(bound) holds on entry
     }
 }
 
 __global__ __launch_bounds__(kThreads) void lpnf_fallback_kernel(ShardQueue exact_q, uint32_t n,
                                                                  const uint32_t *__restrict__ isa,
-                                                                 Pyramid Psa, Pyramid Plcp,
-                                                                 uint32_t *__restrict__ lstar) {
+                                                                 Pyramid Psa, Pyramid Plcp, LstarCodes lstar) {
     const uint32_t shard = blockIdx.x;
     const uint32_t count = exact_q.counts[shard * kQPad];
     const uint32_t *items = exact_q.items + (size_t)shard * exact_q.cap;
     for (uint32_t k = blockIdx.y * blockDim.x + threadIdx.x; k < count; k += gridDim.y * blockDim.x) {
         const uint32_t i = items[k];
         const uint32_t cap = (n - i) < i ? (n - i) : i;  // L* <= i - j <= i and L* <= n - i
-        lstar[i] = lpnf_search(Psa, Plcp, isa[i] - 1u, i, lstar[i], cap);  // P(lstar[i]) holds on entry
+        store_code(lstar, i, lpnf_search(Psa, Plcp, isa[i] - 1u, i, load_code_bound(lstar, i), cap));  // P(bound) holds on entry
+    }
+}
+
+// wide[i] = code16[i], two codes per lane (the 16-bit array is padded to an even count, the wide one to a line)
+__global__ __launch_bounds__(kThreads) void widen_codes_kernel(const uint32_t *__restrict__ pairs, uint32_t npairs,
+                                                               uint2 *__restrict__ wide) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < npairs; k += stride) {
+        const uint32_t v = pairs[k];
+        wide[k] = make_uint2(v & 0xffffu, v >> 16);
+    }
+}
+// ... and the listed codes on top, in a launch of its own behind it; of two entries for one position the larger stays
+__global__ __launch_bounds__(kThreads) void apply_wide_codes_kernel(WideCodes wl, uint32_t count, uint32_t n,
+                                                                    uint32_t *__restrict__ wide) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += stride) {
+        const uint64_t e = wl.items[k];
+        const uint32_t i = (uint32_t)e;
+        if (i < n) atomicMax(&wide[i], (uint32_t)(e >> 32));
     }
 }
 
 }  // namespace
 
+LstarCodes alloc_lstar(Context &ctx, uint32_t n, bool want_narrow) {
+    const SortKnobs &knobs = sort_knobs();
+    LstarCodes c;
+    if (want_narrow && !knobs.no_code16 && ctx.code16_off_n != n && packed_text_order_applies(n, ctx.rec_plan != nullptr)) {
+        c.narrow = ctx.arena.alloc<uint16_t>((size_t)n + 8);
+        c.list.cap = (uint32_t)std::max<size_t>(n / 64, 1024);
+        c.list.items = ctx.arena.alloc<uint64_t>(c.list.cap);
+        c.list.count = ctx.arena.alloc<uint32_t>(1);
+        c.list.max = knobs.code16_max;
+        c.width = 16;
+    } else {
+        c.wide = ctx.arena.alloc<uint32_t>(n);
+    }
+    return c;
+}
+
+uint32_t *widened_lstar(Context &ctx, const LstarCodes &codes, uint32_t n, uint32_t listed) {
+    if (!codes.narrow) return codes.wide;
+    hipStream_t s = ctx.stream;
+    ProfScope ps(ctx.profiler(), "widen_codes", s, 6.0 * (double)n);
+    const uint32_t npairs = (uint32_t)div_up((size_t)n, 2);
+    uint32_t *wide = ctx.arena.alloc<uint32_t>(2 * (size_t)npairs);
+    widen_codes_kernel<<<(unsigned)std::min<size_t>(div_up(npairs, kThreads), 256u * 16u), kThreads, 0, s>>>(
+        reinterpret_cast<const uint32_t *>(codes.narrow), npairs, reinterpret_cast<uint2 *>(wide));
+    KERNEL_CHECK();
+    if (listed) {
+        apply_wide_codes_kernel<<<(unsigned)std::min<size_t>(div_up(listed, kThreads), 1024u), kThreads, 0, s>>>(codes.list, listed,
+                                                                                                                n, wide);
+        KERNEL_CHECK();
+    }
+    return wide;
+}
+
 uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_t *isa, const uint32_t *lcp,
-                     const Pyramid &Psa, const Pyramid &Plcp, uint32_t *lstar, uint32_t *isa_fill,
+                     const Pyramid &Psa, const Pyramid &Plcp, LstarCodes &lstar, uint32_t *isa_fill,
                      const PackedText *fill_pyramids) {
     hipStream_t s = ctx.stream;
     const size_t mark = ctx.arena.mark();
+    static const bool trace = getenv("NOLZSS_TRACE") != nullptr;
+    if (lstar.narrow && !isa_fill) throw HipError("build_lstar: the 16-bit codes come out of the two-value permutation only");
+    if (lstar.narrow) HIP_CHECK(hipMemsetAsync(lstar.list.count, 0, sizeof(uint32_t), s));
+    // The 16-bit form did not work out on this text: everything this stage allocated is released, a 32-bit array is
+    // taken instead and the stage runs again, as for a pending LCP entry below (the pyramids are complete by then).
+    // Calls on a text of this length then start with 32-bit codes (Context::code16_off_n).
+    auto redo_with_wide_codes = [&]() {
+        ctx.arena.rewind(mark);
+        ctx.code16_off_n = n;
+        lstar.narrow = nullptr;
+        lstar.list = WideCodes{};
+        lstar.wide = ctx.arena.alloc<uint32_t>(n);
+        lstar.width = 32;
+        return build_lstar(ctx, n, sa, isa, lcp, Psa, Plcp, lstar, isa_fill, nullptr);
+    };
     // fill_pyramids: Psa / Plcp are allocated but empty (alloc_pyramid): the tile kernel writes their first level,
     // the upper levels are filled behind it, and the check for undecided LCP entries happens on the way
     uint32_t *pending_flag = nullptr;
@@ -359,11 +429,15 @@ uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_
         ProfScope ps(ctx.profiler(), "lpf_to_text_order", s);
         uint32_t *idx[2] = {const_cast<uint32_t *>(sa), scratch_idx};
         uint32_t *val[2] = {by_rank, scratch_val};
-        bucketed_scatter(idx, val, n, lstar, n, ctx.arena, s, ctx.profiler(), true, true, ctx.rec_plan, isa_fill);
+        const bool done = bucketed_scatter(idx, val, n, lstar.wide, n, ctx.arena, s, ctx.profiler(), true, true, ctx.rec_plan,
+                                           isa_fill, true, lstar.narrow ? &lstar : nullptr);
+        if (!done) {
+            if (trace) fprintf(stderr, "[nolzss] code16: the packed text-order form did not finish, 32-bit codes instead\n");
+            return redo_with_wide_codes();
+        }
     }
     uint32_t h[2] = {0, 0};
     read_totals(h);
-    static const bool trace = getenv("NOLZSS_TRACE") != nullptr;
     if (trace) fprintf(stderr, "[nolzss] lpf: %u ranks to the far queue, %u positions to the exact search so far\n", h[1], h[0]);
     if (h[1] > 0) {
         ProfScope ps(ctx.profiler(), "lpf_far", s);
@@ -385,7 +459,31 @@ uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_
         lpnf_fallback_kernel<<<dim3(kQShards, gy), kThreads, 0, s>>>(exact_q, n, isa, Psa, Plcp, lstar);
         KERNEL_CHECK();
     }
+    if (!lstar.narrow) {
+        lstar.width = 32;
+        ctx.arena.rewind(mark);
+        return h[0];
+    }
+    // which form the cursor gets: one small read-back of the list's count
+    uint32_t listed = 0;
+    ctx.read_back(lstar.list.count, &listed, 1);
+    if (listed > lstar.list.cap) {
+        if (trace)
+            fprintf(stderr, "[nolzss] code16: wide-code list overflow, %u codes >= %u (cap %u): 32-bit codes instead\n", listed,
+                    lstar.list.max, lstar.list.cap);
+        return redo_with_wide_codes();
+    }
     ctx.arena.rewind(mark);
+    if (listed == 0) {
+        lstar.width = 16;
+        if (trace) fprintf(stderr, "[nolzss] code16: narrow cursor, 0 wide codes (max %u)\n", lstar.list.max);
+    } else {
+        lstar.wide = widened_lstar(ctx, lstar, n, listed);
+        lstar.width = 32;
+        if (trace)
+            fprintf(stderr, "[nolzss] code16: widened, %u wide codes >= %u applied (cap %u)\n", listed, lstar.list.max,
+                    lstar.list.cap);
+    }
     return h[0];
 }
 

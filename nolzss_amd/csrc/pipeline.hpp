@@ -1,5 +1,6 @@
 // pipeline.hpp -- per-device context and the stage entry points of the factorization pipeline.
 #pragma once
+#include "code16.hpp"
 #include "common.hpp"
 #include "pyramid.hpp"
 #include "text.hpp"
@@ -19,6 +20,9 @@ struct Context {
     // merged batch of long records (set for the duration of one run): the two permutation scatters of the
     // pipeline -- rank[sa[r]] and L*[sa[r]] -- stay inside the records (text_order.hpp, RecordScatterPlan)
     const struct RecordScatterPlan *rec_plan = nullptr;
+    // length of the last text on which the 16-bit codes had to be given up (build_lstar): calls on a text of that
+    // length start with 32-bit codes instead of paying the second run of the stage again
+    uint32_t code16_off_n = 0;
 
     Profiler *profiler() { return prof.enabled() ? &prof : nullptr; }
     // copy `count` (<= 64) device words to host and wait for them
@@ -54,13 +58,21 @@ Pyramid build_lcp_pyramid(Context &ctx, const PackedText &text, const uint32_t *
 struct Pyramid;
 
 // ---- stage 4: per-position factor length codes (lpnf.hip) ---------------------------------
-// lstar[i] = L*[i] (0 = literal).  Returns the number of positions that needed the exact search.
+// lstar[i] = L*[i] (0 = literal), through a handle (code16.hpp).  Returns the number of positions that needed the exact
+// search.  alloc_lstar makes the handle: the 16-bit form (2 n bytes and the wide-code list) if the caller can take it
+// (want_narrow: isa is left to this stage and nothing behind it needs 32-bit codes) and the packed text-order
+// permutation will run, else n 32-bit codes.  On return lstar.width says which array the cursor reads: 16 (no code
+// reached the saturation value) or 32 (lstar.wide: the caller's array, or one this stage took from the arena BEHIND
+// its own temporaries -- widened with the list applied, or from a second run when the list overflowed).
+// widened_lstar: a 32-bit copy of the 16-bit array in the arena, with the first `listed` list entries applied.
+LstarCodes alloc_lstar(Context &ctx, uint32_t n, bool want_narrow);
+uint32_t *widened_lstar(Context &ctx, const LstarCodes &codes, uint32_t n, uint32_t listed);
 // isa_fill (optional): isa[] has not been written yet (build_suffix_array, isa_deferred): it is filled here.
 // fill_pyramids (optional): Psa / Plcp are allocated (alloc_pyramid over sa / lcp) but not computed: the tile kernel
 // of this stage writes their first level from the blocks it has in LDS and the upper levels are filled here -- the
 // caller skips build_pyramid / build_lcp_pyramid (whose check for undecided LCP entries happens here too).
 uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_t *isa, const uint32_t *lcp,
-                     const Pyramid &Psa, const Pyramid &Plcp, uint32_t *lstar, uint32_t *isa_fill = nullptr,
+                     const Pyramid &Psa, const Pyramid &Plcp, LstarCodes &lstar, uint32_t *isa_fill = nullptr,
                      const PackedText *fill_pyramids = nullptr);
 // pieces of build_lcp_pyramid for that form (sa_regroup.hip): the code above which an LCP entry counts as
 // undecided, the comparison of the suffixes around every undecided entry, and the test hook that leaves one undecided
@@ -81,7 +93,9 @@ struct ChainLengthsOut {
     uint32_t **order = nullptr;      // optional: z lengths in factor order, left in the arena like d_fpos_out
 };
 inline uint32_t length_tail_cap(uint32_t n) { return n / kLengthHistBins + 1u; }
-uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const uint32_t *lstar, const uint32_t *sa,
+// lstar.width == 16: the cursor kernels read two bytes per position and exit0 shrinks to two bytes as well (plain mode
+// without rebase or lengths only).
+uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &lstar, const uint32_t *sa,
                        const uint32_t *isa, const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp,
                        void **d_factors_out, uint32_t rcN = 0, const Pyramid *Pmax = nullptr,
                        uint32_t **d_fpos_out = nullptr, const TermTable *rebase = nullptr,

@@ -35,6 +35,9 @@ SortKnobs::SortKnobs() {
     text_order_hist = set("NOLZSS_TEXT_ORDER_HIST");
     const char *esc = getenv("NOLZSS_TEXT_ORDER_ESC");
     text_order_esc = esc ? (long long)strtoul(esc, nullptr, 0) : -1;
+    no_code16 = set("NOLZSS_NO_CODE16");
+    const long long c16 = i64("NOLZSS_CODE16_MAX", 0xffff);
+    code16_max = (uint32_t)(c16 < 1 ? 1 : (c16 > 0xffff ? 0xffff : c16));
 }
 
 const SortKnobs &sort_knobs() {

@@ -89,6 +89,8 @@ struct SortKnobs {
     uint64_t rec_bucket_min;   // NOLZSS_REC_BUCKET_MIN: smallest average record for the record sort and scatter plan (tiles cost 4096 / that)
     bool text_order_hist;      // NOLZSS_TEXT_ORDER_HIST: A/B switch (and tests), the two-value permutation with histograms
     long long text_order_esc;  // NOLZSS_TEXT_ORDER_ESC: (tests) lower escape threshold of the packed form (-1: not set)
+    bool no_code16;            // NOLZSS_NO_CODE16: A/B switch, 32-bit codes in text order throughout (code16.hpp)
+    uint32_t code16_max;       // NOLZSS_CODE16_MAX: (tests) lower saturation value of the 16-bit codes, 1 .. 0xffff
 };
 const SortKnobs &sort_knobs();
 

@@ -562,13 +562,13 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
         HIP_CHECK(hipStreamSynchronize(s));
         arena.rewind(mark);
     }
-    const uint32_t z = resolve_chain(ctx, N, (uint32_t)start_pos, code, sa, isa, lcp, Pmin, Plcp, d_factors_out, N, &Pmax,
+    const uint32_t z = resolve_chain(ctx, N, (uint32_t)start_pos, LstarCodes::of(code), sa, isa, lcp, Pmin, Plcp, d_factors_out, N, &Pmax,
                                      d_fpos_out, nullptr, lengths);
     if (plain_out) {
         // the plain chain over the same positions: counts (and factor starts) only, no records
         ProfScope ps(ctx.profiler(), "plain_chain", s);
         plain_out->fpos = nullptr;
-        plain_out->z = resolve_chain(ctx, N, 0, plain, sa, isa, lcp, Pmin, Plcp, nullptr, 0, nullptr,
+        plain_out->z = resolve_chain(ctx, N, 0, LstarCodes::of(plain), sa, isa, lcp, Pmin, Plcp, nullptr, 0, nullptr,
                                      plain_out->want_fpos ? &plain_out->fpos : nullptr);
     }
     return z;

@@ -379,7 +379,7 @@ uint32_t run_rlz_pipeline(Context &ctx, const uint8_t *d_S, const RlzLayout &lay
     }
     // min SA over I(L) lies in Rblk (the block comes first), max SA in the mirrored block (it comes last), and
     // 2 rcN - max SA - L + 1 with 2 rcN = B - 1 + E is the leftmost forward coordinate
-    return resolve_chain(ctx, lay.chain_end, lay.block_length + 1u, code, sa, isa, lcp, Pmin, Plcp, d_factors_out, lay.rcN,
+    return resolve_chain(ctx, lay.chain_end, lay.block_length + 1u, LstarCodes::of(code), sa, isa, lcp, Pmin, Plcp, d_factors_out, lay.rcN,
                          lay.with_rc ? &Pmax : nullptr, d_fpos_out);
 }
 

@@ -538,16 +538,63 @@ __global__ __launch_bounds__(kWindow2Threads) void window_unpack_kernel(const ui
     }
 }
 
+// The 16-bit form of the codes (code16.hpp): the codes of a window are staged as uint16_t and leave 16 bytes per lane,
+// the ranks as above -- 96 KiB of LDS, 8 + 6 bytes per pair.  A code of wl.max or more is stored as wl.max and goes to
+// the wide-code list (an escaped code too, with the threshold as its value: escape_fixup_kernel appends the true one).
+__global__ __launch_bounds__(kWindow2Threads) void window_unpack16_kernel(const uint64_t *__restrict__ in,
+                                                                          uint16_t *__restrict__ out,
+                                                                          uint32_t *__restrict__ out2, uint32_t n_out,
+                                                                          int window_bits, int low_bits, int rank_bits,
+                                                                          WideCodes wl) {
+    __shared__ __align__(16) uint32_t s_b[1 << kWindowBitsMax];
+    __shared__ __align__(16) uint16_t s_a[1 << kWindowBitsMax];
+    const uint32_t W = 1u << window_bits;
+    const size_t base = (size_t)blockIdx.x << window_bits;
+    const uint32_t len = (uint32_t)((n_out - base < (size_t)W) ? (n_out - base) : (size_t)W);
+    const uint32_t rank_mask = (uint32_t)((1ull << rank_bits) - 1ull);
+    constexpr int kBatch = 4;
+    for (uint32_t t0 = 0; t0 < len; t0 += kBatch * kWindow2Threads) {
+        uint64_t vv[kBatch];
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j) {
+            const uint32_t t = t0 + (uint32_t)j * kWindow2Threads + threadIdx.x;
+            vv[j] = in[base + (t < len ? t : 0u)];  // (no branch around the loads)
+        }
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j) {
+            const uint32_t t = t0 + (uint32_t)j * kWindow2Threads + threadIdx.x;
+            const uint32_t at = (uint32_t)vv[j] & (W - 1u);
+            const uint32_t code = (uint32_t)(vv[j] >> (low_bits + rank_bits));
+            const bool big = t < len && code >= wl.max;
+            if (t < len) {
+                s_a[at] = (uint16_t)(big ? wl.max : code);
+                s_b[at] = ((uint32_t)(vv[j] >> low_bits) & rank_mask) + 1u;
+            }
+            append_wide_code(wl, (uint32_t)base + at, code, big);
+        }
+    }
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < len; t += kWindow2Threads) out2[base + t] = s_b[t];
+    // (a window starts at a multiple of 1024 codes: the 16-byte stores are aligned)
+    for (uint32_t t = threadIdx.x * 8u; t < len; t += kWindow2Threads * 8u) {
+        if (t + 8u <= len) {
+            *reinterpret_cast<uint4 *>(out + base + t) = *reinterpret_cast<const uint4 *>(s_a + t);
+        } else {
+            for (uint32_t k = t; k < len; ++k) out[base + k] = s_a[k];
+        }
+    }
+}
+
 // out[idx[r]] = code[r] for the escaped ranks (none when the list overflowed: the caller then starts over)
 __global__ __launch_bounds__(kThreads) void escape_fixup_kernel(const uint32_t *__restrict__ exc, const uint32_t *__restrict__ ctl,
                                                                 uint32_t cap, const uint32_t *__restrict__ idx,
-                                                                const uint32_t *__restrict__ code, uint32_t *__restrict__ out) {
+                                                                const uint32_t *__restrict__ code, LstarCodes out) {
     const uint32_t cnt = ctl[2];
     if (cnt > cap) return;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < cnt; k += stride) {
         const uint32_t r = exc[k];
-        out[idx[r]] = code[r];
+        store_code(out, idx[r], code[r]);
     }
 }
 
@@ -569,8 +616,9 @@ __global__ __launch_bounds__(kThreads) void code_census_kernel(const uint32_t *_
 }
 
 // lstar[sa[r]] = code[r], isa[sa[r]] = r + 1 by the kernels above; false (nothing usable written) when the exception
-// list overflowed or a look-back gave up -- the caller then runs the histogram form.
-bool packed_text_order(const uint32_t *idx, const uint32_t *code, size_t count, uint32_t *out, uint32_t *out2, int nb, int wb,
+// list overflowed or a look-back gave up -- the caller then runs the histogram form.  out.narrow: the codes leave as
+// uint16_t (code16.hpp).
+bool packed_text_order(const uint32_t *idx, const uint32_t *code, size_t count, const LstarCodes &out, uint32_t *out2, int nb, int wb,
                        uint64_t *buf_a, Arena &arena, hipStream_t stream, Profiler *prof) {
     const bool trace = sort_knobs().trace;
     const int low_bits = wb + kRadixBits;
@@ -615,9 +663,13 @@ bool packed_text_order(const uint32_t *idx, const uint32_t *code, size_t count, 
         KERNEL_CHECK();
     }
     {
-        ProfScope ps(prof, "window_scatter", stream, 16.0 * (double)count);
-        window_unpack_kernel<<<(unsigned)div_up(count, (size_t)1 << wb), kWindow2Threads, 0, stream>>>(
-            buf_b, out, out2, (uint32_t)count, wb, low_bits, nb);
+        ProfScope ps(prof, "window_scatter", stream, (out.narrow ? 14.0 : 16.0) * (double)count);
+        const unsigned windows = (unsigned)div_up(count, (size_t)1 << wb);
+        if (out.narrow)
+            window_unpack16_kernel<<<windows, kWindow2Threads, 0, stream>>>(buf_b, out.narrow, out2, (uint32_t)count, wb, low_bits,
+                                                                           nb, out.list);
+        else
+            window_unpack_kernel<<<windows, kWindow2Threads, 0, stream>>>(buf_b, out.wide, out2, (uint32_t)count, wb, low_bits, nb);
         KERNEL_CHECK();
         escape_fixup_kernel<<<256, kThreads, 0, stream>>>(exc, ctl, cap, idx, code, out);
         KERNEL_CHECK();
@@ -884,10 +936,10 @@ void partial_then_plain_form(uint32_t *idx[2], uint32_t *val[2], size_t count, u
 }  // namespace
 
 // Chooses the form; the forms allocate from the arena, which is released here.
-void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out, Arena &arena,
+bool bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out, Arena &arena,
                       hipStream_t stream, Profiler *prof, bool keep_input, bool keep_val, const RecordScatterPlan *plan,
-                      uint32_t *out2, bool short_codes) {
-    if (count == 0) return;
+                      uint32_t *out2, bool short_codes, const LstarCodes *narrow) {
+    if (count == 0) return narrow == nullptr;
     const size_t amark = arena.mark();
     const int nbits = index_bits(n_out);
     const bool two_passes = nbits <= 2 * kRadixBits + kWindowBitsMax;  // two digits and a window cover the target
@@ -900,11 +952,12 @@ void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t
     if (two_value && short_codes && !sort_knobs().text_order_hist) {
         // one 8-byte word per pair, no histograms: 16 + 16 + 16 bytes per pair; the inputs are only read, so the
         // histogram form can still run when the exception list overflows or a look-back gives up
-        const bool done = packed_text_order(idx[0], val[0], count, out, out2, nbits, wb, reinterpret_cast<uint64_t *>(val[1]), arena,
-                                            stream, prof);
+        const bool done = packed_text_order(idx[0], val[0], count, narrow ? *narrow : LstarCodes::of(out), out2, nbits, wb,
+                                            reinterpret_cast<uint64_t *>(val[1]), arena, stream, prof);
         arena.rewind(amark);
-        if (done) return;
+        if (done) return true;
     }
+    if (narrow) return false;  // (no other form writes 16-bit codes)
     bool separators_ok = true;
     if (two_value) {
         two_value_hist_form(idx, val, count, out, out2, n_out, wb, keep_input, arena, stream, prof);
@@ -919,6 +972,12 @@ void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t
     }
     arena.rewind(amark);
     if (!separators_ok) throw HipError("record scatter: a separator suffix is not the first of its record");
+    return true;
+}
+
+bool packed_text_order_applies(size_t count, bool has_plan) {
+    const int nbits = index_bits(count);
+    return count > (size_t(1) << 24) && nbits <= 2 * kRadixBits + kWindowBitsMax && !has_plan && !sort_knobs().text_order_hist;
 }
 
 void permute_packed(uint32_t *idx, uint64_t *packed, size_t count, uint32_t *out, uint32_t *out2, Arena &arena,

@@ -3,6 +3,7 @@
 // that bring ranks and factor-length codes from suffix-array order into text order: lpnf.hip, rc.hip, sa_regroup.hip
 // and, with a RecordScatterPlan, batch.hip.
 #pragma once
+#include "code16.hpp"
 #include "radix_sort.hpp"
 
 #include <vector>
@@ -40,9 +41,15 @@ struct RecordScatterPlan {
 // histograms, each pair in ONE 8-byte word whose code field holds 72 - 2 * nb bits or more; larger codes take an
 // exception list (and, should it overflow, the histogram form runs after all).  short_codes = false keeps the
 // histogram form: codes that are mostly large (a flag in bit 31) would only overflow the list.
-void bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out,
+// narrow (optional, with out2; out is then not used): the values are factor-length codes and leave in their 16-bit form
+// (code16.hpp), which only the packed form writes -- false, with nothing usable written, when that form does not take
+// this permutation (packed_text_order_applies) or gave up.  Without narrow the result is always true.
+bool bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out,
                       Arena &arena, hipStream_t stream, Profiler *prof, bool keep_input, bool keep_val = true,
-                      const RecordScatterPlan *plan = nullptr, uint32_t *out2 = nullptr, bool short_codes = true);
+                      const RecordScatterPlan *plan = nullptr, uint32_t *out2 = nullptr, bool short_codes = true,
+                      const LstarCodes *narrow = nullptr);
+// does bucketed_scatter take the packed form for a two-value permutation of `count` targets?
+bool packed_text_order_applies(size_t count, bool has_plan);
 // The same permutation for pairs that already carry both values in one 64-bit word (low half -> out, high half ->
 // out2) and are a permutation of [0, count): out[idx[k]] = (uint32_t)packed[k], out2[idx[k]] = packed[k] >> 32.
 // Both inputs are overwritten (they serve as buffers of the later passes).
