@@ -249,9 +249,12 @@ __global__ __launch_bounds__(kFuseThreads) void regroup_kernel(RegroupArgs A) {
         bool head = !in || a == 0 || v != pv;  // "past the end" counts as a head
         // a suffix that meets a terminator inside the key window ties only with copies of itself at
         // other terminators, and the stable sort has left those in their final order
-        if (kRound0 && short_tag) head = head || ((uint32_t)(v >> low_bits) & ((1u << tag_bits) - 1u)) < short_tag;
-        // is the element behind me a head?
-        const uint32_t edge_next = (lane == 63 && in && a + 1 < m) ? (edge[k] != v ? 1u : 0u) : 1u;
+        const bool short_head = kRound0 && short_tag && ((uint32_t)(v >> low_bits) & ((1u << tag_bits) - 1u)) < short_tag;
+        head = head || short_head;
+        // is the element behind me a head?  (across the wavefront's edge only its key is at hand: with my key it has my
+        // tag, so it is short -- a head -- exactly if I am; a short suffix kept as "tied" with its copy at another
+        // terminator went through the direct round as a group of one)
+        const uint32_t edge_next = (lane == 63 && in && a + 1 < m) ? ((edge[k] != v || short_head) ? 1u : 0u) : 1u;
         const bool next_head = lane_next(head ? 1u : 0u, edge_next) != 0;
         const bool keep = in && !(head && next_head);
         hmask[k] = __ballot(in && head);

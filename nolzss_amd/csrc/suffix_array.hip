@@ -609,10 +609,13 @@ int build_suffix_array(Context &ctx, const PackedText &text, uint32_t *sa, uint3
     key_sort_round0(b, plan);
     b.h = (uint64_t)plan.k_syms;
     if (knobs.trace) {
+        // (the name tells rows of the plan with the same width apart: dna_fast, segmented and general all sort 17 bases)
+        static const char *const kPlanNames[] = {"fused", "key16", "key35", "dna_fast", "rec_fast", "independent", "segmented", "general"};
+        const char *name = plan.choice == KeyPlan::kIndependent && text.terms.mirror ? "independent_mirrored" : kPlanNames[plan.choice];
         if (plan.choice == KeyPlan::kKey35)
-            fprintf(stderr, "[nolzss] n=%u: %u suffixes tied after the %d-bit key sort\n", n, b.m, plan.key_bits);
+            fprintf(stderr, "[nolzss] n=%u: %u suffixes tied after the %d-bit key sort (plan: %s)\n", n, b.m, plan.key_bits, name);
         else
-            fprintf(stderr, "[nolzss] n=%u: %u suffixes tied after the %d-symbol key sort\n", n, b.m, plan.k_syms);
+            fprintf(stderr, "[nolzss] n=%u: %u suffixes tied after the %d-symbol key sort (plan: %s)\n", n, b.m, plan.k_syms, name);
     }
     if (b.m > 0 && b.h < n) direct_round(b, plan.k_syms);
     group_sort_passes(b);
