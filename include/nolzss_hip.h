@@ -554,6 +554,63 @@ int nolzss_roundtrip_device(const void *d_text, size_t n, int with_rc, int devic
 int nolzss_debug_count_mismatches(const uint8_t *a, const uint8_t *b, size_t n, int device,
                                   uint64_t *count, uint64_t *first);
 
+/* ---- relative-LZ archive: ranges of the targets from resident records --------------------------- */
+/* Extension.  Every copy of a relative-LZ parse points into the reference block and never into a target, so any byte of
+ * any target is one hop from the record that covers it.  A handle keeps the block and the records in device memory of
+ * its own (every other call may run between two extracts) and an extract turns a batch of (target, lo, hi) ranges into
+ * bytes with one launch: per output byte one search and one gathered byte, no state words and no jump rounds (DESIGN.md
+ * 5, "Relative-LZ archive: ranges from resident records").
+ *   Inputs of open_records: what nolzss_amd.genomics.rlz.absolute_records produces, the decoder's contract with
+ *     prefix = block: the z records tile [block_len, n), the k targets lie end to end behind the block in order, a
+ *     literal has ref == start and length 1 and takes the next byte of `literals`.
+ *   Two rules beyond the decoder's.  Source inside the block: a copy has (ref & ~NOLZSS_RC_MASK) + length <= block_len
+ *     (it replaces the decoder's source range rule: a self-referential factorisation, whose bytes are chains of hops
+ *     of unbounded depth, is refused and not decoded slowly).  Target boundary: sum(target_lengths) == n - block_len
+ *     and no record straddles the end of a target or lies behind the last one.  Empty targets, k == 0, and z == 0 with
+ *     all lengths 0 are valid.
+ *   Refusals at open: NOLZSS_ERR_INVALID_ARGUMENT, the message names the first offending record index and the rule
+ *     (tiling, literal length, source inside the block, target boundary, literal count; lengths that do not sum name
+ *     record z, "behind the last"); nothing is opened.  n beyond the 32-bit pipeline and z >= 2^32 are refused too.
+ *   Ranges: bytes [lo, hi) of target `target`; they may be empty, overlap, repeat and come in any order.  Output:
+ *     the ranges back to back, range i = bytes[offsets[i] : offsets[i + 1]), offsets[i + 1] - offsets[i] == hi - lo.
+ *   Refusals at extract: NOLZSS_ERR_INVALID_ARGUMENT, the message names the first offending range index, nothing is
+ *     written or returned: target >= k, lo > hi, hi > target_lengths[target], 2^32 or more bytes or ranges in one
+ *     call, d_out_capacity < total.
+ *   Complement of a non-nucleotide (a reverse-complement copy over a byte of the block that is not A, C, G or T, a
+ *     separator for instance) is found by the kernel: the call fails with NOLZSS_ERR_INVALID_ARGUMENT, the message
+ *     names the smallest (range index, byte) and its position inside the target, whatever the schedule; extract returns
+ *     nothing, the contents of d_out are then unspecified.  The handle stays usable.
+ *   Extracts of one handle may run from several threads, but a close must not overlap any other call on that handle.
+ *   The calling thread's current device is left as it was. */
+typedef struct nolzss_rlz_archive nolzss_rlz_archive;
+typedef struct nolzss_rlz_range {
+    uint64_t target, lo, hi;          /* bytes [lo, hi) of that target */
+} nolzss_rlz_range;
+typedef struct nolzss_rlz_archive_summary {
+    uint64_t num_targets;
+    uint64_t block_length;
+    uint64_t z, n_literals;
+    uint64_t total_length;            /* sum of the target lengths */
+    const uint64_t *target_lengths;   /* num_targets entries, owned by the handle */
+    int32_t device;
+    uint64_t device_bytes;            /* device memory the handle holds: block, 16 bytes per record, position sample */
+} nolzss_rlz_archive_summary;
+int nolzss_rlz_archive_open_records(const uint8_t *block, size_t block_len, const nolzss_factor *records, size_t z,
+                                    const uint8_t *literals, size_t n_literals, const uint64_t *target_lengths,
+                                    size_t k, int device, nolzss_rlz_archive **h);
+int nolzss_rlz_archive_info(const nolzss_rlz_archive *h, nolzss_rlz_archive_summary *info);
+/* *bytes (total bytes) and *offsets (q + 1 entries): malloc'ed, nolzss_free.  q == 0, or ranges that are all empty,
+ * return without touching the device. */
+int nolzss_rlz_archive_extract(const nolzss_rlz_archive *h, const nolzss_rlz_range *ranges, size_t q, uint8_t **bytes,
+                               uint64_t **offsets, uint64_t *total);
+/* The same layout into d_out_capacity bytes of caller memory on the handle's device (`stream` as
+ * nolzss_factorize_device; the call returns when the bytes are written).  Only the ranges go up and only an error
+ * word comes back; *total = the bytes written.  One 16-byte store per 16 output bytes when d_out is 16-byte aligned. */
+int nolzss_rlz_archive_extract_device(const nolzss_rlz_archive *h, const nolzss_rlz_range *ranges, size_t q,
+                                      void *d_out, size_t d_out_capacity, void *stream, uint64_t *total);
+/* NULL is a no-op. */
+int nolzss_rlz_archive_close(nolzss_rlz_archive *h);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

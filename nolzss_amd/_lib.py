@@ -102,6 +102,18 @@ class DecodeInfo(C.Structure):
                 ("rounds", C.c_uint64), ("max_active", C.c_uint64)]
 
 
+class RlzRange(C.Structure):
+    """Mirror of nolzss_rlz_range (include/nolzss_hip.h)."""
+    _fields_ = [("target", C.c_uint64), ("lo", C.c_uint64), ("hi", C.c_uint64)]
+
+
+class RlzArchiveSummary(C.Structure):
+    """Mirror of nolzss_rlz_archive_summary (include/nolzss_hip.h)."""
+    _fields_ = [("num_targets", C.c_uint64), ("block_length", C.c_uint64), ("z", C.c_uint64), ("n_literals", C.c_uint64),
+                ("total_length", C.c_uint64), ("target_lengths", C.POINTER(C.c_uint64)), ("device", C.c_int32),
+                ("device_bytes", C.c_uint64)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -240,6 +252,11 @@ def _load():
     lib.nolzss_roundtrip.argtypes = [vp, sz, C.c_int, C.c_int, szp, u64p, u64p, dip]
     lib.nolzss_roundtrip_device.argtypes = [vp, sz, C.c_int, C.c_int, vp, szp, u64p, u64p, dip]
     lib.nolzss_debug_count_mismatches.argtypes = [vp, vp, sz, C.c_int, u64p, u64p]
+    lib.nolzss_rlz_archive_open_records.argtypes = [vp, sz, vp, sz, vp, sz, vp, sz, C.c_int, vpp]
+    lib.nolzss_rlz_archive_info.argtypes = [vp, C.POINTER(RlzArchiveSummary)]
+    lib.nolzss_rlz_archive_extract.argtypes = [vp, vp, sz, vpp, vpp, u64p]
+    lib.nolzss_rlz_archive_extract_device.argtypes = [vp, vp, sz, vp, sz, vp, u64p]
+    lib.nolzss_rlz_archive_close.argtypes = [vp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -290,6 +307,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_rlz_codes",
     "nolzss_literal_symbols", "nolzss_decode", "nolzss_roundtrip", "nolzss_roundtrip_device",
     "nolzss_debug_count_mismatches",
+    "nolzss_rlz_archive_open_records", "nolzss_rlz_archive_info", "nolzss_rlz_archive_extract",
+    "nolzss_rlz_archive_extract_device", "nolzss_rlz_archive_close",
 ]
 
 

@@ -1183,6 +1183,104 @@ def decode_array(factors, literals, prefix=b""):
     return np.frombuffer(raw, dtype=np.uint8), _info_dict(info)
 
 
+# ---- relative-LZ archive: ranges of the targets from resident records (genomics/rlz.py) ------------------------
+def _ranges_array(ranges):
+    """-> contiguous (q, 3) uint64 array of (target index, lo, hi) rows, the layout of nolzss_rlz_range"""
+    r = np.asarray(ranges)
+    if r.size == 0:
+        return np.zeros((0, 3), dtype=np.uint64)
+    if r.ndim != 2 or r.shape[1] != 3 or r.dtype.kind not in "iu":
+        raise ValueError("ranges must be (target, lo, hi) rows of integers")
+    if r.dtype.kind == "i" and (r < 0).any():
+        raise ValueError("ranges: no target, lo or hi may be negative")
+    return np.ascontiguousarray(r, dtype=np.uint64)
+
+
+class RlzArchiveHandle:
+    """Extension: the reference block and the records of a relative-LZ collection kept in device memory (C ABI
+    nolzss_rlz_archive_*), any number of range extractions from them.  A context manager; close() may be called more
+    than once, any other use after it raises ValueError."""
+
+    def __init__(self, handle):
+        self._h = handle
+        info = _lib.RlzArchiveSummary()
+        try:
+            check(lib.nolzss_rlz_archive_info(self._h, C.byref(info)))
+        except Exception:
+            self.close()
+            raise
+        self.info = {k: int(getattr(info, k)) for k in ("num_targets", "block_length", "z", "n_literals",
+                                                        "total_length", "device", "device_bytes")}
+        k = info.num_targets
+        self.target_lengths = (np.ctypeslib.as_array(info.target_lengths, shape=(k,)).copy() if k
+                               else np.zeros(0, dtype=np.uint64))
+
+    @classmethod
+    def open_records(cls, block, records, literals, target_lengths):
+        """Host records in the layout of genomics.rlz.absolute_records, uploaded and packed once.  C ABI
+        nolzss_rlz_archive_open_records (its header states the rules)."""
+        bp, bn, keep_b = _as_buffer(block)
+        f = _decode_records(records)
+        lp, ln, keep_l = _as_buffer(literals)
+        lens = np.ascontiguousarray([operator.index(x) for x in target_lengths], dtype=np.uint64)
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_archive_open_records(bp if bn else None, bn, f.ctypes.data if f.size else None, f.size,
+                                                  lp if ln else None, ln, lens.ctypes.data if lens.size else None,
+                                                  lens.size, _default_device, C.byref(h)))
+        return cls(h)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the archive is closed")
+        return self._h
+
+    def extract_array(self, ranges):
+        """(target index, lo, hi) rows -> (uint8 array of the ranges back to back, uint64 offsets of q + 1 entries)."""
+        h = self._handle()
+        r = _ranges_array(ranges)
+        out, offs, total = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        check(lib.nolzss_rlz_archive_extract(h, r.ctypes.data if len(r) else None, len(r), C.byref(out), C.byref(offs),
+                                             C.byref(total)))
+        try:
+            offsets = np.ctypeslib.as_array(C.cast(offs, C.POINTER(C.c_uint64)), shape=(len(r) + 1,)).copy()
+        finally:
+            lib.nolzss_free(offs)
+        owner = _Owned(out)
+        if total.value == 0:
+            return np.zeros(0, dtype=np.uint8), offsets
+        raw = (C.c_uint8 * total.value).from_address(out.value)
+        raw._owner = owner
+        return np.frombuffer(raw, dtype=np.uint8), offsets
+
+    def extract_device(self, ranges, data_ptr: int, capacity: int, stream: int = 0) -> int:
+        """The same layout into `capacity` bytes of device memory at data_ptr, on the handle's device (stream as
+        factorize_device) -> bytes written.  C ABI nolzss_rlz_archive_extract_device."""
+        h = self._handle()
+        r = _ranges_array(ranges)
+        total = C.c_uint64()
+        check(lib.nolzss_rlz_archive_extract_device(h, r.ctypes.data if len(r) else None, len(r),
+                                                    C.c_void_p(data_ptr) if data_ptr else None, capacity,
+                                                    C.c_void_p(stream) if stream else None, C.byref(total)))
+        return total.value
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            check(lib.nolzss_rlz_archive_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _roundtrip_result(z, mismatches, first, info):
     res = {"z": z.value, "mismatches": mismatches.value,
            "first_mismatch": None if first.value == (1 << 64) - 1 else first.value}

@@ -79,6 +79,8 @@ struct Session {
 };
 
 size_t trim_idle_arenas(int device, const Context *keep);
+// a device allocation of a handle's own (hipMalloc; hipFree it): one retry after trimming the idle arenas
+void *device_alloc(Context &ctx, size_t bytes);
 void reserve_arena_for(Context &ctx, size_t n, size_t extra = 0);
 uint8_t *host_stage(Context &ctx, size_t bytes);
 void upload_bytes(Context &ctx, void *d_dst, const void *h_src, size_t n);

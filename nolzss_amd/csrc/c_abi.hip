@@ -59,6 +59,16 @@ size_t trim_idle_arenas(int device, const Context *keep) {
     return released;
 }
 
+void *device_alloc(Context &ctx, size_t bytes) {
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {  // idle arenas of other lanes may hold the memory
+        (void)hipGetLastError();
+        trim_idle_arenas(ctx.device, &ctx);
+        HIP_CHECK(hipMalloc(&p, bytes));
+    }
+    return p;
+}
+
 // The arena for a text of n symbols plus `extra` bytes (uploads): the worst-case size if the device has
 // it, else as much as there is, but never less than the minimum the pipeline needs on ordinary texts --
 // below that the input is refused up front, with the sizes, as an argument error (ValueError in Python)

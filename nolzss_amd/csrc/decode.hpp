@@ -13,6 +13,9 @@ enum DecodeRule : uint32_t {
     kDecodeSourceRange = 3,
     kDecodeLiteralCount = 4,
     kDecodeComplement = 5,
+    // the relative-LZ archive only (rlz_archive.hpp)
+    kDecodeSourceInBlock = 6,
+    kDecodeTargetBoundary = 7,
 };
 
 struct DecodeRefusal : std::invalid_argument {

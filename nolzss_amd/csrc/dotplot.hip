@@ -335,16 +335,6 @@ struct nolzss_dotplot {
 
 namespace {
 
-void *device_alloc(Context &ctx, size_t bytes) {
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {  // idle arenas of other lanes may hold the memory
-        (void)hipGetLastError();
-        trim_idle_arenas(ctx.device, &ctx);
-        HIP_CHECK(hipMalloc(&p, bytes));
-    }
-    return p;
-}
-
 // Takes z records (device memory of the arena, or host memory) into the handle and computes its statistics.
 void adopt_records(Context &ctx, nolzss_dotplot &h, const void *recs, bool on_device, uint64_t z) {
     hipStream_t s = ctx.stream;

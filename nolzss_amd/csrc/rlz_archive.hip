@@ -1,0 +1,285 @@
+// rlz_archive.hip -- the relative-LZ archive: the record check, the resident form, the position sample and the range
+// extraction ("Relative-LZ archive: ranges from resident records"; semantics: include/nolzss_hip.h,
+// nolzss_rlz_archive_*).
+//
+// Every copy points into the reference block, so output byte x of range i is one search and one gathered byte:
+//     range    i = the last range with offsets[i] <= x                    (upper-bound search: empty ranges are skipped)
+//     position p = first[i] + (x - offsets[i])                            (decoded coordinates: behind the block)
+//     record   k = the last record with start <= p                        (search between two entries of the sample)
+//     byte       = block[src + t] | comp(block[src - t]) | the folded symbol,  t = p - start[k]
+// Every loop is bounded by the call's shape and not by its data: log2(q + 1) steps per range search, at most 9 steps per
+// record search (two neighbouring sample entries are at most 256 records apart: every record has a base), 16 bytes
+// per lane.  No spinning, no communication between lanes; the only atomic is the error atomicMin.
+#include "rlz_archive.hpp"
+
+namespace nolzss {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kChunk = 16;  // output bytes of one lane
+
+__device__ __forceinline__ uint32_t complement(uint32_t c) {  // 0: not a nucleotide
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : 0u;
+}
+
+__device__ __forceinline__ bool is_literal(const Rec &f) { return f.ref == f.start; }
+
+// ctl[0]: (record index << 3 | rule) of the first offending record, atomicMin; ctl[1]: literal records
+__global__ __launch_bounds__(kThreads) void archive_check_kernel(const Rec *__restrict__ recs, uint64_t z,
+                                                                 uint64_t block_len, uint64_t n,
+                                                                 const uint64_t *__restrict__ bounds, uint32_t k,
+                                                                 uint32_t *__restrict__ flags,
+                                                                 unsigned long long *__restrict__ ctl) {
+    unsigned long long bad = ~0ull, literals = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < z; i += stride) {
+        const Rec f = recs[i];
+        uint64_t expect = block_len;
+        if (i) {
+            const Rec p = recs[i - 1];
+            expect = p.start + p.length;
+        }
+        uint32_t rule = kDecodeOk;
+        const bool lit = is_literal(f);
+        const uint64_t r = f.ref & ~kRcMask;
+        if (f.start != expect || f.length == 0 || f.start > n || f.length > n - f.start ||
+            (i == z - 1 && f.length != n - f.start))
+            rule = kDecodeTiling;
+        else if (lit && f.length != 1) rule = kDecodeLiteralLength;
+        else if (!lit && (r > block_len || f.length > block_len - r)) rule = kDecodeSourceInBlock;
+        else {
+            // the first boundary behind start ends the target the record lies in (empty targets repeat a boundary)
+            uint32_t lo = 0, hi = k + 1;  // bounds[0 .. lo) <= start
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (bounds[mid] <= f.start) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo > k || f.length > bounds[lo] - f.start) rule = kDecodeTargetBoundary;
+        }
+        if (rule != kDecodeOk) {
+            const unsigned long long key = (i << 3) | rule;
+            bad = key < bad ? key : bad;
+        }
+        flags[i] = lit ? 1u : 0u;
+        literals += lit ? 1u : 0u;
+    }
+    if (bad != ~0ull) atomicMin(&ctl[0], bad);
+    if (literals) atomicAdd(&ctl[1], literals);
+}
+
+// lit_index: the exclusive add-scan of the literal flags
+__global__ __launch_bounds__(kThreads) void archive_pack_kernel(const Rec *__restrict__ recs, uint64_t z,
+                                                                uint64_t block_len,
+                                                                const uint32_t *__restrict__ lit_index,
+                                                                const uint8_t *__restrict__ literals,
+                                                                ArchiveRec *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < z; i += stride) {
+        const Rec f = recs[i];
+        ArchiveRec a;
+        a.start = (uint32_t)(f.start - block_len);
+        a.length = (uint32_t)f.length;
+        if (is_literal(f)) {
+            a.src = 0;
+            a.meta = kArchiveLiteral | ((uint32_t)literals[lit_index[i]] << 8);
+        } else if (f.ref & kRcMask) {
+            a.src = (uint32_t)((f.ref & ~kRcMask) + f.length - 1);
+            a.meta = kArchiveRc;
+        } else {
+            a.src = (uint32_t)f.ref;
+            a.meta = kArchiveForward;
+        }
+        out[i] = a;
+    }
+}
+
+// sample[s] = the last record with start <= 256 * s
+__global__ __launch_bounds__(kThreads) void archive_sample_kernel(const ArchiveRec *__restrict__ recs, uint32_t z,
+                                                                  uint32_t samples, uint32_t *__restrict__ sample) {
+    const uint32_t s = blockIdx.x * kThreads + threadIdx.x;
+    if (s >= samples) return;
+    const uint32_t p = s << kSampleShift;
+    uint32_t lo = 0, hi = z;  // recs[lo].start <= p (record 0 starts at 0), recs[hi].start > p or hi == z
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (recs[mid].start <= p) lo = mid;
+        else hi = mid;
+    }
+    sample[s] = lo;
+}
+
+// the last range i in [lo, q) with offsets[i] <= x; offsets[lo] <= x < offsets[q].  offsets[i + 1] > x: range i is not empty
+__device__ __forceinline__ uint32_t find_range(const uint32_t *__restrict__ offsets, uint32_t q, uint32_t x, uint32_t lo) {
+    uint32_t hi = q;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (offsets[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the record that covers decoded position p (p below the decoded length)
+__device__ __forceinline__ uint32_t find_record(const ArchiveView &v, uint32_t p) {
+    const uint32_t s = p >> kSampleShift;
+    uint32_t lo = v.sample[s];
+    // the record that covers the next sample position starts behind 256 * s, at p or before it or behind it; every
+    // record behind that one starts behind p
+    uint32_t hi = s + 1 < v.samples ? v.sample[s + 1] + 1u : v.z;
+    while (hi - lo > 1) {  // hi - lo <= 257
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (v.recs[mid].start <= p) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ ArchiveRec load_record(const ArchiveView &v, uint32_t k) {
+    const uint4 w = reinterpret_cast<const uint4 *>(v.recs)[k];
+    return ArchiveRec{w.x, w.y, w.z, w.w};
+}
+
+// One lane owns output bytes [16 g, 16 g + 16) of the call; wide: d_out is 16-byte aligned, a whole chunk goes out as
+// one 16-byte store.
+__global__ __launch_bounds__(kThreads) void rlz_extract_kernel(ArchiveView v, const uint32_t *__restrict__ offsets,
+                                                               const uint32_t *__restrict__ first, uint32_t q,
+                                                               uint32_t total, uint8_t *__restrict__ out, uint32_t wide,
+                                                               unsigned long long *__restrict__ err) {
+    const uint64_t at = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) * kChunk;
+    if (at >= total) return;
+    const uint32_t o = (uint32_t)at;
+    const uint32_t count = total - o < kChunk ? total - o : kChunk;
+
+    uint32_t i = find_range(offsets, q, o, 0);
+    uint32_t range_begin = offsets[i], range_end = offsets[i + 1];
+    uint32_t k = find_record(v, first[i] + (o - range_begin));
+    ArchiveRec f = load_record(v, k);
+    uint32_t t = first[i] + (o - range_begin) - f.start;
+    unsigned long long w0 = 0, w1 = 0;
+    // A whole chunk inside one range and one copy record: its 16 source bytes are contiguous in the block, one
+    // (unaligned) 16-byte load.  A reverse-complement chunk with a non-nucleotide goes through the bytewise walk,
+    // which reports the first one.
+    bool done = false;
+    if (count == kChunk && range_end - o >= kChunk && (f.meta & 3u) != kArchiveLiteral && f.length - t >= kChunk) {
+        const bool rc = (f.meta & 3u) == kArchiveRc;
+        ulonglong2 s;
+        __builtin_memcpy(&s, v.block + (rc ? f.src - t - (kChunk - 1) : f.src + t), sizeof s);
+        if (!rc) {
+            w0 = s.x;
+            w1 = s.y;
+            done = true;
+        } else {
+            uint32_t valid = 1;
+#pragma unroll
+            for (uint32_t b = 0; b < kChunk; ++b) {  // output byte b = comp(source byte 15 - b)
+                const uint32_t j = kChunk - 1 - b;
+                const uint32_t c = complement((uint32_t)((j < 8 ? s.x >> (8 * j) : s.y >> (8 * (j - 8))) & 0xffu));
+                valid &= c != 0 ? 1u : 0u;
+                if (b < 8) w0 |= (unsigned long long)c << (8 * b);
+                else w1 |= (unsigned long long)c << (8 * (b - 8));
+            }
+            done = valid != 0;
+            if (!done) w0 = w1 = 0;
+        }
+    }
+    for (uint32_t b = 0; !done && b < count; ++b) {
+        const uint32_t x = o + b;
+        if (x >= range_end) {
+            // x < total = offsets[q] and x >= offsets[i + 1]: i + 2 <= q.  The next range unless it is empty.
+            i = offsets[i + 2] > x ? i + 1 : find_range(offsets, q, x, i + 1);
+            range_begin = offsets[i];
+            range_end = offsets[i + 1];
+            const uint32_t p = first[i] + (x - range_begin);
+            k = find_record(v, p);
+            f = load_record(v, k);
+            t = p - f.start;
+        } else if (t >= f.length) {  // inside a range the next position is the next record's first (tiling)
+            f = load_record(v, ++k);
+            t = 0;
+        }
+        const uint32_t kind = f.meta & 3u;
+        uint32_t c;
+        if (kind == kArchiveLiteral) {
+            c = (f.meta >> 8) & 0xffu;
+        } else if (kind == kArchiveForward) {
+            c = v.block[f.src + t];
+        } else {
+            c = complement(v.block[f.src - t]);
+            if (c == 0) atomicMin(err, ((unsigned long long)i << 32) | (x - range_begin));
+        }
+        ++t;
+        if (b < 8) w0 |= (unsigned long long)c << (8 * b);
+        else w1 |= (unsigned long long)c << (8 * (b - 8));
+    }
+    if (wide && count == kChunk) {
+        *reinterpret_cast<ulonglong2 *>(out + o) = make_ulonglong2(w0, w1);
+    } else {
+        for (uint32_t b = 0; b < count; ++b) out[o + b] = (uint8_t)((b < 8 ? w0 >> (8 * b) : w1 >> (8 * (b - 8))) & 0xffu);
+    }
+}
+
+}  // namespace
+
+const char *archive_rule_text(uint32_t rule) {
+    switch (rule) {
+    case kDecodeTiling: return "tiling (start[0] = block_len, start[k + 1] = start[k] + length[k], length >= 1)";
+    case kDecodeLiteralLength: return "literal length (a literal, ref == start, has length 1)";
+    case kDecodeSourceInBlock:
+        return "source inside the block (ref + length must not exceed block_len: every copy comes from the reference "
+               "block; a self-referential factorisation has no one-hop random access, decode it with nolzss_decode)";
+    case kDecodeTargetBoundary:
+        return "target boundary (a record lies inside one target: it must not straddle the end of a target or lie behind "
+               "the last one)";
+    default: return "unknown rule";
+    }
+}
+
+ArchiveCheck archive_check(Context &ctx, const Rec *d_recs, size_t z, uint64_t block_len, uint64_t n,
+                           const uint64_t *d_bounds, size_t k, uint32_t *lit_flags) {
+    Arena &arena = ctx.arena;
+    hipStream_t s = ctx.stream;
+    const size_t mark = arena.mark();
+    unsigned long long *ctl = arena.alloc<unsigned long long>(2);
+    HIP_CHECK(hipMemsetAsync(ctl, 0xff, sizeof(unsigned long long), s));
+    HIP_CHECK(hipMemsetAsync(ctl + 1, 0, sizeof(unsigned long long), s));
+    {
+        ProfScope ps(ctx.profiler(), "rlz_archive_check", s, 28.0 * (double)z);
+        archive_check_kernel<<<record_grid(z), kThreads, 0, s>>>(d_recs, z, block_len, n, d_bounds, (uint32_t)k, lit_flags,
+                                                                  ctl);
+        KERNEL_CHECK();
+    }
+    uint32_t h[4];
+    ctx.read_back(reinterpret_cast<const uint32_t *>(ctl), h, 4);
+    arena.rewind(mark);
+    ArchiveCheck res;
+    res.bad = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
+    res.literals = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
+    return res;
+}
+
+void archive_pack(Context &ctx, const Rec *d_recs, size_t z, uint64_t block_len, uint64_t n, uint32_t *lit_flags,
+                  const uint8_t *d_literals, ArchiveRec *d_packed, uint32_t *d_sample) {
+    hipStream_t s = ctx.stream;
+    const size_t samples = archive_samples((size_t)(n - block_len));
+    ProfScope ps(ctx.profiler(), "rlz_archive_pack", s, 44.0 * (double)z + 4.0 * (double)samples);
+    scan_exclusive_add_u32(lit_flags, lit_flags, z, nullptr, ctx.arena, s);
+    archive_pack_kernel<<<record_grid(z), kThreads, 0, s>>>(d_recs, z, block_len, lit_flags, d_literals, d_packed);
+    KERNEL_CHECK();
+    archive_sample_kernel<<<(unsigned)div_up(samples, (size_t)kThreads), kThreads, 0, s>>>(d_packed, (uint32_t)z,
+                                                                                           (uint32_t)samples, d_sample);
+    KERNEL_CHECK();
+}
+
+void archive_extract(Context &ctx, const ArchiveView &v, const uint32_t *d_offsets, const uint32_t *d_first, uint32_t q,
+                     uint32_t total, uint8_t *d_out, unsigned long long *d_err) {
+    hipStream_t s = ctx.stream;
+    ProfScope ps(ctx.profiler(), "rlz_extract", s, 2.0 * (double)total + 8.0 * (double)q);
+    const uint64_t lanes = div_up((uint64_t)total, (uint64_t)kChunk);
+    const uint32_t wide = (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 ? 1u : 0u;
+    rlz_extract_kernel<<<(unsigned)div_up(lanes, (uint64_t)kThreads), kThreads, 0, s>>>(v, d_offsets, d_first, q, total, d_out,
+                                                                                        wide, d_err);
+    KERNEL_CHECK();
+}
+
+}  // namespace nolzss

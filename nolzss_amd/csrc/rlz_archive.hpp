@@ -1,0 +1,53 @@
+// rlz_archive.hpp -- the relative-LZ archive on the device: the check of the records at open, the resident form and its
+// position sample, the range extraction (rlz_archive.hip; DESIGN.md 5, "Relative-LZ archive: ranges from resident
+// records"; C ABI: rlz_archive_api.hip, include/nolzss_hip.h, nolzss_rlz_archive_*).
+#pragma once
+#include "decode.hpp"
+
+namespace nolzss {
+
+// Resident form of one record, 16 bytes, read with one 16-byte load.  Positions are relative to the end of the block
+// ("decoded" coordinates, below 2^32 as n <= kMaxText).
+struct ArchiveRec {
+    uint32_t start;   // first decoded position of the record
+    uint32_t length;
+    uint32_t src;     // block position of the source of byte 0: ref (forward), ref + length - 1 (reverse complement)
+    uint32_t meta;    // bits 1..0: kind; bits 15..8: the symbol of a literal
+};
+enum : uint32_t { kArchiveForward = 0, kArchiveRc = 1, kArchiveLiteral = 2 };
+constexpr uint32_t kSampleShift = 8;  // one sample per 256 decoded positions
+
+inline size_t archive_samples(size_t decoded) { return (decoded + ((size_t(1) << kSampleShift) - 1)) >> kSampleShift; }
+
+struct ArchiveCheck {
+    uint64_t bad = ~0ull;   // (record index << 3 | DecodeRule) of the first offending record, ~0: none
+    uint64_t literals = 0;  // literal records
+};
+
+// All pointers are device memory; temporaries come from the arena and are released on return.
+// d_bounds: k + 1 ascending positions, bounds[0] = block_len, bounds[j + 1] = bounds[j] + length of target j.
+// Rules: tiling and literal length as the decoder, source inside the block, target boundary.  lit_flags[k] = 1 for a
+// literal record (z words).
+ArchiveCheck archive_check(Context &ctx, const Rec *d_recs, size_t z, uint64_t block_len, uint64_t n,
+                           const uint64_t *d_bounds, size_t k, uint32_t *lit_flags);
+// Checked records -> the resident form and the position sample (archive_samples(n - block_len) words: the index of the
+// record that covers decoded position 256 * s).  lit_flags is overwritten with its exclusive scan.
+void archive_pack(Context &ctx, const Rec *d_recs, size_t z, uint64_t block_len, uint64_t n, uint32_t *lit_flags,
+                  const uint8_t *d_literals, ArchiveRec *d_packed, uint32_t *d_sample);
+
+struct ArchiveView {
+    const uint8_t *block;
+    const ArchiveRec *recs;
+    const uint32_t *sample;
+    uint32_t z, samples;
+};
+// q ranges, total >= 1 output bytes.  d_offsets: q + 1 prefix sums of the range lengths (d_offsets[q] = total);
+// d_first[i]: the decoded position of the first byte of range i; every range lies inside [0, decoded).  d_err: one
+// word preset to ~0, receives the smallest (range index << 32 | byte of the range) whose reverse-complement copy reads a
+// byte that is not a nucleotide.  One launch on ctx.stream; does not wait.
+void archive_extract(Context &ctx, const ArchiveView &v, const uint32_t *d_offsets, const uint32_t *d_first, uint32_t q,
+                     uint32_t total, uint8_t *d_out, unsigned long long *d_err);
+
+const char *archive_rule_text(uint32_t rule);
+
+}  // namespace nolzss

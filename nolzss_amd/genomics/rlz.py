@@ -10,6 +10,8 @@ Lf = the longest prefix of T[p:] that occurs in Rblk, Lr = the longest whose rev
 with_rc).  Neither: a literal of length 1.  Lf >= Lr: a forward factor, ref = the leftmost occurrence in Rblk.
 Otherwise a reverse-complement factor, ref = the leftmost occurrence of the reverse complement in Rblk.
 """
+import operator
+
 import numpy as np
 
 from .. import _noLZSS as _native
@@ -150,5 +152,197 @@ def rlz_decode(reference, factors, literals, return_info: bool = False):
     return (out, info) if return_info else out
 
 
+ARCHIVE_ARRAYS = ("block", "records", "literals", "target_lengths", "ids", "has_ids")
+
+
+def archive_arrays(block, records, literals, target_lengths, ids=None):
+    """The host form of an archive -> dict of numpy arrays (block and literals uint8, records FACTOR_DTYPE, target
+    lengths uint64, ids as a fixed-width bytes array, has_ids), checked for consistent sizes.  ValueError otherwise.
+    No device."""
+    block = np.frombuffer(bytes(block), dtype=np.uint8)
+    literals = np.frombuffer(bytes(literals), dtype=np.uint8)
+    records = np.ascontiguousarray(records)
+    if records.dtype != _native.FACTOR_DTYPE or records.ndim != 1:
+        raise ValueError("records must be a one-dimensional FACTOR_DTYPE array")
+    lengths = np.asarray(target_lengths)
+    if lengths.size and (lengths.ndim != 1 or lengths.dtype.kind not in "iu" or (lengths.dtype.kind == "i" and
+                                                                                  (lengths < 0).any())):
+        raise ValueError("target_lengths must be a one-dimensional array of non-negative integers")
+    lengths = np.ascontiguousarray(lengths.reshape(-1), dtype=np.uint64)
+    covered = int(records["start"][-1] + records["length"][-1]) - len(block) if len(records) else 0
+    if int(lengths.sum(dtype=np.uint64)) != covered:
+        raise ValueError(f"inconsistent sizes: the target lengths sum to {int(lengths.sum(dtype=np.uint64))} and the "
+                         f"records cover {covered} bytes behind the block of {len(block)}")
+    n_lit = int((records["ref"] == records["start"]).sum())
+    if n_lit != len(literals):
+        raise ValueError(f"inconsistent sizes: {n_lit} literal records and {len(literals)} literal symbols")
+    if ids is None:
+        id_arr = np.zeros(0, dtype="S1")
+    else:
+        names = [i.encode("utf-8") if isinstance(i, str) else bytes(i) for i in ids]
+        if len(names) != len(lengths):
+            raise ValueError(f"inconsistent sizes: {len(names)} ids for {len(lengths)} targets")
+        if len(set(names)) != len(names):
+            raise ValueError("ids must be distinct")
+        if any(name.endswith(b"\0") for name in names):
+            raise ValueError("an id must not end in a NUL byte")
+        id_arr = np.array(names, dtype=f"S{max([len(x) for x in names] + [1])}")
+    return {"block": block, "records": records, "literals": literals, "target_lengths": lengths, "ids": id_arr,
+            "has_ids": np.array(ids is not None)}
+
+
+def save_archive_arrays(path, arrays):
+    """One .npz (numpy.savez, raw) of what archive_arrays returned.  No device."""
+    with open(path, "wb") as fh:
+        np.savez(fh, **{k: arrays[k] for k in ARCHIVE_ARRAYS})
+
+
+def load_archive_arrays(path):
+    """-> (block bytes, records, literals bytes, target lengths, ids or None) of a file save_archive_arrays wrote;
+    ValueError for missing arrays, wrong types or inconsistent sizes.  allow_pickle is off.  No device."""
+    try:
+        with np.load(path, allow_pickle=False) as npz:
+            a = {k: npz[k] for k in ARCHIVE_ARRAYS if k in npz.files}
+    except Exception as e:  # (a truncated or foreign file, pickled object arrays)
+        raise ValueError(f"{path}: not a relative-LZ archive ({e})")
+    missing = [k for k in ARCHIVE_ARRAYS if k not in a]
+    if missing:
+        raise ValueError(f"{path}: not a relative-LZ archive, missing arrays {missing}")
+    if a["block"].dtype != np.uint8 or a["literals"].dtype != np.uint8 or a["block"].ndim != 1 or a["literals"].ndim != 1:
+        raise ValueError(f"{path}: block and literals must be one-dimensional uint8 arrays")
+    if a["ids"].dtype.kind != "S" or a["ids"].ndim != 1 or a["has_ids"].shape != () or a["has_ids"].dtype != np.bool_:
+        raise ValueError(f"{path}: ids must be a one-dimensional fixed-width bytes array and has_ids a flag")
+    if a["target_lengths"].dtype != np.uint64:
+        raise ValueError(f"{path}: target_lengths must be a uint64 array")
+    ids = [bytes(x).decode("utf-8") for x in a["ids"]] if bool(a["has_ids"]) else None
+    chk = archive_arrays(a["block"].tobytes(), a["records"], a["literals"].tobytes(), a["target_lengths"], ids)
+    return chk["block"].tobytes(), chk["records"], chk["literals"].tobytes(), chk["target_lengths"], ids
+
+
+class RlzArchive:
+    """A relative-LZ collection resident on the GPU: the reference block and the records of every target stay in device
+    memory, and any batch of (target, lo, hi) ranges comes back as bytes with one kernel launch -- nothing the caller
+    did not ask for is decoded or crosses PCIe ("Relative-LZ archive: ranges from resident records").
+    Targets are addressed by index, or by id when ids were given.  A context manager; use after close() raises
+    ValueError."""
+
+    def __init__(self, block, records, literals, target_lengths, ids=None, device=None):
+        self._arrays = archive_arrays(block, records, literals, target_lengths, ids)
+        self.ids = None if ids is None else [i if isinstance(i, str) else bytes(i).decode("utf-8") for i in ids]
+        self._index = target_index_map(self.ids)
+        previous = _native.get_device()
+        if device is not None:
+            _native.set_device(device)
+        try:
+            self._handle = _native.RlzArchiveHandle.open_records(
+                self._arrays["block"], self._arrays["records"], self._arrays["literals"], self._arrays["target_lengths"])
+        finally:
+            _native.set_device(previous)
+
+    @classmethod
+    def build(cls, reference, targets, with_rc: bool = True, ids=None):
+        """rlz_factorize + rlz_literals + absolute_records + open: the records make one PCIe round trip here."""
+        factors = rlz_factorize(reference, targets, with_rc=with_rc)
+        return cls.from_factors(reference, factors, rlz_literals(targets, factors), ids=ids)
+
+    @classmethod
+    def from_factors(cls, reference, factors, literals, ids=None):
+        """reference as given to rlz_factorize, and what rlz_factorize and rlz_literals returned."""
+        block, records, lengths = absolute_records(reference, factors)
+        return cls(block, records, b"".join(bytes(x) for x in literals), lengths, ids=ids)
+
+    @classmethod
+    def load(cls, path, device=None):
+        """The file save() wrote; it is checked on the host (ValueError) before the device is touched."""
+        block, records, literals, lengths, ids = load_archive_arrays(path)
+        return cls(block, records, literals, lengths, ids=ids, device=device)
+
+    def save(self, path):
+        """One .npz holding block, records, literals, target lengths and ids, raw."""
+        self._live()
+        save_archive_arrays(path, self._arrays)
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("the archive is closed")
+        return self._handle
+
+    def __len__(self):
+        return len(self._arrays["target_lengths"])
+
+    @property
+    def target_lengths(self):
+        return [int(x) for x in self._arrays["target_lengths"]]
+
+    @property
+    def info(self):
+        return dict(self._live().info)
+
+    def _rows(self, ranges):
+        if isinstance(ranges, np.ndarray) and ranges.dtype.kind in "iu":  # (target index, lo, hi) rows as they are
+            return ranges
+        return [(resolve_target(t, self._index, len(self)), operator.index(lo), operator.index(hi))
+                for t, lo, hi in ranges]
+
+    def extract_array(self, ranges):
+        """(target, lo, hi) triples, or an integer array of (target index, lo, hi) rows -> (uint8 array of the ranges back
+        to back, uint64 offsets of len(ranges) + 1)."""
+        return self._live().extract_array(self._rows(ranges))
+
+    def extract(self, ranges):
+        """(target, lo, hi) triples -> one bytes object per range; ranges may be empty, overlap, repeat, in any order."""
+        data, offsets = self.extract_array(ranges)
+        raw, offs = data.tobytes(), offsets.tolist()
+        return [raw[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+
+    def extract_device(self, ranges, data_ptr: int, capacity: int, stream: int = 0) -> int:
+        """The same bytes into device memory on the archive's device (a torch tensor's data_ptr()) -> bytes written."""
+        return self._live().extract_device(self._rows(ranges), data_ptr, capacity, stream)
+
+    def fetch(self, target, lo: int, hi: int) -> bytes:
+        return self.extract([(target, lo, hi)])[0]
+
+    def target(self, j) -> bytes:
+        j = resolve_target(j, self._index, len(self))
+        return self.fetch(j, 0, int(self._arrays["target_lengths"][j]))
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h is not None:
+            h.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def target_index_map(ids):
+    """ids (or None) -> {id: index}"""
+    return {} if ids is None else {name: j for j, name in enumerate(ids)}
+
+
+def resolve_target(target, index, count):
+    """A target argument -> its index: an id when ids were given (str, or bytes decoded as UTF-8), else an integer in
+    [0, count) -- the library refuses an index beyond the archive, with the range's index in the message."""
+    if isinstance(target, (bytes, bytearray)):
+        target = bytes(target).decode("utf-8")
+    if isinstance(target, str):
+        if target not in index:
+            raise KeyError(f"no target with id {target!r}")
+        return index[target]
+    j = operator.index(target)
+    if j < 0:
+        raise ValueError(f"target index {j} is negative")
+    return j
+
+
 __all__ = ["RLZ_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
-           "rlz_summary", "rlz_literals", "rlz_decode"]
+           "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive"]
