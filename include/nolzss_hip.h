@@ -611,6 +611,53 @@ int nolzss_rlz_archive_extract_device(const nolzss_rlz_archive *h, const nolzss_
 /* NULL is a no-op. */
 int nolzss_rlz_archive_close(nolzss_rlz_archive *h);
 
+/* ---- relative-LZ index: target batches matched against a resident reference ---------------------- */
+/* Extension.  Every target of a relative-LZ parse is matched against the reference block and nothing else, so the
+ * suffixes of the targets never have to be sorted.  A handle keeps the index of the references in device memory of its
+ * own -- the packed index text X, its suffix array, LCP array, the LCP / min / max pyramids and a prefix table -- and a
+ * batch of targets is matched against it by search: no suffix sort runs in a match, and every other call may run
+ * between two matches ("Relative-LZ index: targets matched against a resident reference").
+ *   Index text: X = the string nolzss_rlz_prepare lays out for these references and no target: Rblk s rc(Rm) s .. s
+ *     rc(R1) s with reverse complement (rc_block_start = B + 1, rcN = B, never a pad), Rblk s without.
+ *   Result: record for record what nolzss_rlz_factorize returns for the same references and targets wherever that call
+ *     accepts them; the semantics paragraph of its section applies unchanged.  A batch of k targets is laid out as
+ *     Tcat = T1 s T2 s .. Tk s; position p of Tcat is absolute position B + 1 + p, the position it would have in S, so
+ *     target_offsets, record starts and the literal rule (ref == start) are those of nolzss_rlz_factorize for any k.
+ *   Refusals at open: those of nolzss_rlz_prepare with k = 0 (m == 0 or no reference base, more than 250 sentinels:
+ *     2m + 1 > 250 with reverse complement, m > 250 without, X longer than the 32-bit pipeline takes:
+ *     NOLZSS_ERR_INVALID_ARGUMENT; an invalid reference base: NOLZSS_ERR_RUNTIME), all before any device is touched;
+ *     prefix_syms > 12: NOLZSS_ERR_INVALID_ARGUMENT.  prefix_syms = 0 picks P = clamp(floor(log4 |X|) - 1, 4, 12); 1..12
+ *     force it (tests).  The prefix table has 4^P + 1 entries.
+ *   Refusals of a match: a null array, or B + 1 + sum(len) + k beyond the 32-bit pipeline: NOLZSS_ERR_INVALID_ARGUMENT;
+ *     "Invalid nucleotide 'x' found in sequence j" with j = m + the target's index: NOLZSS_ERR_RUNTIME.  Lower case is
+ *     upper-cased.  There is no limit on k other than the length rule; k == 0 returns an empty result without touching
+ *     the device; empty targets are kept, with 0 factors; with want_factors == 0 only the k counts leave the device.
+ *   Several threads may match against one handle, but a close must not overlap any other call on that handle.  The
+ *     calling thread's current device is left as it was. */
+typedef struct nolzss_rlz_index nolzss_rlz_index;
+typedef struct nolzss_rlz_index_summary {
+    uint64_t num_references, block_length, index_length;  /* m, B, |X| */
+    int32_t with_rc, device;
+    uint32_t prefix_syms;             /* P actually used */
+    uint64_t device_bytes;            /* everything the handle holds, one allocation */
+} nolzss_rlz_index_summary;
+int nolzss_rlz_index_open(const char *const *refs, const size_t *ref_lens, size_t m, int with_rc,
+                          uint32_t prefix_syms, int device, nolzss_rlz_index **h);
+/* Reader and sanitize modes of nolzss_rlz_factorize_fasta; every record of the file is a reference record. */
+int nolzss_rlz_index_open_fasta(const char *reference_fasta_path, int with_rc, int sanitize_mode,
+                                uint32_t prefix_syms, int device, nolzss_rlz_index **h);
+int nolzss_rlz_index_info(const nolzss_rlz_index *h, nolzss_rlz_index_summary *info);
+/* One batch; fills a nolzss_rlz_result exactly as nolzss_rlz_factorize does (no id lists; free it with
+ * nolzss_free_rlz_result). */
+int nolzss_rlz_index_factorize(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens,
+                               size_t k, int want_factors, nolzss_rlz_result *out);
+/* The code (length in bits 0..30, bit 31 = reverse complement, 0 = no match) of every position of Tcat: sum(len) + k
+ * entries, caller-allocated.  Only target positions are specified -- the counterpart of nolzss_debug_rlz_codes. */
+int nolzss_rlz_index_codes(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens,
+                           size_t k, uint32_t *code);
+/* NULL is a no-op. */
+int nolzss_rlz_index_close(nolzss_rlz_index *h);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

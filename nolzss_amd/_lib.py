@@ -114,6 +114,12 @@ class RlzArchiveSummary(C.Structure):
                 ("device_bytes", C.c_uint64)]
 
 
+class RlzIndexSummary(C.Structure):
+    """Mirror of nolzss_rlz_index_summary (include/nolzss_hip.h)."""
+    _fields_ = [("num_references", C.c_uint64), ("block_length", C.c_uint64), ("index_length", C.c_uint64),
+                ("with_rc", C.c_int32), ("device", C.c_int32), ("prefix_syms", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -257,6 +263,12 @@ def _load():
     lib.nolzss_rlz_archive_extract.argtypes = [vp, vp, sz, vpp, vpp, u64p]
     lib.nolzss_rlz_archive_extract_device.argtypes = [vp, vp, sz, vp, sz, vp, u64p]
     lib.nolzss_rlz_archive_close.argtypes = [vp]
+    lib.nolzss_rlz_index_open.argtypes = seqs[:3] + [C.c_int, C.c_uint32, C.c_int, vpp]
+    lib.nolzss_rlz_index_open_fasta.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.c_int, vpp]
+    lib.nolzss_rlz_index_info.argtypes = [vp, C.POINTER(RlzIndexSummary)]
+    lib.nolzss_rlz_index_factorize.argtypes = [vp] + seqs[3:] + [C.c_int, C.POINTER(RlzResult)]
+    lib.nolzss_rlz_index_codes.argtypes = [vp] + seqs[3:] + [vp]
+    lib.nolzss_rlz_index_close.argtypes = [vp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -309,6 +321,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_count_mismatches",
     "nolzss_rlz_archive_open_records", "nolzss_rlz_archive_info", "nolzss_rlz_archive_extract",
     "nolzss_rlz_archive_extract_device", "nolzss_rlz_archive_close",
+    "nolzss_rlz_index_open", "nolzss_rlz_index_open_fasta", "nolzss_rlz_index_info", "nolzss_rlz_index_factorize",
+    "nolzss_rlz_index_codes", "nolzss_rlz_index_close",
 ]
 
 

@@ -1281,6 +1281,81 @@ class RlzArchiveHandle:
             pass
 
 
+# ---- relative-LZ index: target batches matched against a resident reference (genomics/rlz.py) -------------------
+class RlzIndexHandle:
+    """Extension: the suffix structures of a reference block kept in device memory (C ABI nolzss_rlz_index_*), any
+    number of target batches matched against them without a suffix sort.  A context manager; close() may be called
+    more than once, any other use after it raises ValueError."""
+
+    def __init__(self, handle):
+        self._h = handle
+        info = _lib.RlzIndexSummary()
+        try:
+            check(lib.nolzss_rlz_index_info(self._h, C.byref(info)))
+        except Exception:
+            self.close()
+            raise
+        self.info = {name: int(getattr(info, name)) for name, _ in _lib.RlzIndexSummary._fields_}
+
+    @classmethod
+    def open(cls, reference, with_rc: bool = True, prefix_syms: int = 0):
+        """reference: one sequence or a list of sequences.  C ABI nolzss_rlz_index_open (its header states the rules)."""
+        if isinstance(reference, (str, bytes, bytearray)):
+            reference = [reference]
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_index_open(*_seq_args(reference, "reference"), 1 if with_rc else 0,
+                                        operator.index(prefix_syms), _default_device, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def open_fasta(cls, reference_fasta_path, with_rc: bool = True, sanitize_mode: str = "remove_ambiguous",
+                   prefix_syms: int = 0):
+        """Every record of the FASTA file is a reference record.  C ABI nolzss_rlz_index_open_fasta."""
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_index_open_fasta(_str_arg(reference_fasta_path, "reference_fasta_path"), 1 if with_rc else 0,
+                                              _sanitize_mode(sanitize_mode), operator.index(prefix_syms), _default_device,
+                                              C.byref(h)))
+        return cls(h)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the index is closed")
+        return self._h
+
+    def factorize_arrays(self, targets, want_factors: bool = True) -> dict:
+        """One batch -> the dict rlz_factorize_arrays returns for the same references and targets."""
+        h = self._handle()
+        res = _lib.RlzResult()
+        check(lib.nolzss_rlz_index_factorize(h, *_seq_args(targets, "target"), 1 if want_factors else 0, C.byref(res)))
+        return _unpack_rlz_result(res, want_factors)
+
+    def codes(self, targets) -> np.ndarray:
+        """The code (length, bit 31 = reverse complement, 0 = no match) of every position of T1 s T2 s .. Tk s; only
+        target positions are specified.  C ABI nolzss_rlz_index_codes."""
+        h = self._handle()
+        args = _seq_args(targets, "target")
+        code = np.zeros(sum(args[1][j] for j in range(args[2])) + args[2], dtype=np.uint32)
+        check(lib.nolzss_rlz_index_codes(h, *args, code.ctypes.data if code.size else None))
+        return code
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            check(lib.nolzss_rlz_index_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _roundtrip_result(z, mismatches, first, info):
     res = {"z": z.value, "mismatches": mismatches.value,
            "first_mismatch": None if first.value == (1 << 64) - 1 else first.value}

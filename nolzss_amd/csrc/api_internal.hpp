@@ -142,6 +142,15 @@ size_t w_reference(const uint8_t *ref, size_t ref_len, const uint8_t *tgt, size_
 size_t dna_w_reference(const char *ref, size_t ref_len, const char *tgt, size_t tgt_len, int device,
                        nolzss_factor **out);
 
+// ---- relative LZ: the prepared string and its refusals (rlz_api.hip; also rlz_index_api.hip with k = 0) -------------
+struct RlzPrepared {
+    HostBytes S;
+    std::vector<uint64_t> target_offsets;
+    RlzLayout lay;
+};
+void rlz_prepare(const char *const *refs, const size_t *ref_lens, size_t m, const char *const *targets,
+                 const size_t *target_lens, size_t k, bool with_rc, RlzPrepared &out);
+
 // ---- concatenated multi-sequence FASTA (fasta_api.hip) -------------------------------------------------------------
 void prepare_no_rc(const char *const *seqs, const size_t *lens, size_t k, HostBytes &S,
                    size_t &original_length, std::vector<uint64_t> &sentinels);

@@ -5,15 +5,8 @@
 
 namespace nolzss {
 namespace api {
-namespace {
 
 constexpr size_t kMaxSentinels = 250;
-
-struct RlzPrepared {
-    HostBytes S;
-    std::vector<uint64_t> target_offsets;
-    RlzLayout lay;
-};
 
 // S = Rblk s T1 s .. Tk s [pad] rc-block s; every check of the refusal table happens here, before any device is touched
 void rlz_prepare(const char *const *refs, const size_t *ref_lens, size_t m, const char *const *targets,
@@ -79,6 +72,8 @@ void rlz_prepare(const char *const *refs, const size_t *ref_lens, size_t m, cons
     out.lay.rcN = (uint32_t)(with_rc ? (B - 1 + E) / 2 : 0);
     out.lay.with_rc = with_rc;
 }
+
+namespace {
 
 struct RlzRun {
     std::vector<size_t> counts, first;  // per target: records, and the index of its first record in block

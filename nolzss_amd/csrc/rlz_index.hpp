@@ -1,0 +1,95 @@
+// rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
+// against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
+// rlz_index.hip; the handle and its entry points: rlz_index_api.hip).
+#pragma once
+#include "pipeline.hpp"
+
+namespace nolzss {
+
+constexpr uint32_t kIndexMaxPrefix = 12;  // bases of the prefix table's key: 4^12 + 1 entries = 64 MiB
+
+// The index text X = Rblk s [rc-block s] (rlz_api.hip, rlz_prepare without a target) packed segmented at 2 bits, and
+// what a match reads of it.  Every pointer is device memory: arena memory while the index is being built, the handle's
+// own allocation afterwards (rlz_index_copy_into).
+struct RlzIndexView {
+    PackedText text;
+    const uint32_t *sa = nullptr;   // |X|
+    const uint32_t *lcp = nullptr;  // |X| + 1
+    Pyramid Plcp{}, Pmin{}, Pmax{};  // over lcp, min over sa, max over sa (= Pmin without reverse complement)
+    // table[w], w in [0, 4^P]: the number of ranks whose suffix has a zero-padded P-base key below w
+    const uint32_t *table = nullptr;
+    uint32_t P = 0;
+    uint32_t B = 0;  // |Rblk|: a suffix below B is a forward occurrence, one above it lies in the mirrored block
+    bool with_rc = false;
+};
+
+struct IndexRec {
+    uint64_t start, length, ref;
+};
+
+// One pipeline session over the device-resident X (n bytes): pack, suffix array, LCP array, pyramids, prefix table.
+// Everything is left in the arena; the caller owns the mark.
+RlzIndexView rlz_index_build(Context &ctx, const uint8_t *d_X, uint32_t n, uint32_t B, bool with_rc, uint32_t P);
+// Bytes of one allocation that holds everything the view points to (every array 256-byte aligned and padded, as the
+// pyramid queries and the text windows expect), and the copy into such an allocation: returns the rebased view.
+size_t rlz_index_footprint(const RlzIndexView &v);
+RlzIndexView rlz_index_copy_into(Context &ctx, const RlzIndexView &v, void *d_base);
+
+// Per position p < n of the packed batch (pack_independent_text: the target ends are its terminators): len[p] = the
+// longest match of the target suffix at p in X (0: none, and at a separator), rank[p] = a rank whose suffix attains it.
+void rlz_index_search(Context &ctx, const RlzIndexView &ix, const PackedText &batch, uint32_t *d_len, uint32_t *d_rank);
+// The record of each of the z factor starts fpos[k] (positions of the batch): start = B + 1 + fpos[k].
+void rlz_index_records(Context &ctx, const RlzIndexView &ix, const uint32_t *d_fpos, uint32_t z, const uint32_t *d_len,
+                       const uint32_t *d_rank, IndexRec *d_out);
+// The same look-ups over EVERY position: len[p] |= 1 << 31 where the record of p would be a reverse-complement factor.
+void rlz_index_strands(Context &ctx, const RlzIndexView &ix, uint32_t n, uint32_t *d_len, const uint32_t *d_rank);
+
+constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
+
+// Three-way comparison across two packed 2-bit texts (the counterpart of suffix_compare, text.hpp): the suffix of X at
+// `a` against the target suffix at `p` of the batch, which has `rem` symbols before its target's end.  The caller
+// guarantees that the first h0 symbols agree.  lcp = the common prefix, capped by the target's end and by the
+// terminator of the X suffix.  Returns true if the X suffix is the smaller one: the order of text.hpp, with the end of
+// the target as the smallest terminator of all (the target suffix is the smaller one when it ends first or together
+// with the X suffix).  At most min(rem, segment rest) / 32 + kCrossWords words are compared.
+__device__ __forceinline__ bool cross_suffix_less(const uint64_t *__restrict__ xw, const TermTable &xterms, uint32_t a,
+                                                  const uint64_t *__restrict__ tw, uint32_t p, uint32_t rem, uint32_t h0,
+                                                  uint32_t &lcp) {
+    uint32_t k;
+    const uint32_t lx = term_limit(xterms, a, k);
+    const uint32_t limit = lx < rem ? lx : rem;
+    // kCrossWords words of each text per step: their loads are independent of each other, and a match between similar
+    // genomes runs over hundreds of bases (the windows may read up to kCrossWords words past the nearer end: the packed
+    // texts carry 8 zero pad words, text_pack.hip)
+    uint32_t h = h0;
+    while (h < limit) {
+        const uint64_t xbit = ((uint64_t)a + h) * 2, ybit = ((uint64_t)p + h) * 2;
+        const uint64_t *__restrict__ xp = xw + (xbit >> 6), *__restrict__ yp = tw + (ybit >> 6);
+        const int xo = (int)(xbit & 63), yo = (int)(ybit & 63);
+        uint64_t xs[kCrossWords + 1], ys[kCrossWords + 1];
+#pragma unroll
+        for (int j = 0; j <= kCrossWords; ++j) {
+            xs[j] = xp[j];
+            ys[j] = yp[j];
+        }
+#pragma unroll
+        for (int j = 0; j < kCrossWords; ++j) {
+            const uint64_t x = xo ? ((xs[j] << xo) | (xs[j + 1] >> (64 - xo))) : xs[j];
+            const uint64_t y = yo ? ((ys[j] << yo) | (ys[j + 1] >> (64 - yo))) : ys[j];
+            if (x != y) {
+                const uint32_t d = h + 32u * j + (uint32_t)__clzll((long long)(x ^ y)) / 2;
+                if (d < limit) {
+                    lcp = d;
+                    return x < y;
+                }
+                lcp = limit;  // the first difference lies behind the nearer end
+                return lx < rem;
+            }
+        }
+        h += 32u * kCrossWords;
+    }
+    lcp = limit;
+    return lx < rem;
+}
+
+}  // namespace nolzss

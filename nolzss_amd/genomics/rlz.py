@@ -9,6 +9,9 @@ Semantics at position p of target T (Rblk = the reference records joined by one 
 Lf = the longest prefix of T[p:] that occurs in Rblk, Lr = the longest whose reverse complement does (0 without
 with_rc).  Neither: a literal of length 1.  Lf >= Lr: a forward factor, ref = the leftmost occurrence in Rblk.
 Otherwise a reverse-complement factor, ref = the leftmost occurrence of the reverse complement in Rblk.
+
+RlzIndex keeps the suffix structures of the reference on the GPU and matches target batches against them by search: the
+same records, the reference sorted once, and no limit on the number of targets.
 """
 import operator
 
@@ -324,6 +327,120 @@ class RlzArchive:
             pass
 
 
+MAX_TEXT = 0xffffffff - (1 << 19)  # positions the 32-bit device pipeline takes (kMaxText of the library)
+
+
+def plan_index_batches(lengths, block_length, limit=MAX_TEXT, batch_bases=None):
+    """Target lengths -> [(lo, hi)] index ranges of the batches RlzIndex sends, greedy in input order: a batch closes
+    when the next target would pass the length rule block_length + 1 + sum(len) + k <= limit, or batch_bases bases.  A
+    target that breaks a bound alone still gets a batch of its own (the library refuses it if it breaks the length rule).
+    Pure Python, no device."""
+    out, lo, bases = [], 0, 0
+    for j, n in enumerate(lengths):
+        n = operator.index(n)
+        k = j - lo
+        over = block_length + 1 + bases + n + k + 1 > limit or (batch_bases is not None and bases + n > batch_bases)
+        if k and over:
+            out.append((lo, j))
+            lo, bases = j, 0
+        bases += n
+    if len(lengths) > lo:
+        out.append((lo, len(lengths)))
+    return out
+
+
+class RlzIndex:
+    """The suffix structures of a reference block resident on the GPU: target batches are matched against them by
+    search, so the reference is sorted once, a match sorts nothing, and the number of targets is bounded by the length
+    rule alone -- not by the 250 sentinels of rlz_factorize ("Relative-LZ index: targets matched against a
+    resident reference").  Results equal rlz_factorize record for record.  A context manager; use after close() raises
+    ValueError."""
+
+    def __init__(self, handle, reference):
+        self._handle, self._reference = handle, reference
+
+    @classmethod
+    def build(cls, reference, with_rc: bool = True, prefix_syms: int = 0, device=None):
+        """reference: one sequence or a list of sequences.  prefix_syms: bases of the prefix table's key (0: chosen
+        from the index length)."""
+        if isinstance(reference, (str, bytes, bytearray)):
+            reference = [reference]
+        reference = list(reference)
+        return cls(cls._open(device, _native.RlzIndexHandle.open, reference, with_rc=with_rc, prefix_syms=prefix_syms),
+                   reference)
+
+    @classmethod
+    def from_fasta(cls, path, with_rc: bool = True, sanitize_mode: str = "remove_ambiguous", prefix_syms: int = 0,
+                   device=None):
+        """Every record of the FASTA file is a reference record."""
+        handle = cls._open(device, _native.RlzIndexHandle.open_fasta, str(path), with_rc=with_rc,
+                           sanitize_mode=sanitize_mode, prefix_syms=prefix_syms)
+        return cls(handle, [seq for _, seq in _native.debug_parse_fasta(str(path), sanitize_mode)])
+
+    @staticmethod
+    def _open(device, opener, *args, **kwargs):
+        previous = _native.get_device()
+        if device is not None:
+            _native.set_device(device)
+        try:
+            return opener(*args, **kwargs)
+        finally:
+            _native.set_device(previous)
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("the index is closed")
+        return self._handle
+
+    def info(self):
+        """dict(num_references, block_length, index_length, with_rc, device, prefix_syms, device_bytes)"""
+        return dict(self._live().info)
+
+    def _batches(self, targets, batch_bases, want_factors):
+        h = self._live()
+        targets = list(targets)
+        plan = plan_index_batches([len(t) for t in targets], h.info["block_length"], MAX_TEXT, batch_bases)
+        return [h.factorize_arrays(targets[lo:hi], want_factors=want_factors) for lo, hi in plan]
+
+    def factorize(self, targets, batch_bases=None):
+        """What rlz_factorize returns for the reference and these targets: one RLZ_DTYPE array per target, in input
+        order.  A long list goes up in several batches (plan_index_batches)."""
+        return [rebase(f, off) for res in self._batches(targets, batch_bases, True)
+                for f, off in zip(res["factors"], res["target_offsets"])]
+
+    def count_factors(self, targets, batch_bases=None):
+        """Factors per target; only the counts leave the device."""
+        return [c for res in self._batches(targets, batch_bases, False) for c in res["counts"]]
+
+    def codes(self, targets):
+        """One batch: the code (length, bit 31 = reverse complement, 0 = no match) of every position of
+        T1 s T2 s .. Tk s; only target positions are specified."""
+        return self._live().codes(list(targets))
+
+    def archive(self, targets, ids=None):
+        """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
+        targets = list(targets)
+        factors = self.factorize(targets)
+        return RlzArchive.from_factors(self._reference, factors, rlz_literals(targets, factors), ids=ids)
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h is not None:
+            h.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def target_index_map(ids):
     """ids (or None) -> {id: index}"""
     return {} if ids is None else {name: j for j, name in enumerate(ids)}
@@ -345,4 +462,4 @@ def resolve_target(target, index, count):
 
 
 __all__ = ["RLZ_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
-           "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive"]
+           "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
