@@ -92,16 +92,26 @@ struct DebugOut {
     void *records = nullptr;  // n x (start, length, ref): the factor record of every position (position_factors)
 };
 
-// the plain-mode pipeline on a device-resident text / on a host buffer (upload first); returns z
-// lengths (optional, significance.hip): factor lengths instead of records (ChainLengthsOut); the arena is then NOT
-// rewound, so that the caller can download them -- the caller owns the mark
-// d_records_out (optional, factor_maps.hip): the z factor records where resolve_chain left them in the arena, under
-// the same rule
-size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, nolzss_factor **out_host,
-                 DebugOut *dbg, bool records_on_device_only = false, const ChainLengthsOut *lengths = nullptr,
-                 void **d_records_out = nullptr);
-size_t run_plain_host(Context &ctx, const uint8_t *text, size_t n, size_t start_pos, nolzss_factor **out,
-                      DebugOut *dbg);
+// The plain-mode pipeline on a device-resident text, a device-only runner like run_rc_pipeline and run_rlz_pipeline:
+// rq says what is wanted of the chain and receives it in the arena (pipeline.hpp, the arena rule: nothing is rewound,
+// downloaded or waited for here).
+void run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, ChainRequest &rq, DebugOut *dbg = nullptr);
+// ... on a host buffer: upload, run, *out (optional) = the records in a host block; rewinds its own mark; returns z
+size_t run_plain_host(Context &ctx, const uint8_t *text, size_t n, size_t start_pos, nolzss_factor **out = nullptr,
+                      DebugOut *dbg = nullptr);
+
+// ---- factor records down into a host block (c_abi.hip) ---------------------------------------------------------
+// The owner of a host block (alloc_factor_block) until it is released to the C caller: every exit before that frees it.
+struct FreeBlock {
+    void operator()(void *p) const { free_block(p); }
+};
+using FactorBlock = std::unique_ptr<nolzss_factor, FreeBlock>;
+// z records from device memory into a fresh block (empty for z = 0), behind everything queued on ctx.stream; they have
+// arrived on return.  Throws std::bad_alloc or the device's error.
+FactorBlock download_factors(Context &ctx, const void *d_recs, size_t z);
+// The tail of an entry point that ran a runner: rq's records into *out (if out is given), the stream's late errors --
+// they leave an error status and no live pointer --, the profiler.  Returns rq.z.
+size_t deliver(Context &ctx, const ChainRequest &rq, nolzss_factor **out = nullptr);
 
 template <typename F> int guarded(F &&f) {
     try {

@@ -140,12 +140,7 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
     const size_t m2 = 2 * n + 2;  // with_rc: T' sep revcomp(T') sep
     reserve_arena_for(ctx, with_rc ? m2 : n, (with_rc ? m2 : 0) + n + 32 * c + (size_t(1) << 20) +
                                                 (zs_plain ? 4 * n + (size_t(32) << 20) : 0));
-    const size_t mark = arena.mark();
-    struct Rewind {
-        Arena &a;
-        size_t m;
-        ~Rewind() { a.rewind(m); }
-    } rewind{arena, mark};
+    ArenaRewind rewind(arena);
     uint8_t *d_text = arena.alloc<uint8_t>(n);
     if (direct) {
         ProfScope ps(ctx.profiler(), "batch_upload", s, (double)n);
@@ -159,9 +154,10 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
         HIP_CHECK(hipMemcpyAsync(d_text, host, n, hipMemcpyHostToDevice, s));
     }
     PackedText text;
-    void *d_recs = nullptr;
-    uint32_t *d_fpos = nullptr;
-    uint32_t z = 0;
+    // counts come from the factor starts; records are built only when the caller wants them
+    ChainRequest rq;
+    rq.records = fs != nullptr;
+    rq.starts = true;
     RcPlainOut plain;
     plain.want_fpos = c > 1;
     if (with_rc) {
@@ -175,10 +171,8 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
         for (size_t k = seps.size(); k-- > 0;) terms.push_back((uint32_t)(2 * n - seps[k]));
         terms.push_back((uint32_t)(2 * n + 1));
         if (!pack_independent_text(ctx, d_S, m2, terms, text, true)) return false;
-        if (zs_plain)
-            z = run_rc_pipeline_packed(ctx, text, 0, nullptr, &plain, &d_fpos);
-        else
-            z = run_rc_pipeline_packed(ctx, text, 0, &d_recs);
+        rq.records = !zs_plain;  // (the records even for counts: batch_bounds_kernel splits them)
+        run_rc_pipeline_packed(ctx, text, 0, rq, zs_plain ? &plain : nullptr);
     } else {
         if (!pack_independent_text(ctx, d_text, n, seps, text)) return false;
         RecordPlanScope plan_scope(ctx, seps, (uint32_t)n);
@@ -192,12 +186,14 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
         const Pyramid Psa = alloc_pyramid(sa, (uint32_t)n, arena), Plcp = alloc_pyramid(lcp, (uint32_t)n + 1, arena);
         LstarCodes lstar = LstarCodes::of(arena.alloc<uint32_t>(n));  // (merged batch: 32-bit codes)
         build_lstar(ctx, (uint32_t)n, sa, isa, lcp, Psa, Plcp, lstar, isa_deferred ? isa : nullptr, &text);
-        // counts come from the factor starts; records are built only when the caller wants them, and leave
-        // the factor kernel in record coordinates
-        z = resolve_chain(ctx, (uint32_t)n, 0, lstar, sa, isa, lcp, Psa, Plcp, fs ? &d_recs : nullptr, 0, nullptr,
-                          &d_fpos, fs ? &text.terms : nullptr);
+        // (the records leave the factor kernel in record coordinates)
+        RecordLookup lookup{sa, isa, lcp, Psa, Plcp};
+        lookup.rebase = &text.terms;
+        chain_outputs(ctx, mark_chain(ctx, (uint32_t)n, 0, lstar), lookup, false, rq);
     }
-    nolzss_factor *recs = static_cast<nolzss_factor *>(d_recs);
+    const uint32_t z = rq.z;
+    uint32_t *d_fpos = rq.d_starts;
+    nolzss_factor *recs = static_cast<nolzss_factor *>(rq.d_records);
     // where the records' factor lists start and end
     std::vector<uint32_t> fidx(c, z), fidx_plain(zs_plain ? c : 0, plain.z);
     if (c > 1) {
@@ -226,31 +222,20 @@ bool run_merged_chunk(Context &ctx, const uint8_t *const *texts, const size_t *l
         fidx[c - 1] = z;
         if (zs_plain) fidx_plain[c - 1] = plain.z;
     }
+    if (fs && z && with_rc) {
+        batch_rebase_kernel<<<(unsigned)div_up(z, 256), 256, 0, s>>>(recs, z, text.terms);
+        KERNEL_CHECK();
+    }
     nolzss_factor *block = nullptr;
-    if (fs && z) {
-        if (with_rc) {
-            batch_rebase_kernel<<<(unsigned)div_up(z, 256), 256, 0, s>>>(recs, z, text.terms);
-            KERNEL_CHECK();
-        }
-        block = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * (size_t)z));
-        if (!block) throw std::bad_alloc();
-        try {
-            download_bytes(ctx, block, recs, sizeof(nolzss_factor) * (size_t)z);
-        } catch (...) {
-            std::free(block);
-            throw;
-        }
-    }
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        std::free(block);
-        HIP_CHECK(e);
-    }
-    ctx.prof.collect();
+    deliver(ctx, rq, fs ? &block : nullptr);
     if (trace)
         fprintf(stderr, "[nolzss] merged batch run: %zu records, %zu symbols, %u factors: gather %.1f ms, device%s %.1f ms\n",
                 c, n, z, t_concat, block ? " + download" : "", since() - t_concat);
-    if (block) blocks->push_back(block);
+    if (block) {
+        FactorBlock owner(block);  // (until the list has it)
+        blocks->push_back(block);
+        owner.release();
+    }
     for (size_t k = 0; k < c; ++k) {
         const uint32_t a = k ? fidx[k - 1] + 1 : 0, b = fidx[k];
         zs[ids[k]] = b - a;
@@ -299,12 +284,7 @@ bool run_merged_chunk_device(Context &ctx, const void *const *d_texts, const siz
     Arena &arena = ctx.arena;
     hipStream_t s = ctx.stream;
     reserve_arena_for(ctx, n, n + 64 * c + (size_t(1) << 20));
-    const size_t mark = arena.mark();
-    struct Rewind {
-        Arena &a;
-        size_t m;
-        ~Rewind() { a.rewind(m); }
-    } rewind{arena, mark};
+    ArenaRewind rewind(arena);
     std::vector<GatherRec> table(c);
     std::vector<uint32_t> seps;
     seps.reserve(c - 1);
@@ -340,10 +320,14 @@ bool run_merged_chunk_device(Context &ctx, const void *const *d_texts, const siz
     const Pyramid Psa = alloc_pyramid(sa, (uint32_t)n, arena), Plcp = alloc_pyramid(lcp, (uint32_t)n + 1, arena);
     LstarCodes lstar = LstarCodes::of(arena.alloc<uint32_t>(n));  // (merged batch: 32-bit codes)
     build_lstar(ctx, (uint32_t)n, sa, isa, lcp, Psa, Plcp, lstar, isa_deferred ? isa : nullptr, &text);
-    void *d_recs = nullptr;
-    uint32_t *d_fpos = nullptr;
-    const uint32_t z = resolve_chain(ctx, (uint32_t)n, 0, lstar, sa, isa, lcp, Psa, Plcp, emit ? &d_recs : nullptr, 0,
-                                     nullptr, &d_fpos, emit ? &text.terms : nullptr);
+    ChainRequest rq;
+    rq.records = emit;
+    rq.starts = true;
+    RecordLookup lookup{sa, isa, lcp, Psa, Plcp};
+    lookup.rebase = &text.terms;
+    chain_outputs(ctx, mark_chain(ctx, (uint32_t)n, 0, lstar), lookup, false, rq);
+    const uint32_t z = rq.z;
+    const uint32_t *d_fpos = rq.d_starts;
     std::vector<uint32_t> fidx(c, z);
     if (c > 1) {
         uint32_t *d_fidx = arena.alloc<uint32_t>(c);
@@ -356,8 +340,7 @@ bool run_merged_chunk_device(Context &ctx, const void *const *d_texts, const siz
         if (fidx[c - 1]) throw HipError("merged batch: a separator is not a literal factor");
         fidx[c - 1] = z;
     }
-    HIP_CHECK(hipStreamSynchronize(s));
-    ctx.prof.collect();
+    deliver(ctx, rq);
     for (size_t k = 0; k < c; ++k) {
         const uint32_t a = k ? fidx[k - 1] + 1 : 0, b = fidx[k];
         zs[ids[k]] = b - a;
@@ -611,7 +594,7 @@ void factorize_many(const uint8_t *const *texts, const size_t *lens, size_t m, c
                     dna_w_rc_common(texts[j], nullptr, lens[j], devices[d], nullptr, fs ? 2 : 0, fs ? &fs[j] : nullptr, &zs[j], (int)lane,
                                     zs_plain ? &zs_plain[j] : nullptr);
                 else
-                    zs[j] = run_plain_host(ses->ctx(), texts[j], lens[j], 0, fs ? &fs[j] : nullptr, nullptr);
+                    zs[j] = run_plain_host(ses->ctx(), texts[j], lens[j], 0, fs ? &fs[j] : nullptr);
                 ++g_single_records;
                 if (fs && fs[j]) {
                     std::lock_guard<std::mutex> lk(out_mu);
@@ -862,8 +845,11 @@ int nolzss_factorize_batch_device(const void *const *d_texts, const size_t *lens
                     if (k >= m) break;
                     const size_t j = order[k];
                     reserve_arena_for(ses.ctx(), lens[j]);
-                    z[j] = run_plain(ses.ctx(), static_cast<const uint8_t *>(d_texts[j]), lens[j], 0, nullptr, nullptr,
-                                     emit == 1);
+                    ArenaRewind rewind(ses.ctx().arena);
+                    ChainRequest rq;
+                    rq.records = emit == 1;
+                    run_plain(ses.ctx(), static_cast<const uint8_t *>(d_texts[j]), lens[j], 0, rq);
+                    z[j] = deliver(ses.ctx(), rq);
                     ++g_single_records;
                 }
             });

@@ -201,15 +201,31 @@ void copy_out(Context &ctx, uint32_t *host, const uint32_t *dev, size_t count) {
     HIP_CHECK(hipMemcpyAsync(host, dev, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx.stream));
 }
 
-// The plain-mode pipeline on a device-resident text.  Returns z; *out_host (optional) receives
-// a malloc'ed array of z factors.
-size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, nolzss_factor **out_host,
-                 DebugOut *dbg, bool records_on_device_only, const ChainLengthsOut *lengths, void **d_records_out) {
-    if (out_host) *out_host = nullptr;
-    if (d_records_out) *d_records_out = nullptr;
-    if (n == 0 || start_pos >= n) return 0;
+FactorBlock download_factors(Context &ctx, const void *d_recs, size_t z) {
+    FactorBlock block;
+    if (z == 0) return block;
+    block.reset(static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * z)));
+    if (!block) throw std::bad_alloc();
+    ProfScope ps(ctx.profiler(), "factors_d2h", ctx.stream);
+    download_bytes(ctx, block.get(), d_recs, sizeof(nolzss_factor) * z);
+    return block;
+}
+
+size_t deliver(Context &ctx, const ChainRequest &rq, nolzss_factor **out) {
+    FactorBlock block;
+    if (out) block = download_factors(ctx, rq.d_records, rq.z);
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));  // a late device error: an error status and no live pointer
+    ctx.prof.collect();
+    if (out) *out = block.release();
+    return rq.z;
+}
+
+void run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, ChainRequest &rq, DebugOut *dbg) {
+    rq.z = 0;
+    rq.d_records = nullptr;
+    rq.d_starts = nullptr;
+    if (n == 0 || start_pos >= n) return;
     Arena &arena = ctx.arena;
-    const size_t mark = arena.mark();
     hipStream_t s = ctx.stream;
 
     PackedText text = pack_text(ctx, d_text, n);
@@ -220,77 +236,42 @@ size_t run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos
     build_suffix_array(ctx, text, sa, isa, lcp, &isa_deferred);
     // (the pyramids are only allocated here: the candidate kernel writes their first level from the blocks it holds
     // in LDS anyway, build_lstar fills the rest)
-    const Pyramid Psa = alloc_pyramid(sa, (uint32_t)n, arena), Plcp = alloc_pyramid(lcp, (uint32_t)n + 1, arena);
-    // (16-bit codes where the stage can write them; the length histograms read 32-bit codes)
-    LstarCodes lstar = alloc_lstar(ctx, (uint32_t)n, isa_deferred && !lengths);
-    build_lstar(ctx, (uint32_t)n, sa, isa, lcp, Psa, Plcp, lstar, isa_deferred ? isa : nullptr, &text);
+    const RecordLookup lookup{sa, isa, lcp, alloc_pyramid(sa, (uint32_t)n, arena), alloc_pyramid(lcp, (uint32_t)n + 1, arena)};
+    // (16-bit codes where the stage can write them; the length outputs read 32-bit codes)
+    LstarCodes lstar = alloc_lstar(ctx, (uint32_t)n, isa_deferred && !rq.lengths);
+    build_lstar(ctx, (uint32_t)n, sa, isa, lcp, lookup.Psa, lookup.Plcp, lstar, isa_deferred ? isa : nullptr, &text);
     if (dbg) {
         // the exports are 32-bit: 16-bit codes are widened once, for here only -- the cursor below still reads them
         const size_t dmark = arena.mark();
-        const uint32_t *lstar32 = lstar.width == 32 ? lstar.wide : widened_lstar(ctx, lstar, (uint32_t)n, 0);
+        uint32_t *lstar32 = lstar.width == 32 ? lstar.wide : widened_lstar(ctx, lstar, (uint32_t)n, 0);
         copy_out(ctx, dbg->sa, sa, n);
         copy_out(ctx, dbg->isa, isa, n);  // (1-based on the device; nolzss_debug_arrays subtracts the one)
         copy_out(ctx, dbg->lcp, lcp, n + 1);
         copy_out(ctx, dbg->lstar, lstar32, n);
         if (dbg->records) {
-            const void *recs = position_factors(ctx, (uint32_t)n, lstar32, sa, isa, lcp, Psa, Plcp);
+            const void *recs = position_factors(ctx, (uint32_t)n, LstarCodes::of(lstar32), lookup);
             HIP_CHECK(hipMemcpyAsync(dbg->records, recs, n * sizeof(nolzss_factor), hipMemcpyDeviceToHost, s));
         }
         HIP_CHECK(hipStreamSynchronize(s));
         arena.rewind(dmark);
     }
-    void *d_recs = nullptr;
-    const uint32_t z = resolve_chain(ctx, (uint32_t)n, (uint32_t)start_pos, lstar, sa, isa, lcp, Psa, Plcp,
-                                     (out_host || records_on_device_only || d_records_out) ? &d_recs : nullptr, 0, nullptr, nullptr,
-                                     nullptr, lengths);
-    if (out_host && z) {
-        nolzss_factor *h = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * (size_t)z));
-        if (!h) throw std::bad_alloc();
-        ProfScope ps(ctx.profiler(), "factors_d2h", s);
-        try {
-            download_bytes(ctx, h, d_recs, sizeof(nolzss_factor) * (size_t)z);
-        } catch (...) {
-            std::free(h);
-            throw;
-        }
-        *out_host = h;
-    }
-    {
-        const hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {  // a late device error: the caller gets an error status and no live pointer
-            if (out_host && *out_host) {
-                std::free(*out_host);
-                *out_host = nullptr;
-            }
-            HIP_CHECK(e);
-        }
-    }
-    ctx.prof.collect();
-    if (d_records_out) *d_records_out = d_recs;
-    if (!lengths && !d_records_out) arena.rewind(mark);
-    return z;
+    chain_outputs(ctx, mark_chain(ctx, (uint32_t)n, (uint32_t)start_pos, lstar), lookup, false, rq);
 }
 
-size_t run_plain_host(Context &ctx, const uint8_t *text, size_t n, size_t start_pos, nolzss_factor **out,
-                      DebugOut *dbg) {
+size_t run_plain_host(Context &ctx, const uint8_t *text, size_t n, size_t start_pos, nolzss_factor **out, DebugOut *dbg) {
     if (out) *out = nullptr;
     if (n == 0 || start_pos >= n) return 0;
     reserve_arena_for(ctx, n, n);
-    const size_t mark = ctx.arena.mark();
+    ArenaRewind rewind(ctx.arena);
     uint8_t *d_text = ctx.arena.alloc<uint8_t>(n);
     {
         ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream);
         upload_bytes(ctx, d_text, text, n);
     }
-    size_t z;
-    try {
-        z = run_plain(ctx, d_text, n, start_pos, out, dbg);
-    } catch (...) {
-        ctx.arena.rewind(mark);
-        throw;
-    }
-    ctx.arena.rewind(mark);
-    return z;
+    ChainRequest rq;
+    rq.records = out != nullptr;
+    run_plain(ctx, d_text, n, start_pos, rq, dbg);
+    return deliver(ctx, rq, out);
 }
 
 void check_text_args(const void *text, size_t n, size_t start_pos) {
@@ -444,31 +425,13 @@ size_t run_rc_host(Context &ctx, const uint8_t *S, size_t m, size_t start_pos, n
     if (m > kMaxText) throw std::invalid_argument("text too long: the device pipeline uses 32-bit indices");
     if (!rc_guards(m, start_pos)) return 0;
     reserve_arena_for(ctx, m, m);
-    const size_t mark = ctx.arena.mark();
-    size_t z = 0;
-    try {
-        uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
-        upload_bytes(ctx, d_S, S, m);
-        void *d_recs = nullptr;
-        z = run_rc_pipeline(ctx, d_S, m, start_pos, out ? &d_recs : nullptr);
-        if (out && z) {
-            nolzss_factor *h = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * z));
-            if (!h) throw std::bad_alloc();
-            *out = h;  // (freed below if the download fails)
-            download_bytes(ctx, h, d_recs, sizeof(nolzss_factor) * z);
-        }
-        HIP_CHECK(hipStreamSynchronize(ctx.stream));
-        ctx.prof.collect();
-    } catch (...) {
-        ctx.arena.rewind(mark);
-        if (out && *out) {
-            std::free(*out);
-            *out = nullptr;
-        }
-        throw;
-    }
-    ctx.arena.rewind(mark);
-    return z;
+    ArenaRewind rewind(ctx.arena);
+    uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
+    upload_bytes(ctx, d_S, S, m);
+    ChainRequest rq;
+    rq.records = out != nullptr;
+    run_rc_pipeline(ctx, d_S, m, start_pos, rq);
+    return deliver(ctx, rq, out);
 }
 
 }  // namespace api
@@ -511,30 +474,11 @@ void dna_w_rc_common(const uint8_t *text, const uint8_t *d_resident, size_t n, i
         else HIP_CHECK(hipMemcpy(&c, d_T + bad, 1, hipMemcpyDeviceToHost));
         throw std::runtime_error("Invalid nucleotide '" + std::string(1, (char)c) + "' found in sequence 0");
     }
-    void *d_recs = nullptr;
+    ChainRequest rq;
+    rq.records = emit != 0;
     RcPlainOut plain;
-    const size_t count = run_rc_pipeline(ctx, d_S, m, 0, emit ? &d_recs : nullptr, z_plain ? &plain : nullptr);
-    if (emit == 2 && count) {
-        nolzss_factor *h = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * count));
-        if (!h) throw std::bad_alloc();
-        try {
-            download_bytes(ctx, h, d_recs, sizeof(nolzss_factor) * count);
-        } catch (...) {
-            std::free(h);
-            throw;
-        }
-        *out = h;
-    }
-    hipError_t e = hipStreamSynchronize(ctx.stream);
-    if (e != hipSuccess) {
-        if (out && *out) {
-            std::free(*out);
-            *out = nullptr;
-        }
-        HIP_CHECK(e);
-    }
-    ctx.prof.collect();
-    *z = count;
+    run_rc_pipeline(ctx, d_S, m, 0, rq, z_plain ? &plain : nullptr);
+    *z = deliver(ctx, rq, emit == 2 ? out : nullptr);
     if (z_plain) *z_plain = plain.z;
 }
 
@@ -566,7 +510,7 @@ int nolzss_factorize(const uint8_t *text, size_t n, size_t start_pos, int device
         *z = 0;
         check_text_args(text, n, start_pos);
         Session ses(device, nullptr);
-        *z = run_plain_host(ses.ctx(), text, n, start_pos, out, nullptr);
+        *z = run_plain_host(ses.ctx(), text, n, start_pos, out);
     });
 }
 
@@ -576,7 +520,7 @@ int nolzss_count_factors(const uint8_t *text, size_t n, size_t start_pos, int de
         *z = 0;
         check_text_args(text, n, start_pos);
         Session ses(device, nullptr);
-        *z = run_plain_host(ses.ctx(), text, n, start_pos, nullptr, nullptr);
+        *z = run_plain_host(ses.ctx(), text, n, start_pos);
     });
 }
 
@@ -588,7 +532,7 @@ int nolzss_factorize_file(const char *path, size_t start_pos, int device, nolzss
         const FileBytes data = read_file(path);
         check_text_args(data.data(), data.size(), start_pos);
         Session ses(device, nullptr);
-        *z = run_plain_host(ses.ctx(), data.data(), data.size(), start_pos, out, nullptr);
+        *z = run_plain_host(ses.ctx(), data.data(), data.size(), start_pos, out);
     });
 }
 
@@ -599,7 +543,7 @@ int nolzss_count_factors_file(const char *path, size_t start_pos, int device, si
         const FileBytes data = read_file(path);
         check_text_args(data.data(), data.size(), start_pos);
         Session ses(device, nullptr);
-        *z = run_plain_host(ses.ctx(), data.data(), data.size(), start_pos, nullptr, nullptr);
+        *z = run_plain_host(ses.ctx(), data.data(), data.size(), start_pos);
     });
 }
 
@@ -615,8 +559,10 @@ int nolzss_factorize_device(const void *d_text, size_t n, size_t start_pos, int 
         Session ses(device, stream);
         if (!stream) order_behind_default_stream(ses.ctx());
         reserve_arena_for(ses.ctx(), n);
-        *z = run_plain(ses.ctx(), static_cast<const uint8_t *>(d_text), n, start_pos,
-                       emit == 2 ? out_host : nullptr, nullptr, emit == 1);
+        ChainRequest rq;
+        rq.records = emit != 0;
+        run_plain(ses.ctx(), static_cast<const uint8_t *>(d_text), n, start_pos, rq);
+        *z = deliver(ses.ctx(), rq, emit == 2 ? out_host : nullptr);
     });
 }
 
@@ -717,7 +663,7 @@ size_t w_reference(const uint8_t *ref, size_t ref_len, const uint8_t *tgt, size_
     combined.insert(combined.end(), tgt, tgt + tgt_len);
     check_text_args(combined.data(), combined.size(), ref_len + 1);
     Session ses(device, nullptr);
-    return run_plain_host(ses.ctx(), combined.data(), combined.size(), ref_len + 1, out, nullptr);
+    return run_plain_host(ses.ctx(), combined.data(), combined.size(), ref_len + 1, out);
 }
 
 size_t dna_w_reference(const char *ref, size_t ref_len, const char *tgt, size_t tgt_len, int device,
@@ -768,7 +714,7 @@ int nolzss_write_factors_binary_file(const char *in_path, const char *out_path, 
         size_t count;
         {
             Session ses(device, nullptr);
-            count = run_plain_host(ses.ctx(), data.data(), data.size(), 0, &f, nullptr);
+            count = run_plain_host(ses.ctx(), data.data(), data.size(), 0, &f);
         }
         std::unique_ptr<nolzss_factor, decltype(&std::free)> hold(f, &std::free);
         write_v2_file(out_path, f, count, 0, 0, data.size(), std::string());  // factorizer.cpp:447-456

@@ -15,8 +15,10 @@
 //                          (ceil(log2 K) rounds over K << n nodes): reached nodes = tile entries.
 //   4. chain_mark_kernel   per entered tile: one lane walks the tile's chain from the entry in LDS
 //                          point; the marks go out as one ballot word per wavefront row.
-//   5. scan + emit         per-tile counts are scanned and the marked positions written in order;
-//                          factor_kernel then attaches length and leftmost-occurrence reference.
+//   5. scan                per-tile counts are scanned: with the bitmap they are the marked chain (mark_chain).
+// The outputs are taken from the mark, each by a function of its own (pipeline.hpp): chain_starts writes the marked
+// positions in order, chain_records attaches length and leftmost-occurrence reference to them (factor_kernel),
+// chain_lengths reads the codes at the marked positions.
 #include "pipeline.hpp"
 #include "pyramid.hpp"
 #include "scan.hpp"
@@ -463,35 +465,49 @@ inline unsigned grid_for(size_t items, unsigned cap = 256u * 16u) {
     return (unsigned)(g > cap ? cap : g);
 }
 
+// The one place that launches factor_kernel: picks the instantiation from what the lookup carries and the code width.
+void launch_factor_kernel(Context &ctx, const uint32_t *starts, uint32_t z, uint32_t n, const LstarCodes &codes,
+                          const RecordLookup &lk, FactorRec *out) {
+    hipStream_t s = ctx.stream;
+    const bool narrow = codes.width == 16;
+    if (narrow && (lk.Pmax || lk.rebase)) throw HipError("factor records: 16-bit codes are for plain records only");
+    if (lk.Pmax && lk.rebase) throw HipError("factor records: record-relative output exists in plain mode only");
+    const unsigned g = grid_for(z);
+    if (lk.Pmax)
+        factor_kernel<true, false><<<g, kThreads, 0, s>>>(starts, z, codes.wide, lk.isa, lk.sa, lk.lcp, lk.Psa, lk.Plcp, *lk.Pmax,
+                                                          lk.rcN, out, TermTable{}, n);
+    else if (lk.rebase)
+        factor_kernel<false, true><<<g, kThreads, 0, s>>>(starts, z, codes.wide, lk.isa, lk.sa, lk.lcp, lk.Psa, lk.Plcp, lk.Psa, 0u,
+                                                          out, *lk.rebase, n);
+    else if (narrow)
+        factor_kernel<false, false, uint16_t><<<g, kThreads, 0, s>>>(starts, z, codes.narrow, lk.isa, lk.sa, lk.lcp, lk.Psa,
+                                                                     lk.Plcp, lk.Psa, 0u, out, TermTable{}, n);
+    else
+        factor_kernel<false, false><<<g, kThreads, 0, s>>>(starts, z, codes.wide, lk.isa, lk.sa, lk.lcp, lk.Psa, lk.Plcp, lk.Psa, 0u,
+                                                           out, TermTable{}, n);
+    KERNEL_CHECK();
+}
+
 }  // namespace
 
-// Returns z; if d_factors_out != nullptr the z factor records are left in arena memory (this
-// stage's temporaries are then NOT released: the caller rewinds after copying the records out).
-// d_fpos_out (optional) receives the z factor starts, ascending, under the same rule -- without
-// d_factors_out nothing else is built.  rebase (optional, plain mode): the terminator table of a text of
-// independent records; start and ref of every factor are then relative to its record.
-// Plain mode: rcN = 0, Pmax unused.  RC mode: n = N (factorized prefix of S), rcN = N and Pmax
-// is the max pyramid over SA.
-uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes, const uint32_t *sa,
-                       const uint32_t *isa, const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp,
-                       void **d_factors_out, uint32_t rcN, const Pyramid *Pmax, uint32_t **d_fpos_out,
-                       const TermTable *rebase, const ChainLengthsOut *lengths) {
+Chain mark_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes) {
     hipStream_t s = ctx.stream;
     Arena &arena = ctx.arena;
-    if (d_factors_out) *d_factors_out = nullptr;
-    if (d_fpos_out) *d_fpos_out = nullptr;
-    if (start_pos >= n) return 0;
+    Chain chain;
+    chain.n = n;
+    chain.codes = codes;
+    if (start_pos >= n) return chain;
     const bool narrow = codes.width == 16;
-    if (narrow && (rcN || rebase || lengths)) throw HipError("resolve_chain: 16-bit codes are for plain records and counts only");
     const uint32_t *lstar = codes.wide;       // !narrow
     const uint16_t *lstar16 = codes.narrow;  // narrow
 
     const uint32_t num_tiles = (uint32_t)div_up(n, kTile);
     const uint32_t tbits_words = (uint32_t)div_up((size_t)n + 1, 32);
 
-    // persistent across the call: factor records (if requested) live below `mark`
-    uint32_t *fpos = nullptr;
-    const size_t mark = arena.mark();
+    // the mark first: everything behind `tmp` is released before the caller takes an output
+    unsigned long long *cbits = arena.alloc<unsigned long long>((size_t)num_tiles * (kTile / 64));
+    uint32_t *tile_count = arena.alloc<uint32_t>(num_tiles);
+    const size_t tmp = arena.mark();
     uint32_t *exit0 = narrow ? nullptr : arena.alloc<uint32_t>(n);
     uint16_t *exit16 = narrow ? arena.alloc<uint16_t>((size_t)n + 2) : nullptr;
     uint32_t *tbits = arena.alloc<uint32_t>(tbits_words);
@@ -545,8 +561,6 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const Lstar
         tile_entries_kernel<<<grid_for(K), kThreads, 0, s>>>(node_pos, reach, K, entry);
         KERNEL_CHECK();
     }
-    unsigned long long *cbits = arena.alloc<unsigned long long>((size_t)num_tiles * (kTile / 64));
-    uint32_t *tile_count = arena.alloc<uint32_t>(num_tiles);
     {
         ProfScope ps(ctx.profiler(), "chain_mark", s, (narrow ? 2.0 : 4.0) * (double)n);
         if (narrow)
@@ -556,79 +570,32 @@ uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const Lstar
         KERNEL_CHECK();
         scan_exclusive_add_u32(tile_count, tile_count, num_tiles, d_total + 1, arena, s);
     }
-    uint32_t z = 0;
-    ctx.read_back(d_total + 1, &z, 1);
-    if (lengths) {  // factor lengths only: no records, no factor_kernel
-        if (d_factors_out || d_fpos_out) throw HipError("resolve_chain: factor lengths come without records");
-        if (lengths->hist && z) {
-            ProfScope ps(ctx.profiler(), "length_hist", s);
-            const uint32_t nwords = num_tiles * (uint32_t)(kTile / 64);
-            const unsigned g = grid_for(nwords, 1024);
-            if (rcN)
-                length_hist_kernel<true><<<g, kThreads, 0, s>>>(cbits, nwords, lstar, lengths->hist, lengths->tail,
-                                                                lengths->tail_count, lengths->tail_cap);
-            else
-                length_hist_kernel<false><<<g, kThreads, 0, s>>>(cbits, nwords, lstar, lengths->hist, lengths->tail,
-                                                                 lengths->tail_count, lengths->tail_cap);
-            KERNEL_CHECK();
-        }
-        if (!lengths->order || z == 0) {
-            arena.rewind(mark);
-            return z;
-        }
-        fpos = arena.alloc<uint32_t>(z);
-        ProfScope ps(ctx.profiler(), "length_emit", s);
-        emit_positions_kernel<<<num_tiles, 64, 0, s>>>(cbits, tile_count, fpos);
-        KERNEL_CHECK();
-        gather_lengths_kernel<<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar);
-        KERNEL_CHECK();
-        *lengths->order = fpos;
-        return z;
-    }
-    if ((!d_factors_out && !d_fpos_out) || z == 0) {
-        arena.rewind(mark);
-        return z;
-    }
-    fpos = arena.alloc<uint32_t>(z);
-    if (!d_factors_out) {  // the factor starts only (per-record counts of the merged batch)
-        ProfScope ps(ctx.profiler(), "factor_emit", s);
-        emit_positions_kernel<<<num_tiles, 64, 0, s>>>(cbits, tile_count, fpos);
-        KERNEL_CHECK();
-        *d_fpos_out = fpos;
-        return z;
-    }
-    FactorRec *recs_tmp = arena.alloc<FactorRec>(z);
-    {
-        ProfScope ps(ctx.profiler(), "factor_emit", s);
-        emit_positions_kernel<<<num_tiles, 64, 0, s>>>(cbits, tile_count, fpos);
-        KERNEL_CHECK();
-        if (rcN) {
-            if (rebase) throw HipError("resolve_chain: record-relative output exists in plain mode only");
-            factor_kernel<true, false><<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar, isa, sa, lcp, Psa, Plcp, *Pmax,
-                                                                        rcN, recs_tmp, TermTable{}, n);
-        } else if (rebase) {
-            factor_kernel<false, true><<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar, isa, sa, lcp, Psa, Plcp, Psa,
-                                                                        0u, recs_tmp, *rebase, n);
-        } else if (narrow) {
-            factor_kernel<false, false, uint16_t><<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar16, isa, sa, lcp, Psa, Plcp,
-                                                                                   Psa, 0u, recs_tmp, TermTable{}, n);
-        } else {
-            factor_kernel<false, false><<<grid_for(z), kThreads, 0, s>>>(fpos, z, lstar, isa, sa, lcp, Psa, Plcp, Psa,
-                                                                         0u, recs_tmp, TermTable{}, n);
-        }
-        KERNEL_CHECK();
-    }
-    // the caller owns the arena mark: stage temporaries stay allocated until it rewinds
-    *d_factors_out = recs_tmp;
-    if (d_fpos_out) *d_fpos_out = fpos;
-    return z;
+    ctx.read_back(d_total + 1, &chain.z, 1);  // (waits for the stream: the temporaries are no longer read)
+    arena.rewind(tmp);
+    chain.bits = cbits;
+    chain.tile_off = tile_count;
+    chain.num_tiles = num_tiles;
+    return chain;
 }
 
-// Debug hooks: every position is a factor start (pipeline.hpp).  With fpos = 0, 1, .., n - 1 the distance to the next
-// start is 1 everywhere, so factor_kernel takes length and flag from lstar[i] at every position.
-void *position_factors(Context &ctx, uint32_t n, const uint32_t *lstar, const uint32_t *sa, const uint32_t *isa,
-                       const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp, uint32_t rcN, const Pyramid *Pmax,
-                       const TermTable *rebase) {
+uint32_t *chain_starts(Context &ctx, const Chain &chain) {
+    if (chain.z == 0) return nullptr;
+    uint32_t *starts = ctx.arena.alloc<uint32_t>(chain.z);
+    ProfScope ps(ctx.profiler(), "factor_emit", ctx.stream);
+    emit_positions_kernel<<<chain.num_tiles, 64, 0, ctx.stream>>>(chain.bits, chain.tile_off, starts);
+    KERNEL_CHECK();
+    return starts;
+}
+
+void *chain_records(Context &ctx, const Chain &chain, const uint32_t *starts, const RecordLookup &lookup) {
+    if (chain.z == 0) return nullptr;
+    FactorRec *recs = ctx.arena.alloc<FactorRec>(chain.z);
+    ProfScope ps(ctx.profiler(), "factor_emit", ctx.stream);
+    launch_factor_kernel(ctx, starts, chain.z, chain.n, chain.codes, lookup, recs);
+    return recs;
+}
+
+void *position_factors(Context &ctx, uint32_t n, const LstarCodes &codes, const RecordLookup &lookup) {
     if (n == 0) return nullptr;
     hipStream_t s = ctx.stream;
     uint32_t *fpos = ctx.arena.alloc<uint32_t>(n);
@@ -637,19 +604,46 @@ void *position_factors(Context &ctx, uint32_t n, const uint32_t *lstar, const ui
     for (uint32_t i = 0; i < n; ++i) iota[i] = i;
     HIP_CHECK(hipMemcpyAsync(fpos, iota.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));  // iota is a local vector
-    if (rcN) {
-        if (rebase) throw HipError("position_factors: record-relative output exists in plain mode only");
-        factor_kernel<true, false><<<grid_for(n), kThreads, 0, s>>>(fpos, n, lstar, isa, sa, lcp, Psa, Plcp, *Pmax, rcN, recs,
-                                                                    TermTable{}, n);
-    } else if (rebase) {
-        factor_kernel<false, true><<<grid_for(n), kThreads, 0, s>>>(fpos, n, lstar, isa, sa, lcp, Psa, Plcp, Psa, 0u, recs,
-                                                                    *rebase, n);
-    } else {
-        factor_kernel<false, false><<<grid_for(n), kThreads, 0, s>>>(fpos, n, lstar, isa, sa, lcp, Psa, Plcp, Psa, 0u, recs,
-                                                                     TermTable{}, n);
-    }
-    KERNEL_CHECK();
+    launch_factor_kernel(ctx, fpos, n, n, codes, lookup, recs);
     return recs;
+}
+
+void chain_lengths(Context &ctx, const Chain &chain, const ChainLengthsOut &out, bool with_strand) {
+    hipStream_t s = ctx.stream;
+    if (out.order) *out.order = nullptr;
+    if (chain.z == 0) return;
+    if (chain.codes.width != 32) throw HipError("factor lengths: the length kernels read 32-bit codes");
+    const uint32_t *lstar = chain.codes.wide;
+    if (out.hist) {
+        ProfScope ps(ctx.profiler(), "length_hist", s);
+        const uint32_t nwords = chain.num_tiles * (uint32_t)(kTile / 64);
+        const unsigned g = grid_for(nwords, 1024);
+        if (with_strand)
+            length_hist_kernel<true><<<g, kThreads, 0, s>>>(chain.bits, nwords, lstar, out.hist, out.tail, out.tail_count,
+                                                            out.tail_cap);
+        else
+            length_hist_kernel<false><<<g, kThreads, 0, s>>>(chain.bits, nwords, lstar, out.hist, out.tail, out.tail_count,
+                                                             out.tail_cap);
+        KERNEL_CHECK();
+    }
+    if (!out.order) return;
+    uint32_t *lens = ctx.arena.alloc<uint32_t>(chain.z);  // the starts first, then the lengths in their place
+    ProfScope ps(ctx.profiler(), "length_emit", s);
+    emit_positions_kernel<<<chain.num_tiles, 64, 0, s>>>(chain.bits, chain.tile_off, lens);
+    KERNEL_CHECK();
+    gather_lengths_kernel<<<grid_for(chain.z), kThreads, 0, s>>>(lens, chain.z, lstar);
+    KERNEL_CHECK();
+    *out.order = lens;
+}
+
+void chain_outputs(Context &ctx, const Chain &chain, const RecordLookup &lookup, bool with_strand, ChainRequest &rq) {
+    rq.z = chain.z;
+    rq.d_records = nullptr;
+    rq.d_starts = nullptr;
+    if (rq.lengths) chain_lengths(ctx, chain, *rq.lengths, with_strand);
+    if (!rq.records && !rq.starts) return;
+    rq.d_starts = chain_starts(ctx, chain);
+    if (rq.records) rq.d_records = chain_records(ctx, chain, rq.d_starts, lookup);
 }
 
 }  // namespace nolzss

@@ -80,6 +80,14 @@ class Arena {
     size_t cap_ = 0, off_ = 0, peak_ = 0;
 };
 
+// rewinds the arena to where it stood when this was made, on every way out of the scope
+struct ArenaRewind {
+    Arena &arena;
+    size_t mark;
+    explicit ArenaRewind(Arena &a) : arena(a), mark(a.mark()) {}
+    ~ArenaRewind() { arena.rewind(mark); }
+};
+
 // ---------------------------------------------------------------------------------------
 // Stage profiler: HIP events recorded on the pipeline's own stream around named launches.
 // Off by default (zero overhead); bench.py switches it on through nolzss_profile_enable().

@@ -110,7 +110,10 @@ int nolzss_debug_position_factors(const uint8_t *text, size_t n, int device, nol
         upload_bytes(ctx, d_text, text, n);
         DebugOut dbg;
         dbg.records = out;
-        run_plain(ctx, d_text, n, 0, nullptr, &dbg);
+        ArenaRewind rewind(ctx.arena);
+        ChainRequest rq;
+        run_plain(ctx, d_text, n, 0, rq, &dbg);
+        deliver(ctx, rq);
     });
 }
 
@@ -138,7 +141,8 @@ int nolzss_debug_rc_arrays(const uint8_t *S, size_t S_len, int device, int want_
         dbg.plain = want_plain ? plain : nullptr;
         dbg.records = records;
         RcPlainOut plain_out;
-        run_rc_pipeline(ctx, d_S, m, 0, nullptr, want_plain ? &plain_out : nullptr, nullptr, &dbg);
+        ChainRequest rq;
+        run_rc_pipeline(ctx, d_S, m, 0, rq, want_plain ? &plain_out : nullptr, &dbg);
         HIP_CHECK(hipStreamSynchronize(ctx.stream));
         ctx.prof.collect();
         if (isa)

@@ -141,8 +141,8 @@ void roundtrip(const uint8_t *text, const uint8_t *d_resident, size_t n, bool wi
         upload_bytes(ctx, up, text, n);
         d_T = up;
     }
-    void *d_recs = nullptr;
-    size_t zc;
+    ChainRequest rq;
+    rq.records = true;
     const uint8_t *d_text = d_T;  // what the records describe: the bytes, or the upper-cased strand of the prepared string
     if (with_rc) {
         uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
@@ -154,10 +154,12 @@ void roundtrip(const uint8_t *text, const uint8_t *d_resident, size_t n, bool wi
             throw std::runtime_error("Invalid nucleotide '" + std::string(1, (char)c) + "' found in sequence 0");
         }
         d_text = d_S;
-        zc = run_rc_pipeline(ctx, d_S, m, 0, &d_recs);
+        run_rc_pipeline(ctx, d_S, m, 0, rq);
     } else {
-        zc = run_plain(ctx, d_T, n, 0, nullptr, nullptr, false, nullptr, &d_recs);
+        run_plain(ctx, d_T, n, 0, rq);
     }
+    const size_t zc = rq.z;
+    const void *d_recs = rq.d_records;
     *z = zc;
     if (zc == 0 || !d_recs) throw std::runtime_error("round trip: the pipeline left no records");
     // the records stay where the pipeline left them, above its work arrays: the decoder takes what is left of the arena

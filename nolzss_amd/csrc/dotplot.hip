@@ -502,9 +502,8 @@ int nolzss_dotplot_open_text(const uint8_t *text, size_t n, int with_rc, int dev
         if (check_text_source(text, n, with_rc != 0)) {
             Session ses(device, nullptr);
             Context &ctx = ses.ctx();
-            void *d_recs = nullptr;
-            const size_t z = text_records(ctx, text, n, with_rc != 0, size_t(1) << 20, &d_recs);
-            adopt_records(ctx, *dp, d_recs, true, z);
+            const ChainRequest recs = text_records(ctx, text, n, with_rc != 0, size_t(1) << 20);
+            adopt_records(ctx, *dp, recs.d_records, true, recs.z);
             ctx.prof.collect();
         }
         *h = dp.release();
@@ -523,9 +522,8 @@ int nolzss_dotplot_open_fasta(const char *path, int with_rc, int sanitize_mode, 
         if (!ft.empty) {
             Session ses(device, nullptr);
             Context &ctx = ses.ctx();
-            void *d_recs = nullptr;
-            const size_t z = fasta_records(ctx, ft, with_rc != 0, size_t(1) << 20, &d_recs, dp->sentinels);
-            adopt_records(ctx, *dp, d_recs, true, z);
+            const ChainRequest recs = fasta_records(ctx, ft, with_rc != 0, size_t(1) << 20, dp->sentinels);
+            adopt_records(ctx, *dp, recs.d_records, true, recs.z);
             ctx.prof.collect();
         }
         *h = dp.release();

@@ -400,7 +400,7 @@ bool check_text_source(const uint8_t *text, size_t n, bool with_rc) {
     return n != 0;
 }
 
-size_t text_records(Context &ctx, const uint8_t *text, size_t n, bool with_rc, size_t extra, void **d_recs) {
+ChainRequest text_records(Context &ctx, const uint8_t *text, size_t n, bool with_rc, size_t extra) {
     const size_t m = with_rc ? 2 * n + 2 : n;
     reserve_arena_for(ctx, m, m + n + extra);
     uint8_t *d_T = ctx.arena.alloc<uint8_t>(n);
@@ -408,16 +408,22 @@ size_t text_records(Context &ctx, const uint8_t *text, size_t n, bool with_rc, s
         ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream);
         upload_bytes(ctx, d_T, text, n);
     }
-    if (!with_rc) return run_plain(ctx, d_T, n, 0, nullptr, nullptr, false, nullptr, d_recs);
+    ChainRequest rq;
+    rq.records = true;
+    if (!with_rc) {
+        run_plain(ctx, d_T, n, 0, rq);
+        return rq;
+    }
     uint8_t *d_S = ctx.arena.alloc<uint8_t>(m);
     const uint32_t bad = prepare_single_rc_on_device(ctx, d_T, (uint32_t)n, d_S);
     if (bad != 0xffffffffu)
         throw std::runtime_error("Invalid nucleotide '" + std::string(1, (char)text[bad]) + "' found in sequence 0");
-    return run_rc_pipeline(ctx, d_S, m, 0, d_recs);
+    run_rc_pipeline(ctx, d_S, m, 0, rq);
+    return rq;
 }
 
-size_t fasta_records(Context &ctx, const FastaText &ft, bool with_rc, size_t extra, void **d_recs,
-                     std::vector<uint64_t> &sentinels) {
+ChainRequest fasta_records(Context &ctx, const FastaText &ft, bool with_rc, size_t extra,
+                           std::vector<uint64_t> &sentinels) {
     const size_t m = ft.S.size();
     sentinels.clear();  // ascending: the byte behind every forward record but the end of the string
     for (const auto &rec : ft.recs)
@@ -428,8 +434,11 @@ size_t fasta_records(Context &ctx, const FastaText &ft, bool with_rc, size_t ext
         ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream);
         upload_bytes(ctx, d_S, ft.S.data(), m);
     }
-    return with_rc ? run_rc_pipeline(ctx, d_S, m, 0, d_recs)
-                   : run_plain(ctx, d_S, m, 0, nullptr, nullptr, false, nullptr, d_recs);
+    ChainRequest rq;
+    rq.records = true;
+    if (with_rc) run_rc_pipeline(ctx, d_S, m, 0, rq);
+    else run_plain(ctx, d_S, m, 0, rq);
+    return rq;
 }
 
 void text_maps(const uint8_t *text, size_t n, bool with_rc, int device, const nolzss_factor_map_request &rq,
@@ -438,9 +447,9 @@ void text_maps(const uint8_t *text, size_t n, bool with_rc, int device, const no
     if (!check_text_source(text, n, with_rc)) return;
     Session ses(device, nullptr);
     Context &ctx = ses.ctx();
-    void *d_recs = nullptr;
-    r.z = text_records(ctx, text, n, with_rc, maps_extra(rq), &d_recs);
-    bin_device_records(ctx, rq, {}, d_recs, r);
+    const ChainRequest recs = text_records(ctx, text, n, with_rc, maps_extra(rq));
+    r.z = recs.z;
+    bin_device_records(ctx, rq, {}, recs.d_records, r);
 }
 
 void fasta_maps(const char *path, bool with_rc, bool strict, int device, const nolzss_factor_map_request &rq,
@@ -452,9 +461,9 @@ void fasta_maps(const char *path, bool with_rc, bool strict, int device, const n
     std::vector<uint64_t> sentinels;
     Session ses(device, nullptr);
     Context &ctx = ses.ctx();
-    void *d_recs = nullptr;
-    r.z = fasta_records(ctx, ft, with_rc, maps_extra(rq), &d_recs, sentinels);
-    bin_device_records(ctx, rq, sentinels, d_recs, r);
+    const ChainRequest recs = fasta_records(ctx, ft, with_rc, maps_extra(rq), sentinels);
+    r.z = recs.z;
+    bin_device_records(ctx, rq, sentinels, recs.d_records, r);
 }
 
 void records_maps(const nolzss_factor *f, size_t z, const uint64_t *sent_idx, size_t n_sent, int device,

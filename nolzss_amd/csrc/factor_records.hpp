@@ -97,11 +97,11 @@ namespace api {
 // The refusals of nolzss_count_factors / nolzss_count_factors_dna_w_rc; false: nothing to factorize.
 bool check_text_source(const uint8_t *text, size_t n, bool with_rc);
 // Plain mode over the bytes, rc mode over T s0 rc(T) s1 prepared on the device; `extra`: arena bytes the caller
-// takes afterwards.  Returns z; *d_recs: the records in the arena (the caller's Session owns the mark).
-size_t text_records(Context &ctx, const uint8_t *text, size_t n, bool with_rc, size_t extra, void **d_recs);
+// takes afterwards.  Returns z and the records in the arena (ChainRequest, pipeline.hpp; the caller's Session owns the mark).
+ChainRequest text_records(Context &ctx, const uint8_t *text, size_t n, bool with_rc, size_t extra);
 // The prepared string of read_fasta_text; sentinels: the byte behind every forward record but the end of the string.
-size_t fasta_records(Context &ctx, const FastaText &ft, bool with_rc, size_t extra, void **d_recs,
-                     std::vector<uint64_t> &sentinels);
+ChainRequest fasta_records(Context &ctx, const FastaText &ft, bool with_rc, size_t extra,
+                           std::vector<uint64_t> &sentinels);
 
 }  // namespace api
 }  // namespace nolzss

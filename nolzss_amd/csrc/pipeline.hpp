@@ -80,40 +80,75 @@ uint32_t pending_threshold();
 void finish_pending_lcp(Context &ctx, const PackedText &text, const uint32_t *sa, uint32_t *lcp);
 void inject_pending_for_test(Context &ctx, uint32_t *lcp, uint32_t n);
 
-// ---- stage 5: greedy cursor + factor records (chain.hip) ------------------------------------
-// Factor lengths without factor records ("Factor-length histograms"): the chain's marked positions and
-// their L* codes only, factor_kernel is not run.  All device buffers are caller-allocated; hist (kRC: 2 x T bins, the
-// reverse-complement ones behind the forward ones) and *tail_count are zeroed by the caller.
+// ---- stage 5: greedy cursor (chain.hip): mark the chain, then take outputs from it ----------------
+// THE ARENA RULE of this stage and of the pipeline runners below (run_rc_pipeline*, run_rlz_pipeline, api::run_plain):
+// they allocate from ctx.arena and leave what they return there; none of them rewinds below its results.  The caller
+// takes arena.mark() before the call and rewinds when it has finished with the outputs -- the caller owns the mark.
+//
+// mark_chain runs the cursor over the codes from start_pos (start_pos >= n: z = 0, nothing launched) and leaves the
+// marked chain: one bit per position and the scanned factor counts of the 4096-position tiles.  It reads the codes and
+// nothing else; width 16: the cursor kernels read two bytes per position.  Its own temporaries are released before it
+// returns.  A count is mark_chain followed by the caller's rewind.
+struct Chain {
+    uint32_t n = 0, z = 0;  // positions, factors
+    LstarCodes codes;
+    const unsigned long long *bits = nullptr;  // num_tiles x 64 words
+    const uint32_t *tile_off = nullptr;        // factors in front of each tile
+    uint32_t num_tiles = 0;
+};
+Chain mark_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes);
+// The z factor starts, ascending (nullptr for z = 0).  Reads the mark only.
+uint32_t *chain_starts(Context &ctx, const Chain &chain);
+// What a factor record needs beyond its start and the codes: the interval of the factor around its rank, then the
+// leftmost occurrence.  Pmax + rcN (reverse-complement modes): the max pyramid over SA and the N of ref = 2N - max SA
+// - L + 1; the codes then carry the strand in bit 31.  rebase (plain mode only, refused together with Pmax): the
+// terminator table of a text of independent records; start and ref of every factor leave relative to its record.
+struct RecordLookup {
+    const uint32_t *sa = nullptr, *isa = nullptr, *lcp = nullptr;
+    Pyramid Psa, Plcp;
+    const Pyramid *Pmax = nullptr;
+    uint32_t rcN = 0;
+    const TermTable *rebase = nullptr;
+};
+// The z records (start, length, ref as u64) of the factors that begin at `starts` (chain_starts of the same chain).
+// 16-bit codes: plain records only.
+void *chain_records(Context &ctx, const Chain &chain, const uint32_t *starts, const RecordLookup &lookup);
+// Debug hooks (debug_api.hip): the record of EVERY position i < n, i.e. the record output over the starts 0, 1, .., n - 1
+// -- the distance to the next start is 1 everywhere, so the kernel takes length and flag from the code of each position.
+void *position_factors(Context &ctx, uint32_t n, const LstarCodes &codes, const RecordLookup &lookup);
+// Factor lengths without factor records ("Factor-length histograms"): the marked positions and their
+// 32-bit codes only.  All device buffers are caller-allocated; hist (with_strand: 2 x T bins, the reverse-complement
+// ones behind the forward ones) and *tail_count are zeroed by the caller.
 constexpr uint32_t kLengthHistBins = 2048;  // T: dense bins for 1 <= L < T
 struct ChainLengthsOut {
     uint32_t *hist = nullptr;        // per-length counts, or nullptr for no histogram
     uint64_t *tail = nullptr;        // lengths >= T: length | strand << 32, in no particular order
     uint32_t *tail_count = nullptr;  // entries written to tail
     uint32_t tail_cap = 0;           // floor(n / T) + 1: the lengths sum to at most n
-    uint32_t **order = nullptr;      // optional: z lengths in factor order, left in the arena like d_fpos_out
+    uint32_t **order = nullptr;      // optional: z lengths in factor order, left in the arena
 };
 inline uint32_t length_tail_cap(uint32_t n) { return n / kLengthHistBins + 1u; }
-// lstar.width == 16: the cursor kernels read two bytes per position and exit0 shrinks to two bytes as well (plain mode
-// without rebase or lengths only).
-uint32_t resolve_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &lstar, const uint32_t *sa,
-                       const uint32_t *isa, const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp,
-                       void **d_factors_out, uint32_t rcN = 0, const Pyramid *Pmax = nullptr,
-                       uint32_t **d_fpos_out = nullptr, const TermTable *rebase = nullptr,
-                       const ChainLengthsOut *lengths = nullptr);
-// Debug hooks (debug_api.hip): the record (start, length, ref) of EVERY position i < n, as factor_kernel gives it when
-// each position is a factor start -- the kernel reads the length code itself for a factor of length 1, so the existing
-// instantiations launched with fpos = 0, 1, .., n - 1 do that.  The n records (3 x u64 each) are left in the arena:
-// the caller owns the mark.  Arguments as resolve_chain.
-void *position_factors(Context &ctx, uint32_t n, const uint32_t *lstar, const uint32_t *sa, const uint32_t *isa,
-                       const uint32_t *lcp, const Pyramid &Psa, const Pyramid &Plcp, uint32_t rcN = 0,
-                       const Pyramid *Pmax = nullptr, const TermTable *rebase = nullptr);
+// with_strand: bit 31 of a code is the reverse-complement flag and selects the second half of hist
+void chain_lengths(Context &ctx, const Chain &chain, const ChainLengthsOut &out, bool with_strand);
+
+// What the caller of a pipeline runner wants from stage 5, and what the runner left in the arena for it.
+struct ChainRequest {
+    bool records = false, starts = false;      // wanted: factor records / factor starts
+    const ChainLengthsOut *lengths = nullptr;  // wanted: factor lengths
+    uint32_t z = 0;                            // result: the factor count, always
+    void *d_records = nullptr;                 // result: z x (start, length, ref), if records
+    uint32_t *d_starts = nullptr;              // result: z ascending starts, if records or starts
+    bool leaves_output() const { return records || starts || (lengths && lengths->order); }
+};
+// The end of every runner: the marked chain's outputs as the request asks for them.
+void chain_outputs(Context &ctx, const Chain &chain, const RecordLookup &lookup, bool with_strand, ChainRequest &rq);
 
 // ---- reverse-complement mode (rc.hip): whole pipeline over the prepared string S -------------
 struct RcPlainOut;
 struct RcDebugOut;
-uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m, size_t start_pos, void **d_factors_out,
-                         RcPlainOut *plain = nullptr, const ChainLengthsOut *lengths = nullptr,
-                         RcDebugOut *dbg = nullptr);
+// rq: ChainRequest above, over the reverse-complement chain
+void run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m, size_t start_pos, ChainRequest &rq,
+                     RcPlainOut *plain = nullptr, RcDebugOut *dbg = nullptr);
 // plain-mode counts as a by-product of a reverse-complement run: the plain L* of every position i < N comes out of
 // the same candidate kernels (rc.hip) and is chained on its own; z = nolzss_count_factors of the original strand(s),
 // fpos (want_fpos) = its factor starts in the arena, for the per-record split of a merged run
@@ -138,12 +173,9 @@ struct RcDebugOut {
     uint32_t compact = 0;           // the tile kernel wrote the compact output
     uint32_t pending_relaunch = 0;  // an undecided LCP entry sent the tile kernel round a second time
 };
-// the same over a text that has already been packed (merged batch); plain (optional): the plain-mode by-product
-// above; d_fpos_out (optional, with d_factors_out null): the factor starts of the reverse-complement chain
-// lengths (optional, with d_factors_out null): the factor lengths of the reverse-complement chain (ChainLengthsOut)
-uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
-                                RcPlainOut *plain = nullptr, uint32_t **d_fpos_out = nullptr,
-                                const ChainLengthsOut *lengths = nullptr, RcDebugOut *dbg = nullptr);
+// the same over a text that has already been packed (merged batch); plain (optional): the plain-mode by-product above
+void run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, ChainRequest &rq,
+                            RcPlainOut *plain = nullptr, RcDebugOut *dbg = nullptr);
 // d_S (2n + 2 bytes) = T' sep revcomp(T') sep for the n bytes d_T = upper-case records with separator bytes
 // between them; bytes that are not nucleotides (the separators) are copied to their mirror position.
 void prepare_batch_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t n, uint8_t separator, uint8_t *d_S);
@@ -167,11 +199,9 @@ struct RlzLayout {
 // leaves it once build_lcp_pyramid has decided every entry.  E is not read without with_rc.
 void rlz_candidates(Context &ctx, const uint32_t *sa, const uint32_t *lcp, uint32_t m, uint32_t B, uint32_t E, bool with_rc,
                     uint32_t *by_rank);
-// The whole pipeline over the device-resident S; outputs as resolve_chain (records and / or factor starts in the arena,
-// the caller owns the mark; the sentinels between the targets come out as literals).  h_codes (optional, host): the
-// code of every position below chain_end.
-uint32_t run_rlz_pipeline(Context &ctx, const uint8_t *d_S, const RlzLayout &lay, void **d_factors_out,
-                          uint32_t **d_fpos_out = nullptr, uint32_t *h_codes = nullptr);
+// The whole pipeline over the device-resident S; rq: ChainRequest above (the sentinels between the targets come out as
+// literals).  h_codes (optional, host): the code of every position below chain_end.
+void run_rlz_pipeline(Context &ctx, const uint8_t *d_S, const RlzLayout &lay, ChainRequest &rq, uint32_t *h_codes = nullptr);
 // counts[j] = entries of the ascending list d_fpos inside [bounds[2j], bounds[2j + 1]) (all device pointers)
 void rlz_count_per_target(Context &ctx, const uint32_t *d_fpos, uint32_t z, const uint32_t *d_bounds, uint32_t k,
                           uint32_t *d_counts);

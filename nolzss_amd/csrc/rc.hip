@@ -376,15 +376,14 @@ uint32_t prepare_single_rc_on_device(Context &ctx, const uint8_t *d_T, uint32_t 
     return bad;  // 0xffffffff when every byte is a nucleotide
 }
 
-uint32_t run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m_sz, size_t start_pos, void **d_factors_out,
-                         RcPlainOut *plain, const ChainLengthsOut *lengths, RcDebugOut *dbg) {
+void run_rc_pipeline(Context &ctx, const uint8_t *d_S, size_t m_sz, size_t start_pos, ChainRequest &rq, RcPlainOut *plain,
+                     RcDebugOut *dbg) {
     const PackedText text = pack_text(ctx, d_S, m_sz);  // segmented 2-bit packing is detected there
-    return run_rc_pipeline_packed(ctx, text, start_pos, d_factors_out, plain, nullptr, lengths, dbg);
+    run_rc_pipeline_packed(ctx, text, start_pos, rq, plain, dbg);
 }
 
-uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, void **d_factors_out,
-                                RcPlainOut *plain_out, uint32_t **d_fpos_out, const ChainLengthsOut *lengths,
-                                RcDebugOut *dbg) {
+void run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t start_pos, ChainRequest &rq, RcPlainOut *plain_out,
+                            RcDebugOut *dbg) {
     const uint32_t m = text.n;
     const uint32_t N = m / 2 - 1;
     hipStream_t s = ctx.stream;
@@ -555,23 +554,26 @@ uint32_t run_rc_pipeline_packed(Context &ctx, const PackedText &text, size_t sta
         }
         arena.rewind(mark);
     }
+    RecordLookup lookup{sa, isa, lcp, Pmin, Plcp};
+    lookup.Pmax = &Pmax;
+    lookup.rcN = N;
     if (dbg && dbg->records) {
         const size_t mark = arena.mark();
-        const void *recs = position_factors(ctx, N, code, sa, isa, lcp, Pmin, Plcp, N, &Pmax);
+        const void *recs = position_factors(ctx, N, LstarCodes::of(code), lookup);
         HIP_CHECK(hipMemcpyAsync(dbg->records, recs, (size_t)N * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         arena.rewind(mark);
     }
-    const uint32_t z = resolve_chain(ctx, N, (uint32_t)start_pos, LstarCodes::of(code), sa, isa, lcp, Pmin, Plcp, d_factors_out, N, &Pmax,
-                                     d_fpos_out, nullptr, lengths);
+    const size_t chain_mark = arena.mark();
+    chain_outputs(ctx, mark_chain(ctx, N, (uint32_t)start_pos, LstarCodes::of(code)), lookup, true, rq);
     if (plain_out) {
         // the plain chain over the same positions: counts (and factor starts) only, no records
+        if (!rq.leaves_output()) arena.rewind(chain_mark);  // (a count: its mark makes room)
         ProfScope ps(ctx.profiler(), "plain_chain", s);
-        plain_out->fpos = nullptr;
-        plain_out->z = resolve_chain(ctx, N, 0, LstarCodes::of(plain), sa, isa, lcp, Pmin, Plcp, nullptr, 0, nullptr,
-                                     plain_out->want_fpos ? &plain_out->fpos : nullptr);
+        const Chain chain = mark_chain(ctx, N, 0, LstarCodes::of(plain));
+        plain_out->z = chain.z;
+        plain_out->fpos = plain_out->want_fpos ? chain_starts(ctx, chain) : nullptr;
     }
-    return z;
 }
 
 }  // namespace nolzss

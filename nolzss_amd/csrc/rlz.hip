@@ -339,10 +339,7 @@ void rlz_count_per_target(Context &ctx, const uint32_t *d_fpos, uint32_t z, cons
     KERNEL_CHECK();
 }
 
-uint32_t run_rlz_pipeline(Context &ctx, const uint8_t *d_S, const RlzLayout &lay, void **d_factors_out, uint32_t **d_fpos_out,
-                          uint32_t *h_codes) {
-    if (d_factors_out) *d_factors_out = nullptr;
-    if (d_fpos_out) *d_fpos_out = nullptr;
+void run_rlz_pipeline(Context &ctx, const uint8_t *d_S, const RlzLayout &lay, ChainRequest &rq, uint32_t *h_codes) {
     Arena &arena = ctx.arena;
     hipStream_t s = ctx.stream;
     const PackedText text = pack_text(ctx, d_S, lay.total);  // segmented at 2 bits, as the multi-FASTA strings
@@ -379,8 +376,12 @@ uint32_t run_rlz_pipeline(Context &ctx, const uint8_t *d_S, const RlzLayout &lay
     }
     // min SA over I(L) lies in Rblk (the block comes first), max SA in the mirrored block (it comes last), and
     // 2 rcN - max SA - L + 1 with 2 rcN = B - 1 + E is the leftmost forward coordinate
-    return resolve_chain(ctx, lay.chain_end, lay.block_length + 1u, LstarCodes::of(code), sa, isa, lcp, Pmin, Plcp, d_factors_out, lay.rcN,
-                         lay.with_rc ? &Pmax : nullptr, d_fpos_out);
+    RecordLookup lookup{sa, isa, lcp, Pmin, Plcp};
+    if (lay.with_rc) {
+        lookup.Pmax = &Pmax;
+        lookup.rcN = lay.rcN;
+    }
+    chain_outputs(ctx, mark_chain(ctx, lay.chain_end, lay.block_length + 1u, LstarCodes::of(code)), lookup, lay.with_rc, rq);
 }
 
 }  // namespace nolzss

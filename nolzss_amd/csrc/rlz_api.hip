@@ -77,8 +77,7 @@ namespace {
 
 struct RlzRun {
     std::vector<size_t> counts, first;  // per target: records, and the index of its first record in block
-    nolzss_factor *block = nullptr;
-    ~RlzRun() { free_block(block); }
+    FactorBlock block;
 };
 
 // One pipeline run; want_factors: every record comes down (the sentinel literals between the targets with them) and is
@@ -98,17 +97,14 @@ void rlz_run(const RlzPrepared &p, const size_t *target_lens, size_t k, bool wan
         ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream);
         upload_bytes(ctx, d_S, p.S.data(), total);
     }
+    ChainRequest rq;
+    (want_factors ? rq.records : rq.starts) = true;
+    run_rlz_pipeline(ctx, d_S, p.lay, rq, h_codes);
+    const uint32_t z = rq.z;
     if (want_factors) {
-        void *d_recs = nullptr;
-        const size_t z = run_rlz_pipeline(ctx, d_S, p.lay, &d_recs, nullptr, h_codes);
-        if (z) {
-            out.block = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * z));
-            if (!out.block) throw std::bad_alloc();
-            ProfScope ps(ctx.profiler(), "factors_d2h", ctx.stream);
-            download_bytes(ctx, out.block, d_recs, sizeof(nolzss_factor) * z);
-        }
+        out.block = download_factors(ctx, rq.d_records, z);
         HIP_CHECK(hipStreamSynchronize(ctx.stream));
-        const nolzss_factor *f = out.block;
+        const nolzss_factor *f = out.block.get();
         auto first_at = [&](uint64_t pos) {
             return (size_t)(std::lower_bound(f, f + z, pos, [](const nolzss_factor &a, uint64_t x) { return a.start < x; }) - f);
         };
@@ -117,8 +113,6 @@ void rlz_run(const RlzPrepared &p, const size_t *target_lens, size_t k, bool wan
             out.counts[j] = first_at(p.target_offsets[j] + target_lens[j]) - out.first[j];
         }
     } else {
-        uint32_t *d_fpos = nullptr;
-        const uint32_t z = run_rlz_pipeline(ctx, d_S, p.lay, nullptr, &d_fpos, h_codes);
         if (z) {
             std::vector<uint32_t> bounds(2 * k), counts(k);
             for (size_t j = 0; j < k; ++j) {
@@ -127,7 +121,7 @@ void rlz_run(const RlzPrepared &p, const size_t *target_lens, size_t k, bool wan
             }
             uint32_t *d_bounds = ctx.arena.alloc<uint32_t>(2 * k), *d_counts = ctx.arena.alloc<uint32_t>(k);
             HIP_CHECK(hipMemcpyAsync(d_bounds, bounds.data(), bounds.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx.stream));
-            rlz_count_per_target(ctx, d_fpos, z, d_bounds, (uint32_t)k, d_counts);
+            rlz_count_per_target(ctx, rq.d_starts, z, d_bounds, (uint32_t)k, d_counts);
             HIP_CHECK(hipMemcpyAsync(counts.data(), d_counts, k * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx.stream));
             HIP_CHECK(hipStreamSynchronize(ctx.stream));  // (bounds and counts are local vectors)
             for (size_t j = 0; j < k; ++j) out.counts[j] = counts[j];
@@ -173,7 +167,7 @@ void rlz_factorize(const char *const *refs, const size_t *ref_lens, size_t m, co
             res.target_offsets[j] = p.target_offsets[j];
             res.target_lengths[j] = target_lens[j];
             res.counts[j] = run.counts[j];
-            if (want_factors) res.factors[j] = run.block ? run.block + run.first[j] : nullptr;
+            if (want_factors) res.factors[j] = run.block ? run.block.get() + run.first[j] : nullptr;
         }
         if (ref_parse) {
             res.reference_ids = id_blob(ref_parse->ids, &res.reference_ids_bytes);
@@ -184,8 +178,7 @@ void rlz_factorize(const char *const *refs, const size_t *ref_lens, size_t m, co
         nolzss_free_rlz_result(&res);
         throw;
     }
-    res.block = run.block;
-    run.block = nullptr;  // ownership moves to the caller
+    res.block = run.block.release();  // ownership moves to the caller
     *out = res;
 }
 

@@ -127,8 +127,7 @@ void prepare_batch(const nolzss_rlz_index &h, const char *const *targets, const 
 
 struct MatchOut {
     std::vector<size_t> counts, first;  // per target: records, and the index of its first record in block
-    nolzss_factor *block = nullptr;
-    ~MatchOut() { free_block(block); }
+    FactorBlock block;
 };
 
 // One batch against the handle (k >= 1).  h_codes: the codes of every position and nothing else.  Otherwise the chain;
@@ -159,13 +158,12 @@ void match_batch(const nolzss_rlz_index &h, const Batch &b, const size_t *target
         ctx.prof.collect();
         return;
     }
-    // the counts-only form of the chain: it reads the codes and nothing else (chain.hip)
-    uint32_t *d_fpos = nullptr;
-    const Pyramid none{};
-    const uint32_t z = resolve_chain(ctx, (uint32_t)n, 0u, LstarCodes::of(d_len), nullptr, nullptr, nullptr, none, none, nullptr,
-                                     0u, nullptr, &d_fpos);
+    // the chain and its factor starts: they read the codes and nothing else (chain.hip)
+    const Chain chain = mark_chain(ctx, (uint32_t)n, 0u, LstarCodes::of(d_len));
+    const uint32_t z = chain.z;
+    const uint32_t *d_fpos = chain_starts(ctx, chain);
     if (want_factors) {
-        out.block = static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * (z ? z : 1)));
+        out.block.reset(static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * (z ? z : 1))));
         if (!out.block) throw std::bad_alloc();
         const size_t chunk = z < kRecordChunk ? z : kRecordChunk;
         IndexRec *d_recs = ctx.arena.alloc<IndexRec>(chunk ? chunk : 1);
@@ -173,10 +171,10 @@ void match_batch(const nolzss_rlz_index &h, const Batch &b, const size_t *target
             const size_t cnt = z - c0 < chunk ? z - c0 : chunk;
             rlz_index_records(ctx, h.view, d_fpos + c0, (uint32_t)cnt, d_len, d_rank, d_recs);
             ProfScope ps(ctx.profiler(), "factors_d2h", s, (double)(sizeof(IndexRec) * cnt));
-            download_bytes(ctx, out.block + c0, d_recs, sizeof(IndexRec) * cnt);  // (waits: d_recs is free again)
+            download_bytes(ctx, out.block.get() + c0, d_recs, sizeof(IndexRec) * cnt);  // (waits: d_recs is free again)
         }
         HIP_CHECK(hipStreamSynchronize(s));
-        const nolzss_factor *f = out.block;
+        const nolzss_factor *f = out.block.get();
         auto first_at = [&](uint64_t pos) {
             return (size_t)(std::lower_bound(f, f + z, pos, [](const nolzss_factor &a, uint64_t x) { return a.start < x; }) - f);
         };
@@ -228,14 +226,13 @@ void index_factorize(const nolzss_rlz_index &h, const char *const *targets, cons
             res.target_offsets[j] = (uint64_t)h.view.B + 1 + b.offsets[j];
             res.target_lengths[j] = target_lens[j];
             res.counts[j] = run.counts[j];
-            if (want_factors) res.factors[j] = run.block ? run.block + run.first[j] : nullptr;
+            if (want_factors) res.factors[j] = run.block ? run.block.get() + run.first[j] : nullptr;
         }
     } catch (...) {
         nolzss_free_rlz_result(&res);
         throw;
     }
-    res.block = run.block;
-    run.block = nullptr;  // ownership moves to the caller
+    res.block = run.block.release();  // ownership moves to the caller
     *out = res;
 }
 

@@ -1,6 +1,6 @@
 // significance.hip -- factor lengths for the shuffled-control significance analysis ("Factor-length
 // histograms and the keyed shuffle"): the length histogram and the lengths in factor order straight from the chain
-// (resolve_chain with ChainLengthsOut, chain.hip), and the keyed shuffle of the text that gives the control.
+// (chain_lengths, chain.hip), and the keyed shuffle of the text that gives the control.
 //
 // Keyed shuffle: out[s + i] = in[s + pi(i)] for every record [s, s + len).  pi is a balanced 4-round Feistel network
 // on 2k bits, k = the smallest k >= 1 with 4^k >= len, walked in cycles until it lands inside [0, len):
@@ -143,8 +143,11 @@ void run_lengths(Context &ctx, const uint8_t *d_text, size_t n, bool rc, bool wa
     uint32_t z = 0;
     {
         ProfScope ps(ctx.profiler(), "length_pipeline", s);
-        z = rc ? run_rc_pipeline(ctx, d_text, n, 0, nullptr, nullptr, &lo)
-               : (uint32_t)run_plain(ctx, d_text, n, 0, nullptr, nullptr, false, &lo);
+        ChainRequest rq;
+        rq.lengths = &lo;
+        if (rc) run_rc_pipeline(ctx, d_text, n, 0, rq);
+        else run_plain(ctx, d_text, n, 0, rq);
+        z = rq.z;
     }
     out.z = z;
     {  // (closed before collect(): the downloads are timed too)
