@@ -658,6 +658,48 @@ int nolzss_rlz_index_codes(const nolzss_rlz_index *h, const char *const *targets
 /* NULL is a no-op. */
 int nolzss_rlz_index_close(nolzss_rlz_index *h);
 
+/* ---- relative-LZ archive: batches appended from the index ---------------------------------------- */
+/* Extension.  The index and the archive meet on the device: a batch is matched against the index as
+ * nolzss_rlz_index_factorize matches it, and its records go from the match kernels straight into the archive's resident
+ * form -- no record crosses PCIe, and an archive grows batch by batch without a limit on the number of targets (DESIGN.md
+ * 5, "Relative-LZ archive: batches appended from the index").
+ *   open_index: an empty archive (z = 0, no targets) over the reference block of `ix`, on the index's device and bound
+ *     to that index.  The block is Rblk, the reference records upper-cased and joined by one 0x01 each -- byte for byte
+ *     the block of nolzss_amd.genomics.rlz.absolute_records --, unpacked on the device from the packed index text into
+ *     an allocation of the archive's own.  Every index handle carries a serial number, a process-wide counter taken at
+ *     its open; the archive remembers it.  The archive may outlive the index; only an append needs it.
+ *   append_index: the k targets become targets num_targets .. num_targets + k - 1 of the archive, in order.  With the
+ *     batch laid out as Tcat = T1 s .. Tk s, the record of factor start i at batch position p, with j separators below
+ *     p, becomes resident record z_old + i - j with start = decoded_old + p - j; a separator's own literal is dropped,
+ *     so a batch adds exactly (factor starts of the batch) - k records.  The position sample is extended over the new
+ *     positions.  When the record or sample array is too small it is replaced by one of max(needed, 2 x current)
+ *     entries, the old contents copied device to device; device_bytes counts capacity.
+ *   All or nothing: the handle changes only after the device work of the call has finished without error.  Any refusal
+ *     or failure, an arena or device out-of-memory included, leaves the archive exactly as it was and usable.
+ *   Refusals of append: NOLZSS_ERR_INVALID_ARGUMENT before any device work for a null handle or index, an archive not
+ *     opened by open_index, an index whose serial number or device is not the one the archive is bound to;
+ *     NOLZSS_ERR_INVALID_ARGUMENT naming the quantity for decoded_old + sum(len) beyond the 32-bit pipeline (decided
+ *     by the lengths alone) and for z reaching 2^32; and everything nolzss_rlz_index_factorize refuses, with its status
+ *     and message ("sequence j" is m + the target's index in this batch).  k == 0 succeeds without touching the device.
+ *   export: the host form of ANY archive, exactly what nolzss_rlz_archive_open_records takes: the block, z records with
+ *     absolute start = block_len + decoded start, ref carrying NOLZSS_RC_MASK or equal to start for a literal, and the
+ *     literal symbols in record order.  Each of the three comes down once; malloc'ed, nolzss_free.
+ *   An append must not overlap any other call on that archive; the index may serve other threads' matches meanwhile.
+ *   The calling thread's current device is left as it was. */
+typedef struct nolzss_rlz_archive_append_info {
+    uint64_t targets_added, records_added, literals_added, bases_added;
+    uint64_t num_targets, z, total_length;  /* of the archive after the call */
+    uint64_t capacity_records;              /* records the handle's allocation can hold */
+    uint64_t device_bytes;                  /* as in the summary: what the handle holds now */
+    int32_t reallocated;                    /* 1 if the record or sample array moved in this call */
+} nolzss_rlz_archive_append_info;
+int nolzss_rlz_archive_open_index(const nolzss_rlz_index *ix, nolzss_rlz_archive **h);
+/* info may be NULL. */
+int nolzss_rlz_archive_append_index(nolzss_rlz_archive *h, const nolzss_rlz_index *ix, const char *const *targets,
+                                    const size_t *target_lens, size_t k, nolzss_rlz_archive_append_info *info);
+int nolzss_rlz_archive_export(const nolzss_rlz_archive *h, uint8_t **block, size_t *block_len, nolzss_factor **records,
+                              size_t *z, uint8_t **literals, size_t *n_literals);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

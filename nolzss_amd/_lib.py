@@ -114,6 +114,13 @@ class RlzArchiveSummary(C.Structure):
                 ("device_bytes", C.c_uint64)]
 
 
+class RlzArchiveAppendInfo(C.Structure):
+    """Mirror of nolzss_rlz_archive_append_info (include/nolzss_hip.h)."""
+    _fields_ = [("targets_added", C.c_uint64), ("records_added", C.c_uint64), ("literals_added", C.c_uint64),
+                ("bases_added", C.c_uint64), ("num_targets", C.c_uint64), ("z", C.c_uint64), ("total_length", C.c_uint64),
+                ("capacity_records", C.c_uint64), ("device_bytes", C.c_uint64), ("reallocated", C.c_int32)]
+
+
 class RlzIndexSummary(C.Structure):
     """Mirror of nolzss_rlz_index_summary (include/nolzss_hip.h)."""
     _fields_ = [("num_references", C.c_uint64), ("block_length", C.c_uint64), ("index_length", C.c_uint64),
@@ -269,6 +276,9 @@ def _load():
     lib.nolzss_rlz_index_factorize.argtypes = [vp] + seqs[3:] + [C.c_int, C.POINTER(RlzResult)]
     lib.nolzss_rlz_index_codes.argtypes = [vp] + seqs[3:] + [vp]
     lib.nolzss_rlz_index_close.argtypes = [vp]
+    lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
+    lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
+    lib.nolzss_rlz_archive_export.argtypes = [vp, vpp, szp, vpp, szp, vpp, szp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -323,6 +333,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_archive_extract_device", "nolzss_rlz_archive_close",
     "nolzss_rlz_index_open", "nolzss_rlz_index_open_fasta", "nolzss_rlz_index_info", "nolzss_rlz_index_factorize",
     "nolzss_rlz_index_codes", "nolzss_rlz_index_close",
+    "nolzss_rlz_archive_open_index", "nolzss_rlz_archive_append_index", "nolzss_rlz_archive_export",
 ]
 
 

@@ -1203,12 +1203,16 @@ class RlzArchiveHandle:
 
     def __init__(self, handle):
         self._h = handle
-        info = _lib.RlzArchiveSummary()
         try:
-            check(lib.nolzss_rlz_archive_info(self._h, C.byref(info)))
+            self._refresh()
         except Exception:
             self.close()
             raise
+
+    def _refresh(self):
+        """info and target_lengths from the handle's own table (at open, and after every append)"""
+        info = _lib.RlzArchiveSummary()
+        check(lib.nolzss_rlz_archive_info(self._h, C.byref(info)))
         self.info = {k: int(getattr(info, k)) for k in ("num_targets", "block_length", "z", "n_literals",
                                                         "total_length", "device", "device_bytes")}
         k = info.num_targets
@@ -1229,10 +1233,46 @@ class RlzArchiveHandle:
                                                   lens.size, _default_device, C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def open_index(cls, index_handle):
+        """An empty archive over the reference block of an RlzIndexHandle, on its device and bound to it; the block is
+        unpacked on the device from the index text.  C ABI nolzss_rlz_archive_open_index."""
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_archive_open_index(index_handle._handle(), C.byref(h)))
+        return cls(h)
+
     def _handle(self):
         if self._h is None:
             raise ValueError("the archive is closed")
         return self._h
+
+    def append_index(self, index_handle, targets) -> dict:
+        """One batch matched against the index and appended as len(targets) new targets, the records staying on the
+        device -> the call's nolzss_rlz_archive_append_info as a dict.  C ABI nolzss_rlz_archive_append_index."""
+        h = self._handle()
+        info = _lib.RlzArchiveAppendInfo()
+        check(lib.nolzss_rlz_archive_append_index(h, index_handle._handle(), *_seq_args(targets, "target"), C.byref(info)))
+        self._refresh()
+        return {name: int(getattr(info, name)) for name, _ in _lib.RlzArchiveAppendInfo._fields_}
+
+    def export(self):
+        """-> (block bytes, FACTOR_DTYPE records, literals bytes): the host form open_records takes, of an archive of
+        either origin.  C ABI nolzss_rlz_archive_export."""
+        h = self._handle()
+        blk, rec, lit = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        bn, z, ln = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib.nolzss_rlz_archive_export(h, C.byref(blk), C.byref(bn), C.byref(rec), C.byref(z), C.byref(lit),
+                                            C.byref(ln)))
+        try:
+            block, literals = C.string_at(blk, bn.value), C.string_at(lit, ln.value)
+            if z.value:
+                records = np.ctypeslib.as_array(C.cast(rec, C.POINTER(C.c_uint64)), shape=(z.value * 3,)).copy().view(FACTOR_DTYPE)
+            else:
+                records = np.zeros(0, dtype=FACTOR_DTYPE)
+        finally:
+            for q in (blk, rec, lit):
+                lib.nolzss_free(q)
+        return block, records, literals
 
     def extract_array(self, ranges):
         """(target index, lo, hi) rows -> (uint8 array of the ranges back to back, uint64 offsets of q + 1 entries)."""

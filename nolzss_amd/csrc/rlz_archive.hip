@@ -219,7 +219,201 @@ __global__ __launch_bounds__(kThreads) void rlz_extract_kernel(ArchiveView v, co
     }
 }
 
+// ---- batches appended from the index, export ("Relative-LZ archive: batches appended from the index") ----
+// Every kernel below is bounded by the call's shape: the separator search takes ceil(log2(k + 1)) steps, the sample
+// search ceil(log2(new records)) steps, the terminator walk of the unpack at most 32.  No spinning, no communication
+// between workgroups, no atomics (the literal count of an append is one ballot and one store per wavefront); every load stays inside the handle's arrays and the batch's (the indices are checked
+// against the sizes the host passes, not trusted from the data).
+
+// One lane per packed word of the index text: 32 bases -> 32 bytes of Rblk, the terminators below B as 0x01.
+__global__ __launch_bounds__(kThreads) void archive_unpack_kernel(PackedText x, uint32_t B, uint8_t *__restrict__ block) {
+    const uint64_t g = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t at = g * 32u;
+    if (at >= B) return;
+    const uint32_t p0 = (uint32_t)at;
+    const uint32_t count = B - p0 < 32u ? B - p0 : 32u;
+    const uint64_t w = x.words[g];
+    // the terminators in [p0, p0 + count) as a bit mask: the table is ascending and its last entry is the end of the
+    // text, >= B
+    uint32_t seps = 0;
+    uint32_t t = term_lower_bound(x.terms, p0);
+    for (int step = 0; step < 32 && t < x.terms.count; ++step, ++t) {
+        const uint32_t q = x.terms.pos[t];
+        if (q >= p0 + count) break;
+        seps |= 1u << (q - p0);
+    }
+    uint32_t out[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t code = (uint32_t)(w >> (62 - 2 * (4 * q + e))) & 3u;
+            uint32_t c = code == 0 ? 'A' : code == 1 ? 'C' : code == 2 ? 'G' : 'T';
+            c = (seps >> (4 * q + e)) & 1u ? 1u : c;
+            v |= c << (8 * e);
+        }
+        out[q] = v;
+    }
+    if (count == 32u) {  // (block is a device allocation: 32 g is 16-byte aligned)
+        uint4 *dst = reinterpret_cast<uint4 *>(block + p0);
+        dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
+        dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
+    } else {
+#pragma unroll
+        for (uint32_t b = 0; b < 32u; ++b)
+            if (b < count) block[p0 + b] = (uint8_t)(out[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
+// One lane per look-up of the chunk.  lit_counts[blockIdx.x * 4 + wavefront]: the literal records this wavefront wrote
+// (one store per wavefront, every wavefront of the grid writes its own word: the host adds them up).
+__global__ __launch_bounds__(kThreads) void archive_append_kernel(const IndexRec *__restrict__ chunk,
+                                                                  const uint32_t *__restrict__ fpos, uint32_t first,
+                                                                  uint32_t cnt, uint64_t base, AppendBatch b,
+                                                                  ArchiveRec *__restrict__ out,
+                                                                  uint32_t *__restrict__ lit_counts) {
+    const uint64_t t = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    bool literal = false;
+    const uint32_t p = t < cnt ? fpos[t] : b.n;
+    if (p < b.n) {  // (a factor start is a batch position)
+        // j = the separators below p: at most ceil(log2(k + 1)) steps.  Adjacent separators are empty targets.
+        uint32_t lo = 0, hi = b.k;  // seps[0 .. lo) < p <= seps[hi ..)
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (b.seps[mid] < p) lo = mid + 1;
+            else hi = mid;
+        }
+        const uint32_t j = lo;
+        // every separator below p is a factor start below p: j <= first + t
+        const uint64_t o = (uint64_t)b.z_old + first + t - j;
+        if (!(j < b.k && b.seps[j] == p) && o < b.z_new) {  // (not the separator's own literal)
+            const IndexRec f = chunk[t];
+            ArchiveRec a;
+            a.start = b.decoded_old + p - j;
+            a.length = (uint32_t)f.length;
+            if (f.ref == base + p) {
+                a.src = 0;
+                a.meta = kArchiveLiteral | ((uint32_t)b.text[p] << 8);
+                literal = true;
+            } else if (f.ref & kRcMask) {
+                a.src = (uint32_t)((f.ref & ~kRcMask) + f.length - 1);
+                a.meta = kArchiveRc;
+            } else {
+                a.src = (uint32_t)f.ref;
+                a.meta = kArchiveForward;
+            }
+            reinterpret_cast<uint4 *>(out)[o] = make_uint4(a.start, a.length, a.src, a.meta);
+        }
+    }
+    const unsigned long long lits = __ballot(literal);  // (all lanes are back together here)
+    if ((threadIdx.x & (kWave - 1)) == 0) lit_counts[blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave] = (uint32_t)__popcll(lits);
+}
+
+// sample[s] = the last record of [z_old, z_new) with start <= 256 s; recs[z_old].start <= 256 s for every s here
+__global__ __launch_bounds__(kThreads) void archive_extend_sample_kernel(const ArchiveRec *__restrict__ recs, uint32_t z_old,
+                                                                         uint32_t z_new, uint32_t s_lo, uint32_t s_hi,
+                                                                         uint32_t *__restrict__ sample) {
+    const uint64_t g = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (g >= s_hi - s_lo) return;
+    const uint32_t s = s_lo + (uint32_t)g;
+    const uint32_t p = s << kSampleShift;
+    uint32_t lo = z_old, hi = z_new;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (recs[mid].start <= p) lo = mid;
+        else hi = mid;
+    }
+    sample[s] = lo;
+}
+
+__global__ __launch_bounds__(kThreads) void archive_literal_flags_kernel(const ArchiveRec *__restrict__ recs, uint64_t cnt,
+                                                                         uint32_t *__restrict__ flags) {
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < cnt; i += stride)
+        flags[i] = (recs[i].meta & 3u) == kArchiveLiteral ? 1u : 0u;
+}
+
+// lit_index: the exclusive add-scan of the literal flags of ALL records; archive_pack_kernel the other way round
+__global__ __launch_bounds__(kThreads) void archive_export_kernel(const ArchiveRec *__restrict__ recs, uint64_t first,
+                                                                  uint64_t cnt, uint64_t block_len,
+                                                                  const uint32_t *__restrict__ lit_index,
+                                                                  Rec *__restrict__ out, uint8_t *__restrict__ literals) {
+    const uint64_t stride = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t t = (uint64_t)blockIdx.x * kThreads + threadIdx.x; t < cnt; t += stride) {
+        const uint4 w = reinterpret_cast<const uint4 *>(recs)[first + t];
+        const ArchiveRec a{w.x, w.y, w.z, w.w};
+        Rec f;
+        f.start = block_len + a.start;
+        f.length = a.length;
+        const uint32_t kind = a.meta & 3u;
+        if (kind == kArchiveLiteral) {
+            f.ref = f.start;
+            literals[lit_index[first + t]] = (uint8_t)((a.meta >> 8) & 0xffu);
+        } else if (kind == kArchiveRc) {
+            f.ref = ((uint64_t)a.src - (a.length - 1u)) | kRcMask;
+        } else {
+            f.ref = a.src;
+        }
+        out[t] = f;
+    }
+}
+
 }  // namespace
+
+void archive_unpack_block(Context &ctx, const PackedText &x, uint32_t B, uint8_t *d_block) {
+    if (B == 0) return;
+    ProfScope ps(ctx.profiler(), "rlz_archive_unpack", ctx.stream, 1.25 * (double)B);
+    const uint64_t lanes = div_up((uint64_t)B, (uint64_t)32);
+    archive_unpack_kernel<<<(unsigned)div_up(lanes, (uint64_t)kThreads), kThreads, 0, ctx.stream>>>(x, B, d_block);
+    KERNEL_CHECK();
+}
+
+size_t archive_append_counts(size_t cnt) { return div_up(cnt, (size_t)kThreads) * (kThreads / kWave); }
+
+void archive_append_records(Context &ctx, const IndexRec *d_chunk, const uint32_t *d_fpos, uint32_t first, uint32_t cnt,
+                            uint64_t base, const AppendBatch &b, ArchiveRec *d_recs, uint32_t *d_lit_counts) {
+    if (cnt == 0) return;
+    ProfScope ps(ctx.profiler(), "rlz_append_records", ctx.stream, 45.0 * (double)cnt);
+    archive_append_kernel<<<(unsigned)div_up((size_t)cnt, (size_t)kThreads), kThreads, 0, ctx.stream>>>(
+        d_chunk, d_fpos, first, cnt, base, b, d_recs, d_lit_counts);
+    KERNEL_CHECK();
+}
+
+void archive_extend_sample(Context &ctx, const ArchiveRec *d_recs, uint32_t z_old, uint32_t z_new, uint32_t s_lo,
+                           uint32_t s_hi, uint32_t *d_sample) {
+    if (s_hi <= s_lo || z_new <= z_old) return;
+    ProfScope ps(ctx.profiler(), "rlz_append_sample", ctx.stream, 4.0 * (double)(s_hi - s_lo));
+    archive_extend_sample_kernel<<<(unsigned)div_up((size_t)(s_hi - s_lo), (size_t)kThreads), kThreads, 0, ctx.stream>>>(
+        d_recs, z_old, z_new, s_lo, s_hi, d_sample);
+    KERNEL_CHECK();
+}
+
+uint64_t archive_literal_index(Context &ctx, const ArchiveRec *d_recs, size_t cnt, uint32_t *d_index) {
+    if (cnt == 0) return 0;
+    hipStream_t s = ctx.stream;
+    const size_t mark = ctx.arena.mark();
+    uint32_t *d_total = ctx.arena.alloc<uint32_t>(1);
+    {
+        ProfScope ps(ctx.profiler(), "rlz_archive_literal_index", s, 24.0 * (double)cnt);
+        archive_literal_flags_kernel<<<record_grid(cnt), kThreads, 0, s>>>(d_recs, cnt, d_index);
+        KERNEL_CHECK();
+        scan_exclusive_add_u32(d_index, d_index, cnt, d_total, ctx.arena, s);
+    }
+    uint32_t total = 0;
+    ctx.read_back(d_total, &total, 1);
+    ctx.arena.rewind(mark);
+    return total;
+}
+
+void archive_export_records(Context &ctx, const ArchiveRec *d_recs, size_t first, size_t cnt, uint64_t block_len,
+                            const uint32_t *d_index, Rec *d_out, uint8_t *d_literals) {
+    if (cnt == 0) return;
+    ProfScope ps(ctx.profiler(), "rlz_archive_export", ctx.stream, 45.0 * (double)cnt);
+    archive_export_kernel<<<record_grid(cnt), kThreads, 0, ctx.stream>>>(d_recs, first, cnt, block_len, d_index, d_out,
+                                                                        d_literals);
+    KERNEL_CHECK();
+}
 
 const char *archive_rule_text(uint32_t rule) {
     switch (rule) {

@@ -3,6 +3,7 @@
 // records"; C ABI: rlz_archive_api.hip, include/nolzss_hip.h, nolzss_rlz_archive_*).
 #pragma once
 #include "decode.hpp"
+#include "rlz_index.hpp"
 
 namespace nolzss {
 
@@ -49,5 +50,36 @@ void archive_extract(Context &ctx, const ArchiveView &v, const uint32_t *d_offse
                      uint32_t total, uint8_t *d_out, unsigned long long *d_err);
 
 const char *archive_rule_text(uint32_t rule);
+
+// ---- batches appended from the index, and the way back to host records ("Relative-LZ archive: batches
+// appended from the index") ------------------------------------------------------------------------------------------
+// Rblk, bytes [0, B) of the segmented 2-bit index text x: A/C/G/T from the codes, 0x01 at each terminator below B.
+void archive_unpack_block(Context &ctx, const PackedText &x, uint32_t B, uint8_t *d_block);
+
+// One batch T1 s T2 s .. Tk s (n bytes, upper case, in device memory) behind z_old records and decoded_old bytes.
+struct AppendBatch {
+    const uint8_t *text;
+    const uint32_t *seps;  // k ascending separator positions (device)
+    uint32_t n, k;
+    uint32_t z_old, decoded_old;
+    uint32_t z_new;        // z_old + (factor starts of the batch) - k: no record is written at or behind it
+};
+// cnt look-ups of the batch's factor starts d_fpos[0 .. cnt) (batch positions; global start index `first` + t) -> their
+// resident records at d_recs[z_old + first + t - j], j = the separators below the position; a separator's own literal
+// is dropped.  `base` = B + 1, the absolute position of batch position 0.  d_lit_counts: archive_append_counts(cnt)
+// words, all written; their sum is the number of literal records among those the launch wrote.
+size_t archive_append_counts(size_t cnt);
+void archive_append_records(Context &ctx, const IndexRec *d_chunk, const uint32_t *d_fpos, uint32_t first, uint32_t cnt,
+                            uint64_t base, const AppendBatch &b, ArchiveRec *d_recs, uint32_t *d_lit_counts);
+// sample[s] for s in [s_lo, s_hi): the last record of [z_old, z_new) with start <= 256 s (256 s >= start[z_old])
+void archive_extend_sample(Context &ctx, const ArchiveRec *d_recs, uint32_t z_old, uint32_t z_new, uint32_t s_lo,
+                           uint32_t s_hi, uint32_t *d_sample);
+// d_index[t] = the literal records among d_recs[0 .. t), t < cnt (cnt words); returns the literals among all cnt.
+// Waits for the stream.  (Export lays the literal stream out with it.)
+uint64_t archive_literal_index(Context &ctx, const ArchiveRec *d_recs, size_t cnt, uint32_t *d_index);
+// Resident records [first, first + cnt) -> 24-byte records at d_out[0 .. cnt) (start absolute, ref with kRcMask, a
+// literal has ref == start) and the symbols of their literals at d_literals[d_index[first + t]].
+void archive_export_records(Context &ctx, const ArchiveRec *d_recs, size_t first, size_t cnt, uint64_t block_len,
+                            const uint32_t *d_index, Rec *d_out, uint8_t *d_literals);
 
 }  // namespace nolzss

@@ -1,47 +1,14 @@
 // rlz_archive_api.hip -- the relative-LZ archive handle and its entry points: host records in, a resident form kept in
 // device allocations of the handle's own, batches of ranges out (part of the C ABI layer of libnolzss_hip.so,
 // include/nolzss_hip.h, nolzss_rlz_archive_*; the kernels: rlz_archive.hip; DESIGN.md 5, "Relative-LZ archive: ranges
-// from resident records").
-#include "rlz_archive.hpp"
+// from resident records").  Export hands the host form back; open_index and append_index live in rlz_index_api.hip,
+// next to the match they run ("Relative-LZ archive: batches appended from the index").
+#include "rlz_handles.hpp"
 
 using namespace nolzss;
 using namespace nolzss::api;
 
-// The handle: the block, the packed records and the position sample in device allocations of its own (not arena
-// memory, which the next call on the device recycles).  The per-target table stays on the host: it is read when the
-// ranges of a call are turned into decoded positions and prefix sums, which is all the kernel sees of the targets.
-struct nolzss_rlz_archive {
-    int device = 0;
-    uint64_t z = 0, block_len = 0, n_literals = 0, decoded = 0;
-    std::vector<uint64_t> lengths;  // k
-    std::vector<uint64_t> bases;    // k + 1: decoded position of each target, then the decoded length
-    uint8_t *d_block = nullptr;
-    ArchiveRec *d_recs = nullptr;
-    uint32_t *d_sample = nullptr;
-    size_t device_bytes = 0;
-    ~nolzss_rlz_archive() {  // (the calling thread's current device stays what it was)
-        if (!d_block && !d_recs && !d_sample) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        if (d_block) (void)hipFree(d_block);
-        if (d_recs) (void)hipFree(d_recs);
-        if (d_sample) (void)hipFree(d_sample);
-        if (known && current != device) (void)hipSetDevice(current);
-    }
-};
-
 namespace {
-
-// a Session makes the handle's device current: this puts the caller's back
-struct DeviceRestore {
-    int current = -1;
-    bool known;
-    DeviceRestore() : known(hipGetDevice(&current) == hipSuccess) {}
-    ~DeviceRestore() {
-        if (known) (void)hipSetDevice(current);
-    }
-};
 
 std::string literal_count_message(const nolzss_factor *f, size_t z, size_t n_literals) {
     size_t seen = 0;
@@ -89,6 +56,7 @@ void open_records(const uint8_t *block, size_t block_len, const nolzss_factor *r
     if (z == 0) {  // an empty archive: no device
         if (n_literals) throw std::invalid_argument(literal_count_message(records, 0, n_literals));
         if (sum || overflow) throw std::invalid_argument(length_sum_message(0, sum, 0));
+        h->h_block.assign(block, block + block_len);  // (export hands it back; device_bytes stays 0)
         *out = h.release();
         return;
     }
@@ -134,6 +102,8 @@ void open_records(const uint8_t *block, size_t block_len, const nolzss_factor *r
     h->d_recs = static_cast<ArchiveRec *>(device_alloc(ctx, sizeof(ArchiveRec) * z));
     h->d_sample = static_cast<uint32_t *>(device_alloc(ctx, sizeof(uint32_t) * samples));
     h->device_bytes = block_bytes + sizeof(ArchiveRec) * z + sizeof(uint32_t) * samples;
+    h->cap_recs = z;
+    h->cap_samples = samples;
     if (block_len) upload_bytes(ctx, h->d_block, block, block_len);
     archive_pack(ctx, d_raw, z, block_len, n, lit_flags, d_lit, h->d_recs, h->d_sample);
     HIP_CHECK(hipStreamSynchronize(s));
@@ -244,6 +214,56 @@ void extract(const nolzss_rlz_archive &h, const nolzss_rlz_range *ranges, size_t
     *total_out = total;
 }
 
+// The host form back: block, 24-byte records and the literal stream, each downloaded once.
+void export_archive(const nolzss_rlz_archive &h, uint8_t **block, size_t *block_len, nolzss_factor **records, size_t *z,
+                    uint8_t **literals, size_t *n_literals) {
+    const size_t zz = (size_t)h.z, nlit = (size_t)h.n_literals, blen = (size_t)h.block_len;
+    std::unique_ptr<uint8_t, FreeBlock> h_blk(static_cast<uint8_t *>(std::malloc(blen ? blen : 1)));
+    std::unique_ptr<uint8_t, FreeBlock> h_lit(static_cast<uint8_t *>(std::malloc(nlit ? nlit : 1)));
+    FactorBlock h_recs(static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * (zz ? zz : 1))));
+    if (!h_blk || !h_lit || !h_recs) throw std::bad_alloc();
+    if (!h.d_block) {  // no records and no device memory: the host copy of the block
+        if (blen) std::memcpy(h_blk.get(), h.h_block.data(), blen);
+    } else {
+        DeviceRestore restore;
+        Session ses(h.device, nullptr);
+        Context &ctx = ses.ctx();
+        hipStream_t s = ctx.stream;
+        {  // (the scope closes before the stream is waited for and the profiler collected)
+            ProfScope whole(ctx.profiler(), "rlz_archive_export_all", s);
+            const size_t chunk = zz < kRecordChunk ? zz : kRecordChunk;
+            reserve_arena_for(ctx, 0, sizeof(uint32_t) * zz + nlit + sizeof(Rec) * chunk + (size_t(4) << 20));
+            if (blen) {
+                ProfScope ps(ctx.profiler(), "block_d2h", s, (double)blen);
+                download_bytes(ctx, h_blk.get(), h.d_block, blen);
+            }
+            if (zz) {
+                uint32_t *d_index = ctx.arena.alloc<uint32_t>(zz);
+                uint8_t *d_lit = ctx.arena.alloc<uint8_t>(nlit ? nlit : 1);
+                Rec *d_out = ctx.arena.alloc<Rec>(chunk);
+                const uint64_t found = archive_literal_index(ctx, h.d_recs, zz, d_index);
+                if (found != h.n_literals)
+                    throw HipError("rlz archive: the resident records do not hold the literals the handle counts");
+                for (size_t c0 = 0; c0 < zz; c0 += chunk) {
+                    const size_t cnt = zz - c0 < chunk ? zz - c0 : chunk;
+                    archive_export_records(ctx, h.d_recs, c0, cnt, h.block_len, d_index, d_out, d_lit);
+                    ProfScope ps(ctx.profiler(), "factors_d2h", s, (double)(sizeof(Rec) * cnt));
+                    download_bytes(ctx, h_recs.get() + c0, d_out, sizeof(Rec) * cnt);  // (waits: d_out is free again)
+                }
+                if (nlit) download_bytes(ctx, h_lit.get(), d_lit, nlit);
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+        ctx.prof.collect();
+    }
+    *block = h_blk.release();
+    *block_len = blen;
+    *records = h_recs.release();
+    *z = zz;
+    *literals = h_lit.release();
+    *n_literals = nlit;
+}
+
 }  // namespace
 
 extern "C" {
@@ -288,6 +308,20 @@ int nolzss_rlz_archive_extract_device(const nolzss_rlz_archive *h, const nolzss_
         *total = 0;
         if (!h) throw std::invalid_argument("handle is null");
         extract(*h, ranges, q, true, static_cast<uint8_t *>(d_out), d_out_capacity, stream, nullptr, nullptr, total);
+    });
+}
+
+int nolzss_rlz_archive_export(const nolzss_rlz_archive *h, uint8_t **block, size_t *block_len, nolzss_factor **records,
+                              size_t *z, uint8_t **literals, size_t *n_literals) {
+    return guarded([&] {
+        if (!block || !block_len || !records || !z || !literals || !n_literals)
+            throw std::invalid_argument("output pointer is null");
+        *block = nullptr;
+        *records = nullptr;
+        *literals = nullptr;
+        *block_len = *z = *n_literals = 0;
+        if (!h) throw std::invalid_argument("handle is null");
+        export_archive(*h, block, block_len, records, z, literals, n_literals);
     });
 }
 

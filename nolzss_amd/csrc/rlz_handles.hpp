@@ -1,0 +1,72 @@
+// rlz_handles.hpp -- the two resident relative-LZ handles, shared by the translation units of their entry points: an
+// append matches a batch against the index (rlz_index_api.hip) and writes into the archive (rlz_archive_api.hip owns
+// open_records, extract and export).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index".
+#pragma once
+#include "api_internal.hpp"
+#include "rlz_archive.hpp"
+#include "rlz_index.hpp"
+
+// The index handle: everything a match reads, in ONE device allocation (not arena memory, which the next call on the
+// device recycles); the view's pointers lead into it.  A match changes nothing here.
+struct nolzss_rlz_index {
+    int device = 0;
+    uint64_t m = 0;
+    uint64_t serial = 0;  // process-wide, given at open: an archive opened over this index remembers it
+    void *d_base = nullptr;
+    size_t device_bytes = 0;
+    nolzss::RlzIndexView view;
+    ~nolzss_rlz_index() {  // (the calling thread's current device stays what it was)
+        if (!d_base) return;
+        int current = -1;
+        const bool known = hipGetDevice(&current) == hipSuccess;
+        (void)hipSetDevice(device);
+        (void)hipFree(d_base);
+        if (known && current != device) (void)hipSetDevice(current);
+    }
+};
+
+// The archive handle: the block, the packed records and the position sample in device allocations of its own (not arena
+// memory, which the next call on the device recycles).  The per-target table stays on the host: it is read when the
+// ranges of a call are turned into decoded positions and prefix sums, which is all the kernel sees of the targets.
+struct nolzss_rlz_archive {
+    int device = 0;
+    uint64_t z = 0, block_len = 0, n_literals = 0, decoded = 0;
+    std::vector<uint64_t> lengths;  // k
+    std::vector<uint64_t> bases;    // k + 1: decoded position of each target, then the decoded length
+    uint8_t *d_block = nullptr;
+    nolzss::ArchiveRec *d_recs = nullptr;
+    uint32_t *d_sample = nullptr;
+    size_t device_bytes = 0;
+    std::vector<uint8_t> h_block;   // an archive without records holds no device memory: its block, for export
+    // an archive opened over an index (index_serial != 0) grows by appends: what its two arrays can hold
+    uint64_t index_serial = 0;
+    size_t cap_recs = 0, cap_samples = 0;
+    ~nolzss_rlz_archive() {  // (the calling thread's current device stays what it was)
+        if (!d_block && !d_recs && !d_sample) return;
+        int current = -1;
+        const bool known = hipGetDevice(&current) == hipSuccess;
+        (void)hipSetDevice(device);
+        if (d_block) (void)hipFree(d_block);
+        if (d_recs) (void)hipFree(d_recs);
+        if (d_sample) (void)hipFree(d_sample);
+        if (known && current != device) (void)hipSetDevice(current);
+    }
+};
+
+namespace nolzss {
+namespace api {
+
+// a Session makes the handle's device current: this puts the caller's back
+struct DeviceRestore {
+    int current = -1;
+    bool known;
+    DeviceRestore() : known(hipGetDevice(&current) == hipSuccess) {}
+    ~DeviceRestore() {
+        if (known) (void)hipSetDevice(current);
+    }
+};
+
+constexpr size_t kRecordChunk = size_t(1) << 22;  // records per look-up chunk: 96 MiB of arena whatever the batch holds
+
+}  // namespace api
+}  // namespace nolzss

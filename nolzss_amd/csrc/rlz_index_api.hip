@@ -1,48 +1,20 @@
 // rlz_index_api.hip -- the relative-LZ index handle and its entry points: the references in, their suffix structures
 // kept in one device allocation of the handle's own, target batches matched against them (part of the C ABI layer of
 // libnolzss_hip.so, include/nolzss_hip.h, nolzss_rlz_index_*; the kernels: rlz_index.hip; DESIGN.md 5, "Relative-LZ
-// index: targets matched against a resident reference").
-#include "api_internal.hpp"
-#include "rlz_index.hpp"
+// index: targets matched against a resident reference").  Also nolzss_rlz_archive_open_index / _append_index: the
+// archive opened over an index and the batches appended to it on the device, which run the same match (DESIGN.md 5,
+// "Relative-LZ archive: batches appended from the index").
+#include "rlz_handles.hpp"
 
 using namespace nolzss;
 using namespace nolzss::api;
 
-// The handle: everything a match reads, in ONE device allocation (not arena memory, which the next call on the device
-// recycles); the view's pointers lead into it.  A match changes nothing here.
-struct nolzss_rlz_index {
-    int device = 0;
-    uint64_t m = 0;
-    void *d_base = nullptr;
-    size_t device_bytes = 0;
-    RlzIndexView view;
-    ~nolzss_rlz_index() {  // (the calling thread's current device stays what it was)
-        if (!d_base) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        (void)hipFree(d_base);
-        if (known && current != device) (void)hipSetDevice(current);
-    }
-};
-
 namespace {
-
-// a Session makes the handle's device current: this puts the caller's back
-struct DeviceRestore {
-    int current = -1;
-    bool known;
-    DeviceRestore() : known(hipGetDevice(&current) == hipSuccess) {}
-    ~DeviceRestore() {
-        if (known) (void)hipSetDevice(current);
-    }
-};
 
 // device memory per batch position: packed text 1/4, code 4, rank 4, the chain's exits, bitmaps and node lists (12 on
 // ordinary batches, 24 when every position is a node), the factor starts 4 -- not the 52 of a suffix sort
 constexpr size_t kBatchBytesPerPosition = 36;
-constexpr size_t kRecordChunk = size_t(1) << 22;  // records per download: 96 MiB of arena whatever the batch holds
-constexpr uint8_t kSeparator = 1;                 // between the targets of a batch: any byte but A, C, G, T
+constexpr uint8_t kSeparator = 1;  // between the targets of a batch: any byte but A, C, G, T
 
 uint32_t choose_prefix(size_t index_length) {  // clamp(floor(log4 |X|) - 1, 4, 12)
     int l = 0;
@@ -61,9 +33,11 @@ void open_index(const char *const *refs, const size_t *ref_lens, size_t m, bool 
     const size_t total = p.S.size();
     const uint32_t P = prefix_syms ? prefix_syms : choose_prefix(total);
 
+    static std::atomic<uint64_t> serials{0};
     std::unique_ptr<nolzss_rlz_index> h(new nolzss_rlz_index);
     h->device = device;
     h->m = m;
+    h->serial = ++serials;  // (never 0: an archive with serial 0 was not opened over an index)
     DeviceRestore restore;
     Session ses(device, nullptr);
     Context &ctx = ses.ctx();
@@ -130,6 +104,29 @@ struct MatchOut {
     FactorBlock block;
 };
 
+// What every use of a match starts with: the batch up, packed with the target ends as terminators, and searched.
+struct Searched {
+    uint8_t *d_T;              // the batch bytes (upper case, separators)
+    uint32_t *d_len, *d_rank;  // per position: the longest match and a rank that attains it
+};
+
+Searched search_batch(Context &ctx, const nolzss_rlz_index &h, const Batch &b) {
+    const size_t n = b.tcat.size();
+    Searched m;
+    m.d_T = ctx.arena.alloc<uint8_t>(n);
+    {
+        ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream, (double)n);
+        upload_bytes(ctx, m.d_T, b.tcat.data(), n);
+    }
+    PackedText batch;
+    if (!pack_independent_text(ctx, m.d_T, n, b.separators, batch))
+        throw std::runtime_error("rlz index: the batch holds bytes that are neither bases nor its separators");
+    m.d_len = ctx.arena.alloc<uint32_t>(n);
+    m.d_rank = ctx.arena.alloc<uint32_t>(n);
+    rlz_index_search(ctx, h.view, batch, m.d_len, m.d_rank);
+    return m;
+}
+
 // One batch against the handle (k >= 1).  h_codes: the codes of every position and nothing else.  Otherwise the chain;
 // want_factors: every record comes down (the separator literals with them) and is split by searching the ascending
 // starts, else the starts are counted per target on the device and only the k counts cross PCIe.
@@ -142,16 +139,8 @@ void match_batch(const nolzss_rlz_index &h, const Batch &b, const size_t *target
     Context &ctx = ses.ctx();
     hipStream_t s = ctx.stream;
     reserve_arena_for(ctx, 0, kBatchBytesPerPosition * n + 12 * k + sizeof(IndexRec) * kRecordChunk + (size_t(4) << 20));
-    uint8_t *d_T = ctx.arena.alloc<uint8_t>(n);
-    {
-        ProfScope ps(ctx.profiler(), "text_h2d", s, (double)n);
-        upload_bytes(ctx, d_T, b.tcat.data(), n);
-    }
-    PackedText batch;
-    if (!pack_independent_text(ctx, d_T, n, b.separators, batch))
-        throw std::runtime_error("rlz index: the batch holds bytes that are neither bases nor its separators");
-    uint32_t *d_len = ctx.arena.alloc<uint32_t>(n), *d_rank = ctx.arena.alloc<uint32_t>(n);
-    rlz_index_search(ctx, h.view, batch, d_len, d_rank);
+    const Searched m = search_batch(ctx, h, b);
+    uint32_t *d_len = m.d_len, *d_rank = m.d_rank;
     if (h_codes) {
         rlz_index_strands(ctx, h.view, (uint32_t)n, d_len, d_rank);
         download_bytes(ctx, h_codes, d_len, n * sizeof(uint32_t));
@@ -197,6 +186,186 @@ void match_batch(const nolzss_rlz_index &h, const Batch &b, const size_t *target
     }
     HIP_CHECK(hipStreamSynchronize(s));
     ctx.prof.collect();
+}
+
+// ---- the archive over an index: open, and batches appended on the device -------------------------------------------
+void archive_open_index(const nolzss_rlz_index &ix, nolzss_rlz_archive **out) {
+    if (!out) throw std::invalid_argument("output pointer is null");
+    *out = nullptr;
+    std::unique_ptr<nolzss_rlz_archive> h(new nolzss_rlz_archive);
+    h->device = ix.device;
+    h->block_len = ix.view.B;
+    h->index_serial = ix.serial;
+    h->bases.assign(1, 0);
+    DeviceRestore restore;
+    Session ses(ix.device, nullptr);
+    Context &ctx = ses.ctx();
+    {
+        ProfScope whole(ctx.profiler(), "rlz_archive_open_index", ctx.stream);
+        const size_t block_bytes = ix.view.B ? ix.view.B : 1;
+        h->d_block = static_cast<uint8_t *>(device_alloc(ctx, block_bytes));
+        h->device_bytes = block_bytes;
+        archive_unpack_block(ctx, ix.view.text, ix.view.B, h->d_block);
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));
+    ctx.prof.collect();
+    *out = h.release();
+}
+
+size_t append_chunk() {  // NOLZSS_RLZ_APPEND_CHUNK: records per look-up chunk of an append (a test knob)
+    const char *e = std::getenv("NOLZSS_RLZ_APPEND_CHUNK");
+    if (!e || !*e) return kRecordChunk;
+    char *end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    if (*end || v == 0) return kRecordChunk;
+    return v < kRecordChunk ? (size_t)v : kRecordChunk;
+}
+
+// a device array that replaces one of the handle's: freed on the way out unless it was swapped in (then the old one is)
+struct Fresh {
+    void *p = nullptr;
+    ~Fresh() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+void fill_append_info(const nolzss_rlz_archive &a, nolzss_rlz_archive_append_info *info, uint64_t targets, uint64_t records,
+                      uint64_t literals, uint64_t bases, bool reallocated) {
+    if (!info) return;
+    std::memset(info, 0, sizeof *info);
+    info->targets_added = targets;
+    info->records_added = records;
+    info->literals_added = literals;
+    info->bases_added = bases;
+    info->num_targets = a.lengths.size();
+    info->z = a.z;
+    info->total_length = a.decoded;
+    info->capacity_records = a.cap_recs;
+    info->device_bytes = a.device_bytes;
+    info->reallocated = reallocated ? 1 : 0;
+}
+
+void archive_append(nolzss_rlz_archive &a, const nolzss_rlz_index &ix, const char *const *targets, const size_t *target_lens,
+                    size_t k, nolzss_rlz_archive_append_info *info) {
+    if (!a.index_serial)
+        throw std::invalid_argument("rlz archive: append takes an archive opened by nolzss_rlz_archive_open_index");
+    if (a.index_serial != ix.serial || a.device != ix.device)
+        throw std::invalid_argument("rlz archive: the archive is bound to another index (it was opened over index " +
+                                    std::to_string(a.index_serial) + " on device " + std::to_string(a.device) +
+                                    ", this is index " + std::to_string(ix.serial) + " on device " + std::to_string(ix.device) + ")");
+    if (k && targets && target_lens) {  // the lengths alone decide: no target byte is read before this
+        uint64_t sum = 0;
+        bool overflow = false;
+        for (size_t j = 0; j < k; ++j) {
+            overflow |= sum + target_lens[j] < sum;
+            sum += target_lens[j];
+        }
+        if (!overflow && sum <= kMaxText && a.decoded + sum > kMaxText)
+            throw std::invalid_argument("rlz archive: decoded length: the archive holds " + std::to_string(a.decoded) +
+                                        " bytes and the batch " + std::to_string(sum) + ", together beyond the " +
+                                        std::to_string(kMaxText) + " positions the 32-bit device pipeline takes");
+    }
+    Batch b;
+    prepare_batch(ix, targets, target_lens, k, b);
+    if (k == 0) {
+        fill_append_info(a, info, 0, 0, 0, 0, false);
+        return;
+    }
+    const size_t n = b.tcat.size();
+    const uint64_t bases = n - k, base = (uint64_t)ix.view.B + 1;
+    a.lengths.reserve(a.lengths.size() + k);  // (the commit below cannot fail)
+    a.bases.reserve(a.bases.size() + k);
+    const size_t chunk_max = append_chunk();
+
+    DeviceRestore restore;
+    Fresh fresh_recs, fresh_sample;  // (freed while the handle's device is still current)
+    ArchiveRec *recs = a.d_recs;
+    uint32_t *sample = a.d_sample;
+    size_t cap_recs = a.cap_recs, cap_samples = a.cap_samples;
+    uint64_t z_new = 0, added = 0, lit_added = 0;
+    const uint64_t decoded_new = a.decoded + bases;
+    const size_t samples_old = archive_samples((size_t)a.decoded), samples_new = archive_samples((size_t)decoded_new);
+
+    Session ses(ix.device, nullptr);
+    Context &ctx = ses.ctx();
+    hipStream_t s = ctx.stream;
+    std::vector<uint32_t> lit_counts;
+    try {
+        ProfScope whole(ctx.profiler(), "rlz_archive_append", s);
+        reserve_arena_for(ctx, 0, (kBatchBytesPerPosition + 2) * n + 16 * k + sizeof(IndexRec) * (chunk_max < n ? chunk_max : n) +
+                                      (size_t(4) << 20));
+        const Searched m = search_batch(ctx, ix, b);
+        const uint8_t *d_T = m.d_T;
+        uint32_t *d_len = m.d_len, *d_rank = m.d_rank;
+        const Chain chain = mark_chain(ctx, (uint32_t)n, 0u, LstarCodes::of(d_len));
+        const uint32_t zb = chain.z;
+        const uint32_t *d_fpos = chain_starts(ctx, chain);
+        if (zb < k) throw HipError("rlz archive: the chain of a batch holds fewer factor starts than separators");
+        added = zb - k;  // every separator is a factor start of its own
+        z_new = a.z + added;
+        if (z_new > 0xffffffffull)
+            throw std::invalid_argument("rlz archive: z: the archive holds " + std::to_string(a.z) + " records and the batch " +
+                                        std::to_string(added) + ", the position sample indexes records in 32 bits, 2^32 or "
+                                        "more are refused");
+        // growth: max(needed, 2 x current), the old contents copied on the stream; the old array is freed at the commit
+        if (z_new > cap_recs) {
+            cap_recs = std::max<size_t>((size_t)z_new, 2 * cap_recs);
+            fresh_recs.p = device_alloc(ctx, sizeof(ArchiveRec) * cap_recs);
+            recs = static_cast<ArchiveRec *>(fresh_recs.p);
+            if (a.z) HIP_CHECK(hipMemcpyAsync(recs, a.d_recs, sizeof(ArchiveRec) * a.z, hipMemcpyDeviceToDevice, s));
+        }
+        if (samples_new > cap_samples) {
+            cap_samples = std::max<size_t>(samples_new, 2 * cap_samples);
+            fresh_sample.p = device_alloc(ctx, sizeof(uint32_t) * cap_samples);
+            sample = static_cast<uint32_t *>(fresh_sample.p);
+            if (samples_old)
+                HIP_CHECK(hipMemcpyAsync(sample, a.d_sample, sizeof(uint32_t) * samples_old, hipMemcpyDeviceToDevice, s));
+        }
+        uint32_t *d_seps = ctx.arena.alloc<uint32_t>(k);
+        upload_bytes(ctx, d_seps, b.separators.data(), sizeof(uint32_t) * k);
+        const AppendBatch ab{d_T, d_seps, (uint32_t)n, (uint32_t)k, (uint32_t)a.z, (uint32_t)a.decoded, (uint32_t)z_new};
+        const size_t chunk = zb < chunk_max ? zb : chunk_max;
+        IndexRec *d_chunk = ctx.arena.alloc<IndexRec>(chunk ? chunk : 1);
+        // one word per wavefront of the conversion launches: the literals it wrote (at most n / 64 + 4 per chunk words)
+        lit_counts.resize(chunk ? (zb / chunk) * archive_append_counts(chunk) + archive_append_counts(zb % chunk) : 0);
+        uint32_t *d_counts = ctx.arena.alloc<uint32_t>(lit_counts.size() ? lit_counts.size() : 1);
+        size_t counts_at = 0;
+        for (size_t c0 = 0; c0 < zb; c0 += chunk) {  // (one stream: a chunk's conversion has read d_chunk before the next look-up)
+            const size_t cnt = zb - c0 < chunk ? zb - c0 : chunk;
+            rlz_index_records(ctx, ix.view, d_fpos + c0, (uint32_t)cnt, d_len, d_rank, d_chunk);
+            archive_append_records(ctx, d_chunk, d_fpos + c0, (uint32_t)c0, (uint32_t)cnt, base, ab, recs, d_counts + counts_at);
+            counts_at += archive_append_counts(cnt);
+        }
+        archive_extend_sample(ctx, recs, (uint32_t)a.z, (uint32_t)z_new, (uint32_t)samples_old, (uint32_t)samples_new, sample);
+        if (counts_at != lit_counts.size()) throw HipError("rlz archive: the literal counts of an append are laid out wrongly");
+        if (counts_at)
+            HIP_CHECK(hipMemcpyAsync(lit_counts.data(), d_counts, sizeof(uint32_t) * counts_at, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        for (uint32_t c : lit_counts) lit_added += c;
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // nothing still reads the batch or writes the fresh arrays when they go
+        throw;
+    }
+    // (the whole scope recorded its stop event as the block above closed, behind that wait: collect() drops a scope whose
+    // events have not completed)
+    HIP_CHECK(hipStreamSynchronize(s));
+    ctx.prof.collect();
+    // the commit: host state only, after the device work has finished without error; the stream has drained
+    const bool moved = fresh_recs.p || fresh_sample.p;
+    if (fresh_recs.p) std::swap(fresh_recs.p, reinterpret_cast<void *&>(a.d_recs));
+    if (fresh_sample.p) std::swap(fresh_sample.p, reinterpret_cast<void *&>(a.d_sample));
+    a.cap_recs = cap_recs;
+    a.cap_samples = cap_samples;
+    a.z = z_new;
+    a.n_literals += lit_added;
+    for (size_t j = 0; j < k; ++j) {
+        a.lengths.push_back(target_lens[j]);
+        a.decoded += target_lens[j];
+        a.bases.push_back(a.decoded);
+    }
+    a.device_bytes = (a.block_len ? a.block_len : 1) + sizeof(ArchiveRec) * cap_recs + sizeof(uint32_t) * cap_samples;
+    fill_append_info(a, info, k, added, lit_added, bases, moved);
 }
 
 template <typename T> T *calloc_array(size_t count) {
@@ -296,6 +465,23 @@ int nolzss_rlz_index_codes(const nolzss_rlz_index *h, const char *const *targets
         if (!code) throw std::invalid_argument("output pointer is null");
         MatchOut run;
         match_batch(*h, b, target_lens, k, false, code, run);
+    });
+}
+
+int nolzss_rlz_archive_open_index(const nolzss_rlz_index *ix, nolzss_rlz_archive **h) {
+    return guarded([&] {
+        if (h) *h = nullptr;
+        if (!ix) throw std::invalid_argument("index handle is null");
+        archive_open_index(*ix, h);
+    });
+}
+
+int nolzss_rlz_archive_append_index(nolzss_rlz_archive *h, const nolzss_rlz_index *ix, const char *const *targets,
+                                    const size_t *target_lens, size_t k, nolzss_rlz_archive_append_info *info) {
+    return guarded([&] {
+        if (info) std::memset(info, 0, sizeof *info);
+        if (!h || !ix) throw std::invalid_argument("archive or index handle is null");
+        archive_append(*h, *ix, targets, target_lens, k, info);
     });
 }
 

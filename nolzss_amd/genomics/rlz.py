@@ -230,6 +230,7 @@ class RlzArchive:
     ValueError."""
 
     def __init__(self, block, records, literals, target_lengths, ids=None, device=None):
+        self._bound = None  # (the RlzIndex of an archive made by from_index)
         self._arrays = archive_arrays(block, records, literals, target_lengths, ids)
         self.ids = None if ids is None else [i if isinstance(i, str) else bytes(i).decode("utf-8") for i in ids]
         self._index = target_index_map(self.ids)
@@ -260,9 +261,50 @@ class RlzArchive:
         block, records, literals, lengths, ids = load_archive_arrays(path)
         return cls(block, records, literals, lengths, ids=ids, device=device)
 
+    @classmethod
+    def from_index(cls, index, ids=None):
+        """An empty archive bound to an RlzIndex, on its device: append() matches batches against the index and keeps
+        their records on the GPU ("Relative-LZ archive: batches appended from the index").  ids=[]: the
+        archive carries ids and every append must name its targets; None: it does not."""
+        if ids is not None and len(ids):
+            raise ValueError("from_index opens an empty archive: ids must be None or empty, append() takes the ids")
+        self = cls.__new__(cls)
+        self._handle, self._arrays, self._bound = None, None, index
+        self.ids = None if ids is None else []
+        self._index = {}
+        self._handle = _native.RlzArchiveHandle.open_index(index._live())
+        return self
+
+    def append(self, targets, ids=None, batch_bases=None):
+        """Match `targets` against the index of from_index and append them, batch by batch (_plan_append_batches) ->
+        the list of the per-batch info dicts (targets_added, records_added, literals_added, bases_added, num_targets, z,
+        total_length, capacity_records, device_bytes, reallocated).  ids: one per target exactly when the archive
+        carries ids, distinct from each other and from those present.  ValueError before any device work otherwise.  If
+        a later batch fails, the batches before it stay appended."""
+        h = self._live()
+        if self._arrays is not None:
+            raise ValueError("append needs an archive made by RlzArchive.from_index: this one was built from host records")
+        targets = list(targets)
+        names = _check_append_ids(self.ids, ids, len(targets))
+        ih = self._bound._live()
+        plan = _plan_append_batches([len(t) for t in targets], h.info["block_length"], h.info["total_length"], MAX_TEXT,
+                                    batch_bases)
+        out = []
+        for lo, hi in plan:
+            out.append(h.append_index(ih, targets[lo:hi]))
+            if names is not None:
+                for name in names[lo:hi]:
+                    self._index[name] = len(self.ids)
+                    self.ids.append(name)
+        return out
+
     def save(self, path):
         """One .npz holding block, records, literals, target lengths and ids, raw."""
-        self._live()
+        h = self._live()
+        if self._arrays is None:  # index-built: the host form comes back from the device
+            block, records, literals = h.export()
+            save_archive_arrays(path, archive_arrays(block, records, literals, h.target_lengths, self.ids))
+            return
         save_archive_arrays(path, self._arrays)
 
     def _live(self):
@@ -270,12 +312,15 @@ class RlzArchive:
             raise ValueError("the archive is closed")
         return self._handle
 
+    def _lengths(self):
+        return self._live().target_lengths if self._arrays is None else self._arrays["target_lengths"]
+
     def __len__(self):
-        return len(self._arrays["target_lengths"])
+        return len(self._lengths())
 
     @property
     def target_lengths(self):
-        return [int(x) for x in self._arrays["target_lengths"]]
+        return [int(x) for x in self._lengths()]
 
     @property
     def info(self):
@@ -307,7 +352,7 @@ class RlzArchive:
 
     def target(self, j) -> bytes:
         j = resolve_target(j, self._index, len(self))
-        return self.fetch(j, 0, int(self._arrays["target_lengths"][j]))
+        return self.fetch(j, 0, int(self._lengths()[j]))
 
     def close(self) -> None:
         h, self._handle = getattr(self, "_handle", None), None
@@ -347,6 +392,50 @@ def plan_index_batches(lengths, block_length, limit=MAX_TEXT, batch_bases=None):
     if len(lengths) > lo:
         out.append((lo, len(lengths)))
     return out
+
+
+def _plan_append_batches(lengths, block_length, decoded, limit=MAX_TEXT, batch_bases=None):
+    """Target lengths -> [(lo, hi)] index ranges of the batches an archive that holds `decoded` bytes takes, greedy in
+    input order: a batch closes when the next target would pass the length rule block_length + 1 + sum(len) + k <=
+    limit, batch_bases bases, or the room left under the limit, decoded + (everything planned so far) + n <= limit.  A
+    target that breaks a bound alone still gets a batch of its own (the library refuses it).  Pure Python, no device."""
+    out, lo, bases, room = [], 0, 0, limit - decoded
+    for j, n in enumerate(lengths):
+        n = operator.index(n)
+        k = j - lo
+        over = (block_length + 1 + bases + n + k + 1 > limit or (batch_bases is not None and bases + n > batch_bases)
+                or bases + n > room)
+        if k and over:
+            out.append((lo, j))
+            room -= bases
+            lo, bases = j, 0
+        bases += n
+    if len(lengths) > lo:
+        out.append((lo, len(lengths)))
+    return out
+
+
+def _check_append_ids(present, ids, count):
+    """The id rules of RlzArchive.append: `present` is the archive's id list (None: it carries none), ids what the call
+    got for its `count` targets -> the new ids as str (None without ids).  ValueError otherwise.  Pure Python."""
+    if present is None:
+        if ids is not None:
+            raise ValueError("this archive carries no ids: append takes none")
+        return None
+    if ids is None:
+        raise ValueError("this archive carries ids: append needs one per target")
+    raw = [i.encode("utf-8") if isinstance(i, str) else bytes(i) for i in ids]
+    if len(raw) != count:
+        raise ValueError(f"inconsistent sizes: {len(raw)} ids for {count} targets")
+    if any(name.endswith(b"\0") for name in raw):
+        raise ValueError("an id must not end in a NUL byte")
+    names = [name.decode("utf-8") for name in raw]
+    if len(set(names)) != len(names):
+        raise ValueError("ids must be distinct")
+    taken = set(present) & set(names)
+    if taken:
+        raise ValueError(f"ids must be distinct: {sorted(taken)[0]!r} is in the archive already")
+    return names
 
 
 class RlzIndex:
@@ -422,6 +511,17 @@ class RlzIndex:
         targets = list(targets)
         factors = self.factorize(targets)
         return RlzArchive.from_factors(self._reference, factors, rlz_literals(targets, factors), ids=ids)
+
+    def archive_on_device(self, targets, ids=None, batch_bases=None):
+        """The same archive with the records kept on the GPU: RlzArchive.from_index(self) and one append of these
+        targets (several batches for a long list); the archive takes further appends."""
+        arc = RlzArchive.from_index(self, ids=None if ids is None else [])
+        try:
+            arc.append(targets, ids=ids, batch_bases=batch_bases)
+        except Exception:
+            arc.close()
+            raise
+        return arc
 
     def close(self) -> None:
         h, self._handle = getattr(self, "_handle", None), None
