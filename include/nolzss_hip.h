@@ -655,6 +655,44 @@ int nolzss_rlz_index_factorize(const nolzss_rlz_index *h, const char *const *tar
  * entries, caller-allocated.  Only target positions are specified -- the counterpart of nolzss_debug_rlz_codes. */
 int nolzss_rlz_index_codes(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens,
                            size_t k, uint32_t *code);
+/* Pattern count and locate: where a sequence occurs in the reference, and how often ("Relative-LZ index:
+ * pattern count and locate").  Nothing is added to the handle; a batch of q patterns goes up as a target batch does.
+ *   Patterns: nucleotide strings, case-insensitive, validated and upper-cased as targets are.
+ *   Occurrences: a forward occurrence of pattern P at `position` means Rblk[position .. position + |P|) equals P and lies
+ *     inside one reference record; a reverse-strand occurrence at `position` means that stretch equals rc(P), and is only
+ *     reported by an index opened with reverse complement.  A pattern that is its own reverse complement is counted on
+ *     both strands.  An empty pattern has count 0 and no hits; it is not an error.
+ *   count: counts[j] = the occurrences of pattern j on both strands together (q entries, the caller's).
+ *   locate: counts as above.  Every occurrence of a pattern with counts[j] <= max_hits is returned as (position, record,
+ *     is_rc): position is the coordinate in Rblk, record the 0-based reference record.  max_hits == 0 means no cap.  A
+ *     pattern with more than max_hits occurrences reports its count and NO hits, so which hits come back never depends
+ *     on how tied suffixes are ordered.  Layout: hit_offsets has q + 1 entries (the caller's), pattern j owns hits
+ *     [hit_offsets[j], hit_offsets[j + 1]), and inside a pattern the hits ascend by (position, is_rc), forward first;
+ *     they are sorted on the device.  *hits: malloc'ed, nolzss_free; NULL when *num_hits = hit_offsets[q] is 0.
+ *   Refusals before any device work: a null handle, array or output pointer: NOLZSS_ERR_INVALID_ARGUMENT; a locate of
+ *     2^31 or more patterns in one batch (the sort key of a hit keeps its pattern in 31 bits):
+ *     NOLZSS_ERR_INVALID_ARGUMENT; sum(len) + q beyond the 32-bit pipeline: NOLZSS_ERR_INVALID_ARGUMENT; "Invalid
+ *     nucleotide 'x' found in pattern j" (j 0-based in this batch, the first such pattern): NOLZSS_ERR_RUNTIME.  The
+ *     lengths alone decide the length rule and no pattern byte is read before it holds, so a batch that breaks both it
+ *     and the nucleotide rule reports the length.  q == 0 succeeds without touching the device.
+ *   Refusal of the total: when the hits to report number more than the 32-bit pipeline takes, the call returns
+ *     NOLZSS_ERR_INVALID_ARGUMENT naming the total and pointing at max_hits; it is decided once the counts are known
+ *     and before anything is expanded (counts and hit_offsets are then filled, *hits is NULL).
+ *   An arena out-of-memory leaves the handle untouched, as a match does.  Several threads may query one handle; the
+ *     calling thread's current device is left as it was.  NOLZSS_RLZ_LOCATE_CHUNK (tests): hit records per download. */
+typedef struct nolzss_rlz_hit {
+    uint64_t position;
+    uint32_t record;
+    uint32_t is_rc;
+} nolzss_rlz_hit;
+int nolzss_rlz_index_count(const nolzss_rlz_index *h, const char *const *patterns, const size_t *pattern_lens, size_t q,
+                           uint64_t *counts);
+int nolzss_rlz_index_locate(const nolzss_rlz_index *h, const char *const *patterns, const size_t *pattern_lens, size_t q,
+                            uint64_t max_hits, uint64_t *counts, uint64_t *hit_offsets, nolzss_rlz_hit **hits,
+                            size_t *num_hits);
+/* Host only (tests): the bit offsets of the 8-bit digits the sort of a locate's hits runs for a block of block_length
+ * bases and q patterns, least significant first; shifts: 8 entries, the caller's. */
+int nolzss_debug_rlz_locate_shifts(uint64_t block_length, uint64_t q, int *shifts, int *npasses);
 /* NULL is a no-op. */
 int nolzss_rlz_index_close(nolzss_rlz_index *h);
 

@@ -276,6 +276,9 @@ def _load():
     lib.nolzss_rlz_index_factorize.argtypes = [vp] + seqs[3:] + [C.c_int, C.POINTER(RlzResult)]
     lib.nolzss_rlz_index_codes.argtypes = [vp] + seqs[3:] + [vp]
     lib.nolzss_rlz_index_close.argtypes = [vp]
+    lib.nolzss_rlz_index_count.argtypes = [vp] + seqs[3:] + [vp]
+    lib.nolzss_rlz_index_locate.argtypes = [vp] + seqs[3:] + [C.c_uint64, vp, vp, vpp, szp]
+    lib.nolzss_debug_rlz_locate_shifts.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
     lib.nolzss_rlz_archive_export.argtypes = [vp, vpp, szp, vpp, szp, vpp, szp]
@@ -332,7 +335,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_archive_open_records", "nolzss_rlz_archive_info", "nolzss_rlz_archive_extract",
     "nolzss_rlz_archive_extract_device", "nolzss_rlz_archive_close",
     "nolzss_rlz_index_open", "nolzss_rlz_index_open_fasta", "nolzss_rlz_index_info", "nolzss_rlz_index_factorize",
-    "nolzss_rlz_index_codes", "nolzss_rlz_index_close",
+    "nolzss_rlz_index_codes", "nolzss_rlz_index_close", "nolzss_rlz_index_count", "nolzss_rlz_index_locate",
+    "nolzss_debug_rlz_locate_shifts",
     "nolzss_rlz_archive_open_index", "nolzss_rlz_archive_append_index", "nolzss_rlz_archive_export",
 ]
 

@@ -19,6 +19,8 @@ __version__ = lib.nolzss_version().decode()
 
 RC_MASK = 1 << 63
 FACTOR_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8")])
+# nolzss_rlz_hit (include/nolzss_hip.h): an occurrence of a pattern in the reference block
+HIT_DTYPE = np.dtype([("position", "<u8"), ("record", "<u4"), ("is_rc", "<u4")])
 
 _default_device = int(os.environ.get("NOLZSS_DEVICE", os.environ.get("LOCAL_RANK", "0")) or 0)
 
@@ -1377,6 +1379,35 @@ class RlzIndexHandle:
         code = np.zeros(sum(args[1][j] for j in range(args[2])) + args[2], dtype=np.uint32)
         check(lib.nolzss_rlz_index_codes(h, *args, code.ctypes.data if code.size else None))
         return code
+
+    def count(self, patterns) -> np.ndarray:
+        """One batch: the occurrences of every pattern in the reference, both strands together (uint64).  C ABI
+        nolzss_rlz_index_count (its header states the rules)."""
+        h = self._handle()
+        args = _seq_args(patterns, "pattern")
+        counts = np.zeros(args[2], dtype=np.uint64)
+        check(lib.nolzss_rlz_index_count(h, *args, counts.ctypes.data if counts.size else None))
+        return counts
+
+    def locate(self, patterns, max_hits: int = 0):
+        """One batch -> (counts, offsets, hits): uint64 counts, the q + 1 uint64 offsets of the patterns' hits, and the
+        hits as HIT_DTYPE, per pattern ascending by (position, is_rc); a pattern with more than max_hits occurrences
+        (0: no cap) reports its count and no hits.  C ABI nolzss_rlz_index_locate."""
+        h = self._handle()
+        max_hits = operator.index(max_hits)
+        if max_hits < 0:
+            raise ValueError("max_hits must not be negative")
+        args = _seq_args(patterns, "pattern")
+        counts, offsets = np.zeros(args[2], dtype=np.uint64), np.zeros(args[2] + 1, dtype=np.uint64)
+        out, z = C.c_void_p(), C.c_size_t()
+        check(lib.nolzss_rlz_index_locate(h, *args, max_hits, counts.ctypes.data if counts.size else None,
+                                          offsets.ctypes.data, C.byref(out), C.byref(z)))
+        if not out.value or z.value == 0:
+            lib.nolzss_free(out)
+            return counts, offsets, np.zeros(0, dtype=HIT_DTYPE)
+        raw = (C.c_uint64 * (2 * z.value)).from_address(out.value)
+        raw._owner = _Owned(out)
+        return counts, offsets, np.frombuffer(raw, dtype=HIT_DTYPE)
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

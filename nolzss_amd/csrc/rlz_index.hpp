@@ -1,6 +1,6 @@
 // rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
-// rlz_index.hip; the handle and its entry points: rlz_index_api.hip).
+// rlz_index.hip, and rlz_locate.hip for pattern queries; the handle and its entry points: rlz_index_api.hip).
 #pragma once
 #include "pipeline.hpp"
 
@@ -43,6 +43,34 @@ void rlz_index_records(Context &ctx, const RlzIndexView &ix, const uint32_t *d_f
                        const uint32_t *d_rank, IndexRec *d_out);
 // The same look-ups over EVERY position: len[p] |= 1 << 31 where the record of p would be a reverse-complement factor.
 void rlz_index_strands(Context &ctx, const RlzIndexView &ix, uint32_t n, uint32_t *d_len, const uint32_t *d_rank);
+
+// ---- pattern count and locate (rlz_locate.hip; DESIGN.md 5, "Relative-LZ index: pattern count and locate") -----------
+// The batch is P1 s P2 s .. Pq s packed like a target batch: its terminator table (q + 1 entries) gives every pattern's
+// first position and length.
+struct LocateHit {  // nolzss_rlz_hit
+    uint64_t position;
+    uint32_t record, is_rc;
+};
+// Per pattern j < q: cnt[j] = its occurrences in X on both strands, lo[j] = the first rank of its suffix-array interval,
+// rep[j] = cnt[j] where cnt[j] <= cap, else 0 (the hits a locate reports).
+void rlz_index_patterns(Context &ctx, const RlzIndexView &ix, const PackedText &batch, uint32_t q, uint32_t cap,
+                        uint32_t *d_lo, uint32_t *d_cnt, uint32_t *d_rep);
+// off[j] = rep[0] + .. + rep[j - 1] (the caller has made sure the total stays below 2^32)
+void rlz_index_hit_offsets(Context &ctx, const uint32_t *d_rep, uint32_t q, uint32_t *d_off);
+// The T = sum(rep) hits expanded and sorted by (pattern, position, strand): keys[t] = (j << 33) | (position << 1) |
+// is_rc, vals[t] = the 0-based reference record (`records` = their number m).  Arena memory, 24 bytes per hit.
+struct LocateSorted {
+    const uint64_t *keys = nullptr;
+    const uint32_t *vals = nullptr;
+};
+// The bit offsets of the 8-bit digits the sort of the hits runs, least significant first, for a block of B bases and q
+// patterns (host only): at most kLocateMaxPasses, none of them across bit 32 of the key.  Returns their number.
+constexpr int kLocateMaxPasses = 8;
+int rlz_locate_sort_shifts(uint64_t B, uint64_t q, int *shifts);
+LocateSorted rlz_index_hits(Context &ctx, const RlzIndexView &ix, uint32_t records, const PackedText &batch, uint32_t q,
+                            const uint32_t *d_off, const uint32_t *d_lo, uint32_t T);
+// hits [first, first + count) of the sorted pairs unpacked into records
+void rlz_index_hit_records(Context &ctx, const LocateSorted &sorted, size_t first, uint32_t count, LocateHit *d_out);
 
 constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
 

@@ -20,6 +20,7 @@ import numpy as np
 from .. import _noLZSS as _native
 
 RLZ_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8"), ("is_rc", "?"), ("is_literal", "?")])
+HIT_DTYPE = _native.HIT_DTYPE  # (position, record, is_rc): an occurrence of a pattern (RlzIndex.locate)
 
 
 def split_and_rebase(records, target_offsets, target_lengths):
@@ -506,6 +507,42 @@ class RlzIndex:
         T1 s T2 s .. Tk s; only target positions are specified."""
         return self._live().codes(list(targets))
 
+    def _pattern_batches(self, patterns):
+        # the length rule of a pattern batch is sum(len) + q <= MAX_TEXT: the greedy rule of the targets without a block
+        patterns = list(patterns)
+        return patterns, plan_index_batches([len(p) for p in patterns], -1, MAX_TEXT)
+
+    def count(self, patterns):
+        """Occurrences of every pattern in the reference, both strands together (an index without reverse complement
+        counts the forward strand only) -> uint64 array.  Patterns are nucleotide strings, case-insensitive; an empty
+        one counts 0.  A long list goes up in several batches."""
+        h = self._live()
+        patterns, plan = self._pattern_batches(patterns)
+        parts = [h.count(patterns[lo:hi]) for lo, hi in plan]
+        return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+
+    def locate(self, patterns, max_hits: int = 0):
+        """Where every pattern occurs in the reference -> dict(counts, offsets, position, record, record_offset, is_rc).
+        Pattern j owns the hits [offsets[j], offsets[j + 1]), ascending by (position, is_rc), forward first: position is
+        the coordinate in the reference block, record the 0-based reference record, record_offset the position inside
+        that record; a reverse-strand hit (is_rc) means the stretch at position equals the pattern's reverse complement.
+        A pattern with more than max_hits occurrences (0: no cap) reports its count and no hits.  Sorted on the GPU; a
+        long list goes up in several batches, the offsets stitched."""
+        h = self._live()
+        patterns, plan = self._pattern_batches(patterns)
+        counts, offsets, hits, base = [], [np.zeros(1, dtype=np.uint64)], [], 0
+        for lo, hi in plan:
+            c, o, f = h.locate(patterns[lo:hi], max_hits)
+            counts.append(c)
+            offsets.append(o[1:] + np.uint64(base))
+            hits.append(f)
+            base += int(o[-1])
+        f = np.concatenate(hits) if hits else np.zeros(0, dtype=HIT_DTYPE)
+        starts = np.cumsum([0] + [len(r) + 1 for r in self._reference[:-1]], dtype=np.uint64)  # of every record in Rblk
+        return {"counts": np.concatenate(counts) if counts else np.zeros(0, dtype=np.uint64),
+                "offsets": np.concatenate(offsets), "position": f["position"].copy(), "record": f["record"].copy(),
+                "record_offset": f["position"] - starts[f["record"]], "is_rc": f["is_rc"].astype(bool)}
+
     def archive(self, targets, ids=None):
         """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
         targets = list(targets)
@@ -561,5 +598,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
