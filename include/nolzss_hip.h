@@ -768,6 +768,39 @@ int nolzss_debug_rc_arrays(const uint8_t *S, size_t S_len, int device, int want_
 int nolzss_debug_sort_pairs(uint64_t *keys, uint32_t *vals, size_t n, int device);
 /* mode 0: exclusive add-scan, mode 1: inclusive max-scan, in place. */
 int nolzss_debug_scan(uint32_t *data, size_t n, int mode, int device);
+/* The 16-ary min (is_max: max) pyramid over base[0 .. len) and its three queries, run by the device functions of
+ * pyramid.hpp with kMax = is_max.  The base array is uploaded into arena memory with 16 spare entries behind it; those,
+ * the rest of its allocation and the arena span of the upper levels are filled with the byte `poison` (0x00 or 0xFF)
+ * before anything is built, so that what a query or a build reads beyond a level's length is known and adverse.
+ *   mode 0: build_pyramid; with flag_min != 0 (min pyramid, len >= 2: level 1 sets it) *flag = 1 if some base entry is >= flag_min, else 0.
+ *   mode 1 (len >= 2): alloc_pyramid, level1[0 .. first_entry) uploaded into level 1 as the caller's own work,
+ *     fill_pyramid_tail(first_entry) for the rest of level 1, fill_pyramid from level 2; first_entry <= len of level 1.
+ *   queries: nq triples (op, a, b); results: one u32 each.  NOLZSS_PYR_NEAREST_LEFT (r, x), r < len: the largest
+ *     q <= r with base[q] < x (max: > x), 0xffffffff if none.  NOLZSS_PYR_NEAREST_RIGHT (r, x), any r: the smallest
+ *     q >= r, len if none.  NOLZSS_PYR_RANGE (a, b), a <= b < len: min (max) of base[a .. b].
+ *   Out: *nlev, level_lens[0 .. *nlev) (room for 9), the levels back to back from level 0 in `levels` (NULL: not
+ *     wanted; levels_cap entries, at least the sum of the level lengths), *flag (may be NULL when flag_min == 0).
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, len == 0, len >= 2^32, a query outside the
+ * ranges above, an unknown op, mode or poison. */
+enum { NOLZSS_PYR_NEAREST_LEFT = 0, NOLZSS_PYR_NEAREST_RIGHT = 1, NOLZSS_PYR_RANGE = 2 };
+int nolzss_debug_pyramid(const uint32_t *base, size_t len, int is_max, int mode, const uint32_t *level1,
+                         size_t first_entry, uint32_t flag_min, int poison, const uint32_t *queries, size_t nq,
+                         int device, int *nlev, uint32_t *level_lens, uint32_t *levels, size_t levels_cap,
+                         uint32_t *flag, uint32_t *results);
+/* The searches of nearest.hpp over sa[0 .. n) and lcp[0 .. n] (lcp[0] == lcp[n] == 0 is required), on the min and max
+ * pyramids over sa and the min pyramid over lcp from build_pyramid, padding poisoned as above.  sa need not be a
+ * permutation nor lcp a true LCP array.  queries: nq quintuples (op, r, a, b, c), r < n; results: two u32 each.
+ *   NEAR_UP / NEAR_DOWN / FAR_UP / FAR_DOWN, _LESS or _GREATER (the latter on the max pyramid): (r, x, floor) -> (len, pos)
+ *   LCP_INTERVAL (r, d), d >= 1 -> (lo, hi);  LPNF_LEFTMOST (r, d), d >= 1 -> (min SA[I(d)], 0)
+ *   LPNF_SEARCH (r, i, lo, cap), i < n -> (the length, 0); meaningful where P(lo) holds or lo == 0, on a true SA / LCP */
+enum {
+    NOLZSS_NEAR_UP_LESS = 0, NOLZSS_NEAR_UP_GREATER = 1, NOLZSS_NEAR_DOWN_LESS = 2, NOLZSS_NEAR_DOWN_GREATER = 3,
+    NOLZSS_NEAR_FAR_UP_LESS = 4, NOLZSS_NEAR_FAR_UP_GREATER = 5, NOLZSS_NEAR_FAR_DOWN_LESS = 6,
+    NOLZSS_NEAR_FAR_DOWN_GREATER = 7, NOLZSS_NEAR_LCP_INTERVAL = 8, NOLZSS_NEAR_LPNF_LEFTMOST = 9,
+    NOLZSS_NEAR_LPNF_SEARCH = 10
+};
+int nolzss_debug_nearest(const uint32_t *sa, const uint32_t *lcp, size_t n, int poison, const uint32_t *queries,
+                         size_t nq, int device, uint32_t *results);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

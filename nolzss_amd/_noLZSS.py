@@ -1632,3 +1632,55 @@ def debug_scan(data, mode: int):
     data = np.ascontiguousarray(data, dtype=np.uint32).copy()
     check(lib.nolzss_debug_scan(data.ctypes.data, data.size, mode, _default_device))
     return data
+
+
+PYR_NEAREST_LEFT, PYR_NEAREST_RIGHT, PYR_RANGE = range(3)
+(NEAR_UP_LESS, NEAR_UP_GREATER, NEAR_DOWN_LESS, NEAR_DOWN_GREATER, NEAR_FAR_UP_LESS, NEAR_FAR_UP_GREATER,
+ NEAR_FAR_DOWN_LESS, NEAR_FAR_DOWN_GREATER, NEAR_LCP_INTERVAL, NEAR_LPNF_LEFTMOST, NEAR_LPNF_SEARCH) = range(11)
+
+
+def debug_pyramid(base, is_max: bool, queries=None, mode: int = 0, level1=None, first_entry: int = 0,
+                  flag_min: int = 0, poison: int = 0, want_levels: bool = True):
+    """The device pyramid over `base` (u32) and its queries (nolzss_debug_pyramid, test hook).  queries: (nq, 3) rows
+    (op, a, b) with op one of PYR_*.  Returns {"nlev", "lens", "levels": one array per level from level 0 (None if not
+    wanted), "flag", "results": one u32 per query}."""
+    base = np.ascontiguousarray(base, dtype=np.uint32)
+    q = np.ascontiguousarray(queries if queries is not None else np.zeros((0, 3)), dtype=np.uint32).reshape(-1, 3)
+    l1 = np.ascontiguousarray(level1, dtype=np.uint32) if level1 is not None else None
+    if l1 is not None and l1.size < first_entry:
+        raise ValueError("level1 holds fewer than first_entry entries")
+    lens, length = [], base.size
+    while True:  # (room for the levels; the library reports the lengths it used)
+        lens.append(length)
+        if length <= 1 or len(lens) == 9:
+            break
+        length = (length + 15) >> 4
+    levels = np.zeros(max(sum(lens), 1), dtype=np.uint32)
+    got_lens = np.zeros(9, dtype=np.uint32)
+    nlev, flag = C.c_int(), C.c_uint32()
+    results = np.zeros(max(len(q), 1), dtype=np.uint32)
+    check(lib.nolzss_debug_pyramid(base.ctypes.data, base.size, 1 if is_max else 0, mode,
+                                   l1.ctypes.data if l1 is not None else None, first_entry, flag_min, poison,
+                                   q.ctypes.data, len(q), _default_device, C.byref(nlev), got_lens.ctypes.data,
+                                   levels.ctypes.data if want_levels else None, levels.size, C.byref(flag),
+                                   results.ctypes.data))
+    got_lens = [int(v) for v in got_lens[:nlev.value]]
+    ends = np.cumsum(got_lens)
+    return {"nlev": nlev.value, "lens": got_lens,
+            "levels": [levels[e - n:e] for e, n in zip(ends, got_lens)] if want_levels else None,
+            "flag": flag.value, "results": results[:len(q)]}
+
+
+def debug_nearest(sa, lcp, queries, poison: int = 0):
+    """The searches of nearest.hpp on the device over sa (n entries) and lcp (n + 1 entries, first and last 0)
+    (nolzss_debug_nearest, test hook).  queries: (nq, 5) rows (op, r, a, b, c) with op one of NEAR_*.  Returns an
+    (nq, 2) u32 array: (len, pos), (lo, hi) or (value, 0)."""
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    lcp = np.ascontiguousarray(lcp, dtype=np.uint32)
+    if lcp.size != sa.size + 1:
+        raise ValueError("lcp must hold one entry more than sa")
+    q = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, 5)
+    results = np.zeros((max(len(q), 1), 2), dtype=np.uint32)
+    check(lib.nolzss_debug_nearest(sa.ctypes.data, lcp.ctypes.data, sa.size, poison, q.ctypes.data, len(q),
+                                   _default_device, results.ctypes.data))
+    return results[:len(q)]
