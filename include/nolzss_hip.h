@@ -801,6 +801,23 @@ enum {
 };
 int nolzss_debug_nearest(const uint32_t *sa, const uint32_t *lcp, size_t n, int poison, const uint32_t *queries,
                          size_t nq, int device, uint32_t *results);
+/* The LDS tile searches of nearest_lds.hpp over sa[0 .. n) (distinct values) and lcp[0 .. n] (lcp[0] == lcp[n] == 0 is
+ * required; neither need come from a text), padding poisoned as above: stage_tile -> build_block_tables ->
+ * lds_search_wave_blocks, one workgroup per 1024 ranks.
+ *   form NOLZSS_LDS_PLAIN: the template arguments of the plain candidate kernel -- two searches per rank (0: smaller
+ *     suffix start towards smaller ranks, 1: towards larger ranks); strand is ignored.
+ *   form NOLZSS_LDS_RC: those of the reverse-complement kernel -- only ranks with sa[r] < strand search, four searches
+ *     (0, 1 as above; 2, 3: suffix start greater than 2 * strand - sa[r], towards smaller / larger ranks), work lists of
+ *     128 entries (a search that finds its list full: NOLZSS_LDS_OVERFLOW).  The other ranks return 0 / no position.
+ *   len: searches * n words, len[k * n + r] for search k of rank r: the length (0: nothing), or with bit 31 set "left the
+ *     reach" with the bound in bits 0..30, or NOLZSS_LDS_OVERFLOW.  pos: 2 * n words for searches 0 and 1, the suffix
+ *     start of the match or 0xffffffff.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, n == 0, n > 2^31 - 2048, an unknown form or
+ * poison, lcp[0] or lcp[n] != 0. */
+enum { NOLZSS_LDS_PLAIN = 0, NOLZSS_LDS_RC = 1 };
+#define NOLZSS_LDS_OVERFLOW 0xffffffffu
+int nolzss_debug_lds_search(const uint32_t *sa, const uint32_t *lcp, size_t n, int form, uint32_t strand, int poison,
+                            int device, uint32_t *len, uint32_t *pos);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

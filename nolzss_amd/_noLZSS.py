@@ -1684,3 +1684,24 @@ def debug_nearest(sa, lcp, queries, poison: int = 0):
     check(lib.nolzss_debug_nearest(sa.ctypes.data, lcp.ctypes.data, sa.size, poison, q.ctypes.data, len(q),
                                    _default_device, results.ctypes.data))
     return results[:len(q)]
+
+
+LDS_PLAIN, LDS_RC = 0, 1
+LDS_OVERFLOW = 0xffffffff
+
+
+def debug_lds_search(sa, lcp, form: int = LDS_PLAIN, strand: int = 0, poison: int = 0):
+    """The LDS tile searches of nearest_lds.hpp on the device over sa (n distinct entries) and lcp (n + 1 entries, first
+    and last 0), as the plain (LDS_PLAIN, two searches) or the reverse-complement candidate kernel (LDS_RC, four
+    searches of the ranks with sa[r] < strand) runs them (nolzss_debug_lds_search, test hook).  Returns (len, pos):
+    (searches, n) and (2, n) u32 arrays; len has bit 31 set where the search left the reach (bound in the low bits)."""
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    lcp = np.ascontiguousarray(lcp, dtype=np.uint32)
+    if lcp.size != sa.size + 1:
+        raise ValueError("lcp must hold one entry more than sa")
+    searches = 4 if form == LDS_RC else 2
+    length = np.zeros((searches, max(sa.size, 1)), dtype=np.uint32)
+    pos = np.zeros((2, max(sa.size, 1)), dtype=np.uint32)
+    check(lib.nolzss_debug_lds_search(sa.ctypes.data, lcp.ctypes.data, sa.size, form, strand, poison, _default_device,
+                                      length.ctypes.data, pos.ctypes.data))
+    return length, pos

@@ -2,8 +2,11 @@
 // (nearest.hpp): the caller's arrays go into arena memory whose padding holds a poison byte, the pyramids are built the
 // way the pipelines build them, and one lane per query runs the device functions themselves.  No product path calls
 // these (part of the C ABI layer of libnolzss_hip.so, include/nolzss_hip.h).
+// nolzss_debug_lds_search does the same for the LDS tile searches of nearest_lds.hpp, in the two forms the candidate
+// kernels instantiate them (lpnf.hip, rc.hip).
 #include "api_internal.hpp"
 #include "nearest.hpp"
+#include "nearest_lds.hpp"
 
 using namespace nolzss;
 using namespace nolzss::api;
@@ -54,6 +57,50 @@ __global__ __launch_bounds__(kQueryThreads) void debug_nearest_query_kernel(cons
         }
         out[2 * k] = o0;
         out[2 * k + 1] = o1;
+    }
+}
+
+// The searches of one tile as lpf_tile_kernel (kRc = false) and rc_tile_kernel (kRc = true) run them: same staging,
+// same block tables, same template arguments and list sizes; every wavefront then writes out what its own ranks found.
+template <bool kRc>
+__global__ __launch_bounds__(kLdsThreads) void debug_lds_search_kernel(const uint32_t *__restrict__ sa,
+                                                                       const uint32_t *__restrict__ lcp, uint32_t n,
+                                                                       uint32_t N, uint32_t *__restrict__ out_len,
+                                                                       uint32_t *__restrict__ out_pos) {
+    constexpr int NS = kRc ? 4 : 2, NP = 2;
+    constexpr int kListCap = kRc ? 128 : kLdsPerWave;
+    constexpr int kListCapB = 64;
+    __shared__ __align__(16) uint32_t s_sa[kLdsSpan];
+    __shared__ __align__(16) uint32_t s_lcp[kLdsSpan + 4];
+    __shared__ uint32_t s_len[NS * kLdsTile];
+    __shared__ uint16_t s_pos[NP * kLdsTile];
+    __shared__ uint16_t s_list0[kLdsWaves][NS * kListCap];
+    __shared__ uint16_t s_list1[kLdsWaves][NS * kListCapB];
+    __shared__ uint32_t s_blk[(kRc ? 4 : 3) * kBlkTableLen];
+    const uint32_t base = blockIdx.x * (uint32_t)kLdsTile;
+    stage_tile(sa, lcp, n, base, s_sa, s_lcp);
+    __syncthreads();
+    const BlockTables T = block_tables<kRc>(s_blk);
+    build_block_tables<kRc>(s_sa, s_lcp, T);
+    __syncthreads();
+    const int w = threadIdx.x >> 6;
+    const uint32_t far_bit = n <= 0x80000000u ? 0x80000000u : 0u;
+    if constexpr (kRc)
+        lds_search_wave_blocks<NS, NP, true, kListCap, kListCapB>(s_sa, s_lcp, T, n, base, s_len, s_pos, s_list0[w], s_list1[w],
+                                       [N](uint32_t i) { return i < N; }, [N](uint32_t i) { return 2u * N - i; }, far_bit);
+    else
+        lds_search_wave_blocks<NS, NP, false, kListCap, kListCapB>(s_sa, s_lcp, T, n, base, s_len, s_pos, s_list0[w], s_list1[w],
+                                       [](uint32_t) { return true; }, [](uint32_t) { return 0u; }, far_bit);
+    for (int row = 0; row < kLdsPerWave / 64; ++row) {
+        const int t = w * kLdsPerWave + row * 64 + lane_id();
+        const uint64_t rr = (uint64_t)base + t;
+        if (rr >= n) continue;
+        const bool searched = !kRc || s_sa[t + kLdsReach] < N;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            out_len[(size_t)k * n + rr] = searched ? s_len[k * kLdsTile + t] : 0u;
+            if (k < NP) out_pos[(size_t)k * n + rr] = searched ? match_pos(s_sa, s_pos[k * kLdsTile + t]) : kNoPos;
+        }
     }
 }
 
@@ -227,6 +274,40 @@ int nolzss_debug_nearest(const uint32_t *sa, const uint32_t *lcp, size_t n, int 
                                                                            nq, d_res);
         KERNEL_CHECK();
         HIP_CHECK(hipMemcpyAsync(results, d_res, 2 * nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        ctx.arena.rewind(mark);
+    });
+}
+
+int nolzss_debug_lds_search(const uint32_t *sa, const uint32_t *lcp, size_t n, int form, uint32_t strand, int poison,
+                            int device, uint32_t *len, uint32_t *pos) {
+    return guarded([&] {
+        if (!sa || !lcp || !len || !pos) throw std::invalid_argument("null argument");
+        if (n == 0) throw std::invalid_argument("the arrays are empty");
+        if (n > (size_t(1) << 31) - 2 * kLdsTile) throw std::invalid_argument("more than 2^31 - 2048 ranks");
+        if (form != NOLZSS_LDS_PLAIN && form != NOLZSS_LDS_RC) throw std::invalid_argument("unknown form of the LDS searches");
+        check_poison(poison);
+        if (lcp[0] != 0 || lcp[n] != 0) throw std::invalid_argument("lcp[0] and lcp[n] must be 0");
+        const size_t searches = form == NOLZSS_LDS_RC ? 4 : 2;
+
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        ctx.arena.reserve(padded_bytes(n + kSpare) + padded_bytes(n + 1 + kSpare) + (searches + 2) * padded_bytes(n) +
+                          (size_t(64) << 20));
+        const size_t mark = ctx.arena.mark();
+        hipStream_t s = ctx.stream;
+        uint32_t *d_len = ctx.arena.alloc<uint32_t>(searches * n);
+        uint32_t *d_pos = ctx.arena.alloc<uint32_t>(2 * n);
+        const uint32_t *d_sa = upload_poisoned(ctx, sa, n, poison);
+        const uint32_t *d_lcp = upload_poisoned(ctx, lcp, n + 1, poison);
+        const unsigned tiles = (unsigned)div_up(n, (size_t)kLdsTile);
+        if (form == NOLZSS_LDS_RC)
+            debug_lds_search_kernel<true><<<tiles, kLdsThreads, 0, s>>>(d_sa, d_lcp, (uint32_t)n, strand, d_len, d_pos);
+        else
+            debug_lds_search_kernel<false><<<tiles, kLdsThreads, 0, s>>>(d_sa, d_lcp, (uint32_t)n, strand, d_len, d_pos);
+        KERNEL_CHECK();
+        HIP_CHECK(hipMemcpyAsync(len, d_len, searches * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(pos, d_pos, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         ctx.arena.rewind(mark);
     });

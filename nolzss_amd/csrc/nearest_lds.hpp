@@ -12,8 +12,8 @@
 //   * unfinished searches are compacted (ballot + popcount) into per-wave work lists in LDS, ONE LIST PER KIND
 //     of search (smaller / greater suffix start, towards smaller / larger ranks: kind and direction are then
 //     compile-time constants of every round, and an LDS address is the rank's own plus an immediate), and taken
-//     64 at a time: 12 more steps (round A), then 16 BLOCKS nearest first (round B), then the 16 ranks of the
-//     block that stops the search (round C) -- see lds_search_wave_blocks below;
+//     64 at a time: 12 more steps (round A); what is still going then, by kLanesBC lanes per search: 16 BLOCKS nearest
+//     first (round B), then the 16 ranks of the block that stops the search (round C) -- see lds_search_wave_blocks below;
 //   * results per rank and search: the length (4 bytes) and the LOCAL INDEX of the match (2 bytes, match_pos);
 //   * a search that leaves the reach keeps its running LCP minimum as a bound (far_mark): the rank
 //     is finished from global memory with the pyramids only if that bound can still win.
@@ -155,7 +155,9 @@ __device__ __forceinline__ int lds_scan_round(const uint32_t *s_sa, const uint32
 //   round C   the 16 ranks of that block, nearest first, from the minimum carried so far: ends inside.
 // Blocks that overlap ranks already passed are harmless (a minimum is idempotent and those ranks do not
 // qualify).  No stop within the 16 blocks (>= 261 ranks away): the search leaves the reach with its bound,
-// exactly as before.  Every search takes at most four rounds, all of them 64 searches wide.
+// exactly as before.  Every search takes at most four rounds: rounds 0 and A 64 searches wide, rounds B + C -- one search
+// in 17 gets there, about 15 per wavefront and kind -- 64 / kLanesBC searches wide with the blocks and ranks of a search
+// shared out among kLanesBC lanes (below).
 constexpr int kBlk = 16;
 constexpr int kNumBlk = kLdsSpan / kBlk;  // 96
 static_assert(kLdsSpan % kBlk == 0 && kLdsReach % kBlk == 0 && kLdsTile % kBlk == 0, "aligned blocks");
@@ -214,7 +216,57 @@ __device__ __forceinline__ void build_block_tables(const uint32_t *s_sa, const u
     }
 }
 
-// Rounds A, B and C of ONE kind of search (kGreater, kUp) for the unfinished searches of a wavefront, 64 at a time.
+// Rounds B + C give every search a GROUP of kLanesBC adjacent lanes: lane q of the group takes the kBlk / kLanesBC blocks
+// (round B) and ranks (round C) from number q * kBlk / kLanesBC on, nearest first, and the group combines what its lanes
+// found with DPP quad permutes -- about 15 of the 64 searches of a one-lane-per-search pass were alive (one search in 17
+// is still going after 16 steps), and the pass cost the same whatever that number.
+#ifndef NOLZSS_LANES_BC
+#define NOLZSS_LANES_BC 4
+#endif
+constexpr int kLanesBC = NOLZSS_LANES_BC;
+static_assert(kLanesBC == 2 || kLanesBC == 4, "a group of lanes lies inside a DPP quad");
+constexpr int kPerLaneBC = kBlk / kLanesBC;
+
+// min / max over the lanes of a group (every lane of the group receives it)
+template <typename Op> __device__ __forceinline__ uint32_t group_reduce_bc(uint32_t v, Op op) {
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true));  // quad_perm:[1,0,3,2]
+    if (kLanesBC == 4) v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true));  // quad_perm:[2,3,0,1]
+    return v;
+}
+struct OpMaxU32 {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
+};
+// true if a lane of my group in front of me holds a stop (ahead: the bits of those lanes, within my half of the wavefront)
+__device__ __forceinline__ bool stop_in_front_bc(bool stop, int lane, uint32_t ahead) {
+    const uint64_t bal = __ballot(stop);
+    const uint32_t half = lane < 32 ? (uint32_t)bal : (uint32_t)(bal >> 32);
+    return (half & ahead) != 0;
+}
+
+// One lane's share of a round: kSteps entries (c = LCP minimum crossed, v = suffix start) nearest first.  m = the minimum
+// of the entries in front of the first qualifying one (kThrough: and of that one), or of all of them; kk = its number.
+// Returns true if an entry qualifies.  (The loop of lds_scan_round, with the minimum taken before or after the stop.)
+template <int kSteps, bool kGreater, bool kThrough>
+__device__ __forceinline__ bool lds_scan_share(const uint32_t (&c)[kSteps], const uint32_t (&v)[kSteps], uint32_t x, uint32_t &m,
+                                               uint32_t &kk) {
+    bool alive = true;
+    m = 0xffffffffu;
+    kk = 0;
+#pragma unroll
+    for (int k = 0; k < kSteps; ++k) {
+        const uint32_t mk = c[k] < m ? c[k] : m;
+        const bool qual = kGreater ? v[k] > x : v[k] < x;
+        const bool stop = alive && qual;
+        if (kThrough) m = alive ? mk : m;
+        kk = stop ? (uint32_t)k : kk;
+        alive = alive != stop;  // (alive && !qual, without a second comparison)
+        if (!kThrough) m = alive ? mk : m;
+    }
+    return !alive;
+}
+
+// Rounds A, B and C of ONE kind of search (kGreater, kUp) for the unfinished searches of a wavefront: round A 64 at a time,
+// rounds B + C 64 / kLanesBC at a time.
 // list: ranks (index in the wave) still searching after round 0, cnt of them; list_b: kListCapB >= 64 entries for the
 // searches still going after round A -- when the next 64 might not fit, rounds B + C run on what is there first.
 // (kListOverflow, a result of round 0 in lds_search_wave_blocks: "left the reach, nothing known", for a search that
@@ -230,51 +282,67 @@ __device__ __forceinline__ void lds_search_tail(const uint32_t *s_sa, const uint
     const uint32_t *tv = kGreater ? T.mx : T.mn;
     const uint32_t *tc = kUp ? T.lup : T.ldn;
     // ---- rounds B + C for the first cnt_b entries of list_b: by blocks, then inside the block that stops the search ----
+    // lane q of group g works on search c0 + g; `ahead`: the lanes of my group in front of me, as bits of my half of a ballot
+    const int q = lane & (kLanesBC - 1);
+    const uint32_t ahead = ((1u << q) - 1u) << (lane & 31 & ~(kLanesBC - 1));
     auto rounds_bc = [&](uint32_t cnt_b) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        for (uint32_t c0 = 0; c0 < cnt_b; c0 += 64) {
-            const bool have = c0 + lane < cnt_b;
-            const int tl = have ? (int)list_b[c0 + lane] : 0;
+        for (uint32_t c0 = 0; c0 < cnt_b; c0 += 64 / kLanesBC) {
+            const bool have = c0 + (uint32_t)(lane / kLanesBC) < cnt_b;
+            const int tl = have ? (int)list_b[c0 + (uint32_t)(lane / kLanesBC)] : 0;
             const int t = w * kLdsPerWave + tl;
             const int li = t + kLdsReach;
             const uint32_t i = s_sa[li];
             const uint32_t x = kGreater ? thr_gt(i) : i;
             // first block beyond the kLdsStep0 + kStepA ranks already passed (it may overlap them); the 16 blocks from
-            // there reach at most one block outside the staged span (the padded table entries)
+            // there reach at most one block outside the staged span (the padded table entries); mine: from Bq on
             const int b0 = kUp ? (li - (kLdsStep0 + kStepA + 1)) >> 4 : (li + (kLdsStep0 + kStepA + 1)) >> 4;
-            uint32_t c[kBlk], v[kBlk];
+            const int Bq = kUp ? b0 - q * kPerLaneBC : b0 + q * kPerLaneBC;
+            uint32_t c[kPerLaneBC], v[kPerLaneBC];
 #pragma unroll
-            for (int j = 0; j < kBlk; ++j) {
-                const int B = kUp ? b0 - j : b0 + j;
+            for (int j = 0; j < kPerLaneBC; ++j) {
+                const int B = kUp ? Bq - j : Bq + j;
                 c[j] = tc[B];
                 v[j] = tv[B];
             }
-            // run: the minimum in front of the block that stops the search (the first one that holds a qualifying
-            // suffix), or over all 16 blocks -- the bound the search leaves the reach with
-            uint32_t run = have ? res_len[t] : 0xffffffffu;
-            int jstar = -1;
-            bool alive = true;
+            // round B.  My share: the minimum in front of my first block that holds a qualifying suffix, or over all my
+            // blocks.  The group: the first lane with such a block stops the search; run = the minimum carried so far,
+            // the shares of the lanes in front of that lane (all of their blocks) and its own (the blocks in front of the
+            // stop) -- or over all 16 blocks, the bound the search leaves the reach with
+            uint32_t part, jq;
+            const bool stop_b = lds_scan_share<kPerLaneBC, kGreater, false>(c, v, x, part, jq);
+            const bool late_b = stop_in_front_bc(stop_b, lane, ahead);
+            const uint32_t carry = have ? res_len[t] : 0xffffffffu;
+            const uint32_t rest = group_reduce_bc(late_b ? 0xffffffffu : part, OpMinU32());
+            const uint32_t run = carry < rest ? carry : rest;
+            // the block that stops the search, + 1, from the lane that holds it (0: none, the search leaves the reach)
+            const int Bmine = kUp ? Bq - (int)jq : Bq + (int)jq;
+            const uint32_t Bs1 = group_reduce_bc((stop_b && !late_b) ? (uint32_t)(Bmine + 1) : 0u, OpMaxU32());
+            const bool inside = have && Bs1 != 0;
+            // round C: the ranks of block Bs, nearest first, mine from number q * kPerLaneBC on: anchor = the rank just in
+            // front of them
+            const int Bs = (int)Bs1 - 1;
+            const int first = kUp ? kBlk * Bs + kBlk : kBlk * Bs - 1;
+            const int anchor = inside ? (kUp ? first - q * kPerLaneBC : first + q * kPerLaneBC) : li;
 #pragma unroll
-            for (int j = 0; j < kBlk; ++j) {
-                const uint32_t rk = c[j] < run ? c[j] : run;
-                const bool qual = kGreater ? v[j] > x : v[j] < x;
-                const bool stop = alive && qual;
-                jstar = stop ? j : jstar;
-                alive = alive != stop;  // (alive && !qual, without a second comparison)
-                run = alive ? rk : run;
+            for (int k = 0; k < kPerLaneBC; ++k) {
+                const int p = kUp ? anchor - (k + 1) : anchor + (k + 1);
+                c[k] = s_lcp[p + (kUp ? 1 : 0)];
+                v[k] = s_sa[p];
             }
-            const bool inside = have && jstar >= 0;
-            // round C: the ranks of block Bs, nearest first: anchor = the rank just in front of the block
-            const int Bs = kUp ? b0 - jstar : b0 + jstar;
-            const int anchor = inside ? (kUp ? kBlk * Bs + kBlk : kBlk * Bs - 1) : li;
-            uint32_t m = run, at = 0;
-            const int st = lds_scan_round<kBlk, kGreater, kUp>(s_sa, s_lcp, anchor, 0, x, m, at);
-            if (have) {
-                // inside: the block holds a qualifying suffix, so the scan ends there (st 0 or 1); otherwise the
-                // search left the reach
+            uint32_t mine, kq;
+            const bool stop_c = lds_scan_share<kPerLaneBC, kGreater, true>(c, v, x, mine, kq);
+            const bool late_c = stop_in_front_bc(stop_c, lane, ahead);
+            const uint32_t upto = group_reduce_bc(late_c ? 0xffffffffu : mine, OpMinU32());
+            const uint32_t m = run < upto ? run : upto;
+            // inside: the block holds a qualifying suffix, so the scan ends there, in the first lane that saw one: that
+            // lane writes (a minimum that reached 0 discards the match, lds_scan_round); otherwise the search left the
+            // reach, and the first lane of the group says so
+            if (inside ? (stop_c && !late_c) : (have && q == 0)) {
+                const uint32_t at = (uint32_t)(kUp ? anchor - ((int)kq + 1) : anchor + ((int)kq + 1));
                 res_len[t] = inside ? m : far_mark(run, far_bit);
-                if (kHasPos) res_pos[t] = (inside && st == 1) ? (uint16_t)at : kNoMatch;
+                if (kHasPos) res_pos[t] = (inside && m != 0) ? (uint16_t)at : kNoMatch;
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
