@@ -818,6 +818,31 @@ enum { NOLZSS_LDS_PLAIN = 0, NOLZSS_LDS_RC = 1 };
 #define NOLZSS_LDS_OVERFLOW 0xffffffffu
 int nolzss_debug_lds_search(const uint32_t *sa, const uint32_t *lcp, size_t n, int form, uint32_t strand, int poison,
                             int device, uint32_t *len, uint32_t *pos);
+/* The LDS sub-bucket sort (local_sort_kernel and the host function around it, local_sort_sub_buckets) on the caller's
+ * pairs: n pairs (stored word, value) that lie in nb buckets [starts[k], starts[k + 1]) (nb + 1 starts, from 0 up to n).
+ * Runs what the key sorts run behind their most-significant-digit pass: the bucketed view of the starts, one segmented
+ * pass by the digit at bit 24 (256 sub-buckets per bucket), then every sub-bucket by npass digits from shift0 up --
+ * in LDS where it fits a workgroup (18 432 pairs), by segmented passes otherwise.  The forms of the product:
+ *   16-base key: shift0 8, npass 2;  35-bit key: key35, shift0 5, npass 2 (digits of 10 and 9 bits);  records: shift0 0,
+ *   npass 3, any nb.  The bits below shift0 take no part in the order; the sort is stable.
+ * want_regroup (the two key layouts; nb * 256 a multiple of 1024; tags at most 16 / 17): the form with the regroup of
+ * round 0 on the way is asked for, whatever n is.  Where it completes (NOLZSS_LOCAL_SORT_FUSED in *status) the sorted
+ * WORDS ARE NOT WRITTEN -- words_out is left alone -- and lcp[n] (0xffffffff: not a group head), new_slot / new_grp
+ * (room for n; *survivors entries: the tied elements in slot order, each with the slot of its group's head) are filled;
+ * otherwise the plain kernel has run and only words_out / values_out are.
+ * *status: NOLZSS_LOCAL_SORT_FUSED | NOLZSS_LOCAL_SORT_LOOKBACK_GAVE_UP (the fused form ran and fell back) |
+ * NOLZSS_LOCAL_SORT_LANE_ORDER (a lane-order check of the kernel failed: everything was redone by segmented passes) |
+ * (sub-buckets sent to the list of those beyond a workgroup << NOLZSS_LOCAL_SORT_LISTED_SHIFT).  A failed lane-order
+ * check is reported here only: the process-wide switch it throws is put back, later calls run what they would have run.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, n == 0, n >= 2^31, nb == 0 or > 65535, starts
+ * that do not ascend from 0 to n, npass outside 2 .. 3, digits that reach beyond bit 24, key35 with another shift0 or
+ * npass, want_regroup with another form or with nb * 256 not a multiple of 1024. */
+enum { NOLZSS_LOCAL_SORT_FUSED = 1, NOLZSS_LOCAL_SORT_LOOKBACK_GAVE_UP = 2, NOLZSS_LOCAL_SORT_LANE_ORDER = 4,
+       NOLZSS_LOCAL_SORT_LISTED_SHIFT = 8 };
+int nolzss_debug_local_sort(const uint32_t *words, const uint32_t *values, size_t n, const uint32_t *starts, size_t nb,
+                            int shift0, int npass, int key35, int want_regroup, int device, uint32_t *words_out,
+                            uint32_t *values_out, uint32_t *lcp, uint32_t *new_slot, uint32_t *new_grp, uint32_t *survivors,
+                            uint32_t *status);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

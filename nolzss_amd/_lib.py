@@ -294,6 +294,8 @@ def _load():
                                          C.POINTER(C.c_int), vp, vp, sz, vp, vp]
     lib.nolzss_debug_nearest.argtypes = [vp, vp, sz, C.c_int, vp, sz, C.c_int, vp]
     lib.nolzss_debug_lds_search.argtypes = [vp, vp, sz, C.c_int, C.c_uint32, C.c_int, C.c_int, vp, vp]
+    lib.nolzss_debug_local_sort.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                            vp, vp, vp, vp]
     lib.nolzss_debug_arena.argtypes = [C.c_int, szp, szp]
     lib.nolzss_debug_trim_arenas.argtypes = [C.c_int, szp]
     lib.nolzss_debug_parse_fasta.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), szp, C.POINTER(C.c_void_p),
@@ -343,6 +345,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_rlz_locate_shifts",
     "nolzss_rlz_archive_open_index", "nolzss_rlz_archive_append_index", "nolzss_rlz_archive_export",
     "nolzss_debug_pyramid", "nolzss_debug_nearest", "nolzss_debug_lds_search",
+    "nolzss_debug_local_sort",
 ]
 
 

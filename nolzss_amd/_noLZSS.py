@@ -1686,6 +1686,40 @@ def debug_nearest(sa, lcp, queries, poison: int = 0):
     return results[:len(q)]
 
 
+LOCAL_SORT_FUSED, LOCAL_SORT_LOOKBACK_GAVE_UP, LOCAL_SORT_LANE_ORDER, LOCAL_SORT_LISTED_SHIFT = 1, 2, 4, 8
+# the forms of the product: (shift0, npass, key35)
+LOCAL_SORT_KEY16, LOCAL_SORT_KEY35, LOCAL_SORT_RECORDS = (8, 2, False), (5, 2, True), (0, 3, False)
+
+
+def debug_local_sort(words, values, starts, shift0: int, npass: int, key35: bool = False, want_regroup: bool = False):
+    """The LDS sub-bucket sort on the device over caller pairs (nolzss_debug_local_sort, test hook): `words` / `values`
+    lie in the buckets given by `starts` (nb + 1 offsets from 0 to n); one segmented pass by the byte at bit 24, then
+    every sub-bucket by npass digits from shift0 up (local_sort_sub_buckets).  Returns {"words" (None where the form
+    with the regroup on the way completed: it does not write them), "values", "fused", "lookback_gave_up",
+    "lane_order", "listed"} and, where fused, "lcp", "new_slot", "new_grp", "survivors"."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    values = np.ascontiguousarray(values, dtype=np.uint32)
+    starts = np.ascontiguousarray(starts, dtype=np.uint32)
+    if values.size != words.size:
+        raise ValueError("words and values differ in length")
+    n = words.size
+    words_out, values_out = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    lcp, slot, grp = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3)) if want_regroup else (None, None, None)
+    surv, status = C.c_uint32(), C.c_uint32()
+    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    check(lib.nolzss_debug_local_sort(words.ctypes.data, values.ctypes.data, n, starts.ctypes.data, max(starts.size, 1) - 1,
+                                      shift0, npass, 1 if key35 else 0, 1 if want_regroup else 0, _default_device,
+                                      words_out.ctypes.data, values_out.ctypes.data, ptr(lcp), ptr(slot), ptr(grp),
+                                      C.byref(surv) if want_regroup else None, C.byref(status)))
+    st = status.value
+    out = {"words": None if st & LOCAL_SORT_FUSED else words_out[:n], "values": values_out[:n],
+           "fused": bool(st & LOCAL_SORT_FUSED), "lookback_gave_up": bool(st & LOCAL_SORT_LOOKBACK_GAVE_UP),
+           "lane_order": bool(st & LOCAL_SORT_LANE_ORDER), "listed": st >> LOCAL_SORT_LISTED_SHIFT}
+    if out["fused"]:
+        out.update(lcp=lcp[:n], new_slot=slot[:surv.value], new_grp=grp[:surv.value], survivors=surv.value)
+    return out
+
+
 LDS_PLAIN, LDS_RC = 0, 1
 LDS_OVERFLOW = 0xffffffff
 

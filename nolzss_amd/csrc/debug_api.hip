@@ -179,6 +179,61 @@ int nolzss_debug_sort_pairs(uint64_t *keys, uint32_t *vals, size_t n, int device
     });
 }
 
+int nolzss_debug_local_sort(const uint32_t *words, const uint32_t *values, size_t n, const uint32_t *starts, size_t nb,
+                            int shift0, int npass, int key35, int want_regroup, int device, uint32_t *words_out,
+                            uint32_t *values_out, uint32_t *lcp, uint32_t *new_slot, uint32_t *new_grp, uint32_t *survivors,
+                            uint32_t *status) {
+    return guarded([&] {
+        if (!words || !values || !starts || !words_out || !values_out || !status) throw std::invalid_argument("null argument");
+        if (want_regroup && (!lcp || !new_slot || !new_grp || !survivors)) throw std::invalid_argument("null regroup output");
+        if (n == 0 || n >= (size_t(1) << 31)) throw std::invalid_argument("1 .. 2^31 - 1 pairs");
+        if (nb == 0 || nb > 65535) throw std::invalid_argument("1 .. 65535 buckets");
+        if (starts[0] != 0 || starts[nb] != n) throw std::invalid_argument("the bucket starts do not run from 0 to n");
+        for (size_t k = 0; k < nb; ++k)
+            if (starts[k] > starts[k + 1]) throw std::invalid_argument("the bucket starts do not ascend");
+        if (npass < 2 || npass > 3) throw std::invalid_argument("two or three digits");
+        if (key35 ? (shift0 != kP35TagBits || npass != 2) : (shift0 < 0 || shift0 + 8 * npass > 24))
+            throw std::invalid_argument("the digits do not lie between the tag and bit 24 (35-bit key: shift0 5, two digits)");
+        if (want_regroup && (npass != 2 || (!key35 && shift0 != kP16TagBits)))
+            throw std::invalid_argument("the regroup on the way is for the two key layouts of round 0");
+        if (want_regroup && (nb * 256) % 1024 != 0) throw std::invalid_argument("the regroup on the way needs a multiple of 1024 sub-buckets");
+
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        const size_t subs = nb * 256, tiles = n / kSortTile + nb + 1;
+        ctx.arena.reserve(7 * (n * 4 + 256) + 1024 * (2 * tiles + std::min(n, subs)) + 16 * subs + 128 * tiles + (size_t(64) << 20));
+        ArenaRewind rewind(ctx.arena);
+        hipStream_t s = ctx.stream;
+        uint32_t *k[2] = {ctx.arena.alloc<uint32_t>(n), ctx.arena.alloc<uint32_t>(n)};
+        uint32_t *v[2] = {ctx.arena.alloc<uint32_t>(n), ctx.arena.alloc<uint32_t>(n)};
+        HIP_CHECK(hipMemcpyAsync(k[0], words, n * 4, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(v[0], values, n * 4, hipMemcpyHostToDevice, s));
+        Round0Regroup rg;
+        if (want_regroup) {
+            rg.lcp = ctx.arena.alloc<uint32_t>(n);
+            rg.new_slot = ctx.arena.alloc<uint32_t>(n);
+            rg.new_grp = ctx.arena.alloc<uint32_t>(n);
+            rg.d_total = ctx.arena.alloc<uint32_t>(4);
+        }
+        LocalSortReport rep;
+        rep.regroup_any_size = true;
+        debug_local_sort(k, v, n, starts, (uint32_t)nb, shift0, npass, key35 != 0, want_regroup ? &rg : nullptr, rep, ctx.arena, s);
+        *status = (rep.fused_done ? NOLZSS_LOCAL_SORT_FUSED : 0u) | (rep.lookback_gave_up ? NOLZSS_LOCAL_SORT_LOOKBACK_GAVE_UP : 0u) |
+                  (rep.lane_order_failed ? NOLZSS_LOCAL_SORT_LANE_ORDER : 0u) | (rep.listed << NOLZSS_LOCAL_SORT_LISTED_SHIFT);
+        if (!rep.fused_done) HIP_CHECK(hipMemcpyAsync(words_out, k[0], n * 4, hipMemcpyDeviceToHost, s));  // (else: never written)
+        HIP_CHECK(hipMemcpyAsync(values_out, v[0], n * 4, hipMemcpyDeviceToHost, s));
+        if (rep.fused_done) {
+            HIP_CHECK(hipMemcpyAsync(survivors, rg.d_total, 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (*survivors > n) throw std::logic_error("debug_local_sort: more tied elements than pairs");
+            HIP_CHECK(hipMemcpyAsync(lcp, rg.lcp, n * 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(new_slot, rg.new_slot, (size_t)*survivors * 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(new_grp, rg.new_grp, (size_t)*survivors * 4, hipMemcpyDeviceToHost, s));
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak) {
     return guarded([&] {
         if (!capacity || !peak) throw std::invalid_argument("output pointer is null");

@@ -702,9 +702,11 @@ std::atomic<bool> local_sort_off{false};  // a lane-order check of local_sort_ke
 // by one more digit (scanned = the scanned table of that pass, its result in keys_in / vals_in): every sub-bucket is sorted
 // by npass further digits from shift0 up, into keys_out / vals_out.  local_sort_kernel does it in LDS; sub-buckets beyond
 // a workgroup's capacity go through segmented passes.  keys_in / vals_in are scratch afterwards.
+// report (optional; radix_sort.hpp): what ran, for the debug hook.
 void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out, const uint32_t *scanned,
                             const uint32_t *tile0, const uint32_t *bstart, uint32_t num_buckets, int shift0, int npass, size_t n,
-                            Arena &arena, hipStream_t stream, Profiler *prof, Round0Regroup *rg = nullptr, bool key35 = false) {
+                            Arena &arena, hipStream_t stream, Profiler *prof, Round0Regroup *rg = nullptr, bool key35 = false,
+                            LocalSortReport *report = nullptr) {
     if (key35 && (npass != 2 || shift0 != kP35TagBits)) throw HipError("local_sort_sub_buckets: the 35-bit key has two digits above its tag");
     // (segmented passes have 8-bit digits: the 19 bits of the 35-bit key take three, the top one reading five bits that are
     // constant inside a sub-bucket)
@@ -744,7 +746,8 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
     // (it pays where the regroup kernel is expensive -- many tied elements -- and the turns are long: 2^30 bases of the
     // benchmark text 21.7 -> 20.0 ms for sort + regroup, but random DNA of 2^29 bases 10.7 -> 11.2 and of 2^28 bases 6.3 -> 7.5:
     // the look-back and the two loops are a fixed cost per sub-bucket.  NOLZSS_LOCAL_REGROUP_MIN = smallest text that takes it.)
-    if (rg && !knobs.no_local_regroup && !fail_order && npass == 2 && num_sub % 1024u == 0 && n >= knobs.local_regroup_min) {
+    if (rg && !knobs.no_local_regroup && !fail_order && npass == 2 && num_sub % 1024u == 0 &&
+        (n >= knobs.local_regroup_min || (report && report->regroup_any_size))) {
         // the regroup of round 0 on the way -- if no sub-bucket overflows a workgroup (the segmented passes that finish
         // those come after the kernel) and the kernel's checks hold; otherwise the plain form below runs from the same input
         uint32_t *dense = arena.alloc<uint32_t>(num_sub), *prev_sub = arena.alloc<uint32_t>(num_sub), *info = arena.alloc<uint32_t>(2);
@@ -780,7 +783,12 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
 #ifdef NOLZSS_LOCAL_TIMED
             print_phases();
 #endif
+            if (report) {
+                report->lookback_gave_up = h_t[1] != 0;
+                report->lane_order_failed = h_c[2] != 0;
+            }
             if (h_c[2] == 0 && h_t[1] == 0) {
+                if (report) report->fused_done = true;
                 if (prof) prof->add_bytes("rs_local_sort", 8.0 * (double)h_t[0]);  // (slot and group of every tied element)
                 rg->done = true;
                 return;
@@ -810,6 +818,10 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
     uint32_t h_ctl[4];
     HIP_CHECK(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
+    if (report) {
+        report->lane_order_failed = report->lane_order_failed || h_ctl[2] != 0;
+        report->listed = h_ctl[1];
+    }
     const bool redo_all = h_ctl[2] != 0 || fail_order;
     if (h_ctl[2]) {
         // the lane-order check failed somewhere: nothing the kernel wrote is trusted, and it is not asked again

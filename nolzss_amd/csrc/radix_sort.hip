@@ -705,6 +705,26 @@ void radix_sort_record_keys(const PackedText &text, const std::vector<uint32_t> 
     arena.rewind(m);  // (the sorted pairs are in keys32[0] / vals[0])
 }
 
+void debug_local_sort(uint32_t *keys[2], uint32_t *vals[2], size_t n, const uint32_t *h_start, uint32_t nb, int shift0, int npass,
+                      bool key35, Round0Regroup *rg, LocalSortReport &report, Arena &arena, hipStream_t stream) {
+    if (n == 0 || nb == 0 || h_start[0] != 0 || h_start[nb] != n) throw HipError("debug_local_sort: bad bucket table");
+    if (rg) rg->done = false;
+    struct Restore {  // (on every way out)
+        bool was = local_sort_off.load();
+        ~Restore() { local_sort_off.store(was); }
+    } restore;
+    const size_t m = arena.mark();
+    uint32_t *d_tab = arena.alloc<uint32_t>(4 * ((size_t)nb + 1));  // (bucket starts, first tiles: seg_view_of)
+    const SegView seg = seg_view_of(h_start, nb, d_tab, false, nullptr, arena, stream);
+    uint32_t *hist = arena.alloc<uint32_t>((size_t)kBins * seg.num_tiles);
+    // the digit below the bucket's first (keys[0] -> keys[1]), then every sub-bucket by the digits from shift0 up
+    segmented_lsd_passes(keys, vals, 0, n, 24, 1, hist, seg, arena, stream, nullptr);
+    local_sort_sub_buckets(keys[1], vals[1], keys[0], vals[0], hist, d_tab + (nb + 1), d_tab, nb, shift0, npass, n, arena, stream, nullptr,
+                           rg, key35, &report);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    arena.rewind(m);
+}
+
 int radix_sort_segments_u32(uint32_t *keys[2], uint32_t *vals[2], size_t n, const std::vector<uint32_t> &h_start, int npasses,
                             Arena &arena, hipStream_t stream, Profiler *prof) {
     const uint32_t nb = (uint32_t)h_start.size() - 1;  // segments [h_start[k], h_start[k + 1])

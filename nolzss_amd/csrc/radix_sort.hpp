@@ -155,6 +155,23 @@ void radix_sort_dna_keys16(const PackedText &text, uint32_t *keys32[2], uint32_t
 // and passes the answer on as key35: the regroup and the direct round behind the sort must know the layout.
 bool key35_applicable(const PackedText &text);
 
+// What local_sort_sub_buckets (local_sort.hpp) did, for the debug hook below.  regroup_any_size is an INPUT: the regroup on
+// the way is taken whatever the size of the input (NOLZSS_LOCAL_REGROUP_MIN is a choice of speed, not of correctness).
+struct LocalSortReport {
+    bool regroup_any_size = false;
+    bool fused_done = false;         // the form with the regroup of round 0 on the way ran and its checks held
+    bool lookback_gave_up = false;   // ... ran, and a look-back gave up (or NOLZSS_TEST_LOCAL_LOOKBACK_FAILS said so)
+    bool lane_order_failed = false;  // ctl[2] of local_sort_kernel: a lane-order check failed
+    uint32_t listed = 0;             // sub-buckets beyond a workgroup's capacity, sent to the list
+};
+// Test hook (nolzss_debug_local_sort): what the key sorts do behind their most-significant-digit pass, on the caller's
+// pairs.  keys[0] / vals[0] hold n pairs that lie in nb buckets [h_start[k], h_start[k + 1]); seg_view_of, ONE segmented
+// pass by the digit at bit 24, then local_sort_sub_buckets(shift0, npass, key35, rg) with the table of that pass: the
+// sorted pairs end in keys[0] / vals[0] (the keys are not written where rg->done).  The switch that a failed lane-order
+// check throws is put back: report.lane_order_failed says it happened, later sorts of the process are not changed.
+void debug_local_sort(uint32_t *keys[2], uint32_t *vals[2], size_t n, const uint32_t *h_start, uint32_t nb, int shift0, int npass,
+                      bool key35, Round0Regroup *rg, LocalSortReport &report, Arena &arena, hipStream_t stream);
+
 // The same sort on FUSED records [stored key word : 32 | suffix : 32] (round 4, A/B: NOLZSS_FUSED_SORT): rec[0] and rec[1]
 // hold n 64-bit words each; the last pass writes the suffixes to sa_out and the key words to rec[0] (as 32-bit words).
 void radix_sort_dna_keys16_fused(const PackedText &text, uint64_t *rec[2], uint32_t *sa_out, uint32_t *seg_mem,
