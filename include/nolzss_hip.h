@@ -690,6 +690,55 @@ int nolzss_rlz_index_count(const nolzss_rlz_index *h, const char *const *pattern
 int nolzss_rlz_index_locate(const nolzss_rlz_index *h, const char *const *patterns, const size_t *pattern_lens, size_t q,
                             uint64_t max_hits, uint64_t *counts, uint64_t *hit_offsets, nolzss_rlz_hit **hits,
                             size_t *num_hits);
+/* Maximal match seeds: which stretches of the targets occur in the reference, maximally extended, and where (DESIGN.md
+ * 5, "Relative-LZ index: maximal match seeds").  Nothing is added to the handle; the batch goes up as a match lays it
+ * out, Tcat = T1 s T2 s .. Tk s, and is searched once.
+ *   ms[p], for a target position p, is the length of the longest prefix of the target suffix at p that occurs inside one
+ *     reference record -- on either strand when the index has the reverse complement.
+ *   A seed is a super-maximal exact match of a target: an interval [start, start + length) of ONE target, length >= 1,
+ *     that occurs in the reference, cannot be extended by one base to the left or to the right inside its target and
+ *     still occur, and is therefore contained in no other such interval.  Occurrence is closed under taking substrings,
+ *     so ms[p + 1] >= ms[p] - 1, and the seeds are exactly the positions with ms[p] >= 1 and (p is the first position of
+ *     its target, or ms[p - 1] <= ms[p]), each with length ms[p].  Nothing crosses a target's end or a record's end.
+ *   min_length: only seeds with length >= min_length are reported; 0 means 1.  The filter is applied after maximality is
+ *     decided: a seed never becomes maximal because a longer neighbour was filtered out.
+ *   Occurrences of a seed: exactly those of its bytes as the locate above defines them.  A hit is (position, record,
+ *     is_rc) in Rblk coordinates; a reverse-strand hit of a seed of L bases that the mirrored block holds at a lies at
+ *     2 B - a - L + 1; a hit lies inside one record; reverse-strand hits come only from an index opened with reverse
+ *     complement.  count = the occurrences on both strands together, always >= 1.
+ *   max_hits: as in the locate.  A seed with more occurrences than max_hits (0: no cap) reports its count and NO hits, so
+ *     which hits come back never depends on how tied suffixes are ordered.
+ *   Layout: the seeds ascend by (target, start); target is the 0-based index in this batch, start the position inside the
+ *     target.  hit_offsets has num_seeds + 1 entries, seed j owns hits [hit_offsets[j], hit_offsets[j + 1]) (CSR), and
+ *     inside a seed the hits ascend by (position, is_rc), forward first; they are sorted on the device.  seeds is NULL
+ *     when num_seeds is 0, hits is NULL when num_hits is 0, hit_offsets always holds its num_seeds + 1 entries after a
+ *     success.  Free the result with the free function below, whatever the status.
+ *   Refusals: everything a match refuses, with the same status and message (a null array, the length rule, "Invalid
+ *     nucleotide 'x' found in sequence j"); a null handle or output pointer: NOLZSS_ERR_INVALID_ARGUMENT.  Lower case is
+ *     upper-cased.  k == 0, or a batch without a base, succeeds without touching the device.
+ *   More than 2^31 - 1 reported seeds in one batch: NOLZSS_ERR_INVALID_ARGUMENT (the sort key of a hit keeps its seed in
+ *     31 bits).  It takes a batch of more than 2^31 positions and no test reaches it.
+ *   Refusal of the total: when the hits to report number more than the 32-bit pipeline takes, the call returns
+ *     NOLZSS_ERR_INVALID_ARGUMENT naming the total and pointing at max_hits and min_length; it is decided once the counts
+ *     are known and before anything is expanded.  The seeds, their counts and hit_offsets are still returned; hits is
+ *     NULL and num_hits 0.
+ *   An arena out-of-memory leaves the handle untouched, as a match does.  Several threads may query one handle; the
+ *     calling thread's current device is left as it was.  NOLZSS_RLZ_LOCATE_CHUNK (tests): seed records, and hit
+ *     records, per download. */
+typedef struct nolzss_rlz_seed {
+    uint64_t target, start, length, count;
+} nolzss_rlz_seed;
+typedef struct nolzss_rlz_seeds_result {
+    size_t num_seeds;
+    nolzss_rlz_seed *seeds;   /* ascending by (target, start) */
+    uint64_t *hit_offsets;    /* num_seeds + 1 entries */
+    size_t num_hits;
+    nolzss_rlz_hit *hits;     /* NULL when num_hits == 0 */
+} nolzss_rlz_seeds_result;
+int nolzss_rlz_index_seeds(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                           uint64_t min_length, uint64_t max_hits, nolzss_rlz_seeds_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_seeds_result(nolzss_rlz_seeds_result *r);
 /* Host only (tests): the bit offsets of the 8-bit digits the sort of a locate's hits runs for a block of block_length
  * bases and q patterns, least significant first; shifts: 8 entries, the caller's. */
 int nolzss_debug_rlz_locate_shifts(uint64_t block_length, uint64_t q, int *shifts, int *npasses);

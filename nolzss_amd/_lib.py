@@ -127,6 +127,12 @@ class RlzIndexSummary(C.Structure):
                 ("with_rc", C.c_int32), ("device", C.c_int32), ("prefix_syms", C.c_uint32), ("device_bytes", C.c_uint64)]
 
 
+class RlzSeedsResult(C.Structure):
+    """Mirror of nolzss_rlz_seeds_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_seeds", C.c_size_t), ("seeds", C.c_void_p), ("hit_offsets", C.c_void_p), ("num_hits", C.c_size_t),
+                ("hits", C.c_void_p)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -278,6 +284,9 @@ def _load():
     lib.nolzss_rlz_index_close.argtypes = [vp]
     lib.nolzss_rlz_index_count.argtypes = [vp] + seqs[3:] + [vp]
     lib.nolzss_rlz_index_locate.argtypes = [vp] + seqs[3:] + [C.c_uint64, vp, vp, vpp, szp]
+    lib.nolzss_rlz_index_seeds.argtypes = [vp] + seqs[3:] + [C.c_uint64, C.c_uint64, C.POINTER(RlzSeedsResult)]
+    lib.nolzss_free_rlz_seeds_result.argtypes = [C.POINTER(RlzSeedsResult)]
+    lib.nolzss_free_rlz_seeds_result.restype = None
     lib.nolzss_debug_rlz_locate_shifts.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
@@ -342,7 +351,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_archive_extract_device", "nolzss_rlz_archive_close",
     "nolzss_rlz_index_open", "nolzss_rlz_index_open_fasta", "nolzss_rlz_index_info", "nolzss_rlz_index_factorize",
     "nolzss_rlz_index_codes", "nolzss_rlz_index_close", "nolzss_rlz_index_count", "nolzss_rlz_index_locate",
-    "nolzss_debug_rlz_locate_shifts",
+    "nolzss_debug_rlz_locate_shifts", "nolzss_rlz_index_seeds", "nolzss_free_rlz_seeds_result",
     "nolzss_rlz_archive_open_index", "nolzss_rlz_archive_append_index", "nolzss_rlz_archive_export",
     "nolzss_debug_pyramid", "nolzss_debug_nearest", "nolzss_debug_lds_search",
     "nolzss_debug_local_sort",

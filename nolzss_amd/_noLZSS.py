@@ -21,6 +21,8 @@ RC_MASK = 1 << 63
 FACTOR_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8")])
 # nolzss_rlz_hit (include/nolzss_hip.h): an occurrence of a pattern in the reference block
 HIT_DTYPE = np.dtype([("position", "<u8"), ("record", "<u4"), ("is_rc", "<u4")])
+# nolzss_rlz_seed: a maximal exact match of a target with the reference block
+SEED_DTYPE = np.dtype([("target", "<u8"), ("start", "<u8"), ("length", "<u8"), ("count", "<u8")])
 
 _default_device = int(os.environ.get("NOLZSS_DEVICE", os.environ.get("LOCAL_RANK", "0")) or 0)
 
@@ -1408,6 +1410,32 @@ class RlzIndexHandle:
         raw = (C.c_uint64 * (2 * z.value)).from_address(out.value)
         raw._owner = _Owned(out)
         return counts, offsets, np.frombuffer(raw, dtype=HIT_DTYPE)
+
+    def seeds(self, targets, min_length: int = 1, max_hits: int = 0):
+        """One batch -> (seeds, offsets, hits): the maximal exact matches of the targets as SEED_DTYPE (target index in
+        this batch, start inside the target, length, count on both strands), ascending by (target, start); the
+        len(seeds) + 1 uint64 offsets of their hits; the hits as HIT_DTYPE, per seed ascending by (position, is_rc).  Only
+        seeds of at least min_length bases are reported; a seed with more than max_hits occurrences (0: no cap) reports
+        its count and no hits.  C ABI nolzss_rlz_index_seeds (its header states the rules)."""
+        h = self._handle()
+        min_length, max_hits = operator.index(min_length), operator.index(max_hits)
+        if min_length < 0:
+            raise ValueError("min_length must not be negative")
+        if max_hits < 0:
+            raise ValueError("max_hits must not be negative")
+        res = _lib.RlzSeedsResult()
+        try:
+            check(lib.nolzss_rlz_index_seeds(h, *_seq_args(targets, "target"), min_length, max_hits, C.byref(res)))
+            S, T = res.num_seeds, res.num_hits
+            offsets = np.ctypeslib.as_array(C.cast(res.hit_offsets, C.POINTER(C.c_uint64)), shape=(S + 1,)).copy()
+            seeds, hits = np.zeros(S, dtype=SEED_DTYPE), np.zeros(T, dtype=HIT_DTYPE)
+            if S:
+                C.memmove(seeds.ctypes.data, res.seeds, S * SEED_DTYPE.itemsize)
+            if T:
+                C.memmove(hits.ctypes.data, res.hits, T * HIT_DTYPE.itemsize)
+        finally:
+            lib.nolzss_free_rlz_seeds_result(C.byref(res))
+        return seeds, offsets, hits
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None

@@ -46,6 +46,10 @@ using HostBytes = std::vector<uint8_t, DefaultInitAllocator<uint8_t>>;
 // milliseconds were 250 ms on one core for that pair
 template <typename Fn> void host_parallel(size_t n, Fn fn) {
     constexpr size_t kMinPiece = size_t(4) << 20;
+    if (n < 2 * kMinPiece) {  // one piece whatever the machine has: not worth asking it (the call reads the affinity mask,
+        fn((size_t)0, n);     // microseconds each, and a batch of reads makes two of these calls per read)
+        return;
+    }
     unsigned hw = std::thread::hardware_concurrency();
     size_t pieces = std::min<size_t>({(size_t)(hw ? hw : 1u), (size_t)16, n / kMinPiece});
     if (pieces <= 1) {

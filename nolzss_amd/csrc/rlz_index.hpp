@@ -1,6 +1,7 @@
 // rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
-// rlz_index.hip, and rlz_locate.hip for pattern queries; the handle and its entry points: rlz_index_api.hip).
+// rlz_index.hip, rlz_locate.hip for pattern queries and rlz_seeds.hip for maximal match seeds;
+// the handle and its entry points: rlz_index_api.hip).
 #pragma once
 #include "pipeline.hpp"
 
@@ -71,6 +72,29 @@ LocateSorted rlz_index_hits(Context &ctx, const RlzIndexView &ix, uint32_t recor
                             const uint32_t *d_off, const uint32_t *d_lo, uint32_t T);
 // hits [first, first + count) of the sorted pairs unpacked into records
 void rlz_index_hit_records(Context &ctx, const LocateSorted &sorted, size_t first, uint32_t count, LocateHit *d_out);
+
+// ---- maximal match seeds (rlz_seeds.hip; DESIGN.md 5, "Relative-LZ index: maximal match seeds") ----------------------
+// After rlz_index_search over a target batch of n positions: the seeds are the positions p with len[p] >= max(min_len, 1)
+// and (p == 0 or len[p - 1] <= len[p]).
+struct SeedRec {  // nolzss_rlz_seed
+    uint64_t target, start, length, count;
+};
+// flag[p] = 1 at a seed, slot[p] = the seeds in front of p, seeds[0 .. S) = their positions, ascending; *d_total = S
+// (device memory).  flag, slot and seeds hold n entries each.
+void rlz_index_seed_list(Context &ctx, const uint32_t *d_len, uint32_t n, uint32_t min_len, uint32_t *d_flag,
+                         uint32_t *d_slot, uint32_t *d_seeds, uint32_t *d_total);
+// Per seed j of [first, first + count): d_first[j] = the first rank of the LCP interval that holds every occurrence of the
+// seed on both strands, d_rep[j] = their number where it is <= cap, else 0 (the hits that are reported).  With d_out
+// (count entries), the record of seed j -- target, start inside the target, length, occurrences -- goes to d_out[j - first].
+void rlz_index_seed_intervals(Context &ctx, const RlzIndexView &ix, const PackedText &batch, const uint32_t *d_seeds,
+                              uint32_t first, uint32_t count, uint32_t cap, const uint32_t *d_len, const uint32_t *d_rank,
+                              uint32_t *d_first, uint32_t *d_rep, SeedRec *d_out);
+// The T = sum(rep) hits of the S seeds expanded and sorted by (seed, position, strand), laid out as rlz_index_hits lays out
+// the hits of patterns (the caller has made sure that T stays below 2^32 and S below 2^31).  Arena memory: 4 bytes per
+// seed, 24 per hit and the sort's histograms.
+LocateSorted rlz_index_seed_hits(Context &ctx, const RlzIndexView &ix, uint32_t records, uint32_t n, const uint32_t *d_seeds,
+                                 const uint32_t *d_len, uint32_t S, const uint32_t *d_rep, const uint32_t *d_first,
+                                 uint32_t T);
 
 constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
 

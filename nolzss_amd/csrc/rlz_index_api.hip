@@ -4,7 +4,9 @@
 // index: targets matched against a resident reference").  Also nolzss_rlz_archive_open_index / _append_index: the
 // archive opened over an index and the batches appended to it on the device, which run the same match (DESIGN.md 5,
 // "Relative-LZ archive: batches appended from the index"), and nolzss_rlz_index_count / _locate: pattern batches
-// queried against the handle (the kernels: rlz_locate.hip; DESIGN.md 5, "Relative-LZ index: pattern count and locate").
+// queried against the handle (the kernels: rlz_locate.hip; DESIGN.md 5, "Relative-LZ index: pattern count and locate"),
+// and nolzss_rlz_index_seeds: the maximal exact matches of a target batch and their occurrences (the kernels:
+// rlz_seeds.hip; DESIGN.md 5, "Relative-LZ index: maximal match seeds").
 #include "rlz_handles.hpp"
 
 using namespace nolzss;
@@ -163,6 +165,7 @@ struct MatchOut {
 struct Searched {
     uint8_t *d_T;              // the batch bytes (upper case, separators)
     uint32_t *d_len, *d_rank;  // per position: the longest match and a rank that attains it
+    PackedText batch;          // the packed batch: its terminator table holds the target ends
 };
 
 Searched search_batch(Context &ctx, const nolzss_rlz_index &h, const Batch &b) {
@@ -173,12 +176,11 @@ Searched search_batch(Context &ctx, const nolzss_rlz_index &h, const Batch &b) {
         ProfScope ps(ctx.profiler(), "text_h2d", ctx.stream, (double)n);
         upload_bytes(ctx, m.d_T, b.tcat.data(), n);
     }
-    PackedText batch;
-    if (!pack_independent_text(ctx, m.d_T, n, b.separators, batch))
+    if (!pack_independent_text(ctx, m.d_T, n, b.separators, m.batch))
         throw std::runtime_error("rlz index: the batch holds bytes that are neither bases nor its separators");
     m.d_len = ctx.arena.alloc<uint32_t>(n);
     m.d_rank = ctx.arena.alloc<uint32_t>(n);
-    rlz_index_search(ctx, h.view, batch, m.d_len, m.d_rank);
+    rlz_index_search(ctx, h.view, m.batch, m.d_len, m.d_rank);
     return m;
 }
 
@@ -576,6 +578,140 @@ void index_query(const nolzss_rlz_index *h, const char *const *patterns, const s
     }
 }
 
+// ---- maximal match seeds -------------------------------------------------------------------------------------------
+// device memory of a seed query over a batch of n positions and k targets: per position the byte, the packed word
+// (1/4), len, rank, flag and slot (4 each), and -- every position can be a seed (a run of one base against a record of
+// one base), so the seeds' arrays are reserved with the batch and their number never moves the arena -- the list,
+// first, rep and off (4 each): 34; the terminator table; the seed records of a download chunk.  Per hit: as a locate.
+size_t seed_batch_bytes(size_t n, size_t k, size_t chunk) {
+    return 34 * n + 16 * k + sizeof(SeedRec) * chunk + (size_t(4) << 20);
+}
+
+static_assert(sizeof(nolzss_rlz_seed) == sizeof(SeedRec) && sizeof(SeedRec) == 32, "the kernels write nolzss_rlz_seed");
+
+// One batch of k >= 1 targets with at least one base against the handle, inside a session.  res is filled as the
+// results arrive: the seed records and hit_offsets once the counts are known, the hits last.  Returns false when the
+// hit total is beyond the pipeline: res then holds the seeds, their counts and the offsets, *total the number.
+bool query_seeds(Context &ctx, const nolzss_rlz_index &h, const Batch &b, size_t k, uint64_t min_length, uint64_t max_hits,
+                 nolzss_rlz_seeds_result &res, uint64_t *total_out) {
+    const size_t n = b.tcat.size();
+    const uint32_t cap = (max_hits == 0 || max_hits >= 0xffffffffull) ? 0xffffffffu : (uint32_t)max_hits;
+    const uint32_t min_len = min_length >= 0xffffffffull ? 0xffffffffu : (uint32_t)(min_length ? min_length : 1);
+    const size_t chunk_max = chunk_knob("NOLZSS_RLZ_LOCATE_CHUNK");
+    const size_t seed_chunk = n < chunk_max ? n : chunk_max;
+    hipStream_t s = ctx.stream;
+    Searched m;
+    uint32_t *d_seeds = nullptr, *d_first = nullptr, *d_rep = nullptr;
+    uint32_t S = 0;
+    // the batch up, packed and searched as a match does, the seeds flagged and listed: their number comes down as one word
+    auto run_search = [&] {
+        m = search_batch(ctx, h, b);
+        uint32_t *d_flag = ctx.arena.alloc<uint32_t>(n), *d_slot = ctx.arena.alloc<uint32_t>(n);
+        d_seeds = ctx.arena.alloc<uint32_t>(n);
+        uint32_t *d_total = ctx.arena.alloc<uint32_t>(1);
+        rlz_index_seed_list(ctx, m.d_len, (uint32_t)n, min_len, d_flag, d_slot, d_seeds, d_total);
+        download_bytes(ctx, &S, d_total, sizeof(uint32_t));
+        if (S > n) throw HipError("rlz index: more seeds than batch positions");
+        d_first = ctx.arena.alloc<uint32_t>(S ? S : 1);
+        d_rep = ctx.arena.alloc<uint32_t>(S ? S : 1);
+    };
+    reserve_arena_for(ctx, 0, seed_batch_bytes(n, k, seed_chunk));
+    run_search();
+    res.hit_offsets = calloc_array<uint64_t>((size_t)S + 1);
+    if (S == 0) return true;
+    // the sort key of a hit holds its seed in the 31 bits above (position, strand)
+    if (S > 0x7fffffffu) throw std::invalid_argument("rlz index: a batch may report at most 2^31 - 1 seeds, this one has " +
+                                                     std::to_string(S) + ": raise min_length or send fewer targets");
+    res.seeds = static_cast<nolzss_rlz_seed *>(alloc_factor_block(sizeof(nolzss_rlz_seed) * S));
+    if (!res.seeds) throw std::bad_alloc();
+    {
+        const size_t chunk = S < chunk_max ? S : chunk_max;
+        SeedRec *d_recs = ctx.arena.alloc<SeedRec>(chunk);
+        for (size_t c0 = 0; c0 < S; c0 += chunk) {
+            const size_t c = S - c0 < chunk ? S - c0 : chunk;
+            rlz_index_seed_intervals(ctx, h.view, m.batch, d_seeds, (uint32_t)c0, (uint32_t)c, cap, m.d_len, m.d_rank, d_first,
+                                     d_rep, d_recs);
+            ProfScope ps(ctx.profiler(), "seeds_d2h", s, (double)(sizeof(SeedRec) * c));
+            download_bytes(ctx, res.seeds + c0, d_recs, sizeof(SeedRec) * c);  // (waits: d_recs is free again)
+        }
+    }
+    res.num_seeds = S;
+    uint64_t total = 0;  // the hits to report, summed in 64 bits
+    for (size_t j = 0; j < S; ++j) {
+        res.hit_offsets[j] = total;
+        if (res.seeds[j].count <= cap) total += res.seeds[j].count;
+    }
+    res.hit_offsets[S] = total;
+    *total_out = total;
+    if (total == 0) return true;
+    if (total > kMaxText) return false;
+    const size_t T = (size_t)total, chunk = T < chunk_max ? T : chunk_max;
+    // the arena for the hits, by the rule of a locate: a reservation that is not a no-op may replace the slab (and the
+    // new one may be as large as the old), so the arena is then emptied and the batch is searched again in it, its seeds
+    // listed and their intervals looked up -- the records have come down and are not written a second time
+    const size_t extra = seed_batch_bytes(n, k, seed_chunk) + kLocateBytesPerHit * T + sizeof(LocateHit) * chunk;
+    if (arena_bytes_for(0) + extra > ctx.arena.capacity()) {
+        HIP_CHECK(hipStreamSynchronize(s));  // (nothing still reads the slab that goes)
+        reserve_arena_for(ctx, 0, extra);
+        ctx.arena.rewind(0);
+        const uint32_t before = S;
+        run_search();
+        if (S != before) throw HipError("rlz index: the seeds of a batch changed between two searches");
+        rlz_index_seed_intervals(ctx, h.view, m.batch, d_seeds, 0u, S, cap, m.d_len, m.d_rank, d_first, d_rep, nullptr);
+    }
+    const LocateSorted sorted =
+        rlz_index_seed_hits(ctx, h.view, (uint32_t)h.m, (uint32_t)n, d_seeds, m.d_len, S, d_rep, d_first, (uint32_t)T);
+    res.hits = static_cast<nolzss_rlz_hit *>(alloc_factor_block(sizeof(nolzss_rlz_hit) * T));
+    if (!res.hits) throw std::bad_alloc();
+    LocateHit *d_recs = ctx.arena.alloc<LocateHit>(chunk);
+    for (size_t c0 = 0; c0 < T; c0 += chunk) {
+        const size_t c = T - c0 < chunk ? T - c0 : chunk;
+        rlz_index_hit_records(ctx, sorted, c0, (uint32_t)c, d_recs);
+        ProfScope ps(ctx.profiler(), "hits_d2h", s, (double)(sizeof(LocateHit) * c));
+        download_bytes(ctx, res.hits + c0, d_recs, sizeof(LocateHit) * c);  // (waits: d_recs is free again)
+    }
+    res.num_hits = T;
+    return true;
+}
+
+void index_seeds(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                 uint64_t min_length, uint64_t max_hits, nolzss_rlz_seeds_result *out) {
+    if (!out) throw std::invalid_argument("output pointer is null");
+    std::memset(out, 0, sizeof *out);
+    if (!h) throw std::invalid_argument("handle is null");
+    Batch b;
+    prepare_batch(*h, targets, target_lens, k, b);
+    nolzss_rlz_seeds_result res;
+    std::memset(&res, 0, sizeof res);
+    bool fits = true;
+    uint64_t total = 0;
+    try {
+        if (b.tcat.size() == k) {  // no target, or none with a base: the device is not touched
+            res.hit_offsets = calloc_array<uint64_t>(1);
+        } else {
+            DeviceRestore restore;
+            Session ses(h->device, nullptr);
+            Context &ctx = ses.ctx();
+            {
+                ProfScope whole(ctx.profiler(), "rlz_index_seeds", ctx.stream);
+                fits = query_seeds(ctx, *h, b, k, min_length, max_hits, res, &total);
+            }
+            HIP_CHECK(hipStreamSynchronize(ctx.stream));
+            HIP_CHECK(hipGetLastError());
+            ctx.prof.collect();
+        }
+    } catch (...) {
+        nolzss_free_rlz_seeds_result(&res);
+        throw;
+    }
+    *out = res;  // ownership moves to the caller
+    if (!fits)
+        throw std::invalid_argument("rlz index: seeds would report " + std::to_string(total) + " hits, more than the " +
+                                    std::to_string(kMaxText) + " the 32-bit device pipeline takes: lower max_hits (it is " +
+                                    std::to_string(max_hits) + "; 0 means no cap), raise min_length (it is " +
+                                    std::to_string(min_length) + ") or send fewer targets");
+}
+
 }  // namespace
 
 extern "C" {
@@ -651,6 +787,19 @@ int nolzss_rlz_index_locate(const nolzss_rlz_index *h, const char *const *patter
         if (!hits) throw std::invalid_argument("output pointer is null");
         index_query(h, patterns, pattern_lens, q, max_hits, counts, hit_offsets, hits, num_hits);
     });
+}
+
+int nolzss_rlz_index_seeds(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                           uint64_t min_length, uint64_t max_hits, nolzss_rlz_seeds_result *out) {
+    return guarded([&] { index_seeds(h, targets, target_lens, k, min_length, max_hits, out); });
+}
+
+void nolzss_free_rlz_seeds_result(nolzss_rlz_seeds_result *r) {
+    if (!r) return;
+    free_block(r->seeds);
+    free_block(r->hit_offsets);
+    free_block(r->hits);
+    std::memset(r, 0, sizeof *r);
 }
 
 int nolzss_debug_rlz_locate_shifts(uint64_t block_length, uint64_t q, int *shifts, int *npasses) {

@@ -21,6 +21,7 @@ from .. import _noLZSS as _native
 
 RLZ_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8"), ("is_rc", "?"), ("is_literal", "?")])
 HIT_DTYPE = _native.HIT_DTYPE  # (position, record, is_rc): an occurrence of a pattern (RlzIndex.locate)
+SEED_DTYPE = _native.SEED_DTYPE  # (target, start, length, count): a maximal exact match of a target (RlzIndex.seeds)
 
 
 def split_and_rebase(records, target_offsets, target_lengths):
@@ -543,6 +544,40 @@ class RlzIndex:
                 "offsets": np.concatenate(offsets), "position": f["position"].copy(), "record": f["record"].copy(),
                 "record_offset": f["position"] - starts[f["record"]], "is_rc": f["is_rc"].astype(bool)}
 
+    def seeds(self, targets, min_length: int = 1, max_hits: int = 0):
+        """The maximal exact matches of every target with the reference, and where they occur -> dict(target, start,
+        length, counts, offsets, position, record, record_offset, is_rc).  A seed is a stretch [start, start + length) of
+        target `target` that occurs in the reference (on either strand with reverse complement) and cannot be extended
+        by one base to either side inside its target and still occur; the seeds ascend by (target, start).  Only seeds
+        of at least min_length bases are reported (the filter never makes a shorter neighbour maximal).  counts[j] = the
+        occurrences of seed j on both strands; seed j owns the hits [offsets[j], offsets[j + 1]), laid out and sorted as
+        locate lays out the hits of a pattern; a seed with more than max_hits occurrences (0: no cap) reports its count
+        and no hits.  The batch is searched once on the GPU and no per-position array comes down; a long list goes up in
+        several batches (plan_index_batches, a target is never split), target indices and offsets stitched."""
+        h = self._live()
+        min_length, max_hits = operator.index(min_length), operator.index(max_hits)
+        if min_length < 0:
+            raise ValueError("min_length must not be negative")
+        if max_hits < 0:
+            raise ValueError("max_hits must not be negative")
+        targets = list(targets)
+        plan = plan_index_batches([len(t) for t in targets], h.info["block_length"], MAX_TEXT)
+        seeds, offsets, hits, base = [], [np.zeros(1, dtype=np.uint64)], [], 0
+        for lo, hi in plan:
+            s, o, f = h.seeds(targets[lo:hi], min_length, max_hits)
+            s["target"] += np.uint64(lo)
+            seeds.append(s)
+            offsets.append(o[1:] + np.uint64(base))
+            hits.append(f)
+            base += int(o[-1])
+        s = np.concatenate(seeds) if seeds else np.zeros(0, dtype=SEED_DTYPE)
+        f = np.concatenate(hits) if hits else np.zeros(0, dtype=HIT_DTYPE)
+        starts = np.cumsum([0] + [len(r) + 1 for r in self._reference[:-1]], dtype=np.uint64)  # of every record in Rblk
+        return {"target": s["target"].copy(), "start": s["start"].copy(), "length": s["length"].copy(),
+                "counts": s["count"].copy(), "offsets": np.concatenate(offsets), "position": f["position"].copy(),
+                "record": f["record"].copy(), "record_offset": f["position"] - starts[f["record"]],
+                "is_rc": f["is_rc"].astype(bool)}
+
     def archive(self, targets, ids=None):
         """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
         targets = list(targets)
@@ -598,5 +633,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
