@@ -892,6 +892,37 @@ int nolzss_debug_local_sort(const uint32_t *words, const uint32_t *values, size_
                             int shift0, int npass, int key35, int want_regroup, int device, uint32_t *words_out,
                             uint32_t *values_out, uint32_t *lcp, uint32_t *new_slot, uint32_t *new_grp, uint32_t *survivors,
                             uint32_t *status);
+/* The permutation into text order (text_order.hpp: bucketed_scatter, permute_packed) on the caller's pairs.  idx[count] and
+ * val[count] (NOLZSS_TEXT_ORDER_PERMUTE_PACKED: packed[count], 64-bit words, instead of val) are uploaded; out, out2 and
+ * the 16-bit array are filled with `fill` (its low half for the 16-bit array) before the call, so that what no pair names
+ * is known afterwards.  flags: KEEP_INPUT, KEEP_VAL, SHORT_CODES as the arguments of bucketed_scatter; OUT2: the second
+ * target (rank + 1) is wanted; NARROW (with OUT2): the codes leave as uint16_t saturated at code_max, with a wide-code
+ * list of list_cap entries; PERMUTE_PACKED: permute_packed(idx, packed) instead.  rec_ends (optional): n_recs ascending
+ * record ends, the last = count = n_out, handed to record_scatter_plan (report word 9: a plan was made and passed on;
+ * refused, the call runs without one).
+ * Out: out[n_out], out2[n_out] (may be NULL unless OUT2 / PERMUTE_PACKED), narrow[n_out] and list_items[min(listed,
+ * list_cap)] (NARROW), idx_after[count] / val_after[count]: the buffers idx[0] / val[0] as the call left them (not with
+ * PERMUTE_PACKED), report[NOLZSS_TEXT_ORDER_REPORT_WORDS]: 0 the form that ran (NOLZSS_TEXT_ORDER_FORM_*), 1 the packed
+ * form was tried, 2 the codes it escaped, 3 its exception list overflowed, 4 a look-back gave up, 5 index bits of n_out,
+ * 6 window bits, 7 partition passes in front of the plain scatter, 8 the boolean result, 9 plan made, 10 entries
+ * appended to the wide-code list (may exceed list_cap).
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, n_out == 0 or >= 2^32, count >= 2^32, an unknown
+ * flag, NARROW without OUT2 or with code_max outside 1 .. 0xffff, record ends that do not ascend to count = n_out, and
+ * for an idx that is not a permutation of [0, count) where the form relies on one: PERMUTE_PACKED, record ends, or
+ * count == n_out > 2^22.  Elsewhere idx must not name a target below n_out twice (the result would depend on a race;
+ * nothing is stored out of bounds).  A separator suffix that is not the first of its record: NOLZSS_ERR_DEVICE with
+ * bucketed_scatter's message. */
+enum { NOLZSS_TEXT_ORDER_KEEP_INPUT = 1, NOLZSS_TEXT_ORDER_KEEP_VAL = 2, NOLZSS_TEXT_ORDER_SHORT_CODES = 4,
+       NOLZSS_TEXT_ORDER_OUT2 = 8, NOLZSS_TEXT_ORDER_NARROW = 16, NOLZSS_TEXT_ORDER_PERMUTE_PACKED = 32 };
+enum { NOLZSS_TEXT_ORDER_FORM_NONE = 0, NOLZSS_TEXT_ORDER_FORM_PLAIN = 1, NOLZSS_TEXT_ORDER_FORM_PARTIAL_THEN_PLAIN = 2,
+       NOLZSS_TEXT_ORDER_FORM_WINDOW_PERM = 3, NOLZSS_TEXT_ORDER_FORM_TWO_VALUE_HIST = 4, NOLZSS_TEXT_ORDER_FORM_PACKED = 5,
+       NOLZSS_TEXT_ORDER_FORM_RECORD_PLAN = 6, NOLZSS_TEXT_ORDER_FORM_RECORD_PLAN2 = 7,
+       NOLZSS_TEXT_ORDER_FORM_PERMUTE_PLAIN = 8, NOLZSS_TEXT_ORDER_FORM_PERMUTE_WINDOWS = 9 };
+#define NOLZSS_TEXT_ORDER_REPORT_WORDS 12
+int nolzss_debug_text_order(const uint32_t *idx, const uint32_t *val, const uint64_t *packed, size_t count, size_t n_out,
+                            uint32_t flags, uint32_t fill, size_t list_cap, uint32_t code_max, const uint32_t *rec_ends,
+                            size_t n_recs, int device, uint32_t *out, uint32_t *out2, uint16_t *narrow, uint64_t *list_items,
+                            uint32_t *idx_after, uint32_t *val_after, uint32_t *report);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

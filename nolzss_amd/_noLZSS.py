@@ -1748,6 +1748,62 @@ def debug_local_sort(words, values, starts, shift0: int, npass: int, key35: bool
     return out
 
 
+(TEXT_ORDER_KEEP_INPUT, TEXT_ORDER_KEEP_VAL, TEXT_ORDER_SHORT_CODES, TEXT_ORDER_OUT2, TEXT_ORDER_NARROW,
+ TEXT_ORDER_PERMUTE_PACKED) = 1, 2, 4, 8, 16, 32
+TEXT_ORDER_FORMS = ("none", "plain", "partial_then_plain", "window_perm", "two_value_hist", "packed", "record_plan",
+                    "record_plan2", "permute_plain", "permute_windows")
+
+
+def debug_text_order(idx, val=None, n_out=None, *, packed=None, keep_input: bool = True, keep_val: bool = True,
+                     short_codes: bool = True, want_out2: bool = False, narrow=None, rec_ends=None, fill: int = 0):
+    """The permutation into text order on the device over caller pairs (nolzss_debug_text_order, test hook):
+    bucketed_scatter(idx, val) into targets of n_out words pre-filled with `fill`, or with `packed` (u64)
+    permute_packed(idx, packed).  narrow = (list capacity, saturation value): the codes leave as uint16.  rec_ends: the
+    ends of the records of a block-diagonal permutation, for a RecordScatterPlan.  Returns {"out", "out2" (None unless
+    wanted), "narrow", "list" (the stored (position | code << 32) items), "listed", "idx_after", "val_after", "result",
+    "plan_made", "form" (one of TEXT_ORDER_FORMS), "packed_tried", "escaped", "list_overflow", "lookback_gave_up",
+    "nbits", "wb", "partition_passes"}."""
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    count = idx.size
+    permute = packed is not None
+    if permute:
+        packed = np.ascontiguousarray(packed, dtype=np.uint64)
+        if val is not None or packed.size != count:
+            raise ValueError("permute_packed takes idx and as many packed words")
+        n_out = count if n_out is None else n_out
+    else:
+        val = np.ascontiguousarray(val, dtype=np.uint32)
+        if val.size != count or n_out is None:
+            raise ValueError("idx and val differ in length, or n_out is not given")
+    if not 0 < n_out < 1 << 32:
+        raise ValueError("n_out 1 .. 2^32 - 1")
+    flags = ((TEXT_ORDER_KEEP_INPUT if keep_input else 0) | (TEXT_ORDER_KEEP_VAL if keep_val else 0) |
+             (TEXT_ORDER_SHORT_CODES if short_codes else 0) | (TEXT_ORDER_OUT2 if want_out2 else 0) |
+             (TEXT_ORDER_NARROW if narrow is not None else 0) | (TEXT_ORDER_PERMUTE_PACKED if permute else 0))
+    list_cap, code_max = (int(narrow[0]), int(narrow[1])) if narrow is not None else (0, 0)
+    if list_cap < 0 or list_cap >= 1 << 32:
+        raise ValueError("list capacity below 2^32")
+    ends = np.ascontiguousarray(rec_ends, dtype=np.uint32) if rec_ends is not None else None
+    out = np.zeros(n_out, dtype=np.uint32)
+    out2 = np.zeros(n_out, dtype=np.uint32) if (want_out2 or permute) else None
+    narrow_out = np.zeros(n_out, dtype=np.uint16) if narrow is not None else None
+    items = np.zeros(max(list_cap, 1), dtype=np.uint64) if narrow is not None else None
+    idx_after = np.zeros(max(count, 1), dtype=np.uint32) if not permute else None
+    val_after = np.zeros(max(count, 1), dtype=np.uint32) if not permute else None
+    report = np.zeros(12, dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    check(lib.nolzss_debug_text_order(idx.ctypes.data, ptr(val), ptr(packed), count, n_out, flags, fill & 0xffffffff, list_cap,
+                                      code_max, ptr(ends), ends.size if ends is not None else 0, _default_device,
+                                      out.ctypes.data, ptr(out2), ptr(narrow_out), ptr(items), ptr(idx_after), ptr(val_after),
+                                      report.ctypes.data))
+    r = [int(x) for x in report]
+    return {"out": out, "out2": out2, "narrow": narrow_out, "list": items[:min(r[10], list_cap)] if items is not None else None,
+            "listed": r[10], "idx_after": idx_after[:count] if not permute else None,
+            "val_after": val_after[:count] if not permute else None, "result": bool(r[8]), "plan_made": bool(r[9]),
+            "form": TEXT_ORDER_FORMS[r[0]], "packed_tried": bool(r[1]), "escaped": r[2], "list_overflow": bool(r[3]),
+            "lookback_gave_up": bool(r[4]), "nbits": r[5], "wb": r[6], "partition_passes": r[7]}
+
+
 LDS_PLAIN, LDS_RC = 0, 1
 LDS_OVERFLOW = 0xffffffff
 

@@ -234,6 +234,114 @@ int nolzss_debug_local_sort(const uint32_t *words, const uint32_t *values, size_
     });
 }
 
+int nolzss_debug_text_order(const uint32_t *idx, const uint32_t *val, const uint64_t *packed, size_t count, size_t n_out,
+                            uint32_t flags, uint32_t fill, size_t list_cap, uint32_t code_max, const uint32_t *rec_ends,
+                            size_t n_recs, int device, uint32_t *out, uint32_t *out2, uint16_t *narrow, uint64_t *list_items,
+                            uint32_t *idx_after, uint32_t *val_after, uint32_t *report) {
+    return guarded([&] {
+        const bool permute = flags & NOLZSS_TEXT_ORDER_PERMUTE_PACKED, want_out2 = permute || (flags & NOLZSS_TEXT_ORDER_OUT2),
+                   want_narrow = flags & NOLZSS_TEXT_ORDER_NARROW;
+        if (!out || !report || (count && !idx) || (want_out2 && !out2)) throw std::invalid_argument("null argument");
+        if (count && (permute ? !packed : (!val || !idx_after || !val_after))) throw std::invalid_argument("null argument");
+        if (flags >> 6) throw std::invalid_argument("unknown flag");
+        if (n_out == 0 || n_out >= (size_t(1) << 32) || count >= (size_t(1) << 32)) throw std::invalid_argument("n_out 1 .. 2^32 - 1, count below 2^32");
+        if (permute && (want_narrow || rec_ends || count != n_out))
+            throw std::invalid_argument("permute_packed takes a permutation of [0, count) and neither codes of 16 bits nor records");
+        if (want_narrow && (!want_out2 || !narrow || (list_cap && !list_items) || code_max == 0 || code_max > 0xffffu || list_cap >= (size_t(1) << 32)))
+            throw std::invalid_argument("the 16-bit codes need out2, their array, a list and a saturation value of 1 .. 0xffff");
+        if (rec_ends) {
+            if (n_recs == 0 || count != n_out || rec_ends[n_recs - 1] != n_out) throw std::invalid_argument("the record ends do not end at count = n_out");
+            for (size_t k = 0; k + 1 < n_recs; ++k)
+                if (rec_ends[k] >= rec_ends[k + 1]) throw std::invalid_argument("the record ends do not ascend");
+        }
+        // A permutation is the contract of the forms that assemble windows of the target (count == n_out beyond 2^22 pairs,
+        // a plan, permute_packed): checked here, before anything is launched.  Elsewhere idx must be free of duplicates below
+        // n_out (the plain scatter is a race on them), which is the caller's business: any winner stays in bounds.
+        if (permute || rec_ends || (count == n_out && count > (size_t(1) << 22))) {
+            std::vector<uint64_t> seen((count + 63) / 64, 0);
+            for (size_t k = 0; k < count; ++k) {
+                const uint32_t i = idx[k];
+                if (i >= count || (seen[i >> 6] >> (i & 63) & 1)) throw std::invalid_argument("idx is not a permutation of [0, count)");
+                seen[i >> 6] |= uint64_t(1) << (i & 63);
+            }
+        }
+        std::fill(report, report + NOLZSS_TEXT_ORDER_REPORT_WORDS, 0u);
+        static_assert((int)TextOrderForm::kPacked == NOLZSS_TEXT_ORDER_FORM_PACKED &&
+                          (int)TextOrderForm::kPermuteWindows == NOLZSS_TEXT_ORDER_FORM_PERMUTE_WINDOWS,
+                      "the header's values are the enum's");
+
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        hipStream_t s = ctx.stream;
+        // the caller's pairs and their scratch (20 bytes per pair; permute_packed: 12), the targets (10 bytes each with the
+        // list), what the largest form takes on top (permute_packed 12 + 1/4, the window permutation that keeps both inputs
+        // 8 + 1/2, the packed form 8 + 1/8 and then the histogram form 12 + 1/4 bytes per pair), the tables of a plan (1 KiB
+        // of counters and 48 bytes of descriptor per tile -- every 4096 pairs and up to two more per record --, 12 + 8 bytes
+        // per window and record)
+        const size_t tiles = count / kSortTile + 2 * n_recs + 2;
+        ctx.arena.reserve(count * 34 + n_out * 10 + list_cap * 8 + tiles * (4 * 256 + 4 * kSegDescWords + 64) + (size_t(64) << 20));
+        ArenaRewind rewind(ctx.arena);
+        uint32_t *d_out = ctx.arena.alloc<uint32_t>(n_out), *d_out2 = ctx.arena.alloc<uint32_t>(n_out);
+        HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_out), (int)fill, n_out, s));
+        HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_out2), (int)fill, n_out, s));
+        LstarCodes codes;
+        if (want_narrow) {
+            codes.narrow = ctx.arena.alloc<uint16_t>(n_out + 8);  // (padded as alloc_lstar pads it)
+            codes.list.cap = (uint32_t)list_cap;
+            codes.list.items = ctx.arena.alloc<uint64_t>(std::max<size_t>(list_cap, 1));
+            codes.list.count = ctx.arena.alloc<uint32_t>(1);
+            codes.list.max = code_max;
+            HIP_CHECK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(codes.narrow), (unsigned short)fill, n_out + 8, s));
+            HIP_CHECK(hipMemsetAsync(codes.list.count, 0, sizeof(uint32_t), s));
+        }
+        TextOrderReport rep;
+        bool result = true, plan_made = false;
+        const size_t room = std::max<size_t>(count, 1);
+        if (permute) {
+            uint32_t *d_idx = ctx.arena.alloc<uint32_t>(room);
+            uint64_t *d_packed = ctx.arena.alloc<uint64_t>(room);
+            HIP_CHECK(hipMemcpyAsync(d_idx, idx, count * 4, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(d_packed, packed, count * 8, hipMemcpyHostToDevice, s));
+            permute_packed(d_idx, d_packed, count, d_out, d_out2, ctx.arena, s, ctx.profiler(), &rep);
+        } else {
+            uint32_t *d_idx[2] = {ctx.arena.alloc<uint32_t>(room), ctx.arena.alloc<uint32_t>(room)};
+            uint32_t *d_val[2] = {ctx.arena.alloc<uint32_t>(room), ctx.arena.alloc<uint32_t>(2 * room)};  // (two values: 64-bit words)
+            uint32_t *const idx0 = d_idx[0], *const val0 = d_val[0];  // (the function may repoint its arrays)
+            HIP_CHECK(hipMemcpyAsync(idx0, idx, count * 4, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(val0, val, count * 4, hipMemcpyHostToDevice, s));
+            RecordScatterPlan plan;
+            if (rec_ends) plan_made = record_scatter_plan(std::vector<uint32_t>(rec_ends, rec_ends + n_recs), (uint32_t)n_out, ctx.arena, s, plan);
+            result = bucketed_scatter(d_idx, d_val, count, d_out, (uint32_t)n_out, ctx.arena, s, ctx.profiler(),
+                                      flags & NOLZSS_TEXT_ORDER_KEEP_INPUT, flags & NOLZSS_TEXT_ORDER_KEEP_VAL, plan_made ? &plan : nullptr,
+                                      want_out2 ? d_out2 : nullptr, flags & NOLZSS_TEXT_ORDER_SHORT_CODES, want_narrow ? &codes : nullptr, &rep);
+            HIP_CHECK(hipMemcpyAsync(idx_after, idx0, count * 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(val_after, val0, count * 4, hipMemcpyDeviceToHost, s));
+        }
+        HIP_CHECK(hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, s));
+        if (out2) HIP_CHECK(hipMemcpyAsync(out2, d_out2, n_out * 4, hipMemcpyDeviceToHost, s));
+        uint32_t listed = 0;
+        if (want_narrow) {
+            HIP_CHECK(hipMemcpyAsync(narrow, codes.narrow, n_out * 2, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(&listed, codes.list.count, 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            HIP_CHECK(hipMemcpyAsync(list_items, codes.list.items, std::min<size_t>(listed, list_cap) * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+        ctx.prof.collect();
+        report[0] = (uint32_t)rep.form;
+        report[1] = rep.packed_tried;
+        report[2] = rep.escaped;
+        report[3] = rep.list_overflow;
+        report[4] = rep.lookback_gave_up;
+        report[5] = (uint32_t)rep.nbits;
+        report[6] = (uint32_t)rep.wb;
+        report[7] = (uint32_t)rep.partition_passes;
+        report[8] = result;
+        report[9] = plan_made;
+        report[10] = listed;
+    });
+}
+
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak) {
     return guarded([&] {
         if (!capacity || !peak) throw std::invalid_argument("output pointer is null");

@@ -619,7 +619,7 @@ __global__ __launch_bounds__(kThreads) void code_census_kernel(const uint32_t *_
 // list overflowed or a look-back gave up -- the caller then runs the histogram form.  out.narrow: the codes leave as
 // uint16_t (code16.hpp).
 bool packed_text_order(const uint32_t *idx, const uint32_t *code, size_t count, const LstarCodes &out, uint32_t *out2, int nb, int wb,
-                       uint64_t *buf_a, Arena &arena, hipStream_t stream, Profiler *prof) {
+                       uint64_t *buf_a, Arena &arena, hipStream_t stream, Profiler *prof, TextOrderReport &report) {
     const bool trace = sort_knobs().trace;
     const int low_bits = wb + kRadixBits;
     const int code_bits = 64 - nb - low_bits;  // >= 12 for nb <= 30
@@ -678,6 +678,10 @@ bool packed_text_order(const uint32_t *idx, const uint32_t *code, size_t count, 
     HIP_CHECK(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     const bool ok = h[1] == 0 && h[5] == 0 && h[2] <= cap;
+    report.packed_tried = true;
+    report.escaped = h[2];
+    report.list_overflow = h[2] > cap;
+    report.lookback_gave_up = h[1] != 0 || h[5] != 0;
     if (trace) {
         unsigned long long *d_cnt = arena.alloc<unsigned long long>(7), hc[7];
         HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(hc), stream));
@@ -909,15 +913,15 @@ void window_perm_form(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t
 
 // Everything else: the plain scatter -- for a large target behind a partial scatter, one or two partition passes after
 // which all writes in flight fall into 2 MiB windows of the target, which one XCD's L2 can merge.  idx[1] / val[1] may be
-// pointed at other buffers (the arrays are local copies of the caller's pointers).
-void partial_then_plain_form(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out, int nbits, bool big,
+// pointed at other buffers (the arrays are local copies of the caller's pointers).  Returns the partition passes it made.
+int partial_then_plain_form(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out, int nbits, bool big,
                              bool keep_input, bool keep_val, Arena &arena, hipStream_t stream, Profiler *prof) {
-    int cur = 0;
+    int cur = 0, passes = 0;
     const int window_bits = 19;
     if (big && nbits > window_bits) {
         int shift = window_bits;
         radix_sort_pairs(idx, val, count, &shift, 1, arena, stream, prof);
-        cur = 1;
+        cur = passes = 1;
         if (nbits > window_bits + kRadixBits) {
             uint32_t *idx2[2] = {idx[1], keep_input ? arena.alloc<uint32_t>(count) : idx[0]};
             uint32_t *val2[2] = {val[1], (keep_input && keep_val) ? arena.alloc<uint32_t>(count) : val[0]};
@@ -925,12 +929,14 @@ void partial_then_plain_form(uint32_t *idx[2], uint32_t *val[2], size_t count, u
             radix_sort_pairs(idx2, val2, count, &shift, 1, arena, stream, prof);
             idx[1] = idx2[1];
             val[1] = val2[1];
+            passes = 2;
         }
     }
     ProfScope ps(prof, "bucket_scatter", stream, 12.0 * (double)count);
     const uint32_t num_tiles = (uint32_t)div_up(count, kTile);
     plain_scatter_kernel<<<xcd_grid(num_tiles), kThreads, 0, stream>>>(idx[cur], val[cur], count, out, n_out, num_tiles);
     KERNEL_CHECK();
+    return passes;
 }
 
 }  // namespace
@@ -938,12 +944,17 @@ void partial_then_plain_form(uint32_t *idx[2], uint32_t *val[2], size_t count, u
 // Chooses the form; the forms allocate from the arena, which is released here.
 bool bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out, Arena &arena,
                       hipStream_t stream, Profiler *prof, bool keep_input, bool keep_val, const RecordScatterPlan *plan,
-                      uint32_t *out2, bool short_codes, const LstarCodes *narrow) {
+                      uint32_t *out2, bool short_codes, const LstarCodes *narrow, TextOrderReport *report) {
+    TextOrderReport unread;
+    TextOrderReport &rep = report ? *report : unread;
+    rep = TextOrderReport{};
     if (count == 0) return narrow == nullptr;
     const size_t amark = arena.mark();
     const int nbits = index_bits(n_out);
     const bool two_passes = nbits <= 2 * kRadixBits + kWindowBitsMax;  // two digits and a window cover the target
     const int wb = two_passes ? window_bits_of(nbits) : kWindowBitsMax;
+    rep.nbits = nbits;
+    rep.wb = wb;
     const bool big = (size_t)n_out * 4 > (size_t(64) << 20) && count > (size_t(1) << 22);
     const bool perm = big && count == n_out;  // (a permutation of the whole target: the callers' contract)
     const bool has_plan = plan && plan->seg.desc;
@@ -953,22 +964,32 @@ bool bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t
         // one 8-byte word per pair, no histograms: 16 + 16 + 16 bytes per pair; the inputs are only read, so the
         // histogram form can still run when the exception list overflows or a look-back gives up
         const bool done = packed_text_order(idx[0], val[0], count, narrow ? *narrow : LstarCodes::of(out), out2, nbits, wb,
-                                            reinterpret_cast<uint64_t *>(val[1]), arena, stream, prof);
+                                            reinterpret_cast<uint64_t *>(val[1]), arena, stream, prof, rep);
         arena.rewind(amark);
-        if (done) return true;
+        if (done) {
+            rep.form = TextOrderForm::kPacked;
+            return true;
+        }
     }
     if (narrow) return false;  // (no other form writes 16-bit codes)
     bool separators_ok = true;
     if (two_value) {
         two_value_hist_form(idx, val, count, out, out2, n_out, wb, keep_input, arena, stream, prof);
+        rep.form = TextOrderForm::kTwoValueHist;
     } else {
         if (out2 && !plan_form) rank_scatter(idx[0], count, out2, n_out, stream, prof);
-        if (plan_form)
+        if (plan_form) {
             separators_ok = record_plan_form(idx, val, count, out, out2, *plan, arena, stream, prof);
-        else if (perm)
+            rep.form = out2 ? TextOrderForm::kRecordPlan2 : TextOrderForm::kRecordPlan;
+            rep.wb = plan->window_bits;
+        } else if (perm) {
             window_perm_form(idx, val, count, out, n_out, wb, !two_passes, keep_input, keep_val, arena, stream, prof);
-        else
-            partial_then_plain_form(idx, val, count, out, n_out, nbits, big, keep_input, keep_val, arena, stream, prof);
+            rep.form = TextOrderForm::kWindowPerm;
+        } else {
+            rep.partition_passes = partial_then_plain_form(idx, val, count, out, n_out, nbits, big, keep_input, keep_val, arena,
+                                                           stream, prof);
+            rep.form = rep.partition_passes ? TextOrderForm::kPartialThenPlain : TextOrderForm::kPlain;
+        }
     }
     arena.rewind(amark);
     if (!separators_ok) throw HipError("record scatter: a separator suffix is not the first of its record");
@@ -981,10 +1002,17 @@ bool packed_text_order_applies(size_t count, bool has_plan) {
 }
 
 void permute_packed(uint32_t *idx, uint64_t *packed, size_t count, uint32_t *out, uint32_t *out2, Arena &arena,
-                    hipStream_t stream, Profiler *prof) {
+                    hipStream_t stream, Profiler *prof, TextOrderReport *report) {
+    TextOrderReport unread;
+    TextOrderReport &rep = report ? *report : unread;
+    rep = TextOrderReport{};
     if (count == 0) return;
     const int nb = index_bits(count);
+    rep.nbits = nb;
+    rep.wb = window_bits_of(nb);
+    rep.form = TextOrderForm::kPermuteWindows;
     if (count <= (size_t(1) << 22) || nb > 2 * kRadixBits + kWindowBitsMax) {
+        rep.form = TextOrderForm::kPermutePlain;
         ProfScope ps(prof, "bucket_scatter", stream, 20.0 * (double)count);
         const unsigned g = (unsigned)std::min<size_t>(div_up(count, kThreads), 256u * 16u);
         plain_packed_scatter_kernel<<<g, kThreads, 0, stream>>>(idx, packed, count, out, out2);

@@ -35,26 +35,49 @@ struct RecordScatterPlan {
     uint32_t n = 0;
     int window_bits = 0;
 };
+// What bucketed_scatter / permute_packed did with a call (filled on the host only; no kernel knows of it).
+enum class TextOrderForm : int {
+    kNone = 0,          // nothing ran (count == 0), or nothing usable was written (narrow, and the packed form did not finish)
+    kPlain,             // plain_scatter_kernel alone (out2: plain_rank_scatter_kernel beside it)
+    kPartialThenPlain,  // one or two partition passes by the bits above a 2^19 window, then the plain scatter
+    kWindowPerm,        // one value: partition passes and the windows assembled in LDS
+    kTwoValueHist,      // two values in one 64-bit word, passes with histograms
+    kPacked,            // two values and the low index bits in one word, look-back passes (packed_text_order)
+    kRecordPlan,        // RecordScatterPlan: one segmented pass, the record windows, the separators; one value
+    kRecordPlan2,       // ... two values
+    kPermutePlain,      // permute_packed: plain_packed_scatter_kernel
+    kPermuteWindows,    // permute_packed: two passes and the windows
+};
+struct TextOrderReport {
+    TextOrderForm form = TextOrderForm::kNone;  // the form whose result stands
+    bool packed_tried = false;                  // packed_text_order ran (its result stands only with form == kPacked)
+    uint32_t escaped = 0;                       // codes at or above the escape threshold (may exceed the list's capacity)
+    bool list_overflow = false;                 // ... did exceed it
+    bool lookback_gave_up = false;              // a look-back of either pass gave up
+    int partition_passes = 0;                   // kPartialThenPlain: 1 or 2
+    int nbits = 0, wb = 0;                      // index_bits(n_out) and the window bits of the permutation forms
+};
 // out2 (optional): a second target, out2[idx[k]] = k + 1 -- for the pairs (sa[r], code[r]) of the pipeline that is
 // the inverse suffix array in its 1-based form, delivered by the same permutation.  val[1] must then hold
 // 2 * count words (the pairs travel with 64-bit values).  A permutation of up to 2^30 targets then goes without
-// histograms, each pair in ONE 8-byte word whose code field holds 72 - 2 * nb bits or more; larger codes take an
+// histograms, each pair in ONE 8-byte word whose code field holds 72 - 2 * nb bits (21 at nb = 25, where the windows keep 2^10 entries); larger codes take an
 // exception list (and, should it overflow, the histogram form runs after all).  short_codes = false keeps the
 // histogram form: codes that are mostly large (a flag in bit 31) would only overflow the list.
 // narrow (optional, with out2; out is then not used): the values are factor-length codes and leave in their 16-bit form
 // (code16.hpp), which only the packed form writes -- false, with nothing usable written, when that form does not take
 // this permutation (packed_text_order_applies) or gave up.  Without narrow the result is always true.
+// report (optional, for the test hook nolzss_debug_text_order): what the chooser did.
 bool bucketed_scatter(uint32_t *idx[2], uint32_t *val[2], size_t count, uint32_t *out, uint32_t n_out,
                       Arena &arena, hipStream_t stream, Profiler *prof, bool keep_input, bool keep_val = true,
                       const RecordScatterPlan *plan = nullptr, uint32_t *out2 = nullptr, bool short_codes = true,
-                      const LstarCodes *narrow = nullptr);
+                      const LstarCodes *narrow = nullptr, TextOrderReport *report = nullptr);
 // does bucketed_scatter take the packed form for a two-value permutation of `count` targets?
 bool packed_text_order_applies(size_t count, bool has_plan);
 // The same permutation for pairs that already carry both values in one 64-bit word (low half -> out, high half ->
 // out2) and are a permutation of [0, count): out[idx[k]] = (uint32_t)packed[k], out2[idx[k]] = packed[k] >> 32.
 // Both inputs are overwritten (they serve as buffers of the later passes).
 void permute_packed(uint32_t *idx, uint64_t *packed, size_t count, uint32_t *out, uint32_t *out2, Arena &arena,
-                    hipStream_t stream, Profiler *prof);
+                    hipStream_t stream, Profiler *prof, TextOrderReport *report = nullptr);
 // The plan for a text of n symbols whose records end at h_terms[k] (separator positions, the last entry = n);
 // false when the shape does not allow it (a record longer than 2^22 bases, or too many short ones).  The
 // tables live in the arena (not released here).
