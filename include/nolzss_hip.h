@@ -923,6 +923,27 @@ int nolzss_debug_text_order(const uint32_t *idx, const uint32_t *val, const uint
                             uint32_t flags, uint32_t fill, size_t list_cap, uint32_t code_max, const uint32_t *rec_ends,
                             size_t n_recs, int device, uint32_t *out, uint32_t *out2, uint16_t *narrow, uint64_t *list_items,
                             uint32_t *idx_after, uint32_t *val_after, uint32_t *report);
+/* The rounds of one group-sort pass of the suffix-array construction (group_sort.hpp: group_dir_kernel and the tiled,
+ * 128-, 256- and 1024-member forms of group_sort_kernel, as window rounds or as pivot rounds) on the caller's groups,
+ * without the regroup behind them -- the launch function of the construction itself (group_sort_rounds).
+ * text[n] is packed as every text is (pack_text: 2, 4 or 8 bits per symbol by its alphabet; nucleotides plus at most 250
+ * byte values that occur once are packed segmented, the once-only bytes becoming terminators).  sa[n]: only the slots of
+ * the listed groups are read and written.  slot[m] / grp[m]: the active list, in ascending slot order, grp = the head slot
+ * of the entry's group; the members of a group hold consecutive list positions and the slots grp .. grp + size - 1, and
+ * every listed group has at least two members.  h0: the symbols the members of every group agree on, in front of their
+ * terminators (NOT CHECKED: the caller's business; nothing is read out of bounds if it does not hold).  pivot: pivot rounds,
+ * depth_cap symbols deep at the most; else window rounds (depth_cap is not read).  max_rounds <= 24.  lcp_mark (optional,
+ * n entries): the equalising round's filter, only groups with lcp_mark[grp + 1] == 0xffffffff are taken.
+ * Out: sa, out_lo[m] (strictly smaller members of the entry's group), lcp_list[m] (0 at the head of a taken group, the
+ * LCP of a boundary that appeared, else 0xffffffff), *min_depth (symbols every class that stays tied agrees on at least;
+ * 0xffffffff: nothing reported), info (optional, 3 words): bits per symbol, entries of the terminator table, segmented.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, n == 0, m > n, max_rounds > 24, a list entry
+ * with grp > slot or slot >= n, a listed slot whose sa entry is >= n, slots that do not ascend, a group that does not hold
+ * consecutive list positions and the slots from its head slot on, a listed group of one member; behind the packing and
+ * in front of the rounds for more than 65536 terminators. */
+int nolzss_debug_group_sort(const uint8_t *text, size_t n, uint32_t *sa, const uint32_t *slot, const uint32_t *grp, size_t m,
+                            uint32_t h0, int pivot, uint32_t max_rounds, uint32_t depth_cap, const uint32_t *lcp_mark,
+                            int device, uint32_t *out_lo, uint32_t *lcp_list, uint32_t *min_depth, uint32_t *info);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

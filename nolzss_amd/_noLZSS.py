@@ -1804,6 +1804,41 @@ def debug_text_order(idx, val=None, n_out=None, *, packed=None, keep_input: bool
             "lookback_gave_up": bool(r[4]), "nbits": r[5], "wb": r[6], "partition_passes": r[7]}
 
 
+GROUP_SORT_ROUNDS = 24
+
+
+def debug_group_sort(text, sa, slot, grp, h0: int, pivot: bool = False, max_rounds: int = GROUP_SORT_ROUNDS,
+                     depth_cap: int = 0xffffffff, lcp_mark=None):
+    """The rounds of one group-sort pass of the suffix-array construction on the device over caller groups
+    (nolzss_debug_group_sort, test hook): group_dir_kernel and the four forms of group_sort_kernel, as window rounds or
+    (pivot) as pivot rounds at most depth_cap symbols deep, with no regroup behind them.  `text` (bytes) is packed as
+    every text is; `sa` holds n entries, of which only the slots of the listed groups are read and written; `slot` /
+    `grp` are the active list (ascending slots, grp = head slot of the group, groups of at least two members on
+    consecutive list positions and slots); `lcp_mark` (n entries) is the equalising round's filter.
+    PRECONDITION, not checked: the members of every group agree on their first h0 symbols and none of them ends in front
+    of h0.  Returns {"sa", "out_lo", "lcp_list", "min_depth", "bits", "terms", "segmented"}."""
+    text = np.frombuffer(bytes(text), dtype=np.uint8)
+    sa = np.array(sa, dtype=np.uint32)  # (a copy: the call writes it)
+    slot = np.ascontiguousarray(slot, dtype=np.uint32)
+    grp = np.ascontiguousarray(grp, dtype=np.uint32)
+    if sa.size != text.size or slot.size != grp.size:
+        raise ValueError("sa holds one entry per symbol, slot and grp one per list entry")
+    mark = np.ascontiguousarray(lcp_mark, dtype=np.uint32) if lcp_mark is not None else None
+    if mark is not None and mark.size != text.size:
+        raise ValueError("lcp_mark holds one entry per symbol")
+    if not (0 <= h0 < 1 << 32 and 0 <= max_rounds < 1 << 32 and 0 <= depth_cap < 1 << 32):
+        raise ValueError("h0, max_rounds and depth_cap are 32-bit values")
+    m = slot.size
+    out_lo, lcp_list = np.zeros(max(m, 1), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+    depth, info = C.c_uint32(), np.zeros(3, dtype=np.uint32)
+    check(lib.nolzss_debug_group_sort(text.ctypes.data, text.size, sa.ctypes.data, slot.ctypes.data, grp.ctypes.data, m, h0,
+                                      1 if pivot else 0, max_rounds, depth_cap, mark.ctypes.data if mark is not None else None,
+                                      _default_device, out_lo.ctypes.data, lcp_list.ctypes.data, C.byref(depth),
+                                      info.ctypes.data))
+    return {"sa": sa, "out_lo": out_lo[:m], "lcp_list": lcp_list[:m], "min_depth": depth.value, "bits": int(info[0]),
+            "terms": int(info[1]), "segmented": bool(info[2])}
+
+
 LDS_PLAIN, LDS_RC = 0, 1
 LDS_OVERFLOW = 0xffffffff
 

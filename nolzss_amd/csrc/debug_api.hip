@@ -1,6 +1,8 @@
 // debug_api.hip -- debug hooks (plans, intermediate arrays, primitives) and the stage profiler
 // (part of the C ABI layer of libnolzss_hip.so, include/nolzss_hip.h; shared declarations: api_internal.hpp)
 #include "api_internal.hpp"
+#include "queues.hpp"
+#include "sa_internal.hpp"
 
 using namespace nolzss;
 using namespace nolzss::api;
@@ -339,6 +341,61 @@ int nolzss_debug_text_order(const uint32_t *idx, const uint32_t *val, const uint
         report[8] = result;
         report[9] = plan_made;
         report[10] = listed;
+    });
+}
+
+int nolzss_debug_group_sort(const uint8_t *text, size_t n, uint32_t *sa, const uint32_t *slot, const uint32_t *grp, size_t m,
+                            uint32_t h0, int pivot, uint32_t max_rounds, uint32_t depth_cap, const uint32_t *lcp_mark, int device,
+                            uint32_t *out_lo, uint32_t *lcp_list, uint32_t *min_depth, uint32_t *info) {
+    return guarded([&] {
+        if (!text || !sa || !min_depth || (m && (!slot || !grp || !out_lo || !lcp_list))) throw std::invalid_argument("null argument");
+        if (n == 0 || n > kMaxText) throw std::invalid_argument("1 .. 2^32 - 2^19 - 1 symbols");
+        if (m > n) throw std::invalid_argument("more list entries than suffixes");
+        if (max_rounds > kGroupSortRounds) throw std::invalid_argument("more rounds than the kernels' budget");
+        // the list as the kernels rely on it: ascending slots, every group on consecutive list positions and on the slots
+        // from its head slot on, at least two members, every suffix below n
+        for (size_t a = 0, first = 0; a < m; ++a) {
+            const uint32_t g = grp[a], s = slot[a];
+            if (g > s || s >= n) throw std::invalid_argument("a list entry with grp <= slot < n violated");
+            if (sa[s] >= n) throw std::invalid_argument("a listed slot holds no suffix of the text");
+            const bool head = a == 0 || grp[a - 1] != g;
+            if (a > 0 && s <= slot[a - 1]) throw std::invalid_argument("the list is not in ascending slot order");
+            if (head) first = a;
+            if (s != g + (a - first)) throw std::invalid_argument("a group does not hold the slots from its head slot on");
+            if ((a + 1 == m || grp[a + 1] != g) && a == first) throw std::invalid_argument("a listed group of one member");
+        }
+        *min_depth = 0xffffffffu;
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        hipStream_t s = ctx.stream;
+        // text and packed text, sa and the marks, the list and its outputs, three queues of two arrays (a region per shard)
+        ctx.arena.reserve(n * 12 + m * 16 + 24 * (m + 256 * (size_t)kQShards) + (size_t(64) << 20));
+        ArenaRewind rewind(ctx.arena);
+        uint8_t *d_text = ctx.arena.alloc<uint8_t>(n);
+        upload_bytes(ctx, d_text, text, n);
+        const PackedText packed = pack_text(ctx, d_text, n);
+        if (info) {
+            info[0] = (uint32_t)packed.bits;
+            info[1] = packed.terms.count;
+            info[2] = packed.segmented;
+        }
+        // (what suffix_array.hip refuses in front of these rounds: the terminator index travels in 16 bits)
+        if (packed.terms.count > 0x10000u) throw std::invalid_argument("at most 65536 terminators");
+        if (m == 0) return;
+        uint32_t *d_sa = ctx.arena.alloc<uint32_t>(n), *d_mark = lcp_mark ? ctx.arena.alloc<uint32_t>(n) : nullptr;
+        uint32_t *d_slot = ctx.arena.alloc<uint32_t>(m), *d_grp = ctx.arena.alloc<uint32_t>(m);
+        uint32_t *d_lo = ctx.arena.alloc<uint32_t>(m), *d_lcp = ctx.arena.alloc<uint32_t>(m), *d_depth = ctx.arena.alloc<uint32_t>(1);
+        HIP_CHECK(hipMemcpyAsync(d_sa, sa, n * 4, hipMemcpyHostToDevice, s));
+        if (lcp_mark) HIP_CHECK(hipMemcpyAsync(d_mark, lcp_mark, n * 4, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_slot, slot, m * 4, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_grp, grp, m * 4, hipMemcpyHostToDevice, s));
+        group_sort_rounds(ctx, packed, d_slot, d_grp, (uint32_t)m, d_sa, h0, pivot != 0, max_rounds, depth_cap, d_mark, d_lo, d_lcp, d_depth);
+        HIP_CHECK(hipMemcpyAsync(sa, d_sa, n * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(out_lo, d_lo, m * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(lcp_list, d_lcp, m * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(min_depth, d_depth, 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        ctx.prof.collect();
     });
 }
 

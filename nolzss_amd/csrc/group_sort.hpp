@@ -28,7 +28,7 @@ constexpr uint32_t kGroupSortMid = 256;    // up to here: one wavefront per grou
 constexpr uint32_t kGroupSortMid0 = 128;
 constexpr uint32_t kGroupSortMax = 1024;   // up to here: 256 threads per group; beyond: left to the doubling rounds
 constexpr uint32_t kScanWords = 8;         // 64-bit words a member scans per round to find where its segment splits
-constexpr uint32_t kGroupSortRounds = 24;  // rounds before a group gives up (each: kScanWords words + one window)
+// (kGroupSortRounds, the rounds before a group gives up: sa_internal.hpp, the test hook checks its argument against it)
 
 // PIVOT rounds (round 4; kPivot): collections of similar sequences -- dozens to hundreds of copies of a genome, a
 // fraction of a percent apart -- tie in groups as large as the collection, and somebody in such a group differs

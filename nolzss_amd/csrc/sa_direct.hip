@@ -551,25 +551,13 @@ void direct_round(SaBuild &b, int k_syms) {
     if (knobs.trace) fprintf(stderr, "[nolzss]   direct round (cap %u symbols): %u still tied, on at least %llu symbols\n", cap, b.m, (unsigned long long)b.h);
 }
 
-namespace {
-
-enum class GroupSortMode { kDirect2, kEqualise, kPivot };
-
-// One pass of the group-sort kernels over the active list, depth_cap symbols deep at the most (pivot passes), and the
-// regroup behind it.
-void group_sort_pass(SaBuild &b, GroupSortMode mode, uint32_t depth_cap) {
-    const PackedText &text = b.text;
-    hipStream_t s = b.stream();
-    Arena &arena = b.arena();
-    const uint32_t m = b.m;
-    const bool pivot = mode == GroupSortMode::kPivot, equalise = mode == GroupSortMode::kEqualise;
-    const uint32_t max_rounds = equalise ? std::min<uint32_t>(kGroupSortRounds, (b.depth_compared - (uint32_t)b.h + 63u) / 64u) : kGroupSortRounds;
-    const uint32_t *lcp_mark = equalise ? b.lcp : nullptr;
-    const uint32_t *slot = b.slot(), *grp = b.grp();
-    const size_t d2_mark = arena.mark();
-    uint32_t *out_lo = arena.alloc<uint32_t>(m);
-    uint32_t *lcp_list = arena.alloc<uint32_t>(m);
-    uint32_t *d_min_depth = arena.alloc<uint32_t>(1);
+// The rounds of one pass without the regroup behind them (sa_internal.hpp): the queues of the larger groups, group_dir_kernel
+// and the four group_sort_kernel launches, all on the context's stream.  What it takes from the arena is the caller's to rewind.
+void group_sort_rounds(Context &ctx, const PackedText &text, const uint32_t *slot, const uint32_t *grp, uint32_t m, uint32_t *sa,
+                       uint32_t h0, bool pivot, uint32_t max_rounds, uint32_t depth_cap, const uint32_t *lcp_mark,
+                       uint32_t *out_lo, uint32_t *lcp_list, uint32_t *d_min_depth) {
+    hipStream_t s = ctx.stream;
+    Arena &arena = ctx.arena;
     HIP_CHECK(hipMemsetAsync(d_min_depth, 0xff, sizeof(uint32_t), s));
     const unsigned dir_blocks = (unsigned)div_up(m, kThreads);
     ShardQueue q_mid0, q_mid, q_big;
@@ -583,9 +571,8 @@ void group_sort_pass(SaBuild &b, GroupSortMode mode, uint32_t depth_cap) {
     }
     HIP_CHECK(hipMemsetAsync(qcounts, 0, 3 * kQShards * kQPad * sizeof(uint32_t), s));
     {
-        ProfScope ps(b.ctx.profiler(), "sa_direct_sort2", s);
-        const uint32_t h32 = (uint32_t)b.h;
-        group_dir_kernel<<<dir_blocks, kThreads, 0, s>>>(slot, grp, m, h32, out_lo, lcp_list, q_mid0, q_mid, q_big, d_min_depth, lcp_mark);
+        ProfScope ps(ctx.profiler(), "sa_direct_sort2", s);
+        group_dir_kernel<<<dir_blocks, kThreads, 0, s>>>(slot, grp, m, h0, out_lo, lcp_list, q_mid0, q_mid, q_big, d_min_depth, lcp_mark);
         KERNEL_CHECK();
         // small groups by tiles of the list; the larger ones from the queues (the consumers read the shard
         // counts on the device: no read-back in between)
@@ -599,26 +586,47 @@ void group_sort_pass(SaBuild &b, GroupSortMode mode, uint32_t depth_cap) {
             constexpr int kBits = decltype(B)::value;
             if (pivot) {
                 group_sort_kernel<kBits, 64, kSmallN, true, true><<<tiles, 64, 0, s>>>(
-                    q_mid, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
+                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
                 group_sort_kernel<kBits, 128, kMid0N, false, true><<<gm, 128, 0, s>>>(
-                    q_mid0, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
+                    q_mid0, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
                 group_sort_kernel<kBits, 256, kMidN, false, true><<<gm, 256, 0, s>>>(
-                    q_mid, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
+                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
                 group_sort_kernel<kBits, 256, kBigN, false, true><<<gb, 256, 0, s>>>(
-                    q_big, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
+                    q_big, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
             } else {
                 group_sort_kernel<kBits, 64, kSmallN, true><<<tiles, 64, 0, s>>>(
-                    q_mid, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
+                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
                 group_sort_kernel<kBits, 64, kMid0N, false><<<gm, 64, 0, s>>>(
-                    q_mid0, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
+                    q_mid0, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
                 group_sort_kernel<kBits, 64, kMidN, false><<<gm, 64, 0, s>>>(
-                    q_mid, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
+                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
                 group_sort_kernel<kBits, 256, kBigN, false><<<gb, 256, 0, s>>>(
-                    q_big, slot, grp, m, b.sa, text.words, text.terms, h32, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
+                    q_big, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
             }
         });
         KERNEL_CHECK();
     }
+}
+
+namespace {
+
+enum class GroupSortMode { kDirect2, kEqualise, kPivot };
+
+// One pass of the group-sort kernels over the active list, depth_cap symbols deep at the most (pivot passes), and the
+// regroup behind it.
+void group_sort_pass(SaBuild &b, GroupSortMode mode, uint32_t depth_cap) {
+    const PackedText &text = b.text;
+    Arena &arena = b.arena();
+    const uint32_t m = b.m;
+    const bool pivot = mode == GroupSortMode::kPivot, equalise = mode == GroupSortMode::kEqualise;
+    const uint32_t max_rounds = equalise ? std::min<uint32_t>(kGroupSortRounds, (b.depth_compared - (uint32_t)b.h + 63u) / 64u) : kGroupSortRounds;
+    const uint32_t *lcp_mark = equalise ? b.lcp : nullptr;
+    const uint32_t *slot = b.slot(), *grp = b.grp();
+    const size_t d2_mark = arena.mark();
+    uint32_t *out_lo = arena.alloc<uint32_t>(m);
+    uint32_t *lcp_list = arena.alloc<uint32_t>(m);
+    uint32_t *d_min_depth = arena.alloc<uint32_t>(1);
+    group_sort_rounds(b.ctx, text, slot, grp, m, b.sa, (uint32_t)b.h, pivot, max_rounds, depth_cap, lcp_mark, out_lo, lcp_list, d_min_depth);
     RegroupIn in;
     in.lo = out_lo;
     in.lcp_list = lcp_list;

@@ -175,6 +175,16 @@ void write_all_ranks(SaBuild &b);
 // ---- sa_direct.hip --------------------------------------------------------------------------------------------------------
 void direct_round(SaBuild &b, int k_syms);
 void group_sort_passes(SaBuild &b);
+// The rounds of one group-sort pass (group_sort.hpp) over the active list slot[m] / grp[m], without the regroup behind
+// them: group_dir_kernel and the four group_sort_kernel launches, window rounds or (pivot) pivot rounds depth_cap symbols
+// deep, on ctx.stream.  The members of a group agree on h0 symbols; lcp_mark (optional, the equalising round): only the
+// groups whose boundary lcp_mark[g + 1] still holds the plain pending code are taken.  Out: the new order of every taken
+// group in sa, out_lo[m], lcp_list[m] and *d_min_depth (0xffffffff: nothing stays tied below a known depth).  The queues
+// come from ctx.arena: the caller owns the mark.  Shared by group_sort_pass and the test hook nolzss_debug_group_sort.
+constexpr uint32_t kGroupSortRounds = 24;  // rounds before a group gives up (each: kScanWords words + one window)
+void group_sort_rounds(Context &ctx, const PackedText &text, const uint32_t *slot, const uint32_t *grp, uint32_t m, uint32_t *sa,
+                       uint32_t h0, bool pivot, uint32_t max_rounds, uint32_t depth_cap, const uint32_t *lcp_mark,
+                       uint32_t *out_lo, uint32_t *lcp_list, uint32_t *d_min_depth);
 
 // ---- sa_repeats.hip -------------------------------------------------------------------------------------------------------
 // out[0] = members beyond the first `limit` of their group, [1] = groups with more than `limit` members, [2] = groups,
