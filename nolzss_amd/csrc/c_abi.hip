@@ -236,10 +236,19 @@ void run_plain(Context &ctx, const uint8_t *d_text, size_t n, size_t start_pos, 
     build_suffix_array(ctx, text, sa, isa, lcp, &isa_deferred);
     // (the pyramids are only allocated here: the candidate kernel writes their first level from the blocks it holds
     // in LDS anyway, build_lstar fills the rest)
-    const RecordLookup lookup{sa, isa, lcp, alloc_pyramid(sa, (uint32_t)n, arena), alloc_pyramid(lcp, (uint32_t)n + 1, arena)};
+    RecordLookup lookup{sa, isa, lcp, alloc_pyramid(sa, (uint32_t)n, arena), alloc_pyramid(lcp, (uint32_t)n + 1, arena)};
+    // The rank blocks of the factor look-ups (rank_blocks.hpp; 8 n bytes, written by the candidate kernel, alive as long
+    // as the lookup) are taken only by an arena that got its worst-case size: one that settled for less keeps to the
+    // 49 n bytes of the documented capacity, and the look-ups read sa[] / lcp[] as before.  A run that delivers no
+    // records (counts, starts, lengths) looks nothing up and takes none.
+    const bool looks_up = rq.records || (dbg && dbg->records);
+    RankBlock *blocks = looks_up && arena.capacity() >= arena_bytes_for(n) ? alloc_rank_blocks(ctx, (uint32_t)n) : nullptr;
+    lookup.blocks = blocks;
+    static const bool trace = getenv("NOLZSS_TRACE") != nullptr;
+    if (trace && looks_up) fprintf(stderr, "[nolzss] factor look-ups: %s\n", blocks ? "rank blocks" : "sa[] and lcp[]");
     // (16-bit codes where the stage can write them; the length outputs read 32-bit codes)
     LstarCodes lstar = alloc_lstar(ctx, (uint32_t)n, isa_deferred && !rq.lengths);
-    build_lstar(ctx, (uint32_t)n, sa, isa, lcp, lookup.Psa, lookup.Plcp, lstar, isa_deferred ? isa : nullptr, &text);
+    build_lstar(ctx, (uint32_t)n, sa, isa, lcp, lookup.Psa, lookup.Plcp, lstar, isa_deferred ? isa : nullptr, &text, blocks);
     if (dbg) {
         // the exports are 32-bit: 16-bit codes are widened once, for here only -- the cursor below still reads them
         const size_t dmark = arena.mark();

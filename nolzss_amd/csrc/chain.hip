@@ -459,6 +459,110 @@ __global__ __launch_bounds__(kThreads) void factor_kernel(const uint32_t *__rest
     }
 }
 
+// The blocks of a wavefront's 64 factors, read by the wavefront together.  A lane that read its own block would ask for
+// one line with eight 16-byte loads, and every such instruction would touch 64 different lines: the first form of
+// factor_block_kernel did that and was bound by the requests, not by the fills (363 B of fills per factor instead of
+// 610, and 10 % SLOWER than factor_kernel; profiles/factor_rank_blocks_ab.txt).  Here eight consecutive lanes read the
+// eight quads of ONE line per instruction -- round j brings the block of the j-th factor of every group of eight --
+// and the quads change lanes through LDS: every line is requested once.
+constexpr uint32_t kNoBlock = 0xffffffffu;
+struct BlockQuads {
+    uint4 q[8];
+};
+// round j: quad (lane & 7) of the block that lane (lane & ~7) + j wants (kNoBlock: nothing is read)
+__device__ __forceinline__ BlockQuads request_blocks(const RankBlock *__restrict__ blocks, uint32_t want) {
+    const int p = lane_id() & 7, g8 = lane_id() & ~7;
+    BlockQuads Q;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t b = (uint32_t)__shfl((int)want, g8 + j);
+        Q.q[j] = make_uint4(0u, 0u, 0u, 0u);
+        if (b != kNoBlock) Q.q[j] = reinterpret_cast<const uint4 *>(blocks + b)[p];
+    }
+    return Q;
+}
+// rows: 64 x 8 quads of the wavefront's own LDS; quad k of row w sits at slot k ^ (w & 7), so that the eight lanes that
+// write one row and the eight that read eight rows each meet eight different quads of the banks
+__device__ __forceinline__ RankBlock exchange_blocks(uint4 *rows, const BlockQuads &Q) {
+    const int lane = lane_id(), p = lane & 7, g8 = lane & ~7;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rows[(g8 + j) * 8 + (p ^ j)] = Q.q[j];
+    __builtin_amdgcn_wave_barrier();  // (one wavefront: its LDS accesses execute in order)
+    RankBlock B;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint4 x = rows[lane * 8 + (k ^ p)], y = rows[lane * 8 + ((4 + k) ^ p)];
+        B.sa[4 * k] = x.x;
+        B.sa[4 * k + 1] = x.y;
+        B.sa[4 * k + 2] = x.z;
+        B.sa[4 * k + 3] = x.w;
+        B.lcp[4 * k] = y.x;
+        B.lcp[4 * k + 1] = y.y;
+        B.lcp[4 * k + 2] = y.z;
+        B.lcp[4 * k + 3] = y.w;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return B;
+}
+
+// factor_kernel of plain mode over the rank blocks (rank_blocks.hpp): the same records, entry for entry.  A look-up
+// touches isa[i] and the line of rank r; one line more on a side whose interval leaves the block (the lines of both
+// sides are requested together); the pyramids only for an interval that leaves three blocks.  A wavefront keeps its 64
+// factors together through the three steps, so the loop runs over wavefront-sized pieces of the factor list.
+template <typename CodeT>
+__global__ __launch_bounds__(kThreads) void factor_block_kernel(const uint32_t *__restrict__ fpos, uint32_t z,
+                                                                const CodeT *__restrict__ lstar,
+                                                                const uint32_t *__restrict__ isa,
+                                                                const RankBlock *__restrict__ blocks, Pyramid Psa,
+                                                                Pyramid Plcp, FactorRec *__restrict__ out, uint32_t n) {
+    __shared__ uint4 s_rows[kThreads / 64][64 * 8];
+    uint4 *rows = s_rows[threadIdx.x >> 6];
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t k0 = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); k0 < z; k0 += stride) {
+        const size_t k = k0 + (size_t)lane_id();
+        const bool valid = k < z;
+        uint32_t i = 0, L = 0;
+        if (valid) {
+            i = fpos[k];
+            const uint32_t nxt = k + 1 < z ? fpos[k + 1] : n;  // (the length, as in factor_kernel)
+            uint32_t code = nxt - i;
+            if (code == 1u) code = lstar[i];
+            L = code & kLenMask;
+        }
+        const bool search = valid && L != 0;  // (a literal looks nothing up)
+        const uint32_t r = search ? isa[i] - 1u : 0u;
+        const uint32_t b = r >> kRankBlockShift;
+        RankInterval S{};
+        {
+            const RankBlock C = exchange_blocks(rows, request_blocks(blocks, search ? b : kNoBlock));
+            if (search) S = rb_centre(C, r, L);
+        }
+        const bool left = search && S.need_left, right = search && S.need_right;
+        if (__any(left || right)) {
+            const auto far_left = [&](uint32_t q, uint32_t x) { return (uint32_t)pyr_nearest_left<false>(Plcp, q, x); };
+            const auto far_right = [&](uint32_t q, uint32_t x) { return pyr_nearest_right<false>(Plcp, q, x); };
+            const auto range_min = [&](uint32_t a, uint32_t c) { return pyr_range<false>(Psa, a, c); };
+            const BlockQuads QL = request_blocks(blocks, left ? b - 1u : kNoBlock);
+            const BlockQuads QR = request_blocks(blocks, right ? b + 1u : kNoBlock);
+            {
+                const RankBlock Lb = exchange_blocks(rows, QL);
+                if (left) rb_left(S, Lb, b - 1u, L, far_left, range_min);
+            }
+            {
+                const RankBlock Rb = exchange_blocks(rows, QR);
+                if (right) rb_right(S, Rb, b + 1u, L, far_right, range_min);
+            }
+        }
+        if (valid) {
+            FactorRec f;
+            f.start = i;
+            f.length = L ? L : 1u;
+            f.ref = L ? S.mn : i;  // literal: (i, 1, i)
+            out[k] = f;
+        }
+    }
+}
+
 inline unsigned grid_for(size_t items, unsigned cap = 256u * 16u) {
     size_t g = div_up(items, (size_t)kThreads);
     if (g < 1) g = 1;
@@ -479,6 +583,10 @@ void launch_factor_kernel(Context &ctx, const uint32_t *starts, uint32_t z, uint
     else if (lk.rebase)
         factor_kernel<false, true><<<g, kThreads, 0, s>>>(starts, z, codes.wide, lk.isa, lk.sa, lk.lcp, lk.Psa, lk.Plcp, lk.Psa, 0u,
                                                           out, *lk.rebase, n);
+    else if (lk.blocks && narrow)
+        factor_block_kernel<uint16_t><<<g, kThreads, 0, s>>>(starts, z, codes.narrow, lk.isa, lk.blocks, lk.Psa, lk.Plcp, out, n);
+    else if (lk.blocks)
+        factor_block_kernel<uint32_t><<<g, kThreads, 0, s>>>(starts, z, codes.wide, lk.isa, lk.blocks, lk.Psa, lk.Plcp, out, n);
     else if (narrow)
         factor_kernel<false, false, uint16_t><<<g, kThreads, 0, s>>>(starts, z, codes.narrow, lk.isa, lk.sa, lk.lcp, lk.Psa,
                                                                      lk.Plcp, lk.Psa, 0u, out, TermTable{}, n);

@@ -77,7 +77,8 @@ __global__ __launch_bounds__(kLdsThreads) void lpf_tile_kernel(const uint32_t *_
                                                                uint32_t *__restrict__ far_aux,
                                                                unsigned long long *__restrict__ phases,
                                                                uint32_t *__restrict__ psa1, uint32_t *__restrict__ plcp1,
-                                                               uint32_t pending_min, uint32_t *__restrict__ pending_flag) {
+                                                               uint32_t pending_min, uint32_t *__restrict__ pending_flag,
+                                                               RankBlock *__restrict__ rank_blocks) {
     constexpr int NS = 2;
     // (diagnostics, NOLZSS_LPF_PHASES: cycles per phase summed over the wavefronts of every 16th workgroup)
     const bool timed = kTimed && phases != nullptr && (blockIdx.x & 15) == 0;
@@ -113,8 +114,30 @@ __global__ __launch_bounds__(kLdsThreads) void lpf_tile_kernel(const uint32_t *_
             plcp1[first >> 4] = T.ldn[B];
         }
     }
-    if (timed) clk[1] = __builtin_readcyclecounter();
     const int w = threadIdx.x >> 6;
+    // The staged SA and LCP of the wavefront's 256 ranks leave once more as 16 rank blocks (rank_blocks.hpp: the factor
+    // records look their intervals up there): 2 KiB, two 16-byte stores per lane, consecutive lanes to consecutive
+    // addresses.  The array holds whole tiles, so no store has a bound; ranks behind the array get the padding
+    // (sa = 0xffffffff; the LCP entries behind lcp[n] are staged as 0).
+    if (rank_blocks != nullptr) {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 *dst = reinterpret_cast<u32x4 *>(rank_blocks + (size_t)blockIdx.x * (kLdsTile / kBlk) + (size_t)w * (kLdsPerWave / kBlk));
+        const int part = lane_id() & 7;  // quads 0..3 of a block: sa, 4..7: lcp
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int t = w * kLdsPerWave + (j * 8 + (lane_id() >> 3)) * kBlk + (part & 3) * 4;  // first rank of the quad
+            const u32x4 a = *reinterpret_cast<const u32x4 *>(s_sa + kLdsReach + t);
+            const u32x4 c = *reinterpret_cast<const u32x4 *>(s_lcp + kLdsReach + t);
+            const uint64_t g = (uint64_t)base + (uint64_t)t;
+            u32x4 v;
+            v.x = part >= 4 ? c.x : (g < n ? a.x : 0xffffffffu);
+            v.y = part >= 4 ? c.y : (g + 1 < n ? a.y : 0xffffffffu);
+            v.z = part >= 4 ? c.z : (g + 2 < n ? a.z : 0xffffffffu);
+            v.w = part >= 4 ? c.w : (g + 3 < n ? a.w : 0xffffffffu);
+            dst[j * 64 + lane_id()] = v;
+        }
+    }
+    if (timed) clk[1] = __builtin_readcyclecounter();
     const uint32_t far_bit = n <= 0x80000000u ? 0x80000000u : 0u;
     lds_search_wave_blocks<NS, NS, false, kLdsPerWave, kListCapB>(s_sa, s_lcp, T, n, base, s_len, s_pos, s_list0[w], s_list1[w],
                                    [](uint32_t) { return true; }, [](uint32_t) { return 0u; }, far_bit,
@@ -184,6 +207,11 @@ __global__ __launch_bounds__(kLdsThreads) void lpf_tile_kernel(const uint32_t *_
             atomicAdd(phases + 5, 1ull);
         }
     }
+}
+
+// one rank block of padding only: lcp = 0 (lcp[n] among them), sa = 0xffffffff
+__global__ void rank_block_pad_kernel(RankBlock *__restrict__ block) {
+    if (threadIdx.x < 2 * kRankBlock) reinterpret_cast<uint32_t *>(block)[threadIdx.x] = threadIdx.x < kRankBlock ? 0xffffffffu : 0u;
 }
 
 // ranks whose nearest earlier suffix lies outside the LDS reach: pyramid search.  Grid (kQShards, Y).
@@ -301,6 +329,14 @@ LstarCodes alloc_lstar(Context &ctx, uint32_t n, bool want_narrow) {
     return c;
 }
 
+RankBlock *alloc_rank_blocks(Context &ctx, uint32_t n) {
+    static const bool off = getenv("NOLZSS_NO_RANK_BLOCKS") != nullptr;
+    if (off || n == 0) return nullptr;
+    const size_t count = div_up((size_t)n, (size_t)kLdsTile) * (kLdsTile / kRankBlock) + 1;
+    static_assert(kRankBlock == (uint32_t)kBlk, "a rank block is a block of the candidate kernel's tables");
+    return ctx.arena.alloc<RankBlock>(count);
+}
+
 uint32_t *widened_lstar(Context &ctx, const LstarCodes &codes, uint32_t n, uint32_t listed) {
     if (!codes.narrow) return codes.wide;
     hipStream_t s = ctx.stream;
@@ -320,7 +356,7 @@ uint32_t *widened_lstar(Context &ctx, const LstarCodes &codes, uint32_t n, uint3
 
 uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_t *isa, const uint32_t *lcp,
                      const Pyramid &Psa, const Pyramid &Plcp, LstarCodes &lstar, uint32_t *isa_fill,
-                     const PackedText *fill_pyramids) {
+                     const PackedText *fill_pyramids, RankBlock *blocks) {
     hipStream_t s = ctx.stream;
     const size_t mark = ctx.arena.mark();
     static const bool trace = getenv("NOLZSS_TRACE") != nullptr;
@@ -336,7 +372,7 @@ uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_
         lstar.list = WideCodes{};
         lstar.wide = ctx.arena.alloc<uint32_t>(n);
         lstar.width = 32;
-        return build_lstar(ctx, n, sa, isa, lcp, Psa, Plcp, lstar, isa_fill, nullptr);
+        return build_lstar(ctx, n, sa, isa, lcp, Psa, Plcp, lstar, isa_fill, nullptr, blocks);
     };
     // fill_pyramids: Psa / Plcp are allocated but empty (alloc_pyramid): the tile kernel writes their first level,
     // the upper levels are filled behind it, and the check for undecided LCP entries happens on the way
@@ -385,11 +421,16 @@ uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_
         }
         if (phases)
             lpf_tile_kernel<true><<<tiles, kLdsThreads, 0, s>>>(sa, lcp, n, by_rank, exact_q, far_items, far_cnt, far_aux, phases, psa1, plcp1,
-                                                                pending_threshold(), pending_flag);
+                                                                pending_threshold(), pending_flag, blocks);
         else
             lpf_tile_kernel<false><<<tiles, kLdsThreads, 0, s>>>(sa, lcp, n, by_rank, exact_q, far_items, far_cnt, far_aux, nullptr, psa1,
-                                                                 plcp1, pending_threshold(), pending_flag);
+                                                                 plcp1, pending_threshold(), pending_flag, blocks);
         KERNEL_CHECK();
+        // (a text that ends with a tile: the block of lcp[n] has no rank and no tile -- it is all padding)
+        if (blocks && n % kLdsTile == 0) {
+            rank_block_pad_kernel<<<1, 64, 0, s>>>(blocks + (n >> kRankBlockShift));
+            KERNEL_CHECK();
+        }
         if (phases) {
             unsigned long long h[8];
             HIP_CHECK(hipMemcpyAsync(h, phases, 64, hipMemcpyDeviceToHost, s));
@@ -420,7 +461,7 @@ uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_
             finish_pending_lcp(ctx, *fill_pyramids, sa, const_cast<uint32_t *>(lcp));
             fill_pyramid(Psa, 1, false, s);
             fill_pyramid(Plcp, 1, false, s);
-            return build_lstar(ctx, n, sa, isa, lcp, Psa, Plcp, lstar, isa_fill, nullptr);
+            return build_lstar(ctx, n, sa, isa, lcp, Psa, Plcp, lstar, isa_fill, nullptr, blocks);
         }
     }
     {

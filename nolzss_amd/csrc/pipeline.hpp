@@ -3,6 +3,7 @@
 #include "code16.hpp"
 #include "common.hpp"
 #include "pyramid.hpp"
+#include "rank_blocks.hpp"
 #include "text.hpp"
 
 #include <vector>
@@ -71,9 +72,16 @@ uint32_t *widened_lstar(Context &ctx, const LstarCodes &codes, uint32_t n, uint3
 // fill_pyramids (optional): Psa / Plcp are allocated (alloc_pyramid over sa / lcp) but not computed: the tile kernel
 // of this stage writes their first level from the blocks it has in LDS and the upper levels are filled here -- the
 // caller skips build_pyramid / build_lcp_pyramid (whose check for undecided LCP entries happens here too).
+// blocks (optional, plain mode): alloc_rank_blocks(n) of the caller; the tile kernel of this stage copies SA and LCP
+// of its ranks into them (rank_blocks.hpp), on EVERY run of the stage -- the run after the pending-LCP safety net
+// (which changes lcp[]) and the run with wide codes write them again, so they equal the final lcp[] on return.
 uint32_t build_lstar(Context &ctx, uint32_t n, const uint32_t *sa, const uint32_t *isa, const uint32_t *lcp,
                      const Pyramid &Psa, const Pyramid &Plcp, LstarCodes &lstar, uint32_t *isa_fill = nullptr,
-                     const PackedText *fill_pyramids = nullptr);
+                     const PackedText *fill_pyramids = nullptr, RankBlock *blocks = nullptr);
+// The block array of a text of n symbols, in the arena (128-byte aligned): whole tiles of the candidate kernel, so that
+// its stores need no bound, and one block behind them for lcp[n] of a text that ends with a tile.  nullptr with
+// NOLZSS_NO_RANK_BLOCKS.
+RankBlock *alloc_rank_blocks(Context &ctx, uint32_t n);
 // pieces of build_lcp_pyramid for that form (sa_regroup.hip): the code above which an LCP entry counts as
 // undecided, the comparison of the suffixes around every undecided entry, and the test hook that leaves one undecided
 uint32_t pending_threshold();
@@ -103,12 +111,15 @@ uint32_t *chain_starts(Context &ctx, const Chain &chain);
 // leftmost occurrence.  Pmax + rcN (reverse-complement modes): the max pyramid over SA and the N of ref = 2N - max SA
 // - L + 1; the codes then carry the strand in bit 31.  rebase (plain mode only, refused together with Pmax): the
 // terminator table of a text of independent records; start and ref of every factor leave relative to its record.
+// blocks (plain mode without rebase, optional): SA and LCP of every 16 ranks in one line (rank_blocks.hpp); the
+// look-ups then read those instead of sa[] / lcp[].
 struct RecordLookup {
     const uint32_t *sa = nullptr, *isa = nullptr, *lcp = nullptr;
     Pyramid Psa, Plcp;
     const Pyramid *Pmax = nullptr;
     uint32_t rcN = 0;
     const TermTable *rebase = nullptr;
+    const RankBlock *blocks = nullptr;
 };
 // The z records (start, length, ref as u64) of the factors that begin at `starts` (chain_starts of the same chain).
 // 16-bit codes: plain records only.
