@@ -787,6 +787,74 @@ int nolzss_rlz_archive_append_index(nolzss_rlz_archive *h, const nolzss_rlz_inde
 int nolzss_rlz_archive_export(const nolzss_rlz_archive *h, uint8_t **block, size_t *block_len, nolzss_factor **records,
                               size_t *z, uint8_t **literals, size_t *n_literals);
 
+/* ---- relative-LZ archive: locate patterns inside the targets, through the parse ------------------- */
+/* Extension.  In which targets of an archive, and where, does a pattern occur?  Answered on the device without decoding
+ * the targets ("Relative-LZ archive: locate through the parse"; a hybrid index after Ferrada, Gagie,
+ * Hirvola and Puglisi 2014).
+ *   Occurrences: pattern P of m bases, 1 <= m <= M, occurs in target t at `position` when target_t[position .. position +
+ *     m) equals P (is_rc = 0) or, with an index opened with reverse complement, rc(P) (is_rc = 1).  An occurrence lies
+ *     inside one target.  A pattern that is its own reverse complement is reported on both strands, forward first; an
+ *     index without reverse complement reports no is_rc hits; an empty pattern has count 0.
+ *   primary: the records tile the decoded targets.  An occurrence that lies inside ONE copy record is secondary
+ *     (primary = 0); one that crosses a record start or lies in a literal record is primary (primary = 1).
+ *   open: `archive` must have been opened by nolzss_rlz_archive_open_index over `index`.  M = max_pattern_length, 1 ..
+ *     4096, is fixed here; prefix_syms (0: chosen, else 1 .. 12) is the key length of the prefix table of the index over
+ *     the kernel text.  The finder is a SNAPSHOT of the archive: it holds, in device memory of its own, the records
+ *     ordered by their source interval in the block with a max pyramid over the interval ends, the kernel text K -- the
+ *     bytes within max(M - 1, 1) positions of every record start, clipped to the record's target, overlapping or
+ *     touching windows merged, back to back -- with its interval tables, and an index over K built as
+ *     nolzss_rlz_index_open builds one, with the strand setting of `index`.  Archive and index must outlive the finder.
+ *     An archive without records gives a valid finder whose every count is 0; its queries do no device work.
+ *   Refusals of open, before any device work, NOLZSS_ERR_INVALID_ARGUMENT: a null pointer; an archive not opened by
+ *     open_index; an index whose serial number or device is not the one the archive is bound to; M outside 1 .. 4096;
+ *     prefix_syms > 12; a kernel text whose index text could exceed the 32-bit pipeline -- decided by the bound
+ *     min(total_length, 2 max(M - 1, 1) z) on |K|, the message names z, M and that length.
+ *   count / locate: a batch of q patterns, packed and validated exactly as for nolzss_rlz_index_locate, with its
+ *     statuses and messages (a null handle, array or output pointer; 2^31 or more patterns in a locate; the length rule
+ *     before "Invalid nucleotide 'x' found in pattern j", NOLZSS_ERR_RUNTIME).  Further refusals before any device work,
+ *     NOLZSS_ERR_INVALID_ARGUMENT: a pattern longer than M (the first such pattern and M are named); an archive that has
+ *     grown since the open (z or the number of targets differ: open a new finder).  counts[j] = the occurrences of
+ *     pattern j on both strands, exact in 64 bits.  locate: every occurrence of a pattern with counts[j] <= max_hits (0:
+ *     no cap) comes back as (target, position inside the target, is_rc, primary); a pattern above the cap reports its
+ *     count and NO hits.  Layout as in nolzss_rlz_index_locate: hit_offsets has q + 1 entries, inside a pattern the hits
+ *     ascend by (target, position, is_rc); *hits is malloc'ed (nolzss_free), NULL when *num_hits = hit_offsets[q] is 0.
+ *   Refusals of the totals, NOLZSS_ERR_INVALID_ARGUMENT once the counts are known: more occurrences of the batch in the
+ *     block or in K than the 32-bit pipeline takes (decided before anything is expanded; the counts are not known
+ *     then), or more hits to report (counts and hit_offsets are then filled, *hits is NULL).
+ *   An arena out-of-memory leaves finder, archive and index untouched.  Several threads may query one finder; a close,
+ *     or an append to the archive, must not overlap a query.  The calling thread's current device is left as it was.
+ *     NOLZSS_RLZ_LOCATE_CHUNK (tests): hit records per download.
+ *   kernel (test hook): K and its interval tables as malloc'ed host arrays (nolzss_free): interval i holds the decoded
+ *     positions [dstart[i], dstart[i] + kstart[i + 1] - kstart[i]) at K[kstart[i] ..); intervals + 1 entries each,
+ *     kstart[intervals] = |K|, dstart[intervals] = total_length.  A finder without records returns empty K and one entry. */
+typedef struct nolzss_rlz_finder nolzss_rlz_finder;
+typedef struct nolzss_rlz_finder_summary {
+    uint64_t num_targets, z, total_length;  /* of the archive when the finder was opened */
+    uint64_t max_pattern_length;            /* M */
+    uint64_t kernel_length, intervals;      /* |K| and the number of its intervals */
+    int32_t with_rc;
+    int32_t device;
+    uint64_t device_bytes;                  /* what the finder itself holds */
+} nolzss_rlz_finder_summary;
+typedef struct nolzss_rlz_target_hit {
+    uint64_t target;
+    uint64_t position;
+    uint32_t is_rc;
+    uint32_t primary;
+} nolzss_rlz_target_hit;
+int nolzss_rlz_finder_open(const nolzss_rlz_archive *archive, const nolzss_rlz_index *index, uint64_t max_pattern_length,
+                           uint32_t prefix_syms, nolzss_rlz_finder **h);
+int nolzss_rlz_finder_info(const nolzss_rlz_finder *h, nolzss_rlz_finder_summary *info);
+int nolzss_rlz_finder_count(const nolzss_rlz_finder *h, const char *const *patterns, const size_t *pattern_lens, size_t q,
+                            uint64_t *counts);
+int nolzss_rlz_finder_locate(const nolzss_rlz_finder *h, const char *const *patterns, const size_t *pattern_lens,
+                             size_t q, uint64_t max_hits, uint64_t *counts, uint64_t *hit_offsets,
+                             nolzss_rlz_target_hit **hits, size_t *num_hits);
+int nolzss_rlz_finder_kernel(const nolzss_rlz_finder *h, uint8_t **kernel, size_t *kernel_len, uint64_t **kstart,
+                             uint64_t **dstart, size_t *intervals);
+/* NULL is a no-op; the calling thread's current device is left as it was. */
+int nolzss_rlz_finder_close(nolzss_rlz_finder *h);
+
 /* ---- measurement hooks -------------------------------------------------------------------- */
 /* HIP-event timing of every pipeline stage on the context's stream (off by default). */
 int nolzss_profile_enable(int device, int on);

@@ -121,6 +121,13 @@ class RlzArchiveAppendInfo(C.Structure):
                 ("capacity_records", C.c_uint64), ("device_bytes", C.c_uint64), ("reallocated", C.c_int32)]
 
 
+class RlzFinderSummary(C.Structure):
+    """Mirror of nolzss_rlz_finder_summary (include/nolzss_hip.h)."""
+    _fields_ = [("num_targets", C.c_uint64), ("z", C.c_uint64), ("total_length", C.c_uint64),
+                ("max_pattern_length", C.c_uint64), ("kernel_length", C.c_uint64), ("intervals", C.c_uint64),
+                ("with_rc", C.c_int32), ("device", C.c_int32), ("device_bytes", C.c_uint64)]
+
+
 class RlzIndexSummary(C.Structure):
     """Mirror of nolzss_rlz_index_summary (include/nolzss_hip.h)."""
     _fields_ = [("num_references", C.c_uint64), ("block_length", C.c_uint64), ("index_length", C.c_uint64),
@@ -291,6 +298,12 @@ def _load():
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
     lib.nolzss_rlz_archive_export.argtypes = [vp, vpp, szp, vpp, szp, vpp, szp]
+    lib.nolzss_rlz_finder_open.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vpp]
+    lib.nolzss_rlz_finder_info.argtypes = [vp, C.POINTER(RlzFinderSummary)]
+    lib.nolzss_rlz_finder_count.argtypes = [vp] + seqs[3:] + [vp]
+    lib.nolzss_rlz_finder_locate.argtypes = [vp] + seqs[3:] + [C.c_uint64, vp, vp, vpp, szp]
+    lib.nolzss_rlz_finder_kernel.argtypes = [vp, vpp, szp, vpp, vpp, szp]
+    lib.nolzss_rlz_finder_close.argtypes = [vp]
     lib.nolzss_profile_enable.argtypes = [C.c_int, C.c_int]
     lib.nolzss_profile_reset.argtypes = [C.c_int]
     lib.nolzss_profile_report.argtypes = [C.c_int, C.c_char_p, sz]
@@ -357,6 +370,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_index_codes", "nolzss_rlz_index_close", "nolzss_rlz_index_count", "nolzss_rlz_index_locate",
     "nolzss_debug_rlz_locate_shifts", "nolzss_rlz_index_seeds", "nolzss_free_rlz_seeds_result",
     "nolzss_rlz_archive_open_index", "nolzss_rlz_archive_append_index", "nolzss_rlz_archive_export",
+    "nolzss_rlz_finder_open", "nolzss_rlz_finder_info", "nolzss_rlz_finder_count", "nolzss_rlz_finder_locate",
+    "nolzss_rlz_finder_kernel", "nolzss_rlz_finder_close",
     "nolzss_debug_pyramid", "nolzss_debug_nearest", "nolzss_debug_lds_search",
     "nolzss_debug_local_sort", "nolzss_debug_text_order", "nolzss_debug_group_sort",
 ]

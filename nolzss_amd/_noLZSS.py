@@ -21,6 +21,8 @@ RC_MASK = 1 << 63
 FACTOR_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8")])
 # nolzss_rlz_hit (include/nolzss_hip.h): an occurrence of a pattern in the reference block
 HIT_DTYPE = np.dtype([("position", "<u8"), ("record", "<u4"), ("is_rc", "<u4")])
+# an occurrence of a pattern inside a target of an archive (RlzFinderHandle.locate): nolzss_rlz_target_hit
+TARGET_HIT_DTYPE = np.dtype([("target", "<u8"), ("position", "<u8"), ("is_rc", "<u4"), ("primary", "<u4")])
 # nolzss_rlz_seed: a maximal exact match of a target with the reference block
 SEED_DTYPE = np.dtype([("target", "<u8"), ("start", "<u8"), ("length", "<u8"), ("count", "<u8")])
 
@@ -1311,6 +1313,102 @@ class RlzArchiveHandle:
         h, self._h = getattr(self, "_h", None), None
         if h is not None:
             check(lib.nolzss_rlz_archive_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- relative-LZ archive: locate patterns inside the targets, through the parse (genomics/rlz.py) ----------------
+class RlzFinderHandle:
+    """Extension: a snapshot of an index-built archive for pattern queries inside its targets (C ABI
+    nolzss_rlz_finder_*).  It keeps the archive and the index handles alive.  A context manager; close() may be called
+    more than once, any other use after it raises ValueError."""
+
+    def __init__(self, handle, archive_handle, index_handle):
+        self._h, self._archive, self._index = handle, archive_handle, index_handle
+        info = _lib.RlzFinderSummary()
+        try:
+            check(lib.nolzss_rlz_finder_info(self._h, C.byref(info)))
+        except Exception:
+            self.close()
+            raise
+        self.info = {name: int(getattr(info, name)) for name, _ in _lib.RlzFinderSummary._fields_}
+
+    @classmethod
+    def open(cls, archive_handle, index_handle, max_pattern_length: int = 64, prefix_syms: int = 0):
+        """C ABI nolzss_rlz_finder_open (its header states the rules)."""
+        M, P = operator.index(max_pattern_length), operator.index(prefix_syms)
+        if M < 0 or P < 0:
+            raise ValueError("max_pattern_length and prefix_syms must not be negative")
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_finder_open(archive_handle._handle(), index_handle._handle(), M, P, C.byref(h)))
+        return cls(h, archive_handle, index_handle)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the finder is closed")
+        self._archive._handle()  # (a closed archive or index raises here, not in the library)
+        self._index._handle()
+        return self._h
+
+    def count(self, patterns) -> np.ndarray:
+        """One batch: the occurrences of every pattern in the targets, both strands together (uint64).  C ABI
+        nolzss_rlz_finder_count."""
+        h = self._handle()
+        args = _seq_args(patterns, "pattern")
+        counts = np.zeros(args[2], dtype=np.uint64)
+        check(lib.nolzss_rlz_finder_count(h, *args, counts.ctypes.data if counts.size else None))
+        return counts
+
+    def locate(self, patterns, max_hits: int = 0):
+        """One batch -> (counts, offsets, hits): uint64 counts, the q + 1 uint64 offsets of the patterns' hits, and the
+        hits as TARGET_HIT_DTYPE, per pattern ascending by (target, position, is_rc); a pattern with more than max_hits
+        occurrences (0: no cap) reports its count and no hits.  C ABI nolzss_rlz_finder_locate."""
+        h = self._handle()
+        max_hits = operator.index(max_hits)
+        if max_hits < 0:
+            raise ValueError("max_hits must not be negative")
+        args = _seq_args(patterns, "pattern")
+        counts, offsets = np.zeros(args[2], dtype=np.uint64), np.zeros(args[2] + 1, dtype=np.uint64)
+        out, z = C.c_void_p(), C.c_size_t()
+        check(lib.nolzss_rlz_finder_locate(h, *args, max_hits, counts.ctypes.data if counts.size else None,
+                                           offsets.ctypes.data, C.byref(out), C.byref(z)))
+        if not out.value or z.value == 0:
+            lib.nolzss_free(out)
+            return counts, offsets, np.zeros(0, dtype=TARGET_HIT_DTYPE)
+        raw = (C.c_uint64 * (3 * z.value)).from_address(out.value)
+        raw._owner = _Owned(out)
+        return counts, offsets, np.frombuffer(raw, dtype=TARGET_HIT_DTYPE)
+
+    def kernel(self):
+        """Test hook -> (K bytes, kstart, dstart): the kernel text and its interval tables (uint64, intervals + 1
+        entries each).  C ABI nolzss_rlz_finder_kernel."""
+        h = self._handle()
+        K, ks, ds = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n, nI = C.c_size_t(), C.c_size_t()
+        check(lib.nolzss_rlz_finder_kernel(h, C.byref(K), C.byref(n), C.byref(ks), C.byref(ds), C.byref(nI)))
+        try:
+            text = C.string_at(K, n.value)
+            kstart = np.ctypeslib.as_array(C.cast(ks, C.POINTER(C.c_uint64)), shape=(nI.value + 1,)).copy()
+            dstart = np.ctypeslib.as_array(C.cast(ds, C.POINTER(C.c_uint64)), shape=(nI.value + 1,)).copy()
+        finally:
+            for p in (K, ks, ds):
+                lib.nolzss_free(p)
+        return text, kstart, dstart
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            check(lib.nolzss_rlz_finder_close(h))
 
     def __enter__(self):
         return self

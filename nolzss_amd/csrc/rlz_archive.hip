@@ -120,26 +120,6 @@ __device__ __forceinline__ uint32_t find_range(const uint32_t *__restrict__ offs
     return lo;
 }
 
-// the record that covers decoded position p (p below the decoded length)
-__device__ __forceinline__ uint32_t find_record(const ArchiveView &v, uint32_t p) {
-    const uint32_t s = p >> kSampleShift;
-    uint32_t lo = v.sample[s];
-    // the record that covers the next sample position starts behind 256 * s, at p or before it or behind it; every
-    // record behind that one starts behind p
-    uint32_t hi = s + 1 < v.samples ? v.sample[s + 1] + 1u : v.z;
-    while (hi - lo > 1) {  // hi - lo <= 257
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (v.recs[mid].start <= p) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ ArchiveRec load_record(const ArchiveView &v, uint32_t k) {
-    const uint4 w = reinterpret_cast<const uint4 *>(v.recs)[k];
-    return ArchiveRec{w.x, w.y, w.z, w.w};
-}
-
 // One lane owns output bytes [16 g, 16 g + 16) of the call; wide: d_out is 16-byte aligned, a whole chunk goes out as
 // one 16-byte store.
 __global__ __launch_bounds__(kThreads) void rlz_extract_kernel(ArchiveView v, const uint32_t *__restrict__ offsets,
@@ -153,8 +133,8 @@ __global__ __launch_bounds__(kThreads) void rlz_extract_kernel(ArchiveView v, co
 
     uint32_t i = find_range(offsets, q, o, 0);
     uint32_t range_begin = offsets[i], range_end = offsets[i + 1];
-    uint32_t k = find_record(v, first[i] + (o - range_begin));
-    ArchiveRec f = load_record(v, k);
+    uint32_t k = archive_find_record(v, first[i] + (o - range_begin));
+    ArchiveRec f = archive_load_record(v, k);
     uint32_t t = first[i] + (o - range_begin) - f.start;
     unsigned long long w0 = 0, w1 = 0;
     // A whole chunk inside one range and one copy record: its 16 source bytes are contiguous in the block, one
@@ -191,11 +171,11 @@ __global__ __launch_bounds__(kThreads) void rlz_extract_kernel(ArchiveView v, co
             range_begin = offsets[i];
             range_end = offsets[i + 1];
             const uint32_t p = first[i] + (x - range_begin);
-            k = find_record(v, p);
-            f = load_record(v, k);
+            k = archive_find_record(v, p);
+            f = archive_load_record(v, k);
             t = p - f.start;
         } else if (t >= f.length) {  // inside a range the next position is the next record's first (tiling)
-            f = load_record(v, ++k);
+            f = archive_load_record(v, ++k);
             t = 0;
         }
         const uint32_t kind = f.meta & 3u;

@@ -49,6 +49,26 @@ struct ArchiveView {
 void archive_extract(Context &ctx, const ArchiveView &v, const uint32_t *d_offsets, const uint32_t *d_first, uint32_t q,
                      uint32_t total, uint8_t *d_out, unsigned long long *d_err);
 
+// the record that covers decoded position p (p below the decoded length)
+__device__ __forceinline__ uint32_t archive_find_record(const ArchiveView &v, uint32_t p) {
+    const uint32_t s = p >> kSampleShift;
+    uint32_t lo = v.sample[s];
+    // the record that covers the next sample position starts behind 256 * s, at p or before it or behind it; every
+    // record behind that one starts behind p
+    uint32_t hi = s + 1 < v.samples ? v.sample[s + 1] + 1u : v.z;
+    while (hi - lo > 1) {  // hi - lo <= 257
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (v.recs[mid].start <= p) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ ArchiveRec archive_load_record(const ArchiveView &v, uint32_t k) {
+    const uint4 w = reinterpret_cast<const uint4 *>(v.recs)[k];
+    return ArchiveRec{w.x, w.y, w.z, w.w};
+}
+
 const char *archive_rule_text(uint32_t rule);
 
 // ---- batches appended from the index, and the way back to host records ("Relative-LZ archive: batches

@@ -1,9 +1,11 @@
-// rlz_handles.hpp -- the two resident relative-LZ handles, shared by the translation units of their entry points: an
+// rlz_handles.hpp -- the resident relative-LZ handles, shared by the translation units of their entry points: an
 // append matches a batch against the index (rlz_index_api.hip) and writes into the archive (rlz_archive_api.hip owns
-// open_records, extract and export).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index".
+// open_records, extract and export); a finder reads both (rlz_find_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches
+// appended from the index" and "Relative-LZ archive: locate through the parse".
 #pragma once
 #include "api_internal.hpp"
 #include "rlz_archive.hpp"
+#include "rlz_find.hpp"
 #include "rlz_index.hpp"
 
 // The index handle: everything a match reads, in ONE device allocation (not arena memory, which the next call on the
@@ -53,6 +55,35 @@ struct nolzss_rlz_archive {
     }
 };
 
+// The finder handle: a snapshot of an archive opened over an index, for pattern queries in the targets (rlz_find_api.hip;
+// DESIGN.md 5, "Relative-LZ archive: locate through the parse").  It points to the archive and the index it was opened
+// over -- both must outlive it -- and holds in device allocations of its own (not arena memory) the source table, the
+// interval tables with the targets' decoded positions, and the index over the kernel text K.
+struct nolzss_rlz_finder {
+    int device = 0;
+    const nolzss_rlz_archive *archive = nullptr;
+    const nolzss_rlz_index *index = nullptr;
+    uint64_t z = 0, targets = 0, decoded = 0;  // of the archive at the open: a query refuses an archive that has grown
+    uint64_t M = 0, K_len = 0, intervals = 0;
+    bool with_rc = false;
+    void *d_tables = nullptr;  // kstart, dstart, bases
+    void *d_sources = nullptr; // lo, hi, rec and the upper levels of the max pyramid over hi
+    void *d_kindex = nullptr;  // everything kview points to
+    size_t device_bytes = 0;
+    nolzss::FinderView view;
+    nolzss::RlzIndexView kview;
+    ~nolzss_rlz_finder() {  // (the calling thread's current device stays what it was)
+        if (!d_tables && !d_sources && !d_kindex) return;
+        int current = -1;
+        const bool known = hipGetDevice(&current) == hipSuccess;
+        (void)hipSetDevice(device);
+        if (d_tables) (void)hipFree(d_tables);
+        if (d_sources) (void)hipFree(d_sources);
+        if (d_kindex) (void)hipFree(d_kindex);
+        if (known && current != device) (void)hipSetDevice(current);
+    }
+};
+
 namespace nolzss {
 namespace api {
 
@@ -67,6 +98,21 @@ struct DeviceRestore {
 };
 
 constexpr size_t kRecordChunk = size_t(1) << 22;  // records per look-up chunk: 96 MiB of arena whatever the batch holds
+
+// A batch of targets or patterns laid out for the device (rlz_index_api.hip)
+constexpr uint8_t kSeparator = 1;  // between the targets of a batch: any byte but A, C, G, T
+struct Batch {
+    HostBytes tcat;                    // T1 s T2 s .. Tk s
+    std::vector<uint32_t> separators;  // k positions in tcat
+    std::vector<uint64_t> offsets;     // k: the first position of each target in tcat
+};
+// What a pattern query of the index and of the finder share (rlz_index_api.hip): the checks and the layout of a pattern
+// batch, the chunk knobs, and the arena bytes of a batch of n positions and q patterns and of every expanded hit.
+void prepare_patterns(const char *const *patterns, const size_t *pattern_lens, size_t q, Batch &b);
+uint32_t choose_prefix(size_t index_length);  // the prefix table's key for an index text of that length
+size_t chunk_knob(const char *name);
+size_t pattern_batch_bytes(size_t n, size_t q);
+constexpr size_t kLocateBytesPerHit = 25;
 
 }  // namespace api
 }  // namespace nolzss

@@ -17,14 +17,15 @@ namespace {
 // device memory per batch position: packed text 1/4, code 4, rank 4, the chain's exits, bitmaps and node lists (12 on
 // ordinary batches, 24 when every position is a node), the factor starts 4 -- not the 52 of a suffix sort
 constexpr size_t kBatchBytesPerPosition = 36;
-constexpr uint8_t kSeparator = 1;  // between the targets of a batch: any byte but A, C, G, T
 
-uint32_t choose_prefix(size_t index_length) {  // clamp(floor(log4 |X|) - 1, 4, 12)
+}  // namespace
+uint32_t nolzss::api::choose_prefix(size_t index_length) {  // clamp(floor(log4 |X|) - 1, 4, 12)
     int l = 0;
     while ((index_length >> (2 * (l + 1))) != 0) ++l;
     const int P = l - 1;
     return (uint32_t)(P < 4 ? 4 : (P > (int)kIndexMaxPrefix ? (int)kIndexMaxPrefix : P));
 }
+namespace {
 
 void open_index(const char *const *refs, const size_t *ref_lens, size_t m, bool with_rc, uint32_t prefix_syms, int device,
                 nolzss_rlz_index **out) {
@@ -64,12 +65,6 @@ void open_index(const char *const *refs, const size_t *ref_lens, size_t m, bool 
     *out = h.release();
 }
 
-struct Batch {
-    HostBytes tcat;                    // T1 s T2 s .. Tk s
-    std::vector<uint32_t> separators;  // k positions in tcat
-    std::vector<uint64_t> offsets;     // k: the first position of each target in tcat
-};
-
 // every check of a match, in the order the header states them, and the batch laid out
 void prepare_batch(const nolzss_rlz_index &h, const char *const *targets, const size_t *target_lens, size_t k, Batch &b) {
     if (k && (!targets || !target_lens)) throw std::invalid_argument("sequence array is null");
@@ -102,11 +97,15 @@ void prepare_batch(const nolzss_rlz_index &h, const char *const *targets, const 
     }
 }
 
+}  // namespace
+
+// (prepare_patterns, chunk_knob and pattern_batch_bytes are shared with the finder's queries, rlz_find_api.hip:
+// rlz_handles.hpp declares them)
 // The checks of a pattern batch -- the length rule first, decided by the lengths alone, then the bases, as the header
 // states -- and the batch laid out as a target batch is.  A batch holds millions of short patterns: they are validated
 // and upper-cased in one pass over the batch, split between the host threads by position (every pattern is followed by
 // its separator, so the offsets ascend strictly), not one helper call per pattern.
-void prepare_patterns(const char *const *patterns, const size_t *pattern_lens, size_t q, Batch &b) {
+void nolzss::api::prepare_patterns(const char *const *patterns, const size_t *pattern_lens, size_t q, Batch &b) {
     if (q && (!patterns || !pattern_lens)) throw std::invalid_argument("pattern array is null");
     size_t bases = 0;
     bool overflow = false;
@@ -155,6 +154,8 @@ void prepare_patterns(const char *const *patterns, const size_t *pattern_lens, s
                                  std::to_string(j));
     }
 }
+
+namespace {
 
 struct MatchOut {
     std::vector<size_t> counts, first;  // per target: records, and the index of its first record in block
@@ -269,9 +270,11 @@ void archive_open_index(const nolzss_rlz_index &ix, nolzss_rlz_archive **out) {
     *out = h.release();
 }
 
+}  // namespace
+
 // NOLZSS_RLZ_APPEND_CHUNK: records per look-up chunk of an append; NOLZSS_RLZ_LOCATE_CHUNK: hit records per download
 // chunk of a locate (test knobs, read on every call)
-size_t chunk_knob(const char *name) {
+size_t nolzss::api::chunk_knob(const char *name) {
     const char *e = std::getenv(name);
     if (!e || !*e) return kRecordChunk;
     char *end = nullptr;
@@ -279,6 +282,8 @@ size_t chunk_knob(const char *name) {
     if (*end || v == 0) return kRecordChunk;
     return v < kRecordChunk ? (size_t)v : kRecordChunk;
 }
+
+namespace {
 
 // a device array that replaces one of the handle's: freed on the way out unless it was swapped in (then the old one is)
 struct Fresh {
@@ -468,8 +473,9 @@ void index_factorize(const nolzss_rlz_index &h, const char *const *targets, cons
 // device memory of a pattern batch of n positions and q patterns: the bytes, the packed words, the terminator table, and
 // lo, cnt, rep, off; per hit: two key and two value arrays of the sort (24), its histograms (1/4), and the records of a
 // chunk (16)
-size_t pattern_batch_bytes(size_t n, size_t q) { return 2 * n + 24 * q + (size_t(4) << 20); }
-constexpr size_t kLocateBytesPerHit = 25;
+}  // namespace
+size_t nolzss::api::pattern_batch_bytes(size_t n, size_t q) { return 2 * n + 24 * q + (size_t(4) << 20); }
+namespace {
 
 using HitBlock = std::unique_ptr<nolzss_rlz_hit, FreeBlock>;
 static_assert(sizeof(nolzss_rlz_hit) == sizeof(LocateHit) && sizeof(LocateHit) == 16, "the kernels write nolzss_rlz_hit");

@@ -20,6 +20,7 @@ import numpy as np
 from .. import _noLZSS as _native
 
 RLZ_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8"), ("is_rc", "?"), ("is_literal", "?")])
+TARGET_HIT_DTYPE = _native.TARGET_HIT_DTYPE  # (target, position, is_rc, primary): RlzArchiveFinder.locate
 HIT_DTYPE = _native.HIT_DTYPE  # (position, record, is_rc): an occurrence of a pattern (RlzIndex.locate)
 SEED_DTYPE = _native.SEED_DTYPE  # (target, start, length, count): a maximal exact match of a target (RlzIndex.seeds)
 
@@ -300,6 +301,15 @@ class RlzArchive:
                     self.ids.append(name)
         return out
 
+    def finder(self, max_pattern_length: int = 64, prefix_syms: int = 0):
+        """-> RlzArchiveFinder: in which targets, and where, do patterns of up to max_pattern_length bases occur?  A
+        snapshot of the archive as it is now, built on the GPU from the resident records ("Relative-LZ
+        archive: locate through the parse"); after an append, open a new one.  prefix_syms as in RlzIndex.build."""
+        h = self._live()
+        if self._arrays is not None:
+            raise ValueError("finder needs an archive made by RlzArchive.from_index: this one was built from host records")
+        return RlzArchiveFinder(_native.RlzFinderHandle.open(h, self._bound._live(), max_pattern_length, prefix_syms))
+
     def save(self, path):
         """One .npz holding block, records, literals, target lengths and ids, raw."""
         h = self._live()
@@ -355,6 +365,79 @@ class RlzArchive:
     def target(self, j) -> bytes:
         j = resolve_target(j, self._index, len(self))
         return self.fetch(j, 0, int(self._lengths()[j]))
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h is not None:
+            h.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RlzArchiveFinder:
+    """Pattern queries inside the targets of an RlzArchive (RlzArchive.finder).  A context manager; use after close()
+    raises ValueError.  The archive and its index must stay open while it is used."""
+
+    def __init__(self, handle):
+        self._handle = handle
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("the finder is closed")
+        return self._handle
+
+    @property
+    def info(self):
+        """dict(num_targets, z, total_length, max_pattern_length, kernel_length, intervals, with_rc, device,
+        device_bytes)"""
+        return dict(self._live().info)
+
+    @staticmethod
+    def _batches(patterns):
+        patterns = list(patterns)
+        return patterns, plan_index_batches([len(p) for p in patterns], -1, MAX_TEXT)
+
+    def count(self, patterns):
+        """Occurrences of every pattern in the targets, both strands together (an index without reverse complement
+        counts the forward strand only) -> uint64 array.  An empty pattern counts 0."""
+        h = self._live()
+        patterns, plan = self._batches(patterns)
+        parts = [h.count(patterns[lo:hi]) for lo, hi in plan]
+        return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+
+    def locate(self, patterns, max_hits: int = 0):
+        """Where every pattern occurs in the targets -> dict(counts, offsets, target, position, is_rc, primary).  Pattern
+        j owns the hits [offsets[j], offsets[j + 1]), ascending by (target, position, is_rc): target is the 0-based
+        target, position the position inside it; is_rc means the stretch equals the pattern's reverse complement;
+        primary means the occurrence crosses a record start of the parse or is a literal.  A pattern with more than
+        max_hits occurrences (0: no cap) reports its count and no hits."""
+        h = self._live()
+        patterns, plan = self._batches(patterns)
+        counts, offsets, hits, base = [], [np.zeros(1, dtype=np.uint64)], [], 0
+        for lo, hi in plan:
+            c, o, f = h.locate(patterns[lo:hi], max_hits)
+            counts.append(c)
+            offsets.append(o[1:] + np.uint64(base))
+            hits.append(f)
+            base += int(o[-1])
+        f = np.concatenate(hits) if hits else np.zeros(0, dtype=TARGET_HIT_DTYPE)
+        return {"counts": np.concatenate(counts) if counts else np.zeros(0, dtype=np.uint64),
+                "offsets": np.concatenate(offsets), "target": f["target"].copy(), "position": f["position"].copy(),
+                "is_rc": f["is_rc"].astype(bool), "primary": f["primary"].astype(bool)}
+
+    def kernel(self):
+        """Test hook -> (K bytes, kstart, dstart)"""
+        return self._live().kernel()
 
     def close(self) -> None:
         h, self._handle = getattr(self, "_handle", None), None
@@ -633,5 +716,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
