@@ -139,6 +139,22 @@ __device__ __forceinline__ void local_store(const uint32_t *s_stage, uint32_t *_
 // what it needs from the others is the number of tied elements in front (a decoupled look-back over one descriptor per
 // non-empty sub-bucket, lookback.hpp) and, for the LCP of its first boundary, the last key of the sub-bucket in front.
 // The keys are not written at all: 4 bytes per suffix less out, 4 less in, and a kernel less.
+//
+// The walk comes ONE TURN LATE.  Sub-bucket q's predecessors q - 1 .. q - (G - 1) belong to the other G - 1 workgroups in
+// the same turn, so a walk right behind loop 1 waited until everybody in front in q order had finished loop 1 of this
+// turn: a grid-wide rendezvous per turn, ~10 k cycles with eleven waves at a barrier.  Nothing needs the sum there: loop 2
+// reads the masks and per-row prefixes in LDS and the sum, no staged key.  So at the end of loop 1 a workgroup PUBLISHES
+// (aggregate, last key) and notes the turn as pending; the walk, the first boundary and loop 2 of turn t run in turn t + 1
+// behind the staging of its keys, before loop 1 of t + 1 writes the tables again (every wave reads in loop 2 the very
+// entries it writes in loop 1: no barrier between the two), and behind a workgroup's last turn (the flush).  What the walk
+// asks for was published most of a turn ago.  That alone left the walk at 10 k cycles: two dependent reads through the
+// fabric (descriptors, then the last key), each waited for behind every store the wave has in flight.  Both are therefore
+// asked for AHEAD, in front of the last digit's value staging (lookback_walk_preload), and the walk takes them for its first
+// round trip.  2^30 bases: 8.65 -> 7.78 ms (profiles/local_sort_deferred_walk_ab.txt).
+// Forward progress: a walk of sub-bucket q waits for descriptors and last keys of sub-buckets q' < q only.  A workgroup
+// takes its sub-buckets in ascending order and publishes q after the walk of its previous one, p < q, and that walk waits
+// for sub-buckets below p.  By induction on q every sub-bucket is published -- sub-bucket 0 waits for nobody -- as long as
+// its workgroup is resident, so no wait is circular; residency is what the bounded spins below are for.
 constexpr uint32_t kLcpPendingCode = 0xffffffffu;  // (sa_internal.hpp: kLcpPending)
 // The sub-buckets are dealt out statically (that is what lets a workgroup ask for the next one's keys a turn ahead), so a
 // look-back can wait for a workgroup that is not resident -- if another process or stream holds CUs with a kernel of its
@@ -272,6 +288,7 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
     // first key, last key, tied elements in front of the sub-bucket
     __shared__ uint32_t s_cnt[kFuse ? (kLocalRows + 4) * kLocalWaves + 64 : 1], s_lh[kFuse ? (kLocalRows + 4) * kLocalWaves + 64 : 1], s_edge[3];
     __shared__ uint32_t s_giveup;
+    __shared__ uint32_t s_pend[3];  // (kFuse) the pending turn's dense index, number of tied elements, sub-bucket in front
     __shared__ uint64_t s_mask[kFuse ? 2 * ((kLocalRows + 4) * kLocalWaves + 64) : 1];  // (kFuse) heads / tied elements of the 64 places, as lane masks
     const int tid = threadIdx.x;
     const int w = tid >> 6;
@@ -293,6 +310,82 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
         else
             preset_failure = flag != 0u;
     }
+    // (kFuse) The turn whose walk and loop 2 are still to come (pcount = 0: none) -- uniform values, scalar registers; what
+    // only wave 0 needs of it lies in s_pend, the first key still in s_edge[0], the tables of loop 1 where loop 1 left them.
+    uint32_t pfirst = 0, pcount = 0, psub = 0;
+    bool gave_up = false;  // (uniform) a walk of this workgroup has given up: its loop ends behind this turn
+    // The deferred step of the pending turn in two parts with a barrier between them.  deferred_walk: wave 0 walks (every
+    // aggregate in front was published a turn ago or is being waited for, bounded), settles the first boundary with the
+    // last key of the sub-bucket in front and the total.  deferred_loop2: loop 2 of everybody.
+    // after_give_up (the flush behind a turn that gave up): nothing is waited for -- the host sorts again anyway.
+    // pre: the first round trip of the walk and the last key in front, asked for ahead (none at the flush).
+    // (always inlined: called, their captures would be made addressable, and the kernel has no scratch)
+    constexpr int kWalkWin = 4;  // (windows of 64 descriptors per round trip: one trip covers a turn of 256 workgroups)
+    auto deferred_walk = [&](const bool flush, const bool after_give_up, const uint64_t *pre) __attribute__((always_inline)) {
+        if (w == 0) {
+            const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pend[0]);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pend[1]);
+            // (the walk's own flag starts from a constant: started from preset_failure it was a value carried in a vector
+            // register from the top of the kernel, and spilled)
+            bool walk_failed = false;
+            const uint32_t xs = after_give_up ? 0u : lookback_walk_add_wide<kWalkWin>(F.desc, q, total, F.d_total + 1, kLocalSpinLimit, &walk_failed, pre);
+            if (lane == 0) {
+                s_edge[2] = xs;
+                // (the look-back gave up: this workgroup stops behind this turn and its flush; the others give up on their
+                // own next walk.  Looking at the flag in memory every turn cost 0.5 ms here, 13 ms at the top of the turn.)
+                s_giveup = (walk_failed | preset_failure | after_give_up) ? 1u : 0u;
+                if (q + 1u == F.nq) F.d_total[0] = xs + total;
+                uint32_t l0 = 0;  // (the very first suffix of the order)
+                if (q > 0u) {
+                    uint64_t d = pre ? pre[kWalkWin] : 0ull;  // (not asked for ahead, or not there yet: ready = 0)
+                    uint32_t spins = 0;
+                    while ((d >> 32) == 0) {
+                        if (after_give_up || ++spins > kLocalSpinLimit) {  // (never hang the GPU)
+                            atomicExch(F.d_total + 1, 1u);
+                            s_giveup = 1u;
+                            break;
+                        }
+                        if (spins > 1u) __builtin_amdgcn_s_sleep(1);
+                        d = desc_load(F.lastkey + (q - 1u));
+                    }
+                    const uint32_t bucket = psub >> 8, pbucket = s_pend[2] >> 8;  // (its own, that of the sub-bucket in front)
+                    const uint32_t pk = (uint32_t)d, k = s_edge[0];
+                    uint32_t ls;
+                    if constexpr (kKey35) {  // (8 + 27 key bits)
+                        const uint64_t y = ((uint64_t)(bucket ^ pbucket) << (32 - kTagBits)) | (uint64_t)((k ^ pk) >> kTagBits);
+                        ls = y ? (uint32_t)(__builtin_clzll(y) - (64 - kP35KeyBits)) >> 1 : 0xffffffffu;
+                    } else {
+                        const uint32_t y = ((bucket ^ pbucket) << 24) | ((k ^ pk) >> kTagBits);
+                        ls = y ? (uint32_t)__builtin_clz(y) >> 1 : 0xffffffffu;
+                    }
+                    const uint32_t ta = k & kTagMask, tb = pk & kTagMask;
+                    ls = ls < ta ? ls : ta;
+                    l0 = ls < tb ? ls : tb;
+                }
+                F.lcp[pfirst] = l0;
+            }
+        }
+        LOCAL_CK(flush ? 27 : 24)  // deferred walk + first boundary (wave 0)
+    };
+    auto deferred_loop2 = [&](const bool flush) __attribute__((always_inline)) -> bool {
+        LOCAL_CK(flush ? 27 : 25)  // ... everybody
+        // Loop 2: the tied elements -- slot and slot of the group's head, in slot order
+        const uint32_t xsum = s_edge[2];
+        const bool giveup = s_giveup != 0u;  // (uniform)
+        for (uint32_t p0 = 0, e = (uint32_t)w; p0 < pcount; p0 += kLocalThreads, e += kLocalWaves) {
+            const uint64_t hmask = s_mask[2 * e], kmask = s_mask[2 * e + 1];  // (wave-uniform)
+            if ((kmask >> lane) & 1ull) {
+                const uint32_t pl = p0 + (uint32_t)tid;
+                const uint64_t upto = hmask & ((2ull << lane) - 1ull);
+                const uint32_t hidx = upto ? p0 + (uint32_t)w * 64u + (uint32_t)(63 - __builtin_clzll(upto)) : s_lh[e] - 1u;
+                const uint32_t pos = xsum + s_cnt[e] + (uint32_t)__popcll(kmask & ((1ull << lane) - 1ull));
+                F.new_slot[pos] = pfirst + pl;
+                F.new_grp[pos] = pfirst + hidx;
+            }
+        }
+        LOCAL_CK(flush ? 27 : 26)  // deferred loop 2 (wave 0)
+        return giveup;
+    };
     while (count) {  // (uniform)
         // this sub-bucket's values (wanted when its keys have been ranked once) and the NEXT one's keys are asked for
         // before anything else (the values of the next one, too, took the registers over the edge: a prefetched value
@@ -304,6 +397,15 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
             local_load(vals_in, first, count, rows, val, tid);
             local_next(sub_start, num_sub, sub, nfirst, ncount, ctl, large_list, tid, next_sub);
             local_load(keys_in, nfirst, ncount, (int)((ncount + kLocalThreads - 1) / kLocalThreads), nkey, tid);
+        }
+        // (kFuse) dense index and sub-bucket in front, read HERE: where wave 0 wants them everybody else waits for it.
+        // (through the constant address space -- the tables were written before the kernel started: scalar loads into scalar
+        // registers; as vector loads they were waited for with every store in flight, and spilled)
+        uint32_t cur_q = 0, cur_prev = 0;
+        if constexpr (kFuse) {
+            typedef const uint32_t __attribute__((address_space(4))) *ConstTable;
+            cur_q = ((ConstTable)F.dense)[cur_sub];
+            cur_prev = ((ConstTable)F.prev_sub)[cur_sub];
         }
 
         const uint32_t wbase = (uint32_t)w * (uint32_t)(rows * 64) + (uint32_t)lane;
@@ -431,6 +533,17 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
                     // The last digit with the regroup of round 0 on the way.  The VALUES go first: their stores are
                     // buffer stores a lane without work sends out of bounds (no branch: the compiler can count them, and the
                     // wait for the next sub-bucket's keys below lets them drain).
+                    // The pending turn's walk is asked for HERE (lookback.hpp: lookback_walk_preload), ~10 k cycles before
+                    // its answers are wanted and IN FRONT of the values' stores: a load's answer is waited for behind every
+                    // store issued before it.  Every wave runs the loads, wave 0 alone sends any (s_pend: barriers have passed since it was written).
+                    uint64_t pre[kWalkWin + 1];
+                    {
+                        const uint32_t pq = s_pend[0];
+                        const bool on = (w == 0) & (pcount != 0u);
+                        lookback_walk_preload<kWalkWin>(F.desc, F.nq * 8u, pq, on, pre);
+                        pre[kWalkWin] = desc_load_buf(__builtin_amdgcn_make_buffer_rsrc(F.lastkey, 0, (int)(F.nq * 8u), 0x00020000),
+                                                      on & (lane == 0), (int64_t)pq - 1);
+                    }
 #pragma unroll
                     for (int r = 0; r < kLocalRows; ++r)
                         if (r < rows) stage[lrank[r]] = val[r];
@@ -444,12 +557,15 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
                         if (r < rows) stage[lrank[r]] = key[r];
 #pragma unroll
                     for (int r = 0; r < kLocalRows; ++r) key[r] = nkey[r];  // (the next sub-bucket's keys take over)
+                    LOCAL_CK(20)  // keys staged, next keys taken over (wave 0)
+                    // the walk, the first boundary and loop 2 of the turn before, while the tables still hold it; what wave 0
+                    // leaves in s_edge[2] and s_giveup goes through the barrier the staged keys need anyway
+                    if (pcount) deferred_walk(false, false, pre);
                     lds_barrier();
-                    LOCAL_CK(20)  // keys staged, next keys taken over
+                    if (pcount) gave_up = deferred_loop2(false);
                     // What follows walks the sorted keys in the staging buffer in plain loops (place p = p0 + thread): no
                     // arrays in registers -- an unrolled form with 25 more registers spilled whatever was tried.
                     // Loop 1: heads, LCP of the boundaries, and per 64 places the tied elements and the last head.
-                    const uint32_t bucket = cur_sub >> 8;
                     constexpr int kU = 4;  // (places of four rows per turn: their LDS reads go out together)
                     for (uint32_t p0 = 0, e0 = (uint32_t)w; p0 < count; p0 += kU * kLocalThreads, e0 += kU * kLocalWaves) {
                         uint32_t k[kU], edge[kU];
@@ -501,8 +617,7 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
                     lds_barrier();
                     LOCAL_CK(22)  // ... everybody
                     if (w == 0) {
-                        // the first wave: prefixes over the (rows x waves) entries in place order, the look-back for the tied
-                        // elements in front of the sub-bucket, the first boundary
+                        // the first wave: prefixes over the (rows x waves) entries in place order
                         const uint32_t ne = (uint32_t)rows * kLocalWaves;
                         constexpr int kPer = (kLocalRows * kLocalWaves + 63) / 64;
                         uint32_t c[kPer], h[kPer], sum = 0, mx = 0;
@@ -528,65 +643,24 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
                             run += c[j];
                             lasth = h[j] ? h[j] : lasth;
                         }
-                        const uint32_t q = F.dense[cur_sub];
+                        // published: the last key for the first boundary of the sub-bucket behind, the aggregate for the walks
+                        // of everybody behind -- this workgroup's own walk comes a turn later (deferred_walk, above)
+                        const uint32_t q = cur_q;
                         if (lane == 0) desc_store(F.lastkey + q, (1ull << 32) | (uint64_t)s_edge[1]);
-                        bool failed = preset_failure;
-                        const uint32_t xs = lookback_exclusive_add_wide<4>(F.desc, q, total, F.d_total + 1, kLocalSpinLimit, &failed);
+                        lookback_publish_add(F.desc, q, total);
                         if (lane == 0) {
-                            s_edge[2] = xs;
-                            // (the look-back gave up: this workgroup stops behind this turn; the others give up on their own
-                            // next walk.  Looking at the flag in memory every turn cost 0.5 ms here, 13 ms at the top of the turn.)
-                            s_giveup = failed ? 1u : 0u;
-                            if (q + 1u == F.nq) F.d_total[0] = xs + total;
-                            uint32_t l0 = 0;  // (the very first suffix of the order)
-                            if (q > 0u) {
-                                uint64_t d;
-                                uint32_t spins = 0;
-                                while (((d = desc_load(F.lastkey + (q - 1u))) >> 32) == 0) {
-                                    if (++spins > kLocalSpinLimit) {  // (never hang the GPU)
-                                        atomicExch(F.d_total + 1, 1u);
-                                        s_giveup = 1u;
-                                        break;
-                                    }
-                                    __builtin_amdgcn_s_sleep(1);
-                                }
-                                const uint32_t pk = (uint32_t)d, k = s_edge[0];
-                                uint32_t ls;
-                                if constexpr (kKey35) {  // (8 + 27 key bits)
-                                    const uint64_t y = ((uint64_t)(bucket ^ (F.prev_sub[cur_sub] >> 8)) << (32 - kTagBits)) | (uint64_t)((k ^ pk) >> kTagBits);
-                                    ls = y ? (uint32_t)(__builtin_clzll(y) - (64 - kP35KeyBits)) >> 1 : 0xffffffffu;
-                                } else {
-                                    const uint32_t y = ((bucket ^ (F.prev_sub[cur_sub] >> 8)) << 24) | ((k ^ pk) >> kTagBits);
-                                    ls = y ? (uint32_t)__builtin_clz(y) >> 1 : 0xffffffffu;
-                                }
-                                const uint32_t ta = k & kTagMask, tb = pk & kTagMask;
-                                ls = ls < ta ? ls : ta;
-                                l0 = ls < tb ? ls : tb;
-                            }
-                            F.lcp[first] = l0;
+                            s_pend[0] = q;
+                            s_pend[1] = total;
+                            s_pend[2] = cur_prev;
                         }
                     }
-                    LOCAL_CK(23)  // prefixes + look-back + first boundary (wave 0)
-                    lds_barrier();
-                    LOCAL_CK(24)  // ... everybody
-                    // Loop 2: the tied elements -- slot and slot of the group's head, in slot order
-                    const uint32_t xsum = s_edge[2];
-                    const bool giveup = s_giveup != 0u;  // (uniform)
-                    for (uint32_t p0 = 0, e = (uint32_t)w; p0 < count; p0 += kLocalThreads, e += kLocalWaves) {
-                        const uint64_t hmask = s_mask[2 * e], kmask = s_mask[2 * e + 1];  // (wave-uniform)
-                        if ((kmask >> lane) & 1ull) {
-                            const uint32_t pl = p0 + (uint32_t)tid;
-                            const uint64_t upto = hmask & ((2ull << lane) - 1ull);
-                            const uint32_t hidx = upto ? p0 + (uint32_t)w * 64u + (uint32_t)(63 - __builtin_clzll(upto)) : s_lh[e] - 1u;
-                            const uint32_t pos = xsum + s_cnt[e] + (uint32_t)__popcll(kmask & ((1ull << lane) - 1ull));
-                            F.new_slot[pos] = first + pl;
-                            F.new_grp[pos] = first + hidx;
-                        }
-                    }
-                    LOCAL_CK(25)  // loop 2 (wave 0)
-                    lds_barrier();  // (the staging buffer is free again)
-                    LOCAL_CK(26)  // ... everybody
-                    if (giveup) ncount = 0;  // (the loop over the sub-buckets ends)
+                    LOCAL_CK(23)  // prefixes + publish (wave 0)
+                    // (no barrier: the other waves read the tables and the staging buffer next behind the barriers of the
+                    // next turn's passes, or behind the one of the flush)
+                    pfirst = first;
+                    pcount = count;
+                    psub = cur_sub;
+                    if (gave_up) ncount = 0;  // (the loop over the sub-buckets ends)
                     continue;
                 }
             }
@@ -631,6 +705,14 @@ __global__ __launch_bounds__(kLocalThreads) void local_sort_kernel(
 #ifdef NOLZSS_LOCAL_TIMED
         if (tid == 0) atomicAdd(phases + 31, 1ull);
 #endif
+    }
+    if constexpr (kFuse) {
+        // the flush: the last turn of this workgroup is still pending (a workgroup that had no turn has nothing)
+        if (pcount) {
+            deferred_walk(true, gave_up, nullptr);
+            lds_barrier();
+            deferred_loop2(true);
+        }
     }
 #undef LOCAL_CK
     if (!order_ok) atomicOr(&ctl[2], 1u);
@@ -736,8 +818,9 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
             fprintf(stderr, " pass %d: rank(wave 0) %.0f rank(all) %.0f offsets %.0f stage keys %.0f keys back/out %.0f stage values %.0f values back/out %.0f |",
                     p, h[2 + 8 * p] / wn, h[3 + 8 * p] / wn, h[4 + 8 * p] / wn, h[5 + 8 * p] / wn, h[6 + 8 * p] / wn,
                     h[7 + 8 * p] / wn, h[8 + 8 * p] / wn);
-        fprintf(stderr, " fused: stage values %.0f values out %.0f stage keys + take over %.0f loop1 %.0f (all %.0f) look-back %.0f (all %.0f) loop2 %.0f (all %.0f) |",
-                h[18] / wn, h[19] / wn, h[20] / wn, h[21] / wn, h[22] / wn, h[23] / wn, h[24] / wn, h[25] / wn, h[26] / wn);
+        // (in the order of a turn; the flush is once per workgroup, here spread over its turns like everything else)
+        fprintf(stderr, " fused: stage values %.0f values out %.0f stage keys + take over %.0f deferred walk %.0f (all %.0f) deferred loop2 %.0f loop1 %.0f (all %.0f) publish %.0f flush %.0f |",
+                h[18] / wn, h[19] / wn, h[20] / wn, h[24] / wn, h[25] / wn, h[26] / wn, h[21] / wn, h[22] / wn, h[23] / wn, h[27] / wn);
         fprintf(stderr, " hand-over %.0f\n", h[30] / wn);
     };
 #endif
@@ -745,7 +828,9 @@ void local_sort_sub_buckets(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys
     const bool fail_order = knobs.test_local_order_fails;  // (test hook: the redo path)
     // (it pays where the regroup kernel is expensive -- many tied elements -- and the turns are long: 2^30 bases of the
     // benchmark text 21.7 -> 20.0 ms for sort + regroup, but random DNA of 2^29 bases 10.7 -> 11.2 and of 2^28 bases 6.3 -> 7.5:
-    // the look-back and the two loops are a fixed cost per sub-bucket.  NOLZSS_LOCAL_REGROUP_MIN = smallest text that takes it.)
+    // the look-back and the two loops are a fixed cost per sub-bucket.  NOLZSS_LOCAL_REGROUP_MIN = smallest text that takes it.
+    // With the walk a turn late and the 35-bit key: random DNA of 2^29 bases 5.42 -> 4.61, of 2^28 bases 3.79 -> 3.77, one
+    // repetition each -- the threshold waits for whole-step measurements.)
     if (rg && !knobs.no_local_regroup && !fail_order && npass == 2 && num_sub % 1024u == 0 &&
         (n >= knobs.local_regroup_min || (report && report->regroup_any_size))) {
         // the regroup of round 0 on the way -- if no sub-bucket overflows a workgroup (the segmented passes that finish
