@@ -20,11 +20,16 @@
 // of strictly smaller members of its group (out_lo) and the LCP of every boundary that appeared (lcp_list).
 // A group that runs out of its budget keeps what it has separated; the rest stays tied for the doubling rounds,
 // which then pay for rank[] as before.
+// How a round is issued (profiles/group_sort_trips_ab.txt): one trip to the text -- a member that scans asks for the words
+// of its scan, of its segment's first member and of the window behind them at once, and cuts the window out of its
+// registers when the segment's depth is known --, one thread per position in the queue kernels, a ranking walk whose
+// end is known in advance, and queue items taken from a counter of the shard.
 #pragma once
 
 constexpr uint32_t kGroupSortSmall = 64;   // groups up to here: by tiles of the list, one wavefront per tile
-constexpr uint32_t kGroupSortMid = 256;    // up to here: one wavefront per group (two queues: up to 128, up to 256 --
-                                           // the LDS of a workgroup, i.e. how many groups a CU works on at a time)
+constexpr uint32_t kGroupSortMid = 256;    // up to here: one workgroup per group, a thread per member (two queues: up to 128,
+                                           // up to 256 -- the LDS and the wavefronts of a workgroup, i.e. how many groups a CU
+                                           // works on at a time)
 constexpr uint32_t kGroupSortMid0 = 128;
 constexpr uint32_t kGroupSortMax = 1024;   // up to here: 256 threads per group; beyond: left to the doubling rounds
 constexpr uint32_t kScanWords = 8;         // 64-bit words a member scans per round to find where its segment splits
@@ -46,6 +51,16 @@ constexpr uint32_t kScanWords = 8;         // 64-bit words a member scans per ro
 // Segments that agree up to depth_cap are left tied for the doubling rounds, which start there.
 constexpr uint32_t kPivotWords = 32;  // words a member compares with its pivot per round (1024 bases of DNA)
 constexpr uint32_t kPivotBatch = 8;   // ... of which this many per dependent trip to the text
+// threads of the window-round kernels (the pivot kernels: 64, 128, 256, 256).  The two queue kernels: one position per
+// thread, so that a member keeps the words of its scan in registers and walks its segment once.  The tiles of small
+// groups stay at two positions per thread: a second wavefront per tile halves the tiles a CU works on (128 threads:
+// 0.70 against 0.49 ms on the benchmark text, profiles/group_sort_trips_ab.txt).
+constexpr int kGroupSortTiledThreads = 64, kGroupSortMid0Threads = 128, kGroupSortMidThreads = 256;
+// words a scanning member asks for in ONE trip: the kScanWords of the scan and what a window that starts at the scan's
+// stop still needs (2 words and the one that the shift takes from).  A member only asks where a symbol of its own is
+// left, so the first of them lies inside the text and the last inside the zero words behind it (text.hpp, PackedText)
+constexpr uint32_t kScanFetch = kScanWords + 2;
+static_assert(kScanFetch + 1 <= 12, "a fetch that starts inside the text ends inside the pad words of the packed text");
 
 // one queue entry per LARGE group of the leftover list (items = first list position, items2 = members); groups
 // of up to kGroupSortSmall members are found by the tile kernel itself
@@ -143,24 +158,75 @@ __device__ __forceinline__ uint32_t pivot_lrel_of(uint64_t key) {
 }
 // kPivotBatch words of suffix p from symbol h on, as 2 * kPivotBatch 32-bit words in text order (the high half of
 // a 64-bit word first): kPivotBatch + 1 loads, one funnel shift per 32 bits
-template <int BITS>
-__device__ __forceinline__ void pivot_fetch(const uint64_t *__restrict__ words, uint64_t p, uint32_t h, uint32_t (&win)[2 * kPivotBatch]) {
+template <int BITS, uint32_t W = kPivotBatch>
+__device__ __forceinline__ void pivot_fetch(const uint64_t *__restrict__ words, uint64_t p, uint32_t h, uint32_t (&win)[2 * W]) {
     const uint64_t bit = (p + h) * BITS;
     const uint64_t *src = words + (bit >> 6);
-    uint32_t r[2 * kPivotBatch + 2];
+    uint32_t r[2 * W + 2];
 #pragma unroll
-    for (uint32_t k = 0; k <= kPivotBatch; ++k) {
+    for (uint32_t k = 0; k <= W; ++k) {
         const uint64_t v = src[k];
         r[2 * k] = (uint32_t)(v >> 32);
         r[2 * k + 1] = (uint32_t)v;
     }
     const uint32_t skip = (bit & 32) ? 0xffffffffu : 0u;
     const uint32_t o = (uint32_t)bit & 31;
-    uint32_t q[2 * kPivotBatch + 1];
+    uint32_t q[2 * W + 1];
 #pragma unroll
-    for (uint32_t k = 0; k <= 2 * kPivotBatch; ++k) q[k] = (r[k + 1] & skip) | (r[k] & ~skip);
+    for (uint32_t k = 0; k <= 2 * W; ++k) q[k] = (r[k + 1] & skip) | (r[k] & ~skip);
 #pragma unroll
-    for (uint32_t k = 0; k < 2 * kPivotBatch; ++k) win[k] = o ? __builtin_amdgcn_alignbit(q[k], q[k + 1], 32 - o) : q[k];
+    for (uint32_t k = 0; k < 2 * W; ++k) win[k] = o ? __builtin_amdgcn_alignbit(q[k], q[k + 1], 32 - o) : q[k];
+}
+
+// first symbol at which the scans x and y of two members differ, counted from the scan's start (kScanWords words: the
+// scan's reach if they agree)
+template <int BITS, uint32_t WX, uint32_t WY>
+__device__ __forceinline__ uint32_t scan_first_diff(const uint32_t (&x)[WX], const uint32_t (&y)[WY]) {
+    uint32_t fb = 2 * kScanWords, xw = 0, yw = 0;
+#pragma unroll
+    for (int b = 2 * (int)kScanWords - 1; b >= 0; --b) {
+        const bool diff = x[b] != y[b];
+        fb = diff ? (uint32_t)b : fb;
+        xw = diff ? x[b] : xw;
+        yw = diff ? y[b] : yw;
+    }
+    return fb < 2 * kScanWords ? fb * (32 / BITS) + (uint32_t)__clz((int)(xw ^ yw)) / BITS : kScanWords * (64 / BITS);
+}
+
+// group_window of a member whose text from depth d0 on stands in x (kScanFetch words): the window at depth D, d0 <= D <= d0 +
+// kScanWords words, cut from the registers
+template <int BITS>
+__device__ __forceinline__ void group_window_cut(const uint32_t (&x)[2 * kScanFetch], uint32_t d0, uint32_t D, uint32_t lim,
+                                                 uint32_t term, uint64_t &k0, uint64_t &k1, uint32_t &tt) {
+    constexpr uint32_t kPer = 64 / BITS, kPer32 = 32 / BITS;
+    const uint32_t rem = lim > D ? lim - D : 0u;
+    const uint32_t tag = rem < 2 * kPer ? rem : 2 * kPer;
+    uint64_t w0 = 0, w1 = 0;
+    if (tag) {
+        const uint32_t i = (D - d0) / kPer32, o = ((D - d0) % kPer32) * BITS;
+        uint32_t a[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t j = 0; j <= 2 * kScanWords; ++j) {
+#pragma unroll
+            for (uint32_t c = 0; c < 5; ++c) a[c] = (i == j && j + c < 2 * kScanFetch) ? x[j + c < 2 * kScanFetch ? j + c : 0] : a[c];
+        }
+        uint32_t v[4];
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) v[c] = o ? __builtin_amdgcn_alignbit(a[c], a[c + 1], 32 - o) : a[c];
+        w0 = ((uint64_t)v[0] << 32) | v[1];
+        w1 = ((uint64_t)v[2] << 32) | v[3];
+        if (tag < kPer) {
+            w0 &= ~((~0ull) >> (tag * BITS));
+            w1 = 0;
+        } else if (tag == kPer) {
+            w1 = 0;
+        } else if (tag < 2 * kPer) {
+            w1 &= ~((~0ull) >> ((tag - kPer) * BITS));
+        }
+    }
+    k0 = w0;
+    k1 = w1;
+    tt = (tag << 16) | (tag < 2 * kPer ? (term & 0xffffu) : 0u);
 }
 
 // kTiled = false: one workgroup per queue entry (a group of up to NMAX members), grid (kQShards, Y).
@@ -170,7 +236,11 @@ __device__ __forceinline__ void pivot_fetch(const uint64_t *__restrict__ words, 
 //   round trips to the text.  List positions are sorted positions: a group's members hold consecutive list
 //   positions (and slots), and sorting only ever moves members inside their group.
 // kPivot: pivot rounds instead of window rounds (above); depth_cap: segments that agree that far stay tied.
-template <int BITS, int THREADS, int NMAX, bool kTiled, bool kPivot = false>
+// kTimed (NOLZSS_GROUP_SORT_PHASES): a separate instantiation whose thread 0 adds, in every 8th workgroup, the cycles of each
+// phase to phases[0 .. 5] (set-up, scan, window, ranking, boundaries + next segments, output), the rounds to [6], the groups
+// (tiles) to [7]; the words its scanning members needed to [8] and their number to [9].  The untimed form has none of it.
+constexpr int kGroupSortPhaseWords = 16;
+template <int BITS, int THREADS, int NMAX, bool kTiled, bool kPivot = false, bool kTimed = false>
 __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const uint32_t *__restrict__ act_slot,
                                                              const uint32_t *__restrict__ act_grp, uint32_t m,
                                                              uint32_t *sa, const uint64_t *__restrict__ words,
@@ -179,8 +249,21 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
                                                              uint32_t *__restrict__ lcp_list,
                                                              uint32_t *__restrict__ min_depth,
                                                              const uint32_t *__restrict__ lcp_mark, uint32_t max_rounds,
-                                                             uint32_t depth_cap = 0xffffffffu) {
+                                                             uint32_t depth_cap = 0xffffffffu,
+                                                             unsigned long long *__restrict__ phases = nullptr) {
     constexpr uint32_t kPer = 64 / BITS;
+    const bool wg_timed = kTimed && phases != nullptr && ((blockIdx.x + blockIdx.y) & 7) == 0;
+    const bool timed = wg_timed && threadIdx.x == 0;
+    __shared__ uint32_t s_stat[kTimed ? 2 : 1];  // (timed) words the scanning members needed, scanning members
+    if (kTimed && timed) s_stat[0] = s_stat[1] = 0;
+    unsigned long long ck_last = 0, ck_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto tick = [&](int phase) {  // (the cycles since the last tick go to `phase`)
+        if (kTimed && timed) {
+            const unsigned long long now = __builtin_readcyclecounter();
+            ck_acc[phase] += now - ck_last;
+            ck_last = now;
+        }
+    };
     constexpr int kWavesB = THREADS / 64;
     constexpr uint32_t kTile = NMAX / 2;  // (tiled) list positions whose groups this workgroup takes
     static_assert(!kTiled || kTile == kGroupSortSmall, "a tile's span holds every small group that starts in it");
@@ -198,13 +281,20 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
     __shared__ uint8_t s_scanit[NMAX];     // [segment starts] the last round did not split it: scan ahead first
     __shared__ uint32_t s_blcp[NMAX];      // [new heads] LCP with the position in front
     __shared__ uint32_t s_depth[NMAX];     // [segment starts] symbols all members of the segment agree on
-    __shared__ uint32_t s_tmp[NMAX];       // scratch: minimum of the scans, then the depth of the next round
+    __shared__ uint32_t s_tmp[NMAX];       // scratch: the depth of the next round (pivot rounds: first the minimum of the scans)
+    __shared__ uint32_t s_dmin[kPivot ? 1 : NMAX];  // [segment starts, window rounds] depth of this round: the segment's own,
+                                                    // or the minimum of its members' scans (preset by the round in front)
+    __shared__ uint16_t s_end[kPivot ? 1 : NMAX];   // [segment starts, window rounds] position behind the segment's last member
     __shared__ uint32_t s_scan[kWavesB + 1];
     __shared__ uint32_t s_any;
     const uint32_t t = threadIdx.x;
     const uint32_t shard = blockIdx.x;
     const uint32_t count = kTiled ? 1u : q.counts[shard * kQPad];
-    for (uint32_t item = kTiled ? 0u : blockIdx.y; item < count; item += kTiled ? 1u : gridDim.y) {
+    // (queue kernels) items are TAKEN, not dealt: the first gridDim.y items of a shard go to its workgroups by their number,
+    // every further one to whoever asks the shard's second counter first -- a workgroup that drew slow groups leaves the
+    // others to its neighbours.  One atomic per item, asked for while the group before is set up; nobody waits for anybody.
+    __shared__ uint32_t s_item;
+    for (uint32_t item = kTiled ? 0u : blockIdx.y; item < count;) {
         // list positions [base, base + span): position e of the arrays is list element base + e
         uint32_t base, span, N;
         if (kTiled) {
@@ -218,6 +308,12 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
             while (N < span) N <<= 1;
         }
         __syncthreads();  // (the arrays of the group before this one are done with)
+        uint32_t next_item = 0;
+        if (!kTiled && t == 0) next_item = gridDim.y + atomicAdd(q.counts + shard * kQPad + 1, 1u);
+        if (kTimed && timed) {
+            ck_last = __builtin_readcyclecounter();
+            ck_acc[7] += 1;
+        }
         if (kTiled) {  // sizes of the groups that start in the tile, told by their last member
             for (uint32_t e = t; e < (uint32_t)NMAX; e += THREADS) s_tmp[e] = 0;
             __syncthreads();
@@ -239,9 +335,13 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
                     const uint32_t gs = s_tmp[e - j];
                     mine = gs != 0 && gs <= kGroupSortSmall;       // ... and is small
                     if (mine && lcp_mark != nullptr) mine = lcp_mark[g + 1] == kLcpPending;  // ... and was not compared yet
+                    if constexpr (!kPivot)
+                        if (mine && j + 1 == gs) s_end[e - j] = (uint16_t)(e + 1);  // (the group's last member)
                 }
             } else if (mine) {
                 slot = act_grp[base] + e;  // (the group's members hold the slots from its head slot on)
+                if constexpr (!kPivot)
+                    if (e + 1 == span) s_end[0] = (uint16_t)span;
             }
             uint32_t p = 0, lim = 0, term = 0;
             if (mine) {
@@ -263,11 +363,17 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
             s_head[e] = (!mine || j == 0) ? 1 : 0;
             s_blcp[e] = kLcpPending;
             s_depth[e] = h0;
+            if constexpr (!kPivot) s_dmin[e] = h0;  // (the first round does not scan)
         }
-        if (t == 0) s_head[N] = 1;
+        if (t == 0) {
+            s_head[N] = 1;
+            s_item = next_item;
+        }
         __syncthreads();
+        tick(0);
         bool tied = true;
         for (uint32_t round = 0; tied && round < max_rounds; ++round) {
+            if (kTimed && timed) ck_acc[6] += 1;
             constexpr int kE = NMAX / THREADS;  // positions per thread: e = t + k * THREADS
             uint64_t rk0[kE], rk1[kE];
             uint32_t rtt[kE], rmem[kE], rhs[kE];
@@ -340,42 +446,17 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
                     s_key[e] = key;
                 }
                 __syncthreads();
+                tick(1);
             } else {
-            // ---- 1. a segment that the last round did not split: how far does every member agree with its first
-            // member?  (a scan of up to kScanWords words; the others take their window where they stand)
-            for (uint32_t e = t; e < span; e += THREADS) {
-                const uint32_t mem = s_ord[e];
-                s_split[e] = 0;
-                s_tmp[e] = (s_act[mem] && s_seg[mem] == e && !s_scanit[e]) ? s_depth[e] : 0xffffffffu;
-            }
-            __syncthreads();
-            for (uint32_t e = t; e < span; e += THREADS) {
-                const uint32_t mem = s_ord[e];
-                if (!s_act[mem]) continue;
-                const uint32_t hs = s_seg[mem];
-                if (hs == e || !s_scanit[hs]) continue;  // (the first member itself: somebody else reports)
-                const uint32_t d0 = s_depth[hs];
-                const uint32_t lead = s_ord[hs];
-                const uint32_t la = s_lim[mem], lb = s_lim[lead];
-                const uint32_t limit = la < lb ? la : lb;
-                const uint32_t stop = d0 + kScanWords * kPer;
-                uint32_t h = d0;
-                const uint64_t pa = s_pos[mem], pb = s_pos[lead];
-                while (h < limit && h < stop) {
-                    const uint64_t x = sym_word<BITS>(words, pa + h);
-                    const uint64_t y = sym_word<BITS>(words, pb + h);
-                    if (x != y) {
-                        h += (uint32_t)__clzll((long long)(x ^ y)) / BITS;
-                        break;
-                    }
-                    h += kPer;
-                }
-                h = h < limit ? h : limit;
-                h = h < stop ? h : stop;
-                atomicMin(&s_tmp[hs], h);
-            }
-            __syncthreads();
-            // ---- 2. the window at the segment's new depth: kept in registers and parked BY POSITION for the ranking
+            // ---- 1. ONE trip to the text per round.  A segment that the last round did not split scans: how far does every
+            // member agree with its first member (up to kScanWords words)?  The segment's depth is the minimum, known behind
+            // the barrier, and the window stands there -- so a member of such a segment (its first member too) asks for
+            // its kScanFetch words at once, those of the first member next to them, and cuts its window out of them when the
+            // depth is known (kCut: one position per thread; with more the words would not stay in registers, and the
+            // window is fetched behind the barrier as it used to be).  The others take their window where they stand.
+            constexpr bool kCut = kE == 1;
+            uint32_t xs[kCut ? 2 * kScanFetch : 1], rd0 = 0;
+            bool cut = false;
 #pragma unroll
             for (int k = 0; k < kE; ++k) {
                 const uint32_t e = t + (uint32_t)k * THREADS;
@@ -384,22 +465,84 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
                 rtt[k] = rmem[k] = rhs[k] = 0;
                 if (e >= span) continue;
                 const uint32_t mem = s_ord[e];
+                s_split[e] = 0;
                 if (!s_act[mem]) continue;
                 ract[k] = true;
                 rmem[k] = mem;
-                rhs[k] = s_seg[mem];
-                const uint32_t D = s_tmp[rhs[k]];
-                group_window<BITS>(words, s_pos[mem], D, s_lim[mem], s_term[mem], rk0[k], rk1[k], rtt[k]);
-                s_key[e] = rk0[k];
-                s_key2[e] = rk1[k];
-                s_tt[e] = rtt[k];
+                const uint32_t hs = s_seg[mem];
+                rhs[k] = hs;
+                const uint32_t d0 = s_depth[hs];
+                const uint32_t la = s_lim[mem];
+                const uint64_t pa = s_pos[mem];
+                if (!s_scanit[hs]) {
+                    if constexpr (kCut) {
+                        group_window<BITS>(words, (uint32_t)pa, d0, la, s_term[mem], rk0[k], rk1[k], rtt[k]);
+                        s_key[e] = rk0[k];
+                        s_key2[e] = rk1[k];
+                        s_tt[e] = rtt[k];
+                    }
+                    continue;
+                }
+                const uint32_t lead = s_ord[hs];
+                const uint32_t lb = s_lim[lead];
+                const uint32_t limit = la < lb ? la : lb;
+                const uint32_t stop = d0 + kScanWords * kPer;
+                uint32_t h = d0;
+                if constexpr (kCut) {
+                    cut = true;
+                    rd0 = d0;
+#pragma unroll
+                    for (uint32_t c = 0; c < 2 * kScanFetch; ++c) xs[c] = 0;
+                    if (d0 < la) pivot_fetch<BITS, kScanFetch>(words, pa, d0, xs);
+                    if (e != hs && d0 < limit) {
+                        uint32_t y[2 * kScanWords];
+                        pivot_fetch<BITS, kScanWords>(words, (uint64_t)s_pos[lead], d0, y);
+                        h = d0 + scan_first_diff<BITS>(xs, y);
+                    }
+                } else {
+                    if (e != hs && d0 < limit) {
+                        uint32_t x[2 * kScanWords], y[2 * kScanWords];
+                        pivot_fetch<BITS, kScanWords>(words, pa, d0, x);
+                        pivot_fetch<BITS, kScanWords>(words, (uint64_t)s_pos[lead], d0, y);
+                        h = d0 + scan_first_diff<BITS>(x, y);
+                    }
+                }
+                if (e == hs) continue;  // (the first member itself: somebody else reports)
+                h = h < limit ? h : limit;
+                h = h < stop ? h : stop;
+                if (kTimed && wg_timed) {  // words this member needed
+                    atomicAdd(&s_stat[0], d0 < limit ? (h - d0) / kPer + (h < stop ? 1u : 0u) : 0u);
+                    atomicAdd(&s_stat[1], 1u);
+                }
+                atomicMin(&s_dmin[hs], h);
             }
             __syncthreads();
+            tick(1);
+            // ---- 2. the window at the segment's depth: kept in registers and parked BY POSITION for the ranking
 #pragma unroll
-            for (int k = 0; k < kE; ++k) {  // (s_depth of a segment start: read above, written here)
+            for (int k = 0; k < kE; ++k) {
                 const uint32_t e = t + (uint32_t)k * THREADS;
-                if (ract[k] && rhs[k] == e) s_depth[e] = s_tmp[e];
+                if (!ract[k]) continue;
+                const uint32_t D = s_dmin[rhs[k]];
+                if constexpr (kCut) {
+                    if (cut) {
+                        const uint32_t mem = rmem[k];
+                        group_window_cut<BITS>(xs, rd0, D, s_lim[mem], s_term[mem], rk0[k], rk1[k], rtt[k]);
+                        s_key[e] = rk0[k];
+                        s_key2[e] = rk1[k];
+                        s_tt[e] = rtt[k];
+                    }
+                } else {
+                    const uint32_t mem = rmem[k];
+                    group_window<BITS>(words, s_pos[mem], D, s_lim[mem], s_term[mem], rk0[k], rk1[k], rtt[k]);
+                    s_key[e] = rk0[k];
+                    s_key2[e] = rk1[k];
+                    s_tt[e] = rtt[k];
+                }
+                if (rhs[k] == e) s_depth[e] = D;  // (a segment start: read in front of the barrier, written here)
             }
+            __syncthreads();
+            tick(2);
             }  // (!kPivot)
             // ---- 3. my place inside my segment: members with a smaller (window, terminator), plus the equal ones in
             // front of me.  Every lane walks its own segment (the members of a segment read the same entries: LDS
@@ -422,18 +565,43 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
                     npos[k] = rhs[k] + less + eqb;
                     continue;
                 }
-                for (uint32_t x = rhs[k];; ++x) {
-                    if (x > rhs[k] && s_head[x]) break;  // (s_head[N] = 1 ends the last segment)
-                    const uint64_t xk0 = s_key[x], xk1 = s_key2[x];
+                // (the segment's end is known, s_end: four first words are read at a time, none of them waits for a test
+                // of the one in front; the second word and the terminator word only where the first one is equal)
+                const uint32_t end = s_end[rhs[k]];
+                const uint64_t my0 = rk0[k], my1 = rk1[k];
+                const uint32_t mytt = rtt[k];
+                auto rest = [&](uint32_t x) {  // an entry whose first word equals mine
+                    const uint64_t xk1 = s_key2[x];
                     const uint32_t xtt = s_tt[x];
-                    const bool lt = xk0 != rk0[k] ? xk0 < rk0[k] : (xk1 != rk1[k] ? xk1 < rk1[k] : xtt < rtt[k]);
-                    const bool eq = xk0 == rk0[k] && xk1 == rk1[k] && xtt == rtt[k];
-                    less += lt ? 1u : 0u;
-                    eqb += (eq && x < e) ? 1u : 0u;
+                    less += (xk1 != my1 ? xk1 < my1 : xtt < mytt) ? 1u : 0u;
+                    eqb += (xk1 == my1 && xtt == mytt && x < e) ? 1u : 0u;
+                };
+                uint32_t x = rhs[k];
+                for (; x + 4 <= end; x += 4) {
+                    uint64_t a[4];
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; ++c) a[c] = s_key[x + c];
+                    bool same = false;
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; ++c) {
+                        less += a[c] < my0 ? 1u : 0u;
+                        same |= a[c] == my0;
+                    }
+                    if (same) {
+#pragma unroll
+                        for (uint32_t c = 0; c < 4; ++c)
+                            if (a[c] == my0) rest(x + c);
+                    }
+                }
+                for (; x < end; ++x) {
+                    const uint64_t xk0 = s_key[x];
+                    if (xk0 == my0) rest(x);
+                    else less += xk0 < my0 ? 1u : 0u;
                 }
                 npos[k] = rhs[k] + less + eqb;
             }
             __syncthreads();
+            tick(3);
 #pragma unroll
             for (int k = 0; k < kE; ++k) {
                 if (!ract[k]) continue;
@@ -522,13 +690,18 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
                         any |= act;
                         if (hs == e) {  // a segment start (old or new) of a segment that was tied
                             s_depth[e] = s_tmp[e];
-                            s_scanit[e] = kPivot ? 0 : (s_split[old_hs] ? 0 : 1);
+                            const bool scan = kPivot ? false : s_split[old_hs] == 0;
+                            s_scanit[e] = scan ? 1 : 0;
+                            if constexpr (!kPivot) s_dmin[e] = scan ? 0xffffffffu : s_tmp[e];
                         }
+                        if constexpr (!kPivot)
+                            if (s_head[e + 1]) s_end[hs] = (uint16_t)(e + 1);  // (the segment's last member)
                     }
                 if (any) s_any = 1;
                 __syncthreads();
                 tied = s_any != 0;
             }
+            tick(4);
         }
         // ---- output
         if (tied) {  // the depth every group that stays tied agrees on (the doubling rounds start there)
@@ -549,5 +722,13 @@ __global__ __launch_bounds__(THREADS) void group_sort_kernel(ShardQueue q, const
             out_lo[a] = (uint32_t)s_seg[mem] - gs;  // strictly smaller members of my group
             lcp_list[a] = e == gs ? 0u : (s_head[e] ? s_blcp[e] : kLcpPending);
         }
+        tick(5);
+        item = kTiled ? count : s_item;  // (written in front of the barrier behind the set-up, next behind the one at the top)
+    }
+    if (kTimed && timed) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) atomicAdd(phases + k, ck_acc[k]);
+        atomicAdd(phases + 8, (unsigned long long)s_stat[0]);
+        atomicAdd(phases + 9, (unsigned long long)s_stat[1]);
     }
 }

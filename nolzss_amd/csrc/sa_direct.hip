@@ -582,29 +582,52 @@ void group_sort_rounds(Context &ctx, const PackedText &text, const uint32_t *slo
         const unsigned ym = (unsigned)std::min<size_t>(64, std::max<size_t>(1, div_up(m, (size_t)kQShards * 64)));
         const unsigned yb = (unsigned)std::min<size_t>(16, std::max<size_t>(1, div_up(m, (size_t)kQShards * 256)));
         const dim3 gm(kQShards, ym), gb(kQShards, yb);
+        // (NOLZSS_GROUP_SORT_PHASES: the timed instantiations, one row of clocks per launch)
+        unsigned long long *gphases = nullptr;
+        if (sa_knobs().group_sort_phases) {
+            gphases = arena.alloc<unsigned long long>(4 * kGroupSortPhaseWords);
+            HIP_CHECK(hipMemsetAsync(gphases, 0, 4 * kGroupSortPhaseWords * sizeof(unsigned long long), s));
+        }
         dispatch_bits(text.bits, [&](auto B) {
             constexpr int kBits = decltype(B)::value;
+            auto launch = [&](auto P, auto T) {
+                constexpr bool kP = decltype(P)::value, kT = decltype(T)::value;
+                unsigned long long *ph = gphases;
+                auto row = [&](int k) { return ph ? ph + k * kGroupSortPhaseWords : nullptr; };
+                group_sort_kernel<kBits, kGroupSortTiledThreads, kSmallN, true, kP, kT><<<tiles, kGroupSortTiledThreads, 0, s>>>(
+                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap, row(0));
+                constexpr int kT0 = kP ? 128 : kGroupSortMid0Threads, kT1 = kP ? 256 : kGroupSortMidThreads;
+                group_sort_kernel<kBits, kT0, kMid0N, false, kP, kT><<<gm, kT0, 0, s>>>(
+                    q_mid0, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap, row(1));
+                group_sort_kernel<kBits, kT1, kMidN, false, kP, kT><<<gm, kT1, 0, s>>>(
+                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap, row(2));
+                group_sort_kernel<kBits, 256, kBigN, false, kP, kT><<<gb, 256, 0, s>>>(
+                    q_big, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap, row(3));
+            };
             if (pivot) {
-                group_sort_kernel<kBits, 64, kSmallN, true, true><<<tiles, 64, 0, s>>>(
-                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
-                group_sort_kernel<kBits, 128, kMid0N, false, true><<<gm, 128, 0, s>>>(
-                    q_mid0, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
-                group_sort_kernel<kBits, 256, kMidN, false, true><<<gm, 256, 0, s>>>(
-                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
-                group_sort_kernel<kBits, 256, kBigN, false, true><<<gb, 256, 0, s>>>(
-                    q_big, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds, depth_cap);
+                if (gphases) launch(std::true_type{}, std::true_type{});
+                else launch(std::true_type{}, std::false_type{});
             } else {
-                group_sort_kernel<kBits, 64, kSmallN, true><<<tiles, 64, 0, s>>>(
-                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
-                group_sort_kernel<kBits, 64, kMid0N, false><<<gm, 64, 0, s>>>(
-                    q_mid0, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
-                group_sort_kernel<kBits, 64, kMidN, false><<<gm, 64, 0, s>>>(
-                    q_mid, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
-                group_sort_kernel<kBits, 256, kBigN, false><<<gb, 256, 0, s>>>(
-                    q_big, slot, grp, m, sa, text.words, text.terms, h0, out_lo, lcp_list, d_min_depth, lcp_mark, max_rounds);
+                if (gphases) launch(std::false_type{}, std::true_type{});
+                else launch(std::false_type{}, std::false_type{});
             }
         });
         KERNEL_CHECK();
+        if (gphases) {
+            unsigned long long hp[4 * kGroupSortPhaseWords];
+            HIP_CHECK(hipMemcpyAsync(hp, gphases, sizeof(hp), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            static const char *const kForm[4] = {"tiles", "up to 128", "up to 256", "up to 1024"};
+            for (int k = 0; k < 4; ++k) {
+                const unsigned long long *r = hp + k * kGroupSortPhaseWords;
+                if (!r[7]) continue;
+                const double g = (double)r[7];
+                fprintf(stderr, "[nolzss] group_sort %s phases %s (cycles per group, %llu sampled): set-up %.0f  scan %.0f  window %.0f  ranking %.0f  "
+                                "boundaries+segments %.0f  output %.0f  rounds %.2f  scan words per scanning member %.2f (%llu scans)\n",
+                        pivot ? "pivot" : "window", kForm[k], r[7], r[0] / g, r[1] / g, r[2] / g, r[3] / g, r[4] / g, r[5] / g, r[6] / g,
+                        r[9] ? (double)r[8] / (double)r[9] : 0.0, r[9]);
+            }
+        }
     }
 }
 

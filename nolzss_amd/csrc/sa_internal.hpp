@@ -67,6 +67,7 @@ struct SaKnobs {
     uint32_t refine_words;    // NOLZSS_REFINE_WORDS: cap of the direct round, at most 32 words (1024 bases of DNA) deep;
                               // longer ties are cheaper in the doubling rounds
     bool refine_phases;       // NOLZSS_REFINE_PHASES: (diagnostics) cycles per phase of group_refine_kernel
+    bool group_sort_phases;   // NOLZSS_GROUP_SORT_PHASES: (diagnostics) cycles per phase of the group_sort_kernel launches
     bool no_stragglers;       // NOLZSS_NO_STRAGGLERS: (A/B switch)
     bool no_direct2;          // NOLZSS_NO_DIRECT2: A/B switch, no second direct round (and no equalising round)
     uint32_t direct2_div;     // NOLZSS_DIRECT2_MAX: largest share of the text, 1 / this, that takes the second direct round --

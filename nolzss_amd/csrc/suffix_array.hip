@@ -239,6 +239,7 @@ SaKnobs::SaKnobs() {
     regroup_phases = set("NOLZSS_REGROUP_PHASES");
     refine_words = u32("NOLZSS_REFINE_WORDS", 32u);
     refine_phases = set("NOLZSS_REFINE_PHASES");
+    group_sort_phases = set("NOLZSS_GROUP_SORT_PHASES");
     no_stragglers = set("NOLZSS_NO_STRAGGLERS");
     no_direct2 = set("NOLZSS_NO_DIRECT2");
     direct2_div = u32("NOLZSS_DIRECT2_MAX", 64u);
