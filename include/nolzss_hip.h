@@ -1012,6 +1012,31 @@ int nolzss_debug_text_order(const uint32_t *idx, const uint32_t *val, const uint
 int nolzss_debug_group_sort(const uint8_t *text, size_t n, uint32_t *sa, const uint32_t *slot, const uint32_t *grp, size_t m,
                             uint32_t h0, int pivot, uint32_t max_rounds, uint32_t depth_cap, const uint32_t *lcp_mark,
                             int device, uint32_t *out_lo, uint32_t *lcp_list, uint32_t *min_depth, uint32_t *info);
+/* The greedy cursor (chain.hip: mark_chain, chain_starts, chain_lengths) and the widening of 16-bit codes (lpnf.hip:
+ * widened_lstar) on the caller's codes -- the production functions, which read the codes and nothing else.  codes[n]: one
+ * u32 per position, length in bits 0..30 (0 = literal), bit 31 the strand.  The cursor runs p -> p + max(1, length) from
+ * start_pos (start_pos >= n: *z = 0, nothing is launched; n == 0 returns at once).
+ *   width 32: the codes as they are.
+ *   width 16, list_max == 0: the codes narrowed into a uint16_t array allocated and padded as the pipeline's own (n + 8
+ *     entries), the padding filled with the half-word `poison`; every code must be below 0xffff.  The cursor kernels read
+ *     two bytes per position.  lengths / hist asked of this form: NOLZSS_ERR_DEVICE (the length kernels read 32-bit codes).
+ *   width 16, list_max 1 .. 0xffff: the narrow array as above (codes <= list_max) and list[list_len], entries
+ *     (position | code << 32), of which the first `listed` are applied by widened_lstar: of two entries for one position
+ *     the larger counts, an entry with position >= n is ignored.  The widened array (widened[n], optional) is what the
+ *     cursor then runs on, as 32-bit codes.
+ * with_strand: hist holds 2 x 2048 bins, those of the codes with bit 31 behind the others (else 2048 bins; bit 31 is
+ * masked out of the length either way).  bounds (optional): 2k ascending u32, counts[j] = starts inside [bounds[2j],
+ * bounds[2j + 1]) (rlz_count_per_target over the emitted starts).
+ * Out, each but z optional: *z, starts[z] (room for n), lengths[z] in factor order (room for n: max(1, code & 0x7fffffff)
+ * of every start), hist (bin strand * 2048 + L for L < 2048) with tail[*tail_count] (room for n / 2048 + 1: L | strand <<
+ * 32 for L >= 2048, in no particular order), widened[n], counts[k].  For z == 0 hist, *tail_count and counts are zero.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, another width, n > 2^32 - 2^19 - 1, a poison
+ * above 0xffff, a 16-bit code >= 0xffff (with a list: > list_max), hist without tail and tail_count, bounds that do not
+ * ascend, listed > list_len, a list or `widened` without list_max, list_max with width 32 or above 0xffff. */
+int nolzss_debug_chain(const uint32_t *codes, size_t n, size_t start_pos, int width, uint32_t poison, const uint64_t *list,
+                       size_t list_len, size_t listed, uint32_t list_max, int with_strand, const uint32_t *bounds, size_t k,
+                       int device, uint32_t *z, uint32_t *starts, uint32_t *lengths, uint32_t *hist, uint64_t *tail,
+                       uint32_t *tail_count, uint32_t *widened, uint32_t *counts);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

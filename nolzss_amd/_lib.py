@@ -322,6 +322,8 @@ def _load():
                                             vp, vp, vp, vp, vp, vp, vp]
     lib.nolzss_debug_group_sort.argtypes = [vp, sz, vp, vp, vp, sz, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_int,
                                             vp, vp, vp, vp]
+    lib.nolzss_debug_chain.argtypes = [vp, sz, sz, C.c_int, C.c_uint32, vp, sz, sz, C.c_uint32, C.c_int, vp, sz, C.c_int,
+                                       vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nolzss_debug_arena.argtypes = [C.c_int, szp, szp]
     lib.nolzss_debug_trim_arenas.argtypes = [C.c_int, szp]
     lib.nolzss_debug_parse_fasta.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), szp, C.POINTER(C.c_void_p),
@@ -374,6 +376,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_finder_kernel", "nolzss_rlz_finder_close",
     "nolzss_debug_pyramid", "nolzss_debug_nearest", "nolzss_debug_lds_search",
     "nolzss_debug_local_sort", "nolzss_debug_text_order", "nolzss_debug_group_sort",
+    "nolzss_debug_chain",
 ]
 
 

@@ -1956,3 +1956,45 @@ def debug_lds_search(sa, lcp, form: int = LDS_PLAIN, strand: int = 0, poison: in
     check(lib.nolzss_debug_lds_search(sa.ctypes.data, lcp.ctypes.data, sa.size, form, strand, poison, _default_device,
                                       length.ctypes.data, pos.ctypes.data))
     return length, pos
+
+
+LENGTH_HIST_BINS = 2048
+
+
+def debug_chain(codes, start_pos: int = 0, width: int = 32, poison: int = 0, wide_list=None, listed=None,
+                list_max: int = 0, with_strand: bool = False, bounds=None, want_lengths: bool = True,
+                want_hist: bool = True):
+    """The greedy cursor on the device over caller codes (nolzss_debug_chain, test hook): mark_chain, chain_starts and
+    chain_lengths of the pipeline itself.  `codes`: one u32 per position (length in bits 0..30, 0 = literal, bit 31 the
+    strand).  width 16: the codes are narrowed into a uint16 array padded as the pipeline's own, the padding filled
+    with the half-word `poison`.  list_max (width 16): `wide_list` holds (position | code << 32) entries of which the
+    first `listed` (default: all) are applied by widened_lstar; the cursor then runs on the widened 32-bit array.
+    `bounds`: 2k ascending u32 for counts of the starts per [lo, hi).  Returns {"z", "starts", "lengths", "hist", "tail"
+    (sorted: the kernel writes it in no particular order), "widened", "counts"}; what was not asked for is None."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint32)
+    n = codes.size
+    if not (0 <= start_pos < 1 << 64 and 0 <= poison < 1 << 32 and 0 <= list_max < 1 << 32):
+        raise ValueError("start_pos, poison and list_max are unsigned values")
+    items = np.ascontiguousarray(wide_list, dtype=np.uint64) if wide_list is not None else None
+    list_len = items.size if items is not None else 0
+    listed = list_len if listed is None else int(listed)
+    bnd = np.ascontiguousarray(bounds, dtype=np.uint32) if bounds is not None else None
+    if bnd is not None and bnd.size % 2:
+        raise ValueError("the bounds come in pairs")
+    k = bnd.size // 2 if bnd is not None else 0
+    bins = LENGTH_HIST_BINS * (2 if with_strand else 1)
+    z, tail_count = C.c_uint32(), C.c_uint32()
+    starts = np.zeros(max(n, 1), dtype=np.uint32)
+    lengths = np.zeros(max(n, 1), dtype=np.uint32) if want_lengths else None
+    hist = np.zeros(bins, dtype=np.uint32) if want_hist else None
+    tail = np.zeros(n // LENGTH_HIST_BINS + 1, dtype=np.uint64) if want_hist else None
+    widened = np.zeros(max(n, 1), dtype=np.uint32) if list_max else None
+    counts = np.zeros(max(k, 1), dtype=np.uint32) if bnd is not None else None
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    check(lib.nolzss_debug_chain(ptr(codes), n, start_pos, width, poison, ptr(items), list_len, listed, list_max,
+                                 1 if with_strand else 0, ptr(bnd), k, _default_device, C.byref(z), starts.ctypes.data,
+                                 ptr(lengths), ptr(hist), ptr(tail), C.byref(tail_count) if want_hist else None,
+                                 ptr(widened), ptr(counts)))
+    return {"z": z.value, "starts": starts[:z.value], "lengths": lengths[:z.value] if want_lengths else None,
+            "hist": hist, "tail": np.sort(tail[:tail_count.value]) if want_hist else None,
+            "widened": widened[:n] if list_max else None, "counts": counts[:k] if bnd is not None else None}

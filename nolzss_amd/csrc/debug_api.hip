@@ -399,6 +399,109 @@ int nolzss_debug_group_sort(const uint8_t *text, size_t n, uint32_t *sa, const u
     });
 }
 
+int nolzss_debug_chain(const uint32_t *codes, size_t n, size_t start_pos, int width, uint32_t poison, const uint64_t *list,
+                       size_t list_len, size_t listed, uint32_t list_max, int with_strand, const uint32_t *bounds, size_t k,
+                       int device, uint32_t *z, uint32_t *starts, uint32_t *lengths, uint32_t *hist, uint64_t *tail,
+                       uint32_t *tail_count, uint32_t *widened, uint32_t *counts) {
+    return guarded([&] {
+        const bool widen = list_max != 0;
+        if (!z || (n && !codes)) throw std::invalid_argument("null argument");
+        if (width != 16 && width != 32) throw std::invalid_argument("codes of 16 or of 32 bits");
+        if (n > kMaxText) throw std::invalid_argument("too many codes: the device pipeline uses 32-bit indices");
+        if (poison > 0xffffu) throw std::invalid_argument("the poison is a half-word");
+        if (hist && (!tail || !tail_count)) throw std::invalid_argument("a histogram needs its tail list and the count of it");
+        if ((k && (!bounds || !counts)) || k >= (size_t(1) << 31)) throw std::invalid_argument("k ranges need 2k bounds and k counts");
+        for (size_t j = 0; j + 1 < 2 * k; ++j)
+            if (bounds[j] > bounds[j + 1]) throw std::invalid_argument("the bounds do not ascend");
+        if (widen) {
+            if (width != 16 || list_max > 0xffffu) throw std::invalid_argument("a wide-code list goes with 16-bit codes saturated at 1 .. 0xffff");
+            if ((list_len && !list) || listed > list_len || list_len >= (size_t(1) << 32))
+                throw std::invalid_argument("listed entries beyond the list, or no list");
+        } else if (list || list_len || listed || widened) {
+            throw std::invalid_argument("a wide-code list and the widened codes need list_max");
+        }
+        if (width == 16) {
+            const uint32_t top = widen ? list_max : 0xfffeu;  // (without a list no code may reach the saturation value)
+            for (size_t i = 0; i < n; ++i)
+                if (codes[i] > top) throw std::invalid_argument(widen ? "a 16-bit code above list_max" : "a code >= 0xffff among 16-bit codes");
+        }
+        *z = 0;
+        if (tail_count) *tail_count = 0;
+        const size_t bins = with_strand ? 2 * (size_t)kLengthHistBins : (size_t)kLengthHistBins;
+        if (hist) std::fill(hist, hist + bins, 0u);
+        if (counts) std::fill(counts, counts + k, 0u);
+        if (n == 0) return;
+
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        hipStream_t s = ctx.stream;
+        // the codes (and their widened copy), the cursor's arrays (exits, bitmaps, four words per node) and the outputs
+        ctx.arena.reserve(n * 48 + list_len * 8 + k * 12 + (size_t(64) << 20));
+        ArenaRewind rewind(ctx.arena);
+        LstarCodes lc;
+        if (width == 32) {
+            lc = LstarCodes::of(ctx.arena.alloc<uint32_t>(n));
+            HIP_CHECK(hipMemcpyAsync(lc.wide, codes, n * 4, hipMemcpyHostToDevice, s));
+        } else {
+            std::vector<uint16_t> half(n + 8, (uint16_t)poison);  // (padded as alloc_lstar pads the array)
+            for (size_t i = 0; i < n; ++i) half[i] = (uint16_t)codes[i];
+            lc.narrow = ctx.arena.alloc<uint16_t>(n + 8);
+            lc.width = 16;
+            HIP_CHECK(hipMemcpyAsync(lc.narrow, half.data(), (n + 8) * 2, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s));  // half is a local vector
+        }
+        if (widen) {  // as build_lstar hands the codes on when the list holds entries
+            const uint32_t count = (uint32_t)listed;
+            lc.list.cap = (uint32_t)std::max<size_t>(list_len, 1);
+            lc.list.items = ctx.arena.alloc<uint64_t>(lc.list.cap);
+            lc.list.count = ctx.arena.alloc<uint32_t>(1);
+            lc.list.max = list_max;
+            HIP_CHECK(hipMemcpyAsync(lc.list.items, list, list_len * 8, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(lc.list.count, &count, 4, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s));  // count is a local
+            lc.wide = widened_lstar(ctx, lc, (uint32_t)n, count);
+            lc.width = 32;
+            if (widened) HIP_CHECK(hipMemcpyAsync(widened, lc.wide, n * 4, hipMemcpyDeviceToHost, s));
+        }
+        const Chain chain = mark_chain(ctx, (uint32_t)n, (uint32_t)std::min(start_pos, n), lc);
+        *z = chain.z;
+        uint32_t *d_order = nullptr, *d_hist = nullptr;
+        ChainLengthsOut lo;
+        if (chain.z && (hist || lengths)) {
+            if (hist) {
+                lo.tail_cap = length_tail_cap((uint32_t)n);
+                d_hist = ctx.arena.alloc<uint32_t>(bins + 1);
+                lo.hist = d_hist;
+                lo.tail_count = d_hist + bins;
+                lo.tail = ctx.arena.alloc<uint64_t>(lo.tail_cap);
+                HIP_CHECK(hipMemsetAsync(d_hist, 0, (bins + 1) * 4, s));
+            }
+            if (lengths) lo.order = &d_order;
+            chain_lengths(ctx, chain, lo, with_strand != 0);  // (16-bit codes: refused there)
+        }
+        if (chain.z && (starts || k)) {
+            const uint32_t *d_starts = chain_starts(ctx, chain);
+            if (starts) HIP_CHECK(hipMemcpyAsync(starts, d_starts, (size_t)chain.z * 4, hipMemcpyDeviceToHost, s));
+            if (k) {
+                uint32_t *d_bounds = ctx.arena.alloc<uint32_t>(2 * k), *d_counts = ctx.arena.alloc<uint32_t>(k);
+                HIP_CHECK(hipMemcpyAsync(d_bounds, bounds, 2 * k * 4, hipMemcpyHostToDevice, s));
+                rlz_count_per_target(ctx, d_starts, chain.z, d_bounds, (uint32_t)k, d_counts);
+                HIP_CHECK(hipMemcpyAsync(counts, d_counts, k * 4, hipMemcpyDeviceToHost, s));
+            }
+        }
+        if (d_order) HIP_CHECK(hipMemcpyAsync(lengths, d_order, (size_t)chain.z * 4, hipMemcpyDeviceToHost, s));
+        if (d_hist) {
+            HIP_CHECK(hipMemcpyAsync(hist, d_hist, bins * 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(tail_count, d_hist + bins, 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (*tail_count > lo.tail_cap) throw std::logic_error("debug_chain: more long factors than the tail list holds");
+            HIP_CHECK(hipMemcpyAsync(tail, lo.tail, (size_t)*tail_count * 8, hipMemcpyDeviceToHost, s));
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+        ctx.prof.collect();
+    });
+}
+
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak) {
     return guarded([&] {
         if (!capacity || !peak) throw std::invalid_argument("output pointer is null");
