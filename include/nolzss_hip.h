@@ -739,6 +739,64 @@ int nolzss_rlz_index_seeds(const nolzss_rlz_index *h, const char *const *targets
                            uint64_t min_length, uint64_t max_hits, nolzss_rlz_seeds_result *out);
 /* NULL is a no-op; the result is zeroed. */
 void nolzss_free_rlz_seeds_result(nolzss_rlz_seeds_result *r);
+/* Colinear seed chains: where every target lies -- which record, which strand, which interval, how well supported
+ * ("Relative-LZ index: colinear seed chains").  The call follows nolzss_rlz_index_seeds up to the sorted
+ * hits, which stay on the device, and chains them there; neither seeds nor hits come down.
+ *   Parameters: min_length and max_hits are exactly those of nolzss_rlz_index_seeds; a seed with more than max_hits
+ *     occurrences contributes no anchor.  max_gap and bandwidth are plain bounds: there is no "0 means unlimited", a value
+ *     above any coordinate difference never binds, and the device clamps both to 2^32 - 1.
+ *   Anchors: every reported hit (position x, record r, is_rc) of every seed (target t, start s, length L) is an anchor
+ *     with q = s and the reference coordinate y = x on the forward strand, y = 2 B - x - L + 1 on the reverse strand: the
+ *     coordinate the match has in the mirrored block of the index text X.  On either strand a colinear alignment
+ *     therefore runs upward in both q and y.
+ *   Groups: the anchors are grouped by (target, is_rc, record) and ordered by (y, q) inside a group; that pair is unique
+ *     inside a group.
+ *   Recurrence: the look-back is NOLZSS_RLZ_CHAIN_LOOKBACK, a constant of the ABI because it defines the result.  For
+ *     anchor i of a group the candidates are the j with 1 <= i - j <= 64 in group order, dq = q_i - q_j >= 1, dy = y_i -
+ *     y_j >= 1, max(dq, dy) <= max_gap and |dq - dy| <= bandwidth.  f(i) = max(L_i, max over j of f(j) + min(L_i, dq, dy)
+ *     - |dq - dy|); pred(i) is the candidate that attains the maximum if that maximum is strictly greater than L_i, of
+ *     equal candidates the nearest (the largest j); otherwise i has no predecessor.  Scores are compared in 64 bits and
+ *     fit 32: f(i) <= L(first) + q_i - q(first) < 2^32, since a target of 2^31 bases or more is refused.
+ *   The chain of a group: its end e is the smallest index with maximal f; it is reported iff f(e) >= min_score; its
+ *     anchors are e, pred(e), .., reported in ascending q.  One chain per (target, strand, record).
+ *   Chain record: t_start = q of the first anchor, t_end = q + L of the last (ends ascend with starts: the seeds are
+ *     super-maximal); r_start = the MIN of x and r_end = the MAX of x + L over the chain's anchors, in Rblk coordinates
+ *     (y + L is not monotone along a chain whose diagonals differ); score = f(e); primary = 1 on the chain of largest
+ *     score of its target, on ties the first in output order.
+ *   Layout: the chains ascend by (target, is_rc, record).  anchor_offsets has num_chains + 1 entries, chain c owns the
+ *     anchors [anchor_offsets[c], anchor_offsets[c + 1]) (CSR); an anchor's position is x as a hit reports it.  chains is
+ *     NULL when num_chains is 0, anchors is NULL when num_anchors is 0, anchor_offsets always holds its num_chains + 1
+ *     entries after a success.  num_seeds and num_seed_hits are diagnostics: the seeds reported and the hits expanded.
+ *   Refusals, all before any device work: everything nolzss_rlz_index_seeds refuses, with the same status and message; a
+ *     null params; more than 2^24 targets in one batch (the group sort key keeps target, group and y in 24 + 8 + 32
+ *     bits); a target of 2^31 bases or more: NOLZSS_ERR_INVALID_ARGUMENT.  k == 0, or a batch without a base, succeeds
+ *     without touching the device.  The refusal of the hit total applies unchanged; it leaves an empty result and the
+ *     status.
+ *   An arena out-of-memory leaves the handle untouched.  Several threads may query one handle; the calling thread's
+ *     current device is left as it was.  NOLZSS_RLZ_LOCATE_CHUNK (tests): chain records, and anchors, per download. */
+#define NOLZSS_RLZ_CHAIN_LOOKBACK 64
+typedef struct nolzss_rlz_chain_params {
+    uint64_t min_length, max_hits, max_gap, bandwidth, min_score;
+} nolzss_rlz_chain_params;
+typedef struct nolzss_rlz_chain {
+    uint64_t target, t_start, t_end, r_start, r_end, score;
+    uint32_t record, is_rc, num_anchors, primary;
+} nolzss_rlz_chain;
+typedef struct nolzss_rlz_chain_anchor {
+    uint64_t t_start, position, length;
+} nolzss_rlz_chain_anchor;
+typedef struct nolzss_rlz_seed_chains_result {
+    size_t num_chains;
+    nolzss_rlz_chain *chains;         /* ascending by (target, is_rc, record); NULL when num_chains == 0 */
+    uint64_t *anchor_offsets;         /* num_chains + 1 entries */
+    size_t num_anchors;
+    nolzss_rlz_chain_anchor *anchors; /* NULL when num_anchors == 0 */
+    size_t num_seeds, num_seed_hits;
+} nolzss_rlz_seed_chains_result;
+int nolzss_rlz_index_seed_chains(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                                 const nolzss_rlz_chain_params *params, nolzss_rlz_seed_chains_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_seed_chains_result(nolzss_rlz_seed_chains_result *r);
 /* Host only (tests): the bit offsets of the 8-bit digits the sort of a locate's hits runs for a block of block_length
  * bases and q patterns, least significant first; shifts: 8 entries, the caller's. */
 int nolzss_debug_rlz_locate_shifts(uint64_t block_length, uint64_t q, int *shifts, int *npasses);
@@ -1037,6 +1095,19 @@ int nolzss_debug_chain(const uint32_t *codes, size_t n, size_t start_pos, int wi
                        size_t list_len, size_t listed, uint32_t list_max, int with_strand, const uint32_t *bounds, size_t k,
                        int device, uint32_t *z, uint32_t *starts, uint32_t *lengths, uint32_t *hist, uint64_t *tail,
                        uint32_t *tail_count, uint32_t *widened, uint32_t *counts);
+/* The seed-chain stages from the group heads to the chain records (rlz_seed_chain.hip: rlz_seed_chain_run, the
+ * production function) on the caller's anchors, by the rules of nolzss_rlz_index_seed_chains.  target, group, y, q,
+ * length: n entries each, already ordered by (target, group, y, q); group = is_rc * m + record, and x is derived from y
+ * with B and m (x = y below group m, else 2 B - y - length + 1).  Of params, max_gap, bandwidth and min_score are read.
+ * Every device array is followed by padding filled with 0xff bytes.
+ * Out: f[n] and pred[n] per anchor, group-local (pred 0xffffffff: none); *res as the query returns it (num_seeds and
+ * num_seed_hits are 0), freed with nolzss_free_rlz_seed_chains_result.  n == 0 succeeds without a launch.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any launch for null pointers, n >= 2^31, m == 0 or m > 128, a target >= 2^24, a
+ * group >= 2 m, length == 0, q + length >= 2^31, a reverse-strand anchor with y + length > 2 B + 1, entries out of order,
+ * or a (y, q) pair that occurs twice in a group. */
+int nolzss_debug_rlz_seed_chain(const uint32_t *target, const uint32_t *group, const uint32_t *y, const uint32_t *q,
+                                const uint32_t *length, size_t n, const nolzss_rlz_chain_params *params, uint64_t B,
+                                uint32_t m, int device, uint32_t *f, uint32_t *pred, nolzss_rlz_seed_chains_result *res);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

@@ -140,6 +140,19 @@ class RlzSeedsResult(C.Structure):
                 ("hits", C.c_void_p)]
 
 
+class RlzChainParams(C.Structure):
+    """Mirror of nolzss_rlz_chain_params (include/nolzss_hip.h)."""
+    _fields_ = [("min_length", C.c_uint64), ("max_hits", C.c_uint64), ("max_gap", C.c_uint64), ("bandwidth", C.c_uint64),
+                ("min_score", C.c_uint64)]
+
+
+class RlzSeedChainsResult(C.Structure):
+    """Mirror of nolzss_rlz_seed_chains_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_chains", C.c_size_t), ("chains", C.c_void_p), ("anchor_offsets", C.c_void_p),
+                ("num_anchors", C.c_size_t), ("anchors", C.c_void_p), ("num_seeds", C.c_size_t),
+                ("num_seed_hits", C.c_size_t)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -294,6 +307,11 @@ def _load():
     lib.nolzss_rlz_index_seeds.argtypes = [vp] + seqs[3:] + [C.c_uint64, C.c_uint64, C.POINTER(RlzSeedsResult)]
     lib.nolzss_free_rlz_seeds_result.argtypes = [C.POINTER(RlzSeedsResult)]
     lib.nolzss_free_rlz_seeds_result.restype = None
+    lib.nolzss_rlz_index_seed_chains.argtypes = [vp] + seqs[3:] + [C.POINTER(RlzChainParams), C.POINTER(RlzSeedChainsResult)]
+    lib.nolzss_free_rlz_seed_chains_result.argtypes = [C.POINTER(RlzSeedChainsResult)]
+    lib.nolzss_free_rlz_seed_chains_result.restype = None
+    lib.nolzss_debug_rlz_seed_chain.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(RlzChainParams), C.c_uint64, C.c_uint32,
+                                                C.c_int, vp, vp, C.POINTER(RlzSeedChainsResult)]
     lib.nolzss_debug_rlz_locate_shifts.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
@@ -377,6 +395,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_pyramid", "nolzss_debug_nearest", "nolzss_debug_lds_search",
     "nolzss_debug_local_sort", "nolzss_debug_text_order", "nolzss_debug_group_sort",
     "nolzss_debug_chain",
+    "nolzss_rlz_index_seed_chains", "nolzss_free_rlz_seed_chains_result", "nolzss_debug_rlz_seed_chain",
 ]
 
 

@@ -25,6 +25,10 @@ HIT_DTYPE = np.dtype([("position", "<u8"), ("record", "<u4"), ("is_rc", "<u4")])
 TARGET_HIT_DTYPE = np.dtype([("target", "<u8"), ("position", "<u8"), ("is_rc", "<u4"), ("primary", "<u4")])
 # nolzss_rlz_seed: a maximal exact match of a target with the reference block
 SEED_DTYPE = np.dtype([("target", "<u8"), ("start", "<u8"), ("length", "<u8"), ("count", "<u8")])
+# nolzss_rlz_chain and nolzss_rlz_chain_anchor (include/nolzss_hip.h): a seed chain and one of its anchors
+CHAIN_DTYPE = np.dtype([("target", "<u8"), ("t_start", "<u8"), ("t_end", "<u8"), ("r_start", "<u8"), ("r_end", "<u8"),
+                        ("score", "<u8"), ("record", "<u4"), ("is_rc", "<u4"), ("num_anchors", "<u4"), ("primary", "<u4")])
+CHAIN_ANCHOR_DTYPE = np.dtype([("t_start", "<u8"), ("position", "<u8"), ("length", "<u8")])
 
 _default_device = int(os.environ.get("NOLZSS_DEVICE", os.environ.get("LOCAL_RANK", "0")) or 0)
 
@@ -1423,6 +1427,33 @@ class RlzFinderHandle:
             pass
 
 
+def _chain_params(min_length, max_hits, max_gap, bandwidth, min_score):
+    """The parameters of a seed-chain query as the C struct; ValueError for a negative one or one beyond 64 bits."""
+    values = {"min_length": min_length, "max_hits": max_hits, "max_gap": max_gap, "bandwidth": bandwidth,
+              "min_score": min_score}
+    params = _lib.RlzChainParams()
+    for name, v in values.items():
+        v = operator.index(v)
+        if v < 0:
+            raise ValueError(f"{name} must not be negative")
+        if v >= 1 << 64:
+            raise ValueError(f"{name} must fit 64 bits")
+        setattr(params, name, v)
+    return params
+
+
+def _unpack_seed_chains(res):
+    """nolzss_rlz_seed_chains_result -> (chains, anchor_offsets, anchors) as copies; the caller frees the result."""
+    n, a = res.num_chains, res.num_anchors
+    offsets = np.ctypeslib.as_array(C.cast(res.anchor_offsets, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+    chains, anchors = np.zeros(n, dtype=CHAIN_DTYPE), np.zeros(a, dtype=CHAIN_ANCHOR_DTYPE)
+    if n:
+        C.memmove(chains.ctypes.data, res.chains, n * CHAIN_DTYPE.itemsize)
+    if a:
+        C.memmove(anchors.ctypes.data, res.anchors, a * CHAIN_ANCHOR_DTYPE.itemsize)
+    return chains, offsets, anchors
+
+
 # ---- relative-LZ index: target batches matched against a resident reference (genomics/rlz.py) -------------------
 class RlzIndexHandle:
     """Extension: the suffix structures of a reference block kept in device memory (C ABI nolzss_rlz_index_*), any
@@ -1534,6 +1565,22 @@ class RlzIndexHandle:
         finally:
             lib.nolzss_free_rlz_seeds_result(C.byref(res))
         return seeds, offsets, hits
+
+    def seed_chains(self, targets, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 500,
+                    min_score: int = 40):
+        """One batch -> (chains, anchor_offsets, anchors, num_seeds, num_seed_hits): the colinear chain of the seeds of
+        every (target, strand, record) as CHAIN_DTYPE, ascending by (target, is_rc, record); the len(chains) + 1 uint64
+        offsets of their anchors; the anchors as CHAIN_ANCHOR_DTYPE, per chain ascending by t_start; the seeds reported
+        and the hits expanded on the device (diagnostics).  C ABI nolzss_rlz_index_seed_chains (its header states the
+        rules)."""
+        h = self._handle()
+        params = _chain_params(min_length, max_hits, max_gap, bandwidth, min_score)
+        res = _lib.RlzSeedChainsResult()
+        try:
+            check(lib.nolzss_rlz_index_seed_chains(h, *_seq_args(targets, "target"), C.byref(params), C.byref(res)))
+            return _unpack_seed_chains(res) + (int(res.num_seeds), int(res.num_seed_hits))
+        finally:
+            lib.nolzss_free_rlz_seed_chains_result(C.byref(res))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -1998,3 +2045,25 @@ def debug_chain(codes, start_pos: int = 0, width: int = 32, poison: int = 0, wid
     return {"z": z.value, "starts": starts[:z.value], "lengths": lengths[:z.value] if want_lengths else None,
             "hist": hist, "tail": np.sort(tail[:tail_count.value]) if want_hist else None,
             "widened": widened[:n] if list_max else None, "counts": counts[:k] if bnd is not None else None}
+
+
+def debug_rlz_seed_chain(target, group, y, q, length, block_length: int, records: int, max_gap: int, bandwidth: int,
+                         min_score: int = 0):
+    """The seed-chain stages from the group heads to the chain records on caller anchors (nolzss_debug_rlz_seed_chain,
+    test hook): five arrays of n entries ordered by (target, group, y, q), group = is_rc * records + record.  Returns
+    {"f", "pred" (uint32 per anchor, group-local; 0xffffffff: none), "chains", "anchor_offsets", "anchors"}."""
+    arrays = [np.ascontiguousarray(a, dtype=np.uint32) for a in (target, group, y, q, length)]
+    n = arrays[0].size
+    if any(a.size != n for a in arrays):
+        raise ValueError("the anchor arrays hold one entry per anchor")
+    params = _chain_params(0, 0, max_gap, bandwidth, min_score)
+    f, pred = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    res = _lib.RlzSeedChainsResult()
+    try:
+        check(lib.nolzss_debug_rlz_seed_chain(*[a.ctypes.data if n else None for a in arrays], n, C.byref(params),
+                                              operator.index(block_length), operator.index(records), _default_device,
+                                              f.ctypes.data, pred.ctypes.data, C.byref(res)))
+        chains, offsets, anchors = _unpack_seed_chains(res)
+    finally:
+        lib.nolzss_free_rlz_seed_chains_result(C.byref(res))
+    return {"f": f[:n], "pred": pred[:n], "chains": chains, "anchor_offsets": offsets, "anchors": anchors}

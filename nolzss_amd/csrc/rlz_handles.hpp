@@ -113,6 +113,11 @@ uint32_t choose_prefix(size_t index_length);  // the prefix table's key for an i
 size_t chunk_knob(const char *name);
 size_t pattern_batch_bytes(size_t n, size_t q);
 constexpr size_t kLocateBytesPerHit = 25;
+// What the seed-chain query and its debug hook (debug_rlz.hip) share: the device's view of the parameters, and the chains
+// of a run brought down into the host blocks of a result (anchor_offsets is allocated there; chunked by
+// NOLZSS_RLZ_LOCATE_CHUNK).
+ChainRules chain_rules(const nolzss_rlz_chain_params &p, uint64_t records, uint64_t B);
+void deliver_chains(Context &ctx, const ChainsOut &run, nolzss_rlz_seed_chains_result &res);
 
 }  // namespace api
 }  // namespace nolzss

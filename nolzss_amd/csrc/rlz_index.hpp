@@ -1,6 +1,7 @@
 // rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
-// rlz_index.hip, rlz_locate.hip for pattern queries and rlz_seeds.hip for maximal match seeds;
+// rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds and rlz_seed_chain.hip for
+// their colinear chains;
 // the handle and its entry points: rlz_index_api.hip).
 #pragma once
 #include "pipeline.hpp"
@@ -95,6 +96,53 @@ void rlz_index_seed_intervals(Context &ctx, const RlzIndexView &ix, const Packed
 LocateSorted rlz_index_seed_hits(Context &ctx, const RlzIndexView &ix, uint32_t records, uint32_t n, const uint32_t *d_seeds,
                                  const uint32_t *d_len, uint32_t S, const uint32_t *d_rep, const uint32_t *d_first,
                                  uint32_t T);
+
+// ---- colinear seed chains (rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index: colinear seed chains") ---------------
+// An anchor is one reported hit of one seed: q = the seed's start inside its target, y = its coordinate in X (the hit's
+// position on the forward strand, the mirrored block's on the reverse strand), len = the seed's length.  The anchors lie
+// in group order: keys[i] = (target << 40) | (group << 32) | y ascending, group = is_rc * records + record, equal keys by
+// ascending q.  The rules of the recurrence: include/nolzss_hip.h, nolzss_rlz_index_seed_chains.
+constexpr uint32_t kChainLookback = 64;      // NOLZSS_RLZ_CHAIN_LOOKBACK: the ring is one wavefront wide
+constexpr uint32_t kChainNoPred = 0xffffffffu;
+constexpr uint64_t kChainMaxTargets = 1ull << 24;  // the key keeps target, group and y in 24 + 8 + 32 bits
+struct ChainAnchors {
+    const uint64_t *keys = nullptr;
+    const uint32_t *q = nullptr, *len = nullptr;
+    uint32_t n = 0;
+};
+struct ChainRules {
+    uint32_t max_gap = 0, bandwidth = 0;  // (clamped to 2^32 - 1: no coordinate difference is larger)
+    uint64_t min_score = 0;
+    uint32_t records = 0;  // m: a group >= m is a reverse-strand group of record group - m
+    uint32_t B = 0;        // x = 2 B - y - len + 1 on the reverse strand
+};
+struct ChainRec {  // nolzss_rlz_chain
+    uint64_t target, t_start, t_end, r_start, r_end, score;
+    uint32_t record, is_rc, num_anchors, primary;
+};
+struct ChainAnchorRec {  // nolzss_rlz_chain_anchor
+    uint64_t t_start, position, length;
+};
+struct ChainsOut {  // arena memory
+    uint32_t num_chains = 0, num_anchors = 0;
+    const ChainRec *chains = nullptr;          // num_chains, ascending by (target, is_rc, record)
+    const uint64_t *offsets = nullptr;         // num_chains + 1
+    const ChainAnchorRec *anchors = nullptr;   // num_anchors
+    const uint32_t *f = nullptr, *pred = nullptr;  // per anchor, group-local (pred: kChainNoPred without one)
+};
+// The bit offsets of the 8-bit digits the sort of the anchors runs, least significant first, for y < y_end, `groups`
+// groups and k targets (host only): at most kLocateMaxPasses.  Returns their number.
+int rlz_chain_sort_shifts(uint64_t y_end, uint64_t groups, uint64_t k, int *shifts);
+// *d_total = rep[0] + .. + rep[S - 1], summed in 64 bits (device memory): the hits a seed query would expand
+void rlz_index_rep_total(Context &ctx, const uint32_t *d_rep, uint32_t S, uint64_t *d_total);
+// The T sorted hits of rlz_index_seed_hits (S seeds over a batch of n positions) as anchors in group order.  Arena
+// memory: 40 bytes per hit and the sort's histograms.
+ChainAnchors rlz_seed_chain_anchors(Context &ctx, const RlzIndexView &ix, uint32_t records, const PackedText &batch,
+                                    const uint32_t *d_seeds, const uint32_t *d_len, uint32_t S, const LocateSorted &sorted,
+                                    uint32_t T);
+// Group heads, the recurrence, ends, backtrack and primary flags over anchors in group order (a.n >= 1).  Waits for the
+// stream twice (the number of groups, then the totals).  Arena memory: at most 152 bytes per anchor.
+ChainsOut rlz_seed_chain_run(Context &ctx, const ChainAnchors &a, const ChainRules &rules);
 
 constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
 

@@ -6,7 +6,9 @@
 // "Relative-LZ archive: batches appended from the index"), and nolzss_rlz_index_count / _locate: pattern batches
 // queried against the handle (the kernels: rlz_locate.hip; DESIGN.md 5, "Relative-LZ index: pattern count and locate"),
 // and nolzss_rlz_index_seeds: the maximal exact matches of a target batch and their occurrences (the kernels:
-// rlz_seeds.hip; DESIGN.md 5, "Relative-LZ index: maximal match seeds").
+// rlz_seeds.hip; DESIGN.md 5, "Relative-LZ index: maximal match seeds"), and nolzss_rlz_index_seed_chains: the seeds of
+// every target chained into placements on the device (the kernels: rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index:
+// colinear seed chains").
 #include "rlz_handles.hpp"
 
 using namespace nolzss;
@@ -718,9 +720,185 @@ void index_seeds(const nolzss_rlz_index *h, const char *const *targets, const si
                                     std::to_string(min_length) + ") or send fewer targets");
 }
 
+// ---- colinear seed chains ------------------------------------------------------------------------------------------
+// device memory per hit of a seed-chain query, on top of the 25 of the expanded and sorted hits: the anchors in group
+// order (two key and two value arrays of the second sort, q and L by slot and by anchor: 40, the histograms 1) and what
+// rlz_seed_chain_run states (152); every group and every chain anchor is at most one per hit
+constexpr size_t kChainBytesPerHit = 40 + 1 + 152;
+
+static_assert(sizeof(nolzss_rlz_chain) == sizeof(ChainRec) && sizeof(ChainRec) == 64, "the kernels write nolzss_rlz_chain");
+static_assert(sizeof(nolzss_rlz_chain_anchor) == sizeof(ChainAnchorRec) && sizeof(ChainAnchorRec) == 24,
+              "the kernels write nolzss_rlz_chain_anchor");
+static_assert(NOLZSS_RLZ_CHAIN_LOOKBACK == kChainLookback, "the look-back is a constant of the ABI");
+
+// `count` records of `size` bytes from device memory into a host array, NOLZSS_RLZ_LOCATE_CHUNK records per copy
+void download_records(Context &ctx, const char *scope, void *h_dst, const void *d_src, size_t count, size_t size) {
+    const size_t chunk_max = chunk_knob("NOLZSS_RLZ_LOCATE_CHUNK");
+    for (size_t c0 = 0; c0 < count; c0 += chunk_max) {
+        const size_t c = count - c0 < chunk_max ? count - c0 : chunk_max;
+        ProfScope ps(ctx.profiler(), scope, ctx.stream, (double)(size * c));
+        download_bytes(ctx, static_cast<char *>(h_dst) + c0 * size, static_cast<const char *>(d_src) + c0 * size, c * size);
+    }
+}
+
+}  // namespace
+// the chains of a run into the host blocks of a result (anchor_offsets: allocated here)
+void nolzss::api::deliver_chains(Context &ctx, const ChainsOut &run, nolzss_rlz_seed_chains_result &res) {
+    const size_t C = run.num_chains, A = run.num_anchors;
+    res.anchor_offsets = calloc_array<uint64_t>(C + 1);
+    if (C == 0) return;
+    res.chains = static_cast<nolzss_rlz_chain *>(alloc_factor_block(sizeof(nolzss_rlz_chain) * C));
+    if (!res.chains) throw std::bad_alloc();
+    res.anchors = static_cast<nolzss_rlz_chain_anchor *>(alloc_factor_block(sizeof(nolzss_rlz_chain_anchor) * A));
+    if (!res.anchors) throw std::bad_alloc();
+    download_records(ctx, "chains_d2h", res.chains, run.chains, C, sizeof(nolzss_rlz_chain));
+    download_records(ctx, "chain_offsets_d2h", res.anchor_offsets, run.offsets, C + 1, sizeof(uint64_t));
+    download_records(ctx, "chain_anchors_d2h", res.anchors, run.anchors, A, sizeof(nolzss_rlz_chain_anchor));
+    res.num_chains = C;
+    res.num_anchors = A;
+}
+
+ChainRules nolzss::api::chain_rules(const nolzss_rlz_chain_params &p, uint64_t records, uint64_t B) {
+    ChainRules r;
+    r.max_gap = p.max_gap >= 0xffffffffull ? 0xffffffffu : (uint32_t)p.max_gap;
+    r.bandwidth = p.bandwidth >= 0xffffffffull ? 0xffffffffu : (uint32_t)p.bandwidth;
+    r.min_score = p.min_score;
+    r.records = (uint32_t)records;
+    r.B = (uint32_t)B;
+    return r;
+}
+
+namespace {
+
+// One batch of k >= 1 targets with at least one base against the handle, inside a session: the path of query_seeds up to
+// the sorted hits, which stay on the device, then the chain stages.  Returns false when the hit total is beyond the
+// pipeline: res is then empty, *total the number.
+bool query_seed_chains(Context &ctx, const nolzss_rlz_index &h, const Batch &b, size_t k, const nolzss_rlz_chain_params &p,
+                       nolzss_rlz_seed_chains_result &res, uint64_t *total_out) {
+    const size_t n = b.tcat.size();
+    const uint32_t cap = (p.max_hits == 0 || p.max_hits >= 0xffffffffull) ? 0xffffffffu : (uint32_t)p.max_hits;
+    const uint32_t min_len = p.min_length >= 0xffffffffull ? 0xffffffffu : (uint32_t)(p.min_length ? p.min_length : 1);
+    hipStream_t s = ctx.stream;
+    Searched m;
+    uint32_t *d_seeds = nullptr, *d_first = nullptr, *d_rep = nullptr;
+    uint32_t S = 0;
+    // as query_seeds: the batch searched, the seeds listed, their intervals looked up -- no record is written
+    auto run_search = [&] {
+        m = search_batch(ctx, h, b);
+        uint32_t *d_flag = ctx.arena.alloc<uint32_t>(n), *d_slot = ctx.arena.alloc<uint32_t>(n);
+        d_seeds = ctx.arena.alloc<uint32_t>(n);
+        uint32_t *d_total = ctx.arena.alloc<uint32_t>(1);
+        rlz_index_seed_list(ctx, m.d_len, (uint32_t)n, min_len, d_flag, d_slot, d_seeds, d_total);
+        download_bytes(ctx, &S, d_total, sizeof(uint32_t));
+        if (S > n) throw HipError("rlz index: more seeds than batch positions");
+        d_first = ctx.arena.alloc<uint32_t>(S ? S : 1);
+        d_rep = ctx.arena.alloc<uint32_t>(S ? S : 1);
+        if (S > 0x7fffffffu) return;
+        rlz_index_seed_intervals(ctx, h.view, m.batch, d_seeds, 0u, S, cap, m.d_len, m.d_rank, d_first, d_rep, nullptr);
+    };
+    reserve_arena_for(ctx, 0, seed_batch_bytes(n, k, 0));
+    run_search();
+    if (S > 0x7fffffffu) throw std::invalid_argument("rlz index: a batch may report at most 2^31 - 1 seeds, this one has " +
+                                                     std::to_string(S) + ": raise min_length or send fewer targets");
+    res.num_seeds = S;
+    uint64_t total = 0;  // the hits to expand, summed in 64 bits on the device: one word comes down
+    if (S) {
+        uint64_t *d_sum = ctx.arena.alloc<uint64_t>(1);
+        rlz_index_rep_total(ctx, d_rep, S, d_sum);
+        download_bytes(ctx, &total, d_sum, sizeof(uint64_t));
+    }
+    *total_out = total;
+    if (total > kMaxText) return false;
+    if (total == 0) {
+        res.anchor_offsets = calloc_array<uint64_t>(1);
+        return true;
+    }
+    const size_t T = (size_t)total;
+    // the arena for the hits, by the two-reservation rule of a locate and of the seeds, extended by the per-hit and
+    // per-group arrays of the chain stages: a reservation that is not a no-op may replace the slab, so the arena is then
+    // emptied and the batch is searched again in it
+    const size_t extra = seed_batch_bytes(n, k, 0) + (kLocateBytesPerHit + kChainBytesPerHit) * T;
+    if (arena_bytes_for(0) + extra > ctx.arena.capacity()) {
+        HIP_CHECK(hipStreamSynchronize(s));  // (nothing still reads the slab that goes)
+        reserve_arena_for(ctx, 0, extra);
+        ctx.arena.rewind(0);
+        const uint32_t before = S;
+        run_search();
+        if (S != before) throw HipError("rlz index: the seeds of a batch changed between two searches");
+    }
+    const LocateSorted sorted =
+        rlz_index_seed_hits(ctx, h.view, (uint32_t)h.m, (uint32_t)n, d_seeds, m.d_len, S, d_rep, d_first, (uint32_t)T);
+    res.num_seed_hits = T;
+    const ChainAnchors anchors = rlz_seed_chain_anchors(ctx, h.view, (uint32_t)h.m, m.batch, d_seeds, m.d_len, S, sorted, (uint32_t)T);
+    const ChainsOut run = rlz_seed_chain_run(ctx, anchors, chain_rules(p, h.m, h.view.B));
+    deliver_chains(ctx, run, res);
+    return true;
+}
+
+void index_seed_chains(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                       const nolzss_rlz_chain_params *params, nolzss_rlz_seed_chains_result *out) {
+    if (!out) throw std::invalid_argument("output pointer is null");
+    std::memset(out, 0, sizeof *out);
+    if (!h) throw std::invalid_argument("handle is null");
+    if (!params) throw std::invalid_argument("rlz index: seed chains need their parameters: params is null");
+    if (k > kChainMaxTargets)
+        throw std::invalid_argument("rlz index: seed chains take at most 2^24 targets per batch, this one has " + std::to_string(k) +
+                                    " (the group sort key keeps the target in 24 bits): send fewer targets");
+    for (size_t j = 0; target_lens && j < k; ++j)  // (the lengths alone decide; a null array is the batch's refusal below)
+        if (target_lens[j] >= (size_t(1) << 31))
+            throw std::invalid_argument("rlz index: seed chains take targets below 2^31 bases, target " + std::to_string(j) +
+                                        " has " + std::to_string(target_lens[j]) + " (a chain's score is kept in 32 bits)");
+    Batch b;
+    prepare_batch(*h, targets, target_lens, k, b);
+    nolzss_rlz_seed_chains_result res;
+    std::memset(&res, 0, sizeof res);
+    bool fits = true;
+    uint64_t total = 0;
+    try {
+        if (b.tcat.size() == k) {  // no target, or none with a base: the device is not touched
+            res.anchor_offsets = calloc_array<uint64_t>(1);
+        } else {
+            DeviceRestore restore;
+            Session ses(h->device, nullptr);
+            Context &ctx = ses.ctx();
+            {
+                ProfScope whole(ctx.profiler(), "rlz_index_seed_chains", ctx.stream);
+                fits = query_seed_chains(ctx, *h, b, k, *params, res, &total);
+            }
+            HIP_CHECK(hipStreamSynchronize(ctx.stream));
+            HIP_CHECK(hipGetLastError());
+            ctx.prof.collect();
+        }
+    } catch (...) {
+        nolzss_free_rlz_seed_chains_result(&res);
+        throw;
+    }
+    if (!fits) {  // an empty result and the status
+        nolzss_free_rlz_seed_chains_result(&res);
+        throw std::invalid_argument("rlz index: seeds would report " + std::to_string(total) + " hits, more than the " +
+                                    std::to_string(kMaxText) + " the 32-bit device pipeline takes: lower max_hits (it is " +
+                                    std::to_string(params->max_hits) + "; 0 means no cap), raise min_length (it is " +
+                                    std::to_string(params->min_length) + ") or send fewer targets");
+    }
+    *out = res;  // ownership moves to the caller
+}
+
 }  // namespace
 
 extern "C" {
+
+int nolzss_rlz_index_seed_chains(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                                 const nolzss_rlz_chain_params *params, nolzss_rlz_seed_chains_result *out) {
+    return guarded([&] { index_seed_chains(h, targets, target_lens, k, params, out); });
+}
+
+void nolzss_free_rlz_seed_chains_result(nolzss_rlz_seed_chains_result *r) {
+    if (!r) return;
+    free_block(r->chains);
+    free_block(r->anchor_offsets);
+    free_block(r->anchors);
+    std::memset(r, 0, sizeof *r);
+}
 
 int nolzss_rlz_index_open(const char *const *refs, const size_t *ref_lens, size_t m, int with_rc, uint32_t prefix_syms,
                           int device, nolzss_rlz_index **h) {

@@ -23,6 +23,9 @@ RLZ_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8"), ("is_
 TARGET_HIT_DTYPE = _native.TARGET_HIT_DTYPE  # (target, position, is_rc, primary): RlzArchiveFinder.locate
 HIT_DTYPE = _native.HIT_DTYPE  # (position, record, is_rc): an occurrence of a pattern (RlzIndex.locate)
 SEED_DTYPE = _native.SEED_DTYPE  # (target, start, length, count): a maximal exact match of a target (RlzIndex.seeds)
+CHAIN_DTYPE = _native.CHAIN_DTYPE  # a seed chain: one placement of a target in a record and strand (RlzIndex.seed_chains)
+CHAIN_ANCHOR_DTYPE = _native.CHAIN_ANCHOR_DTYPE  # (t_start, position, length): one anchor of a seed chain
+MAX_CHAIN_TARGETS = 1 << 24  # targets per batch of a seed-chain query: the group sort key keeps the target in 24 bits
 
 
 def split_and_rebase(records, target_offsets, target_lengths):
@@ -460,16 +463,17 @@ class RlzArchiveFinder:
 MAX_TEXT = 0xffffffff - (1 << 19)  # positions the 32-bit device pipeline takes (kMaxText of the library)
 
 
-def plan_index_batches(lengths, block_length, limit=MAX_TEXT, batch_bases=None):
+def plan_index_batches(lengths, block_length, limit=MAX_TEXT, batch_bases=None, max_targets=None):
     """Target lengths -> [(lo, hi)] index ranges of the batches RlzIndex sends, greedy in input order: a batch closes
-    when the next target would pass the length rule block_length + 1 + sum(len) + k <= limit, or batch_bases bases.  A
-    target that breaks a bound alone still gets a batch of its own (the library refuses it if it breaks the length rule).
-    Pure Python, no device."""
+    when the next target would pass the length rule block_length + 1 + sum(len) + k <= limit, batch_bases bases, or
+    max_targets targets (the seed chains: MAX_CHAIN_TARGETS).  A target that breaks a bound alone still gets a batch of
+    its own (the library refuses it if it breaks the length rule).  Pure Python, no device."""
     out, lo, bases = [], 0, 0
     for j, n in enumerate(lengths):
         n = operator.index(n)
         k = j - lo
-        over = block_length + 1 + bases + n + k + 1 > limit or (batch_bases is not None and bases + n > batch_bases)
+        over = (block_length + 1 + bases + n + k + 1 > limit or (batch_bases is not None and bases + n > batch_bases)
+                or (max_targets is not None and k + 1 > max_targets))
         if k and over:
             out.append((lo, j))
             lo, bases = j, 0
@@ -661,6 +665,49 @@ class RlzIndex:
                 "record": f["record"].copy(), "record_offset": f["position"] - starts[f["record"]],
                 "is_rc": f["is_rc"].astype(bool)}
 
+    def seed_chains(self, targets, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 500,
+                    min_score: int = 40, batch_bases=None):
+        """Where every target lies in the reference: its seeds (as seeds(targets, min_length, max_hits) finds them; a seed
+        with more than max_hits occurrences contributes nothing) chained colinearly on the GPU, one chain per (target,
+        strand, record) -> dict(target, record, is_rc, score, t_start, t_end, r_start, r_end, record_offset, num_anchors,
+        primary, anchor_offsets, anchor_t_start, anchor_position, anchor_length).  Chain c covers [t_start, t_end) of
+        target `target` and [r_start, r_end) of the reference block (record_offset = r_start inside record `record`); on
+        the reverse strand (is_rc) the target's reverse complement lies there.  Two anchors are linked when both
+        coordinates ascend, neither gap exceeds max_gap and the gaps differ by at most bandwidth; a link scores the new
+        bases minus the difference of the gaps, over the 64 anchors in front of an anchor; a chain is reported when its
+        score reaches min_score, and primary marks the best chain of its target.  Chain c owns the anchors
+        [anchor_offsets[c], anchor_offsets[c + 1]), ascending in the target; anchor_position is the coordinate a hit of
+        seeds() reports.  The chains ascend by (target, is_rc, record).  Neither seeds nor hits leave the device; a long
+        list goes up in several batches (plan_index_batches, at most 2^24 targets each, a target is never split, so
+        batching changes nothing), target indices and offsets stitched.  The read and its reverse complement may score
+        a few points apart: the overlap term of a link is not symmetric in direction."""
+        h = self._live()
+        args = [operator.index(v) for v in (min_length, max_hits, max_gap, bandwidth, min_score)]
+        for name, v in zip(("min_length", "max_hits", "max_gap", "bandwidth", "min_score"), args):
+            if v < 0:
+                raise ValueError(f"{name} must not be negative")
+        targets = list(targets)
+        plan = plan_index_batches([len(t) for t in targets], h.info["block_length"], MAX_TEXT, batch_bases,
+                                  max_targets=MAX_CHAIN_TARGETS)
+        chains, offsets, anchors, base = [], [np.zeros(1, dtype=np.uint64)], [], 0
+        for lo, hi in plan:
+            c, o, a, _, _ = h.seed_chains(targets[lo:hi], *args)
+            c["target"] += np.uint64(lo)
+            chains.append(c)
+            offsets.append(o[1:] + np.uint64(base))
+            anchors.append(a)
+            base += int(o[-1])
+        c = np.concatenate(chains) if chains else np.zeros(0, dtype=CHAIN_DTYPE)
+        a = np.concatenate(anchors) if anchors else np.zeros(0, dtype=CHAIN_ANCHOR_DTYPE)
+        starts = np.cumsum([0] + [len(r) + 1 for r in self._reference[:-1]], dtype=np.uint64)  # of every record in Rblk
+        return {"target": c["target"].copy(), "record": c["record"].copy(), "is_rc": c["is_rc"].astype(bool),
+                "score": c["score"].copy(), "t_start": c["t_start"].copy(), "t_end": c["t_end"].copy(),
+                "r_start": c["r_start"].copy(), "r_end": c["r_end"].copy(),
+                "record_offset": c["r_start"] - starts[c["record"]], "num_anchors": c["num_anchors"].copy(),
+                "primary": c["primary"].astype(bool), "anchor_offsets": np.concatenate(offsets),
+                "anchor_t_start": a["t_start"].copy(), "anchor_position": a["position"].copy(),
+                "anchor_length": a["length"].copy()}
+
     def archive(self, targets, ids=None):
         """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
         targets = list(targets)
@@ -716,5 +763,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
