@@ -797,6 +797,74 @@ int nolzss_rlz_index_seed_chains(const nolzss_rlz_index *h, const char *const *t
                                  const nolzss_rlz_chain_params *params, nolzss_rlz_seed_chains_result *out);
 /* NULL is a no-op; the result is zeroed. */
 void nolzss_free_rlz_seed_chains_result(nolzss_rlz_seed_chains_result *r);
+/* Base-level alignments of the seed chains: which bases match, which differ, where the insertions and deletions are
+ * ("Relative-LZ index: base-level alignments").  The call follows nolzss_rlz_index_seed_chains up to its
+ * chains, which stay on the device, and aligns every chain there; neither seeds, hits nor anchors come down.
+ *   Parameters: min_length, max_hits, max_gap, bandwidth and min_score mean exactly what they mean in
+ *     nolzss_rlz_index_seed_chains; the chains aligned are exactly the chains that call reports for them, in the same
+ *     order, one alignment per chain.  band: the diagonals allowed on either side.  max_flank: the longest flank aligned.
+ *   Coordinates: q inside the target and y in the index text X, as the chain stage uses them: y = x on the forward strand,
+ *     y = 2 B - x - L + 1 (the mirrored block's coordinate) on the reverse strand, where the alignment reads forward too.
+ *     A record r = [S_r, E_r) of the block spans [S_r, E_r) in y on the forward strand and [2 B + 1 - E_r, 2 B + 1 - S_r)
+ *     on the reverse strand.  No job reads X outside its chain's record span.
+ *   Anchor trim: for consecutive anchors p, i of a chain, dq = q_i - q_p >= 1, dy = y_i - y_p >= 1, ov = max(0, L_p - dq,
+ *     L_p - dy); the earlier anchor keeps L'_p = L_p - ov >= 1 bases, the last anchor of a chain is not trimmed, and an
+ *     anchor contributes L' columns of `=`.
+ *   Gap job between p and i: the query Q = target[q_p + L'_p, q_i) of gq = dq - L'_p bases against the reference R =
+ *     X[y_p + L'_p, y_i) of gy = dy - L'_p bases, delta = gy - gq.  Allowed diagonals d = j - i in [min(0, delta) - band,
+ *     max(0, delta) + band], at most NOLZSS_RLZ_ALIGN_LANES of them.  D[0][0] = 0 and D[i][j] is the minimum over the
+ *     predecessors that exist inside the rectangle and the band of: the diagonal D[i-1][j-1] + (Q[i-1] != R[j-1]); up,
+ *     D[i-1][j] + 1, a query base, op I; left, D[i][j-1] + 1, a reference base, op D.  The job's cost is D[gq][gy].
+ *     Traceback from (gq, gy): at every cell the FIRST of diagonal, up, left that attains D is taken; a diagonal step is
+ *     `=` or X.  gq == 0 or gy == 0 needs no recurrence: gy times D, or gq times I.
+ *   Right flank: fq = target_len - (q_e + L_e) query bases behind the last anchor e, A = the bases of the record span
+ *     behind y_e + L_e.  fq == 0: nothing.  fq > max_flank: the flank is clipped.  Otherwise W = min(A, fq + band),
+ *     diagonals [-band, band], the same recurrence on (fq + 1) x (W + 1) anchored at (0, 0); the end cell is free on the
+ *     reference side: the j in [max(0, fq - band), min(W, fq + band)] with the least D[fq][j], ties to the least |j - fq|,
+ *     then to the smaller j.  If that range is empty the flank is clipped.  Traceback by the same rule.
+ *   Left flank: the same job on the reversed strings -- the query runs q_0 - 1, q_0 - 2, .., 0, X is read downward from
+ *     y_0 - 1 to the start of the record span -- and the job's ops are then reversed.
+ *   A clipped flank contributes no column; t_start / t_end show the clip.
+ *   Alignment record, one per chain: target, record, is_rc, score and primary are the chain's.  [t_start, t_end) is the
+ *     aligned part of the target, [r_start, r_end) the aligned part of the block in Rblk coordinates -- [y_begin, y_end)
+ *     on the forward strand, [2 B + 1 - y_end, 2 B + 1 - y_begin) on the reverse strand.  edit_distance is the sum of the
+ *     job costs, columns the number of alignment columns.
+ *   Ops: CSR -- op_offsets has num_alignments + 1 entries, alignment c owns ops [op_offsets[c], op_offsets[c + 1]), and
+ *     an op is (length << 4) | code with BAM's codes: I = 1 (a target base, no block base), D = 2 (a block base, no target
+ *     base), `=` = 7, X = 8.  The ops ascend in q: left flank, then anchors and gaps alternating, then the right flank;
+ *     adjacent ops of equal code are merged, so no two neighbours share a code.  On the reverse strand the ops still
+ *     ascend in q: they consume the block from r_end DOWNWARD, complemented -- the target stretch equals the reverse
+ *     complement of Rblk[r_start, r_end) edited by the ops read back to front.
+ *   Refusals, all before any device work: everything nolzss_rlz_index_seed_chains refuses, with the same status and
+ *     message; bandwidth + 2 band + 1 > NOLZSS_RLZ_ALIGN_LANES (a job's diagonals are the lanes of one wavefront, and the
+ *     constant defines the result); a target of 2^28 bases or more (an op keeps its length in 28 bits):
+ *     NOLZSS_ERR_INVALID_ARGUMENT.  k == 0, or a batch without a base, succeeds without touching the device.  The
+ *     refusal of the hit total applies unchanged; DP rows, column slots or columns beyond 2^32 - 1 in one batch are
+ *     refused with the same status.  Either leaves an empty result.
+ *   Layout: alignments, op_offsets, ops; alignments and ops are NULL at zero counts, op_offsets always holds its
+ *     num_alignments + 1 entries after a success.
+ *   An arena out-of-memory leaves the handle untouched.  Several threads may query one handle; the calling thread's
+ *     current device is left as it was.  NOLZSS_RLZ_LOCATE_CHUNK (tests): records, offsets and ops per download. */
+#define NOLZSS_RLZ_ALIGN_LANES 64
+typedef struct nolzss_rlz_align_params {
+    uint64_t min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank;
+} nolzss_rlz_align_params;
+typedef struct nolzss_rlz_alignment {
+    uint64_t target, t_start, t_end, r_start, r_end, score, edit_distance, columns;
+    uint32_t record, is_rc, num_ops, primary;
+} nolzss_rlz_alignment;
+typedef struct nolzss_rlz_align_result {
+    size_t num_alignments;
+    nolzss_rlz_alignment *alignments; /* in the order of the chains; NULL when num_alignments == 0 */
+    uint64_t *op_offsets;             /* num_alignments + 1 entries */
+    size_t num_ops;
+    uint32_t *ops;                    /* (length << 4) | code; NULL when num_ops == 0 */
+    size_t num_jobs, num_rows;        /* diagnostics: the jobs planned and the DP rows run */
+} nolzss_rlz_align_result;
+int nolzss_rlz_index_align(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                           const nolzss_rlz_align_params *params, nolzss_rlz_align_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_align_result(nolzss_rlz_align_result *r);
 /* Host only (tests): the bit offsets of the 8-bit digits the sort of a locate's hits runs for a block of block_length
  * bases and q patterns, least significant first; shifts: 8 entries, the caller's. */
 int nolzss_debug_rlz_locate_shifts(uint64_t block_length, uint64_t q, int *shifts, int *npasses);
@@ -1108,6 +1176,22 @@ int nolzss_debug_chain(const uint32_t *codes, size_t n, size_t start_pos, int wi
 int nolzss_debug_rlz_seed_chain(const uint32_t *target, const uint32_t *group, const uint32_t *y, const uint32_t *q,
                                 const uint32_t *length, size_t n, const nolzss_rlz_chain_params *params, uint64_t B,
                                 uint32_t m, int device, uint32_t *f, uint32_t *pred, nolzss_rlz_seed_chains_result *res);
+/* The alignment stages from the job offsets to the traceback (rlz_align.hip: rlz_align_sizes, rlz_align_layout,
+ * rlz_align_dp, rlz_align_traceback, the production functions) on the caller's jobs, by the rules of
+ * nolzss_rlz_index_align.  query / reference: plain ACGT bytes (case-insensitive), packed as a target batch is.
+ * Job j of n: kind[j] 0 = gap, 1 = right flank, 2 = left flank; a gap reads nq[j] query bases from q0[j] and ny[j]
+ * reference bases from y0[j]; a right flank reads nq[j] = fq query bases from q0[j] with ny[j] = A reference bases
+ * available from y0[j]; a left flank reads fq query bases downward from q0[j] - 1 with A reference bases available below
+ * y0[j].  max_flank does not apply.  The job array is followed by 64 entries filled with 0xff bytes.
+ * Out: cost[n], end_col[n] (a gap: ny; a flank: the end cell's j; a clipped flank: 0 with cost 0 and no column),
+ * col_offsets[n + 1] and *cols: one code byte (1, 2, 7, 8) per alignment column of every job, in ascending q, malloc'ed
+ * (nolzss_free; NULL without a column).  n == 0 succeeds without a launch.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any launch for null pointers, n >= 2^24, an invalid base, a kind above 2, a job
+ * that leaves either text, 2 band + 1 > 64, or a gap with |ny - nq| + 2 band + 1 > 64. */
+int nolzss_debug_rlz_align_jobs(const char *query, size_t query_len, const char *reference, size_t reference_len,
+                                const uint32_t *kind, const uint32_t *q0, const uint32_t *nq, const uint32_t *y0,
+                                const uint32_t *ny, size_t n, uint32_t band, int device, uint32_t *cost, uint32_t *end_col,
+                                uint64_t *col_offsets, uint8_t **cols);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

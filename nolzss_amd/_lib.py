@@ -153,6 +153,18 @@ class RlzSeedChainsResult(C.Structure):
                 ("num_seed_hits", C.c_size_t)]
 
 
+class RlzAlignParams(C.Structure):
+    """Mirror of nolzss_rlz_align_params (include/nolzss_hip.h)."""
+    _fields_ = [("min_length", C.c_uint64), ("max_hits", C.c_uint64), ("max_gap", C.c_uint64), ("bandwidth", C.c_uint64),
+                ("min_score", C.c_uint64), ("band", C.c_uint64), ("max_flank", C.c_uint64)]
+
+
+class RlzAlignResult(C.Structure):
+    """Mirror of nolzss_rlz_align_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_alignments", C.c_size_t), ("alignments", C.c_void_p), ("op_offsets", C.c_void_p),
+                ("num_ops", C.c_size_t), ("ops", C.c_void_p), ("num_jobs", C.c_size_t), ("num_rows", C.c_size_t)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -312,6 +324,11 @@ def _load():
     lib.nolzss_free_rlz_seed_chains_result.restype = None
     lib.nolzss_debug_rlz_seed_chain.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(RlzChainParams), C.c_uint64, C.c_uint32,
                                                 C.c_int, vp, vp, C.POINTER(RlzSeedChainsResult)]
+    lib.nolzss_rlz_index_align.argtypes = [vp] + seqs[3:] + [C.POINTER(RlzAlignParams), C.POINTER(RlzAlignResult)]
+    lib.nolzss_free_rlz_align_result.argtypes = [C.POINTER(RlzAlignResult)]
+    lib.nolzss_free_rlz_align_result.restype = None
+    lib.nolzss_debug_rlz_align_jobs.argtypes = [C.c_char_p, sz, C.c_char_p, sz, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_int,
+                                                vp, vp, vp, vpp]
     lib.nolzss_debug_rlz_locate_shifts.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
@@ -396,6 +413,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_local_sort", "nolzss_debug_text_order", "nolzss_debug_group_sort",
     "nolzss_debug_chain",
     "nolzss_rlz_index_seed_chains", "nolzss_free_rlz_seed_chains_result", "nolzss_debug_rlz_seed_chain",
+    "nolzss_rlz_index_align", "nolzss_free_rlz_align_result", "nolzss_debug_rlz_align_jobs",
 ]
 
 

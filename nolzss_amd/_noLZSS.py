@@ -29,6 +29,10 @@ SEED_DTYPE = np.dtype([("target", "<u8"), ("start", "<u8"), ("length", "<u8"), (
 CHAIN_DTYPE = np.dtype([("target", "<u8"), ("t_start", "<u8"), ("t_end", "<u8"), ("r_start", "<u8"), ("r_end", "<u8"),
                         ("score", "<u8"), ("record", "<u4"), ("is_rc", "<u4"), ("num_anchors", "<u4"), ("primary", "<u4")])
 CHAIN_ANCHOR_DTYPE = np.dtype([("t_start", "<u8"), ("position", "<u8"), ("length", "<u8")])
+# nolzss_rlz_alignment: the base-level alignment of one seed chain (RlzIndexHandle.align)
+ALIGN_DTYPE = np.dtype([("target", "<u8"), ("t_start", "<u8"), ("t_end", "<u8"), ("r_start", "<u8"), ("r_end", "<u8"),
+                        ("score", "<u8"), ("edit_distance", "<u8"), ("columns", "<u8"), ("record", "<u4"), ("is_rc", "<u4"),
+                        ("num_ops", "<u4"), ("primary", "<u4")])
 
 _default_device = int(os.environ.get("NOLZSS_DEVICE", os.environ.get("LOCAL_RANK", "0")) or 0)
 
@@ -1454,6 +1458,30 @@ def _unpack_seed_chains(res):
     return chains, offsets, anchors
 
 
+ALIGN_LANES = 64  # NOLZSS_RLZ_ALIGN_LANES: the diagonals of an alignment job are the lanes of one wavefront
+
+
+def _align_params(min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank):
+    """The parameters of an align query as the C struct; ValueError for a negative one, one beyond 64 bits, or more than
+    ALIGN_LANES diagonals -- before any native call."""
+    values = {"min_length": min_length, "max_hits": max_hits, "max_gap": max_gap, "bandwidth": bandwidth,
+              "min_score": min_score, "band": band, "max_flank": max_flank}
+    params = _lib.RlzAlignParams()
+    for name, v in values.items():
+        v = operator.index(v)
+        if v < 0:
+            raise ValueError(f"{name} must not be negative")
+        if v >= 1 << 64:
+            raise ValueError(f"{name} must fit 64 bits")
+        values[name] = v
+    if values["bandwidth"] + 2 * values["band"] + 1 > ALIGN_LANES:
+        raise ValueError(f"an alignment job has at most {ALIGN_LANES} diagonals: bandwidth + 2 * band + 1 is "
+                         f"{values['bandwidth']} + 2 * {values['band']} + 1; lower bandwidth or band")
+    for name, v in values.items():
+        setattr(params, name, v)
+    return params
+
+
 # ---- relative-LZ index: target batches matched against a resident reference (genomics/rlz.py) -------------------
 class RlzIndexHandle:
     """Extension: the suffix structures of a reference block kept in device memory (C ABI nolzss_rlz_index_*), any
@@ -1581,6 +1609,28 @@ class RlzIndexHandle:
             return _unpack_seed_chains(res) + (int(res.num_seeds), int(res.num_seed_hits))
         finally:
             lib.nolzss_free_rlz_seed_chains_result(C.byref(res))
+
+    def align(self, targets, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 31,
+              min_score: int = 40, band: int = 16, max_flank: int = 256):
+        """One batch -> (alignments, op_offsets, ops, num_jobs, num_rows): one ALIGN_DTYPE record per chain of
+        seed_chains at the same first five parameters, in the same order; the len(alignments) + 1 uint64 offsets of
+        their ops; the ops as uint32 (length << 4 | code: I = 1, D = 2, `=` = 7, X = 8), ascending in the target; the
+        jobs planned and the DP rows run (diagnostics).  C ABI nolzss_rlz_index_align (its header states the rules)."""
+        params = _align_params(min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank)
+        h = self._handle()
+        res = _lib.RlzAlignResult()
+        try:
+            check(lib.nolzss_rlz_index_align(h, *_seq_args(targets, "target"), C.byref(params), C.byref(res)))
+            n, t = res.num_alignments, res.num_ops
+            offsets = np.ctypeslib.as_array(C.cast(res.op_offsets, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+            recs, ops = np.zeros(n, dtype=ALIGN_DTYPE), np.zeros(t, dtype=np.uint32)
+            if n:
+                C.memmove(recs.ctypes.data, res.alignments, n * ALIGN_DTYPE.itemsize)
+            if t:
+                C.memmove(ops.ctypes.data, res.ops, t * 4)
+            return recs, offsets, ops, int(res.num_jobs), int(res.num_rows)
+        finally:
+            lib.nolzss_free_rlz_align_result(C.byref(res))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -2067,3 +2117,35 @@ def debug_rlz_seed_chain(target, group, y, q, length, block_length: int, records
     finally:
         lib.nolzss_free_rlz_seed_chains_result(C.byref(res))
     return {"f": f[:n], "pred": pred[:n], "chains": chains, "anchor_offsets": offsets, "anchors": anchors}
+
+
+def debug_rlz_align_jobs(query, reference, kind, q0, nq, y0, ny, band: int):
+    """The alignment stages from the job offsets to the traceback on caller jobs (nolzss_debug_rlz_align_jobs, test
+    hook): query and reference are ACGT strings; job j is (kind: 0 gap, 1 right flank, 2 left flank; q0, nq; y0, ny -- of
+    a flank the query bases to align and the reference bases available, of a left flank below q0 / y0).  Returns {"cost",
+    "end_col" (uint32 per job), "col_offsets" (uint64, n + 1), "cols" (uint8: one code per alignment column of every
+    job, ascending in the query)}."""
+    query = query.encode("ascii") if isinstance(query, str) else bytes(query)
+    reference = reference.encode("ascii") if isinstance(reference, str) else bytes(reference)
+    arrays = [np.ascontiguousarray(a, dtype=np.uint32) for a in (kind, q0, nq, y0, ny)]
+    n = arrays[0].size
+    if any(a.size != n for a in arrays):
+        raise ValueError("the job arrays hold one entry per job")
+    band = operator.index(band)
+    if band < 0 or band >= 1 << 32:
+        raise ValueError("band must fit 32 bits")
+    cost, end_col = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    cols = C.c_void_p()
+    try:
+        check(lib.nolzss_debug_rlz_align_jobs(query, len(query), reference, len(reference),
+                                              *[a.ctypes.data if n else None for a in arrays], n, band, _default_device,
+                                              cost.ctypes.data, end_col.ctypes.data, offsets.ctypes.data, C.byref(cols)))
+        total = int(offsets[-1])
+        out = np.zeros(total, dtype=np.uint8)
+        if total:
+            C.memmove(out.ctypes.data, cols, total)
+    finally:
+        if cols:
+            lib.nolzss_free(cols)
+    return {"cost": cost[:n], "end_col": end_col[:n], "col_offsets": offsets, "cols": out}

@@ -1,6 +1,8 @@
 // debug_rlz.hip -- test hooks of the relative-LZ index (part of the C ABI layer of libnolzss_hip.so, include/nolzss_hip.h,
 // the debug section): nolzss_debug_rlz_seed_chain, the seed-chain stages on a caller's anchors (the kernels:
-// rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index: colinear seed chains").
+// rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index: colinear seed chains"), and nolzss_debug_rlz_align_jobs, the
+// alignment stages on a caller's jobs (the kernels: rlz_align.hip; DESIGN.md 5, "Relative-LZ index: base-level
+// alignments").
 #include "rlz_handles.hpp"
 
 using namespace nolzss;
@@ -78,9 +80,122 @@ void debug_seed_chain(const uint32_t *target, const uint32_t *group, const uint3
     *out = res;
 }
 
+// text s, upper-cased, as a batch of one target: uploaded and packed as production packs a batch
+PackedText pack_debug_text(Context &ctx, const char *text, size_t len, const char *what) {
+    HostBytes bytes(len + 1);
+    for (size_t i = 0; i < len; ++i) bytes[i] = (uint8_t)text[i] & 0xdfu;  // (the caller has checked the bases)
+    bytes[len] = kSeparator;
+    uint8_t *d_text = ctx.arena.alloc<uint8_t>(len + 1);
+    upload_bytes(ctx, d_text, bytes.data(), len + 1);
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));  // (bytes is a local)
+    PackedText t;
+    if (!pack_independent_text(ctx, d_text, len + 1, std::vector<uint32_t>{(uint32_t)len}, t))
+        throw std::runtime_error(std::string(what) + ": bytes that are neither bases nor the separator");
+    t.n = (uint32_t)len;  // (the jobs end in front of the separator)
+    return t;
+}
+
+// The debug hook: the checks of the caller's jobs, then the production stages from the sizes to the traceback.
+void debug_align_jobs(const char *query, size_t query_len, const char *reference, size_t reference_len, const uint32_t *kind,
+                      const uint32_t *q0, const uint32_t *nq, const uint32_t *y0, const uint32_t *ny, size_t n, uint32_t band,
+                      int device, uint32_t *cost, uint32_t *end_col, uint64_t *col_offsets, uint8_t **cols) {
+    if (!cols || !col_offsets) throw std::invalid_argument("output pointer is null");
+    *cols = nullptr;
+    col_offsets[0] = 0;
+    if ((query_len && !query) || (reference_len && !reference)) throw std::invalid_argument("null argument");
+    if (n && (!kind || !q0 || !nq || !y0 || !ny || !cost || !end_col)) throw std::invalid_argument("null argument");
+    if (n >= (size_t(1) << 24)) throw std::invalid_argument("too many jobs");
+    if (query_len >= kAlignMaxTarget || reference_len >= kAlignMaxTarget) throw std::invalid_argument("a text of 2^28 bases or more");
+    if (2 * (uint64_t)band + 1 > kAlignLanes) throw std::invalid_argument("2 band + 1 is more than 64 diagonals");
+    for (size_t i = 0; i < query_len + reference_len; ++i) {
+        const uint8_t c = (uint8_t)(i < query_len ? query[i] : reference[i - query_len]) & 0xdfu;
+        if (c != 'A' && c != 'C' && c != 'G' && c != 'T')
+            throw std::invalid_argument(i < query_len ? "query: an invalid base at " + std::to_string(i)
+                                                      : "reference: an invalid base at " + std::to_string(i - query_len));
+    }
+    constexpr size_t kPad = 64;  // entries behind the job array, filled with 0xff bytes
+    std::vector<AlignJob> jobs(n + kPad);
+    std::memset(jobs.data() + n, 0xff, sizeof(AlignJob) * kPad);
+    uint64_t rows = 0, slots = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const std::string at = "job " + std::to_string(i);
+        if (kind[i] > kAlignLeft) throw std::invalid_argument(at + ": a kind above 2");
+        const uint64_t q = q0[i], y = y0[i], a = nq[i], c = ny[i];
+        const bool inside = kind[i] == kAlignLeft ? (q <= query_len && a <= q && y <= reference_len && c <= y)
+                                                  : (q <= query_len && a <= query_len - q && y <= reference_len && c <= reference_len - y);
+        if (!inside) throw std::invalid_argument(at + ": leaves a text");
+        if (kind[i] == kAlignGap) {
+            const uint64_t delta = a > c ? a - c : c - a;
+            if (delta + 2 * (uint64_t)band + 1 > kAlignLanes) throw std::invalid_argument(at + ": more than 64 diagonals");
+            jobs[i] = align_gap_job(q0[i], nq[i], y0[i], ny[i], band);
+        } else {
+            jobs[i] = align_flank_job(kind[i], q0[i], nq[i], y0[i], ny[i], band, ~0ull);
+        }
+        rows += jobs[i].dp ? jobs[i].nq : 0;
+        slots += (uint64_t)jobs[i].nq + jobs[i].ny + 1;
+    }
+    if (rows > 0xffffffffull || slots > 0xffffffffull) throw std::invalid_argument("DP rows or column slots beyond 2^32 - 1");
+    if (n == 0) return;
+    Session ses(device, nullptr);
+    Context &ctx = ses.ctx();
+    hipStream_t s = ctx.stream;
+    ctx.arena.reserve(2 * (query_len + reference_len) + (48 + 12 + 20) * (n + kPad) + 16 * (size_t)rows + (size_t)slots + (size_t(64) << 20));
+    ArenaRewind rewind(ctx.arena);
+    const PackedText qt = pack_debug_text(ctx, query, query_len, "query");
+    const PackedText xt = pack_debug_text(ctx, reference, reference_len, "reference");
+    AlignJob *d_jobs = ctx.arena.alloc<AlignJob>(n + kPad);
+    HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(AlignJob) * (n + kPad), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (a local vector)
+    AlignJobs a;
+    a.J = (uint32_t)n;
+    a.jobs = d_jobs;
+    rlz_align_sizes(ctx, a);
+    if (a.total_rows != rows || a.total_slots != slots) throw HipError("rlz align: the sizes of the jobs differ from the host's");
+    rlz_align_layout(ctx, a);
+    rlz_align_dp(ctx, a, qt, xt);
+    rlz_align_traceback(ctx, a);
+    std::vector<uint32_t> col_off(n), ncols(n);
+    std::vector<uint8_t> codes((size_t)slots);
+    HIP_CHECK(hipMemcpyAsync(cost, a.cost, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(end_col, a.endj, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(col_off.data(), a.col_off, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(ncols.data(), a.ncols, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(codes.data(), a.codes, (size_t)slots, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    ctx.prof.collect();
+    // the used slots of every job, in ascending q: the first ncols of a left flank, the last ncols of the others
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t room = (uint64_t)jobs[i].nq + jobs[i].ny;
+        if (ncols[i] > room || (uint64_t)col_off[i] + room + 1 > slots) throw HipError("rlz align: a job's columns leave its slots");
+        total += ncols[i];
+        col_offsets[i + 1] = total;
+    }
+    if (total == 0) return;
+    uint8_t *flat = static_cast<uint8_t *>(std::malloc(total));
+    if (!flat) throw std::bad_alloc();
+    for (size_t i = 0; i < n; ++i) {
+        const size_t room = (size_t)jobs[i].nq + jobs[i].ny;
+        const size_t first = kind[i] == kAlignLeft ? 0 : room - ncols[i];
+        std::memcpy(flat + col_offsets[i], codes.data() + col_off[i] + first, ncols[i]);
+    }
+    *cols = flat;
+}
+
 }  // namespace
 
 extern "C" {
+
+int nolzss_debug_rlz_align_jobs(const char *query, size_t query_len, const char *reference, size_t reference_len,
+                                const uint32_t *kind, const uint32_t *q0, const uint32_t *nq, const uint32_t *y0,
+                                const uint32_t *ny, size_t n, uint32_t band, int device, uint32_t *cost, uint32_t *end_col,
+                                uint64_t *col_offsets, uint8_t **cols) {
+    return guarded([&] {
+        debug_align_jobs(query, query_len, reference, reference_len, kind, q0, nq, y0, ny, n, band, device, cost, end_col,
+                         col_offsets, cols);
+    });
+}
 
 int nolzss_debug_rlz_seed_chain(const uint32_t *target, const uint32_t *group, const uint32_t *y, const uint32_t *q,
                                 const uint32_t *length, size_t n, const nolzss_rlz_chain_params *params, uint64_t B,

@@ -1,7 +1,7 @@
 // rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
-// rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds and rlz_seed_chain.hip for
-// their colinear chains;
+// rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds, rlz_seed_chain.hip for
+// their colinear chains and rlz_align.hip for the base-level alignments of those;
 // the handle and its entry points: rlz_index_api.hip).
 #pragma once
 #include "pipeline.hpp"
@@ -143,6 +143,107 @@ ChainAnchors rlz_seed_chain_anchors(Context &ctx, const RlzIndexView &ix, uint32
 // Group heads, the recurrence, ends, backtrack and primary flags over anchors in group order (a.n >= 1).  Waits for the
 // stream twice (the number of groups, then the totals).  Arena memory: at most 152 bytes per anchor.
 ChainsOut rlz_seed_chain_run(Context &ctx, const ChainAnchors &a, const ChainRules &rules);
+
+// ---- base-level alignments of the seed chains (rlz_align.hip; DESIGN.md 5, "Relative-LZ index: base-level alignments") -
+// One banded edit-distance job per gap between consecutive anchors of a chain and per flank of a chain, by the rules of
+// nolzss_rlz_index_align (include/nolzss_hip.h).  A job reads nq query bases from position qpos of the packed query text
+// and ny reference bases from position ypos of the packed reference text, upward (gap, right flank) or downward (left
+// flank: the job runs on the reversed strings).  Lane l of the job's wavefront is diagonal lo + l, `width` of them.
+constexpr uint32_t kAlignLanes = 64;  // NOLZSS_RLZ_ALIGN_LANES: the diagonals of a job are the lanes of one wavefront
+constexpr uint32_t kAlignGap = 0, kAlignRight = 1, kAlignLeft = 2;
+constexpr uint32_t kAlignNoAnchor = 0xffffffffu;
+constexpr uint32_t kAlignI = 1, kAlignD = 2, kAlignEq = 7, kAlignX = 8;  // BAM's codes
+constexpr uint64_t kAlignMaxTarget = 1ull << 28;                          // an op keeps its length in 28 bits
+struct AlignJob {
+    uint32_t kind = kAlignGap;
+    uint32_t dp = 0;              // 1: the wavefront runs the recurrence (nq >= 1 and ny >= 1); 0: cost and endj stand below
+    uint32_t qpos = 0, ypos = 0;  // the first base read of either text
+    uint32_t nq = 0, ny = 0;      // rows and columns of the rectangle (0 and 0: a clipped or empty flank)
+    int32_t lo = 0;               // the lowest allowed diagonal j - i
+    uint32_t width = 1;           // allowed diagonals, 1 .. 64
+    uint32_t anchor = kAlignNoAnchor;  // the chain anchor whose `=` run follows the job's columns (production)
+    uint32_t cost = 0, endj = 0;  // of a job without recurrence
+    uint32_t pad = 0;
+};
+// The gap job between two anchors: gq query bases at qpos, gy reference bases at ypos.
+__host__ __device__ inline AlignJob align_gap_job(uint32_t qpos, uint32_t gq, uint32_t ypos, uint32_t gy, uint32_t band) {
+    AlignJob j;
+    const int64_t delta = (int64_t)gy - (int64_t)gq;
+    const int64_t lo = (delta < 0 ? delta : 0) - (int64_t)band, hi = (delta > 0 ? delta : 0) + (int64_t)band;
+    j.kind = kAlignGap;
+    j.qpos = qpos;
+    j.ypos = ypos;
+    j.nq = gq;
+    j.ny = gy;
+    j.lo = (int32_t)lo;
+    j.width = (uint32_t)(hi - lo + 1);
+    j.dp = (gq && gy) ? 1u : 0u;
+    j.cost = j.dp ? 0u : gq + gy;
+    j.endj = gy;
+    return j;
+}
+// A flank job of fq query bases with `avail` bases of the record span beside it.  Right flank: the texts are read upward
+// from qpos / ypos.  Left flank: qend / yend are the anchor's coordinates and the texts are read downward from qend - 1 /
+// yend - 1.  A clipped flank (fq == 0, fq > max_flank, or no end cell inside the band) has nq = ny = 0.
+__host__ __device__ inline AlignJob align_flank_job(uint32_t kind, uint32_t qat, uint32_t fq, uint32_t yat, uint32_t avail,
+                                                    uint32_t band, uint64_t max_flank) {
+    AlignJob j;
+    j.kind = kind;
+    j.lo = -(int32_t)band;
+    j.width = 2u * band + 1u;
+    if (fq == 0 || (uint64_t)fq > max_flank) return j;
+    const uint64_t reach = (uint64_t)fq + band;
+    const uint32_t W = (uint64_t)avail < reach ? avail : (uint32_t)reach;
+    if ((uint64_t)W + band < (uint64_t)fq) return j;  // no end cell: [max(0, fq - band), min(W, fq + band)] is empty
+    j.qpos = kind == kAlignLeft ? qat - 1u : qat;
+    j.ypos = kind == kAlignLeft ? yat - 1u : yat;
+    j.nq = fq;
+    j.ny = W;
+    j.dp = W ? 1u : 0u;
+    j.cost = j.dp ? 0u : fq;
+    j.endj = 0;
+    return j;
+}
+struct AlignRec {  // nolzss_rlz_alignment
+    uint64_t target, t_start, t_end, r_start, r_end, score, edit_distance, columns;
+    uint32_t record, is_rc, num_ops, primary;
+};
+// The jobs of a run and everything the stages leave per job.  Arena memory.
+struct AlignJobs {
+    uint32_t J = 0, A = 0;  // jobs; chain anchors (0 in the debug hook)
+    const AlignJob *jobs = nullptr;
+    const uint32_t *alen = nullptr;  // L' per chain anchor (production; nullptr in the debug hook)
+    uint32_t *rows = nullptr, *slots = nullptr, *weight = nullptr;  // rlz_align_sizes: DP rows, column slots, max columns
+    uint64_t total_rows = 0, total_slots = 0, total_weight = 0;      // their sums in 64 bits
+    uint32_t *row_off = nullptr, *col_off = nullptr;                 // rlz_align_layout
+    unsigned long long *dirs = nullptr;  // 2 words per DP row: bit l of word 0 / 1 = bit 0 / 1 of lane l's direction
+    uint8_t *codes = nullptr;            // one code byte per column slot, 0: unused
+    uint32_t *cost = nullptr, *endj = nullptr, *ncols = nullptr;  // per job: rlz_align_dp, rlz_align_traceback
+};
+struct AlignOut {  // arena memory
+    uint32_t num_alignments = 0, num_ops = 0;
+    const AlignRec *recs = nullptr;       // one per chain, in chain order
+    const uint64_t *op_offsets = nullptr; // num_alignments + 1
+    const uint32_t *ops = nullptr;        // (length << 4) | code
+};
+// One lane per chain anchor writes L' and the gap job behind it, the first and last anchor of a chain its flank jobs:
+// chain c with anchors [o, o + d) owns the jobs [o + c, o + c + d] -- left flank, d - 1 gaps, right flank.  Arena memory:
+// 48 bytes per job, 4 per anchor.
+AlignJobs rlz_align_plan(Context &ctx, const RlzIndexView &ix, const PackedText &batch, const ChainsOut &chains, uint32_t band,
+                         uint64_t max_flank);
+// rows / slots / weight of every job and their 64-bit totals (waits for the stream once).  12 bytes per job.
+void rlz_align_sizes(Context &ctx, AlignJobs &a);
+// The offsets of the rows and of the column slots, the direction rows, the code bytes (zeroed) and the per-job results.
+// The caller has made sure that the three totals stay below 2^32.  Arena memory: 20 bytes per job, 16 per DP row, 1 per
+// slot.
+void rlz_align_layout(Context &ctx, AlignJobs &a);
+// The recurrence, one wavefront per job: qt / xt are the packed query and reference texts.
+void rlz_align_dp(Context &ctx, const AlignJobs &a, const PackedText &qt, const PackedText &xt);
+// One lane per job walks the direction bits back and writes the job's code bytes and their number.
+void rlz_align_traceback(Context &ctx, const AlignJobs &a);
+// Heads, scans, ops and one record per chain.  Waits for the stream once (the number of ops).  Arena memory: 16 bytes
+// per slot, 12 per op, 88 per chain.
+AlignOut rlz_align_ops(Context &ctx, const AlignJobs &a, const ChainsOut &chains, const ChainRules &rules);
 
 constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
 

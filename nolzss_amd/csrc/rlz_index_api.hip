@@ -8,7 +8,8 @@
 // and nolzss_rlz_index_seeds: the maximal exact matches of a target batch and their occurrences (the kernels:
 // rlz_seeds.hip; DESIGN.md 5, "Relative-LZ index: maximal match seeds"), and nolzss_rlz_index_seed_chains: the seeds of
 // every target chained into placements on the device (the kernels: rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index:
-// colinear seed chains").
+// colinear seed chains"), and nolzss_rlz_index_align: every such chain aligned base by base on the device (the kernels:
+// rlz_align.hip; DESIGN.md 5, "Relative-LZ index: base-level alignments").
 #include "rlz_handles.hpp"
 
 using namespace nolzss;
@@ -883,9 +884,206 @@ void index_seed_chains(const nolzss_rlz_index *h, const char *const *targets, co
     *out = res;  // ownership moves to the caller
 }
 
+// ---- base-level alignments -----------------------------------------------------------------------------------------
+// device memory of the align stages, on top of a seed-chain query.  Per hit -- a chain has at least one anchor and an
+// anchor is a hit, so the jobs, one per anchor and one more per chain, are at most two per hit --: the jobs with their
+// sizes, offsets and results (48 + 12 + 20 each), L' per anchor (4) and the record and op offset of a chain (88): at most 264.
+// Per DP row the two direction words: 16.  Per column slot the code byte, flag, weight and their scans (17) and, an op
+// being at most one per slot, its start, code and word (12), rounded up for the scans' tile sums: 32.
+constexpr size_t kAlignBytesPerHit = 264, kAlignBytesPerRow = 16, kAlignBytesPerSlot = 32;
+
+static_assert(sizeof(nolzss_rlz_alignment) == sizeof(AlignRec) && sizeof(AlignRec) == 80, "the kernels write nolzss_rlz_alignment");
+static_assert(NOLZSS_RLZ_ALIGN_LANES == kAlignLanes, "the diagonals of a job are a constant of the ABI");
+static_assert(sizeof(AlignJob) == 48, "the arena accounting counts 48 bytes per job");
+
+// the alignments of a run into the host blocks of a result (op_offsets: allocated here)
+void deliver_alignments(Context &ctx, const AlignOut &run, nolzss_rlz_align_result &res) {
+    const size_t C = run.num_alignments, N = run.num_ops;
+    res.op_offsets = calloc_array<uint64_t>(C + 1);
+    if (C == 0) return;
+    res.alignments = static_cast<nolzss_rlz_alignment *>(alloc_factor_block(sizeof(nolzss_rlz_alignment) * C));
+    if (!res.alignments) throw std::bad_alloc();
+    res.ops = static_cast<uint32_t *>(alloc_factor_block(sizeof(uint32_t) * N));
+    if (!res.ops) throw std::bad_alloc();
+    download_records(ctx, "align_records_d2h", res.alignments, run.recs, C, sizeof(nolzss_rlz_alignment));
+    download_records(ctx, "align_offsets_d2h", res.op_offsets, run.op_offsets, C + 1, sizeof(uint64_t));
+    download_records(ctx, "align_ops_d2h", res.ops, run.ops, N, sizeof(uint32_t));
+    res.num_alignments = C;
+    res.num_ops = N;
+}
+
+// One batch of k >= 1 targets with at least one base against the handle, inside a session: the path of
+// query_seed_chains up to the chains, which stay on the device, then the align stages.  Returns false with *why when a
+// total is beyond the pipeline: res is then empty.
+bool query_align(Context &ctx, const nolzss_rlz_index &h, const Batch &b, size_t k, const nolzss_rlz_align_params &p,
+                 nolzss_rlz_align_result &res, std::string *why) {
+    const size_t n = b.tcat.size();
+    const uint32_t cap = (p.max_hits == 0 || p.max_hits >= 0xffffffffull) ? 0xffffffffu : (uint32_t)p.max_hits;
+    const uint32_t min_len = p.min_length >= 0xffffffffull ? 0xffffffffu : (uint32_t)(p.min_length ? p.min_length : 1);
+    nolzss_rlz_chain_params cp;
+    cp.min_length = p.min_length;
+    cp.max_hits = p.max_hits;
+    cp.max_gap = p.max_gap;
+    cp.bandwidth = p.bandwidth;
+    cp.min_score = p.min_score;
+    const ChainRules rules = chain_rules(cp, h.m, h.view.B);
+    hipStream_t s = ctx.stream;
+    Searched m;
+    uint32_t *d_seeds = nullptr, *d_first = nullptr, *d_rep = nullptr;
+    uint32_t S = 0;
+    // as query_seed_chains: the batch searched, the seeds listed, their intervals looked up
+    auto run_search = [&] {
+        m = search_batch(ctx, h, b);
+        uint32_t *d_flag = ctx.arena.alloc<uint32_t>(n), *d_slot = ctx.arena.alloc<uint32_t>(n);
+        d_seeds = ctx.arena.alloc<uint32_t>(n);
+        uint32_t *d_total = ctx.arena.alloc<uint32_t>(1);
+        rlz_index_seed_list(ctx, m.d_len, (uint32_t)n, min_len, d_flag, d_slot, d_seeds, d_total);
+        download_bytes(ctx, &S, d_total, sizeof(uint32_t));
+        if (S > n) throw HipError("rlz index: more seeds than batch positions");
+        d_first = ctx.arena.alloc<uint32_t>(S ? S : 1);
+        d_rep = ctx.arena.alloc<uint32_t>(S ? S : 1);
+        if (S > 0x7fffffffu) return;
+        rlz_index_seed_intervals(ctx, h.view, m.batch, d_seeds, 0u, S, cap, m.d_len, m.d_rank, d_first, d_rep, nullptr);
+    };
+    reserve_arena_for(ctx, 0, seed_batch_bytes(n, k, 0));
+    run_search();
+    if (S > 0x7fffffffu) throw std::invalid_argument("rlz index: a batch may report at most 2^31 - 1 seeds, this one has " +
+                                                     std::to_string(S) + ": raise min_length or send fewer targets");
+    uint64_t total = 0;  // the hits to expand, summed in 64 bits on the device: one word comes down
+    if (S) {
+        uint64_t *d_sum = ctx.arena.alloc<uint64_t>(1);
+        rlz_index_rep_total(ctx, d_rep, S, d_sum);
+        download_bytes(ctx, &total, d_sum, sizeof(uint64_t));
+    }
+    if (total > kMaxText) {
+        *why = "rlz index: seeds would report " + std::to_string(total) + " hits, more than the " + std::to_string(kMaxText) +
+               " the 32-bit device pipeline takes: lower max_hits (it is " + std::to_string(p.max_hits) +
+               "; 0 means no cap), raise min_length (it is " + std::to_string(p.min_length) + ") or send fewer targets";
+        return false;
+    }
+    if (total == 0) {
+        res.op_offsets = calloc_array<uint64_t>(1);
+        return true;
+    }
+    const size_t T = (size_t)total;
+    // the chains and the jobs of the batch, planned and sized: three totals come down
+    ChainsOut run;
+    AlignJobs jobs;
+    auto run_chains = [&] {
+        const LocateSorted sorted =
+            rlz_index_seed_hits(ctx, h.view, (uint32_t)h.m, (uint32_t)n, d_seeds, m.d_len, S, d_rep, d_first, (uint32_t)T);
+        const ChainAnchors anchors = rlz_seed_chain_anchors(ctx, h.view, (uint32_t)h.m, m.batch, d_seeds, m.d_len, S, sorted, (uint32_t)T);
+        run = rlz_seed_chain_run(ctx, anchors, rules);
+        jobs = rlz_align_plan(ctx, h.view, m.batch, run, (uint32_t)p.band, p.max_flank);
+        rlz_align_sizes(ctx, jobs);
+    };
+    // the arena by the two-reservation rule of the seeds and the seed chains, twice: once the hits are counted for what
+    // is per hit, once the jobs are sized for what is per DP row and per column slot.  A reservation that is not a no-op
+    // may replace the slab, so the arena is then emptied and the batch is searched -- and the second time chained and
+    // planned -- again in it
+    auto regrow = [&](size_t extra) {
+        if (arena_bytes_for(0) + extra <= ctx.arena.capacity()) return false;
+        HIP_CHECK(hipStreamSynchronize(s));  // (nothing still reads the slab that goes)
+        reserve_arena_for(ctx, 0, extra);
+        ctx.arena.rewind(0);
+        const uint32_t before = S;
+        run_search();
+        if (S != before) throw HipError("rlz index: the seeds of a batch changed between two searches");
+        return true;
+    };
+    const size_t per_hit = seed_batch_bytes(n, k, 0) + (kLocateBytesPerHit + kChainBytesPerHit + kAlignBytesPerHit) * T;
+    regrow(per_hit);
+    run_chains();
+    if (run.num_chains == 0) {
+        res.op_offsets = calloc_array<uint64_t>(1);
+        return true;
+    }
+    const uint64_t rows = jobs.total_rows, slots = jobs.total_slots, weight = jobs.total_weight;
+    if (rows > 0xffffffffull || slots > 0xffffffffull || weight > 0xffffffffull) {
+        *why = "rlz index: the alignments of this batch take " + std::to_string(rows) + " DP rows, " + std::to_string(slots) +
+               " column slots and up to " + std::to_string(weight) + " columns, and each is counted in 32 bits: send fewer targets";
+        return false;
+    }
+    if (regrow(per_hit + kAlignBytesPerRow * (size_t)rows + kAlignBytesPerSlot * (size_t)slots)) {
+        run_chains();
+        if (jobs.total_rows != rows || jobs.total_slots != slots || jobs.total_weight != weight)
+            throw HipError("rlz index: the alignment jobs of a batch changed between two runs");
+    }
+    rlz_align_layout(ctx, jobs);
+    rlz_align_dp(ctx, jobs, m.batch, h.view.text);
+    rlz_align_traceback(ctx, jobs);
+    const AlignOut aligned = rlz_align_ops(ctx, jobs, run, rules);
+    res.num_jobs = jobs.J;
+    res.num_rows = (size_t)rows;
+    deliver_alignments(ctx, aligned, res);
+    return true;
+}
+
+void index_align(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                 const nolzss_rlz_align_params *params, nolzss_rlz_align_result *out) {
+    if (!out) throw std::invalid_argument("output pointer is null");
+    std::memset(out, 0, sizeof *out);
+    if (!h) throw std::invalid_argument("handle is null");
+    if (!params) throw std::invalid_argument("rlz index: alignments need their parameters: params is null");
+    if (k > kChainMaxTargets)
+        throw std::invalid_argument("rlz index: seed chains take at most 2^24 targets per batch, this one has " + std::to_string(k) +
+                                    " (the group sort key keeps the target in 24 bits): send fewer targets");
+    if (params->bandwidth >= kAlignLanes || params->band >= kAlignLanes || params->bandwidth + 2 * params->band + 1 > kAlignLanes)
+        throw std::invalid_argument("rlz index: an alignment job has at most 64 diagonals, one per lane of a wavefront: bandwidth + 2 "
+                                    "band + 1 is " + std::to_string(params->bandwidth) + " + 2 * " + std::to_string(params->band) +
+                                    " + 1: lower bandwidth or band");
+    for (size_t j = 0; target_lens && j < k; ++j)  // (the lengths alone decide; a null array is the batch's refusal below)
+        if (target_lens[j] >= kAlignMaxTarget)
+            throw std::invalid_argument("rlz index: alignments take targets below 2^28 bases, target " + std::to_string(j) + " has " +
+                                        std::to_string(target_lens[j]) + " (an op keeps its length in 28 bits)");
+    Batch b;
+    prepare_batch(*h, targets, target_lens, k, b);
+    nolzss_rlz_align_result res;
+    std::memset(&res, 0, sizeof res);
+    bool fits = true;
+    std::string why;
+    try {
+        if (b.tcat.size() == k) {  // no target, or none with a base: the device is not touched
+            res.op_offsets = calloc_array<uint64_t>(1);
+        } else {
+            DeviceRestore restore;
+            Session ses(h->device, nullptr);
+            Context &ctx = ses.ctx();
+            {
+                ProfScope whole(ctx.profiler(), "rlz_index_align", ctx.stream);
+                fits = query_align(ctx, *h, b, k, *params, res, &why);
+            }
+            HIP_CHECK(hipStreamSynchronize(ctx.stream));
+            HIP_CHECK(hipGetLastError());
+            ctx.prof.collect();
+        }
+    } catch (...) {
+        nolzss_free_rlz_align_result(&res);
+        throw;
+    }
+    if (!fits) {  // an empty result and the status
+        nolzss_free_rlz_align_result(&res);
+        throw std::invalid_argument(why);
+    }
+    *out = res;  // ownership moves to the caller
+}
+
 }  // namespace
 
 extern "C" {
+
+int nolzss_rlz_index_align(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                           const nolzss_rlz_align_params *params, nolzss_rlz_align_result *out) {
+    return guarded([&] { index_align(h, targets, target_lens, k, params, out); });
+}
+
+void nolzss_free_rlz_align_result(nolzss_rlz_align_result *r) {
+    if (!r) return;
+    free_block(r->alignments);
+    free_block(r->op_offsets);
+    free_block(r->ops);
+    std::memset(r, 0, sizeof *r);
+}
 
 int nolzss_rlz_index_seed_chains(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
                                  const nolzss_rlz_chain_params *params, nolzss_rlz_seed_chains_result *out) {

@@ -25,7 +25,16 @@ HIT_DTYPE = _native.HIT_DTYPE  # (position, record, is_rc): an occurrence of a p
 SEED_DTYPE = _native.SEED_DTYPE  # (target, start, length, count): a maximal exact match of a target (RlzIndex.seeds)
 CHAIN_DTYPE = _native.CHAIN_DTYPE  # a seed chain: one placement of a target in a record and strand (RlzIndex.seed_chains)
 CHAIN_ANCHOR_DTYPE = _native.CHAIN_ANCHOR_DTYPE  # (t_start, position, length): one anchor of a seed chain
+ALIGN_DTYPE = _native.ALIGN_DTYPE  # the base-level alignment of one seed chain (RlzIndex.align)
+ALIGN_LANES = _native.ALIGN_LANES  # diagonals of an alignment job: bandwidth + 2 * band + 1 must not exceed it
+CIGAR_LETTERS = {1: "I", 2: "D", 7: "=", 8: "X"}  # BAM's op codes, as RlzIndex.align reports them
 MAX_CHAIN_TARGETS = 1 << 24  # targets per batch of a seed-chain query: the group sort key keeps the target in 24 bits
+
+
+def cigar_string(ops):
+    """The ops of one alignment (uint32: length << 4 | code, as RlzIndex.align returns them in `ops`) as a CIGAR string
+    with the extended letters: `=` match, X mismatch, I a target base without a reference base, D the reverse."""
+    return "".join(f"{int(op) >> 4}{CIGAR_LETTERS[int(op) & 15]}" for op in np.asarray(ops, dtype=np.uint32))
 
 
 def split_and_rebase(records, target_offsets, target_lengths):
@@ -708,6 +717,49 @@ class RlzIndex:
                 "anchor_t_start": a["t_start"].copy(), "anchor_position": a["position"].copy(),
                 "anchor_length": a["length"].copy()}
 
+    def align(self, targets, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 31,
+              min_score: int = 40, band: int = 16, max_flank: int = 256, batch_bases=None):
+        """The base-level alignment of every chain seed_chains reports at the same first five parameters, in the same
+        order, computed on the GPU -> dict(target, record, is_rc, score, primary, t_start, t_end, r_start, r_end,
+        record_offset, edit_distance, columns, num_ops, op_offsets, ops).  Alignment c aligns [t_start, t_end) of its
+        target with [r_start, r_end) of the reference block (record_offset = r_start inside record `record`) at
+        edit_distance mismatches, inserted and deleted bases, and owns ops[op_offsets[c]:op_offsets[c + 1]]: uint32
+        (length << 4) | code with BAM's codes I = 1, D = 2, `=` = 7, X = 8 (cigar_string renders them), ascending in the
+        target, neighbours never of one code.  On the reverse strand (is_rc) the ops still ascend in the target and
+        consume the block from r_end downward, complemented.  Between consecutive anchors of a chain a banded edit
+        distance runs over the diagonals within `band` of the two anchors' diagonals; the flanks beside the first and
+        the last anchor are aligned end to end in the target and free in the reference, inside the record, unless
+        they are longer than max_flank -- then, or when the record ends too early, the flank is clipped and t_start /
+        t_end show it.  bandwidth + 2 * band + 1 must not exceed 64 (ValueError).  Batches as seed_chains does."""
+        args = [operator.index(v) for v in (min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank)]
+        names = ("min_length", "max_hits", "max_gap", "bandwidth", "min_score", "band", "max_flank")
+        for name, v in zip(names, args):
+            if v < 0:
+                raise ValueError(f"{name} must not be negative")
+        if args[3] + 2 * args[5] + 1 > ALIGN_LANES:
+            raise ValueError(f"an alignment job has at most {ALIGN_LANES} diagonals: bandwidth + 2 * band + 1 is "
+                             f"{args[3]} + 2 * {args[5]} + 1; lower bandwidth or band")
+        h = self._live()
+        targets = list(targets)
+        plan = plan_index_batches([len(t) for t in targets], h.info["block_length"], MAX_TEXT, batch_bases,
+                                  max_targets=MAX_CHAIN_TARGETS)
+        recs, offsets, ops, base = [], [np.zeros(1, dtype=np.uint64)], [], 0
+        for lo, hi in plan:
+            r, o, p, _, _ = h.align(targets[lo:hi], *args)
+            r["target"] += np.uint64(lo)
+            recs.append(r)
+            offsets.append(o[1:] + np.uint64(base))
+            ops.append(p)
+            base += int(o[-1])
+        r = np.concatenate(recs) if recs else np.zeros(0, dtype=ALIGN_DTYPE)
+        starts = np.cumsum([0] + [len(x) + 1 for x in self._reference[:-1]], dtype=np.uint64)  # of every record in Rblk
+        return {"target": r["target"].copy(), "record": r["record"].copy(), "is_rc": r["is_rc"].astype(bool),
+                "score": r["score"].copy(), "primary": r["primary"].astype(bool), "t_start": r["t_start"].copy(),
+                "t_end": r["t_end"].copy(), "r_start": r["r_start"].copy(), "r_end": r["r_end"].copy(),
+                "record_offset": r["r_start"] - starts[r["record"]], "edit_distance": r["edit_distance"].copy(),
+                "columns": r["columns"].copy(), "num_ops": r["num_ops"].copy(), "op_offsets": np.concatenate(offsets),
+                "ops": np.concatenate(ops) if ops else np.zeros(0, dtype=np.uint32)}
+
     def archive(self, targets, ids=None):
         """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
         targets = list(targets)
@@ -763,5 +815,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
