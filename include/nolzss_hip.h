@@ -1163,6 +1163,11 @@ int nolzss_debug_chain(const uint32_t *codes, size_t n, size_t start_pos, int wi
                        size_t list_len, size_t listed, uint32_t list_max, int with_strand, const uint32_t *bounds, size_t k,
                        int device, uint32_t *z, uint32_t *starts, uint32_t *lengths, uint32_t *hist, uint64_t *tail,
                        uint32_t *tail_count, uint32_t *widened, uint32_t *counts);
+/* What the last run of the cursor (mark_chain) on the device's context did: info[0] = 0 nothing ran (start_pos >= n),
+ * 1 the speculative walk delivered the mark, 2 it raised its flag and the exact stages ran behind it, 3 the exact stages
+ * alone (NOLZSS_NO_SPEC_CURSOR); info[1] = the tiles whose walk from the entry did not meet the speculative walk (with
+ * NOLZSS_TEST_SPEC_CURSOR_FAILS one more). */
+int nolzss_debug_cursor(int device, uint32_t *info);
 /* The seed-chain stages from the group heads to the chain records (rlz_seed_chain.hip: rlz_seed_chain_run, the
  * production function) on the caller's anchors, by the rules of nolzss_rlz_index_seed_chains.  target, group, y, q,
  * length: n entries each, already ordered by (target, group, y, q); group = is_rc * m + record, and x is derived from y

@@ -2067,7 +2067,8 @@ def debug_chain(codes, start_pos: int = 0, width: int = 32, poison: int = 0, wid
     with the half-word `poison`.  list_max (width 16): `wide_list` holds (position | code << 32) entries of which the
     first `listed` (default: all) are applied by widened_lstar; the cursor then runs on the widened 32-bit array.
     `bounds`: 2k ascending u32 for counts of the starts per [lo, hi).  Returns {"z", "starts", "lengths", "hist", "tail"
-    (sorted: the kernel writes it in no particular order), "widened", "counts"}; what was not asked for is None."""
+    (sorted: the kernel writes it in no particular order), "widened", "counts", "cursor"}; what was not asked for is
+    None.  "cursor" = (path, failed tiles) of the call (debug_cursor)."""
     codes = np.ascontiguousarray(codes, dtype=np.uint32)
     n = codes.size
     if not (0 <= start_pos < 1 << 64 and 0 <= poison < 1 << 32 and 0 <= list_max < 1 << 32):
@@ -2094,7 +2095,20 @@ def debug_chain(codes, start_pos: int = 0, width: int = 32, poison: int = 0, wid
                                  ptr(widened), ptr(counts)))
     return {"z": z.value, "starts": starts[:z.value], "lengths": lengths[:z.value] if want_lengths else None,
             "hist": hist, "tail": np.sort(tail[:tail_count.value]) if want_hist else None,
-            "widened": widened[:n] if list_max else None, "counts": counts[:k] if bnd is not None else None}
+            "widened": widened[:n] if list_max else None, "counts": counts[:k] if bnd is not None else None,
+            "cursor": debug_cursor() if hasattr(lib, "nolzss_debug_cursor") else None}  # (NOLZSS_LIB: an older build)
+
+
+CURSOR_PATHS = ("none", "speculative", "failed_over", "exact")
+
+
+def debug_cursor():
+    """(path, failed tiles) of the last run of the cursor on the device (nolzss_debug_cursor): path "none" (nothing to
+    walk), "speculative", "failed_over" (the speculative walk raised its flag, the exact stages ran) or "exact"
+    (NOLZSS_NO_SPEC_CURSOR); the tiles whose walk from the entry did not meet the speculative walk."""
+    info = np.zeros(2, dtype=np.uint32)
+    check(lib.nolzss_debug_cursor(_default_device, info.ctypes.data))
+    return CURSOR_PATHS[int(info[0])], int(info[1])
 
 
 def debug_rlz_seed_chain(target, group, y, q, length, block_length: int, records: int, max_gap: int, bandwidth: int,

@@ -3,7 +3,10 @@
 // The reference advances one factor at a time: lambda = next_leaf(lambda, l)
 // (/root/reference/src/cpp/factorizer_core.hpp:113-115).  With L*[i] known for every position,
 // the cursor is the chain  p -> next(p) = p + max(1, L*[p])  from start_pos, and the factors are
-// exactly the chain positions < n.  next(p) > p, which makes the chain resolvable in O(n) work:
+// exactly the chain positions < n.  mark_chain first runs the speculative cursor (further down: one walk per tile from
+// the tile's first position, a path over the tiles, a head fix per reached tile), which is exact on any codes but only
+// delivers where the walks meet; where one does not, the exact stages run on the same codes.  They rest on next(p) > p,
+// which makes the chain resolvable in O(n) work:
 //
 //   1. chain_exit_kernel   per 4096-position tile: in-LDS pointer jumping gives exit0[p] = first
 //                          chain position at or beyond the tile end; every distinct exit target
@@ -290,6 +293,215 @@ __global__ __launch_bounds__(64) void chain_mark_kernel(const CodeT *__restrict_
     }
     __syncthreads();
     chain_bits[word0 + lane] = bits[lane];
+}
+
+// ---- the speculative cursor ("cursor") ----------------------------------------------------------------------
+// next() is monotone on real codes (L*[i + 1] >= L*[i] - 1), so the chains from two positions of a tile merge within a
+// few hops.  Every tile is therefore walked ONCE, from its first position, before its true entry is known; the exits of
+// those walks give a path over the tiles, and a reached tile whose true entry is another position only walks from that
+// entry until it lands on a marked position.  The result is exact whatever the codes are: a tile whose walk from the
+// entry neither meets the speculative walk nor leaves at the same exit raises a flag, and mark_chain then runs the
+// exact stages above on the same codes.
+constexpr uint32_t kVisited = 0x8000u;  // on a jump table entry (<= kTile = 0x1000): the walk came past
+
+// the tile's jump table: jmp[lp] = position behind lp within the tile, kTile: leaves it (or lp is no position).  Local
+// positions [from, from + count), from and count multiples of 128; table index = lp - from.
+// kBatch loads per lane are in flight together.
+template <typename CodeT, int kBatch>
+__device__ __forceinline__ void load_jumps(const CodeT *__restrict__ lstar, uint32_t n, uint32_t base, uint32_t tile_end,
+                                           uint32_t from, uint32_t count, uint16_t *jmp, int lane) {
+    auto local_next = [&](uint32_t p, uint32_t code) -> uint32_t {
+        if (p >= n) return (uint32_t)kTile;
+        const uint32_t nx = next_pos(p, code, n);
+        return nx < tile_end ? nx - base : (uint32_t)kTile;
+    };
+    if constexpr (sizeof(CodeT) == 2) {  // two codes per load and lane (the array is padded to an even count)
+        const uint32_t *__restrict__ pairs = reinterpret_cast<const uint32_t *>(lstar);
+        const uint32_t last_pair = (n - 1u) >> 1;
+        for (uint32_t j0 = 0; j0 < count / 128u; j0 += kBatch) {
+            uint32_t ls[kBatch];
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t pr = ((base + from) >> 1) + (j0 + j) * 64u + lane;
+                ls[j] = pairs[pr < last_pair ? pr : last_pair];
+            }
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t i = 2u * ((j0 + j) * 64u + lane);
+                if (i < count) {
+                    const uint32_t p = base + from + i;
+                    *reinterpret_cast<uint32_t *>(&jmp[i]) = local_next(p, ls[j] & 0xffffu) | (local_next(p + 1u, ls[j] >> 16) << 16);
+                }
+            }
+        }
+    } else {
+        for (uint32_t j0 = 0; j0 < count / 64u; j0 += kBatch) {
+            uint32_t ls[kBatch];
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t p = base + from + (j0 + j) * 64u + lane;
+                ls[j] = lstar[p < n ? p : n - 1u];
+            }
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const uint32_t i = (j0 + j) * 64u + lane;
+                if (i < count) jmp[i] = (uint16_t)local_next(base + from + i, ls[j]);
+            }
+        }
+    }
+}
+
+// Step 1, one wavefront per tile: the walk from the tile's first position (in the tile of start_pos: from start_pos;
+// the tiles in front of it hold no chain position and only report a terminal exit).  Writes the 64 bitmap words of the
+// walk and spec_exit[t] = the first position of the walk at or behind the tile end (n: the walk ends the text).
+// The walking lane only flags the table entries it passes -- a store nothing waits for -- and the 64 lanes collect the
+// flags into words afterwards: a read-modify-write of a bitmap word per hop made every hop two dependent LDS accesses.
+template <typename CodeT>
+__global__ __launch_bounds__(64) void chain_spec_walk_kernel(const CodeT *__restrict__ lstar, uint32_t n, uint32_t start_pos,
+                                                             unsigned long long *__restrict__ chain_bits,
+                                                             uint32_t *__restrict__ spec_exit) {
+    __shared__ __align__(16) uint16_t jmp[kTile];
+    const uint32_t base = blockIdx.x * (uint32_t)kTile;
+    const uint32_t tile_end = (n - base < (uint32_t)kTile) ? n : base + kTile;
+    const int lane = threadIdx.x;
+    if (tile_end <= start_pos) {
+        if (lane == 0) spec_exit[blockIdx.x] = n;
+        return;
+    }
+    load_jumps<CodeT, 16>(lstar, n, base, tile_end, 0u, (uint32_t)kTile, jmp, lane);
+    __syncthreads();  // (one wavefront: a fence)
+    if (lane == 0) {
+        uint32_t p = start_pos > base ? start_pos - base : 0u, last;
+        do {
+            last = p;
+            const uint32_t nx = jmp[p];
+            jmp[p] = (uint16_t)(nx | kVisited);
+            p = nx;
+        } while (p < (uint32_t)kTile);
+        spec_exit[blockIdx.x] = next_pos(base + last, lstar[base + last], n);
+    }
+    __syncthreads();
+    // lane l gathers the flags of positions 64 l .. 64 l + 63, eight positions per 16-byte read; the lanes start at
+    // different eighths, which spreads one instruction's reads over the banks
+    const uint4 *rows = reinterpret_cast<const uint4 *>(jmp);
+    unsigned long long word = 0ull;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int c = (k + lane) & 7;
+        const uint4 v = rows[lane * 8 + c];
+        auto two = [](uint32_t d) -> uint32_t { return ((d >> 15) & 1u) | ((d >> 30) & 2u); };
+        const uint32_t b = two(v.x) | (two(v.y) << 2) | (two(v.z) << 4) | (two(v.w) << 6);
+        word |= (unsigned long long)b << (8 * c);
+    }
+    chain_bits[(size_t)blockIdx.x * (kTile / 64) + lane] = word;
+}
+
+// Step 2 runs wyllie_kernel over the tiles: nxt[t] = tile of spec_exit[t] (num_tiles: none), reached from the tile of
+// start_pos.
+__global__ __launch_bounds__(kThreads) void spec_edges_kernel(const uint32_t *__restrict__ spec_exit, uint32_t n,
+                                                              uint32_t num_tiles, uint32_t start_tile,
+                                                              uint32_t *__restrict__ nxt, uint32_t *__restrict__ reach,
+                                                              uint32_t *__restrict__ entry) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t <= num_tiles; t += stride) {
+        const uint32_t e = t < num_tiles ? spec_exit[t] : n;
+        nxt[t] = e >= n ? num_tiles : e / (uint32_t)kTile;
+        reach[t] = t == start_tile ? 1u : 0u;
+        if (t < num_tiles) entry[t] = kNone;
+    }
+}
+
+// entry[t'] = spec_exit[t] for the reached tiles t: a path gives every tile one reached predecessor at the most
+__global__ __launch_bounds__(kThreads) void spec_entries_kernel(const uint32_t *__restrict__ spec_exit,
+                                                                const uint32_t *__restrict__ reach, uint32_t n,
+                                                                uint32_t num_tiles, uint32_t start_pos,
+                                                                uint32_t *__restrict__ entry) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < num_tiles; t += stride) {
+        if (!reach[t]) continue;
+        if (t == start_pos / (uint32_t)kTile) entry[t] = start_pos;
+        const uint32_t e = spec_exit[t];
+        if (e < n) entry[e / (uint32_t)kTile] = e;
+    }
+}
+
+// Step 3, one wavefront per tile.  Not reached: the words are cleared.  Entered where step 1 began its walk: the words
+// stand.  Entered elsewhere: one lane walks from the entry (codes loaded kFixChunk positions at a time, from the entry
+// on) until it lands on a position m that step 1 marked: from m on the two walks are one, so the words are the new
+// marks plus the marks of step 1 at and behind m.  A walk that leaves the tile without landing on a mark is accepted if
+// it leaves at spec_exit[t] -- no mark of step 1 survives then -- and counted in *failed otherwise.
+constexpr uint32_t kFixChunk = 1024;
+template <typename CodeT>
+__global__ __launch_bounds__(64) void chain_spec_fix_kernel(const CodeT *__restrict__ lstar, uint32_t n, uint32_t start_pos,
+                                                            const uint32_t *__restrict__ entry,
+                                                            const uint32_t *__restrict__ spec_exit,
+                                                            unsigned long long *__restrict__ chain_bits,
+                                                            uint32_t *__restrict__ tile_count, uint32_t *__restrict__ failed,
+                                                            uint32_t fail_tile) {
+    __shared__ __align__(16) uint16_t jmp[kFixChunk];
+    __shared__ unsigned long long spec[kTile / 64], mine[kTile / 64];
+    __shared__ uint32_t state[3];  // where the walk stands, what ended it, the last position it marked
+    enum : uint32_t { kGoOn = 0, kMerged = 1, kLeft = 2 };
+    const uint32_t base = blockIdx.x * (uint32_t)kTile;
+    const uint32_t tile_end = (n - base < (uint32_t)kTile) ? n : base + kTile;
+    const int lane = threadIdx.x;
+    const size_t word0 = (size_t)blockIdx.x * (kTile / 64);
+    const uint32_t e = entry[blockIdx.x];
+    if (lane == 0 && blockIdx.x == fail_tile) atomicAdd(failed, 1u);  // (tests: fail_tile is kNone otherwise)
+    if (e == kNone) {
+        chain_bits[word0 + lane] = 0ull;
+        if (lane == 0) tile_count[blockIdx.x] = 0;
+        return;
+    }
+    unsigned long long word = chain_bits[word0 + lane];
+    const uint32_t walked_from = start_pos > base ? start_pos : base;
+    if (e != walked_from) {
+        spec[lane] = word;
+        mine[lane] = 0ull;
+        __syncthreads();  // (one wavefront: a fence)
+        uint32_t p = e - base, status = kGoOn, last = p;
+        while (status == kGoOn) {
+            const uint32_t from = p & ~127u;
+            const uint32_t count = (uint32_t)kTile - from < kFixChunk ? (uint32_t)kTile - from : kFixChunk;
+            if (!((spec[p >> 6] >> (p & 63)) & 1ull)) load_jumps<CodeT, (int)(kFixChunk / 128u * sizeof(CodeT) / 2u)>(lstar, n, base, tile_end, from, count, jmp, lane);
+            __syncthreads();
+            if (lane == 0) {
+                for (;;) {
+                    if (p >= (uint32_t)kTile) {
+                        status = kLeft;
+                        break;
+                    }
+                    if ((spec[p >> 6] >> (p & 63)) & 1ull) {
+                        status = kMerged;
+                        break;
+                    }
+                    if (p >= from + count) break;  // the next chunk
+                    mine[p >> 6] |= 1ull << (p & 63);
+                    last = p;
+                    p = jmp[p - from];
+                }
+                state[0] = p;
+                state[1] = status;
+                state[2] = last;
+            }
+            __syncthreads();
+            p = state[0];
+            status = state[1];
+            last = state[2];
+        }
+        unsigned long long keep = 0ull;
+        if (status == kMerged) {
+            const uint32_t mw = p >> 6;
+            keep = (uint32_t)lane > mw ? ~0ull : ((uint32_t)lane == mw ? ~0ull << (p & 63) : 0ull);
+        } else if (lane == 0 && next_pos(base + last, lstar[base + last], n) != spec_exit[blockIdx.x]) {
+            atomicAdd(failed, 1u);
+        }
+        word = mine[lane] | (word & keep);
+        chain_bits[word0 + lane] = word;
+    }
+    const uint32_t c = (uint32_t)__popcll(word);
+    const uint32_t total = wave_scan_inclusive(c, OpAdd<uint32_t>());
+    if (lane == 63) tile_count[blockIdx.x] = total;
 }
 
 // one wavefront per tile: lane l owns bitmap word l of the tile
@@ -598,23 +810,20 @@ void launch_factor_kernel(Context &ctx, const uint32_t *starts, uint32_t z, uint
 
 }  // namespace
 
-Chain mark_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes) {
+namespace {
+
+// The exact cursor (stages 1 to 5 of the header): right on any codes without a condition; the speculative cursor falls
+// back on it.  Fills cbits and tile_count (scanned); returns z.  Its temporaries are released before it returns.
+uint32_t mark_chain_exact(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes, unsigned long long *cbits,
+                          uint32_t *tile_count) {
     hipStream_t s = ctx.stream;
     Arena &arena = ctx.arena;
-    Chain chain;
-    chain.n = n;
-    chain.codes = codes;
-    if (start_pos >= n) return chain;
     const bool narrow = codes.width == 16;
     const uint32_t *lstar = codes.wide;       // !narrow
     const uint16_t *lstar16 = codes.narrow;  // narrow
-
     const uint32_t num_tiles = (uint32_t)div_up(n, kTile);
     const uint32_t tbits_words = (uint32_t)div_up((size_t)n + 1, 32);
 
-    // the mark first: everything behind `tmp` is released before the caller takes an output
-    unsigned long long *cbits = arena.alloc<unsigned long long>((size_t)num_tiles * (kTile / 64));
-    uint32_t *tile_count = arena.alloc<uint32_t>(num_tiles);
     const size_t tmp = arena.mark();
     uint32_t *exit0 = narrow ? nullptr : arena.alloc<uint32_t>(n);
     uint16_t *exit16 = narrow ? arena.alloc<uint16_t>((size_t)n + 2) : nullptr;
@@ -678,8 +887,103 @@ Chain mark_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes 
         KERNEL_CHECK();
         scan_exclusive_add_u32(tile_count, tile_count, num_tiles, d_total + 1, arena, s);
     }
-    ctx.read_back(d_total + 1, &chain.z, 1);  // (waits for the stream: the temporaries are no longer read)
+    uint32_t z = 0;
+    ctx.read_back(d_total + 1, &z, 1);  // (waits for the stream: the temporaries are no longer read)
     arena.rewind(tmp);
+    return z;
+}
+
+// The speculative cursor (the kernels above): cbits and tile_count (scanned) are right and *z is set if it returns 0;
+// otherwise it returns the number of tiles whose walk from the entry did not meet the walk from the tile start, and
+// nothing it wrote counts.  One read-back, of z and that number.  force_fail (NOLZSS_TEST_SPEC_CURSOR_FAILS): the tile of
+// start_pos raises the flag on top of what it finds.
+uint32_t mark_chain_spec(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes, unsigned long long *cbits,
+                         uint32_t *tile_count, bool force_fail, uint32_t *z) {
+    hipStream_t s = ctx.stream;
+    Arena &arena = ctx.arena;
+    const bool narrow = codes.width == 16;
+    const uint32_t num_tiles = (uint32_t)div_up(n, kTile);
+    const uint32_t start_tile = start_pos / (uint32_t)kTile;
+
+    const size_t tmp = arena.mark();
+    uint32_t *spec_exit = arena.alloc<uint32_t>(num_tiles);
+    uint32_t *nxt[2] = {arena.alloc<uint32_t>(num_tiles + 1), arena.alloc<uint32_t>(num_tiles + 1)};
+    uint32_t *reach = arena.alloc<uint32_t>(num_tiles + 1);
+    uint32_t *entry = arena.alloc<uint32_t>(num_tiles);
+    uint32_t *d_result = arena.alloc<uint32_t>(2);  // z, failed tiles
+    const uint32_t fail_tile = force_fail ? start_tile : kNone;
+    HIP_CHECK(hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), s));
+    {
+        ProfScope ps(ctx.profiler(), "chain_spec_walk", s, (narrow ? 2.0 : 4.0) * (double)n);
+        if (narrow)
+            chain_spec_walk_kernel<uint16_t><<<num_tiles, 64, 0, s>>>(codes.narrow, n, start_pos, cbits, spec_exit);
+        else
+            chain_spec_walk_kernel<uint32_t><<<num_tiles, 64, 0, s>>>(codes.wide, n, start_pos, cbits, spec_exit);
+        KERNEL_CHECK();
+    }
+    {
+        ProfScope ps(ctx.profiler(), "chain_spec_path", s);
+        spec_edges_kernel<<<grid_for((size_t)num_tiles + 1), kThreads, 0, s>>>(spec_exit, n, num_tiles, start_tile, nxt[0], reach,
+                                                                             entry);
+        KERNEL_CHECK();
+        int rounds = 1;
+        while ((1ull << rounds) < (uint64_t)num_tiles + 1) ++rounds;
+        int cur = 0;
+        for (int r = 0; r < rounds; ++r) {
+            wyllie_kernel<<<grid_for(num_tiles), kThreads, 0, s>>>(nxt[cur], nxt[cur ^ 1], num_tiles, reach);
+            KERNEL_CHECK();
+            cur ^= 1;
+        }
+        spec_entries_kernel<<<grid_for(num_tiles), kThreads, 0, s>>>(spec_exit, reach, n, num_tiles, start_pos, entry);
+        KERNEL_CHECK();
+    }
+    {
+        ProfScope ps(ctx.profiler(), "chain_spec_fix", s);
+        if (narrow)
+            chain_spec_fix_kernel<uint16_t><<<num_tiles, 64, 0, s>>>(codes.narrow, n, start_pos, entry, spec_exit, cbits, tile_count,
+                                                                    d_result + 1, fail_tile);
+        else
+            chain_spec_fix_kernel<uint32_t><<<num_tiles, 64, 0, s>>>(codes.wide, n, start_pos, entry, spec_exit, cbits, tile_count,
+                                                                    d_result + 1, fail_tile);
+        KERNEL_CHECK();
+        scan_exclusive_add_u32(tile_count, tile_count, num_tiles, d_result, arena, s);
+    }
+    uint32_t result[2] = {0, 0};
+    ctx.read_back(d_result, result, 2);  // (waits for the stream: the temporaries are no longer read)
+    arena.rewind(tmp);
+    *z = result[0];
+    return result[1];
+}
+
+}  // namespace
+
+// NOLZSS_NO_SPEC_CURSOR: the exact stages only (A/B runs).  NOLZSS_TEST_SPEC_CURSOR_FAILS: the speculative cursor reports
+// a failed tile, so that the fall-back runs on any input (tests).
+Chain mark_chain(Context &ctx, uint32_t n, uint32_t start_pos, const LstarCodes &codes) {
+    Arena &arena = ctx.arena;
+    Chain chain;
+    chain.n = n;
+    chain.codes = codes;
+    ctx.cursor_path = kCursorNone;
+    ctx.cursor_failed_tiles = 0;
+    if (start_pos >= n) return chain;
+    static const bool no_spec = getenv("NOLZSS_NO_SPEC_CURSOR") != nullptr;
+    static const bool force_fail = getenv("NOLZSS_TEST_SPEC_CURSOR_FAILS") != nullptr;
+    static const bool trace = getenv("NOLZSS_TRACE") != nullptr;
+
+    const uint32_t num_tiles = (uint32_t)div_up(n, kTile);
+    // the mark first: everything behind it is released before the caller takes an output
+    unsigned long long *cbits = arena.alloc<unsigned long long>((size_t)num_tiles * (kTile / 64));
+    uint32_t *tile_count = arena.alloc<uint32_t>(num_tiles);
+    uint32_t failed = 0;
+    if (!no_spec) failed = mark_chain_spec(ctx, n, start_pos, codes, cbits, tile_count, force_fail, &chain.z);
+    if (no_spec || failed) chain.z = mark_chain_exact(ctx, n, start_pos, codes, cbits, tile_count);
+    ctx.cursor_path = no_spec ? kCursorExact : (failed ? kCursorFailedOver : kCursorSpeculative);
+    ctx.cursor_failed_tiles = failed;
+    if (trace)
+        fprintf(stderr, "[nolzss] cursor: %s, %u of %u tiles failed\n",
+                no_spec ? "exact stages" : (failed ? "speculative walk, then the exact stages" : "speculative walk"), failed,
+                num_tiles);
     chain.bits = cbits;
     chain.tile_off = tile_count;
     chain.num_tiles = num_tiles;

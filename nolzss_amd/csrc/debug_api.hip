@@ -502,6 +502,15 @@ int nolzss_debug_chain(const uint32_t *codes, size_t n, size_t start_pos, int wi
     });
 }
 
+int nolzss_debug_cursor(int device, uint32_t *info) {
+    return guarded([&] {
+        if (!info) throw std::invalid_argument("output pointer is null");
+        Session ses(device, nullptr);
+        info[0] = ses.ctx().cursor_path;
+        info[1] = ses.ctx().cursor_failed_tiles;
+    });
+}
+
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak) {
     return guarded([&] {
         if (!capacity || !peak) throw std::invalid_argument("output pointer is null");

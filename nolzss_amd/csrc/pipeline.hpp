@@ -24,6 +24,9 @@ struct Context {
     // length of the last text on which the 16-bit codes had to be given up (build_lstar): calls on a text of that
     // length start with 32-bit codes instead of paying the second run of the stage again
     uint32_t code16_off_n = 0;
+    // what the last mark_chain on this context did (chain.hip; nolzss_debug_cursor): one of kCursor*, and the tiles
+    // whose walk from the entry did not meet the speculative walk
+    uint32_t cursor_path = 0, cursor_failed_tiles = 0;
 
     Profiler *profiler() { return prof.enabled() ? &prof : nullptr; }
     // copy `count` (<= 64) device words to host and wait for them
@@ -97,6 +100,12 @@ void inject_pending_for_test(Context &ctx, uint32_t *lcp, uint32_t n);
 // marked chain: one bit per position and the scanned factor counts of the 4096-position tiles.  It reads the codes and
 // nothing else; width 16: the cursor kernels read two bytes per position.  Its own temporaries are released before it
 // returns.  A count is mark_chain followed by the caller's rewind.
+enum : uint32_t {
+    kCursorNone = 0,         // nothing ran (start_pos >= n)
+    kCursorSpeculative = 1,  // the speculative walk delivered the mark
+    kCursorFailedOver = 2,   // ... raised its flag, and the exact stages ran behind it
+    kCursorExact = 3,        // the exact stages alone (NOLZSS_NO_SPEC_CURSOR)
+};
 struct Chain {
     uint32_t n = 0, z = 0;  // positions, factors
     LstarCodes codes;
