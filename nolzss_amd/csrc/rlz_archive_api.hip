@@ -1,8 +1,9 @@
 // rlz_archive_api.hip -- the relative-LZ archive handle and its entry points: host records in, a resident form kept in
 // device allocations of the handle's own, batches of ranges out (part of the C ABI layer of libnolzss_hip.so,
 // include/nolzss_hip.h, nolzss_rlz_archive_*; the kernels: rlz_archive.hip; DESIGN.md 5, "Relative-LZ archive: ranges
-// from resident records").  Export hands the host form back; open_index and append_index live in rlz_index_api.hip,
-// next to the match they run ("Relative-LZ archive: batches appended from the index").
+// from resident records").  Export hands the host form back.  Also nolzss_rlz_archive_open_index / _append_index: the
+// archive opened over an index and the batches appended to it on the device, which run the index's match
+// (search_batch, rlz_index_api.hip; DESIGN.md 5, "Relative-LZ archive: batches appended from the index").
 #include "rlz_handles.hpp"
 
 using namespace nolzss;
@@ -244,12 +245,9 @@ void export_archive(const nolzss_rlz_archive &h, uint8_t **block, size_t *block_
                 const uint64_t found = archive_literal_index(ctx, h.d_recs, zz, d_index);
                 if (found != h.n_literals)
                     throw HipError("rlz archive: the resident records do not hold the literals the handle counts");
-                for (size_t c0 = 0; c0 < zz; c0 += chunk) {
-                    const size_t cnt = zz - c0 < chunk ? zz - c0 : chunk;
+                download_produced(ctx, "factors_d2h", h_recs.get(), d_out, zz, sizeof(Rec), chunk, [&](size_t c0, size_t cnt) {
                     archive_export_records(ctx, h.d_recs, c0, cnt, h.block_len, d_index, d_out, d_lit);
-                    ProfScope ps(ctx.profiler(), "factors_d2h", s, (double)(sizeof(Rec) * cnt));
-                    download_bytes(ctx, h_recs.get() + c0, d_out, sizeof(Rec) * cnt);  // (waits: d_out is free again)
-                }
+                });
                 if (nlit) download_bytes(ctx, h_lit.get(), d_lit, nlit);
             }
         }
@@ -262,6 +260,177 @@ void export_archive(const nolzss_rlz_archive &h, uint8_t **block, size_t *block_
     *z = zz;
     *literals = h_lit.release();
     *n_literals = nlit;
+}
+
+// ---- the archive over an index: open, and batches appended on the device -------------------------------------------
+void archive_open_index(const nolzss_rlz_index &ix, nolzss_rlz_archive **out) {
+    if (!out) throw std::invalid_argument("output pointer is null");
+    *out = nullptr;
+    std::unique_ptr<nolzss_rlz_archive> h(new nolzss_rlz_archive);
+    h->device = ix.device;
+    h->block_len = ix.view.B;
+    h->index_serial = ix.serial;
+    h->bases.assign(1, 0);
+    DeviceRestore restore;
+    Session ses(ix.device, nullptr);
+    Context &ctx = ses.ctx();
+    {
+        ProfScope whole(ctx.profiler(), "rlz_archive_open_index", ctx.stream);
+        const size_t block_bytes = ix.view.B ? ix.view.B : 1;
+        h->d_block = static_cast<uint8_t *>(device_alloc(ctx, block_bytes));
+        h->device_bytes = block_bytes;
+        archive_unpack_block(ctx, ix.view.text, ix.view.B, h->d_block);
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));
+    ctx.prof.collect();
+    *out = h.release();
+}
+
+// a device array that replaces one of the handle's: freed on the way out unless it was swapped in (then the old one is)
+struct Fresh {
+    void *p = nullptr;
+    ~Fresh() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+void fill_append_info(const nolzss_rlz_archive &a, nolzss_rlz_archive_append_info *info, uint64_t targets, uint64_t records,
+                      uint64_t literals, uint64_t bases, bool reallocated) {
+    if (!info) return;
+    std::memset(info, 0, sizeof *info);
+    info->targets_added = targets;
+    info->records_added = records;
+    info->literals_added = literals;
+    info->bases_added = bases;
+    info->num_targets = a.lengths.size();
+    info->z = a.z;
+    info->total_length = a.decoded;
+    info->capacity_records = a.cap_recs;
+    info->device_bytes = a.device_bytes;
+    info->reallocated = reallocated ? 1 : 0;
+}
+
+void archive_append(nolzss_rlz_archive &a, const nolzss_rlz_index &ix, const char *const *targets, const size_t *target_lens,
+                    size_t k, nolzss_rlz_archive_append_info *info) {
+    if (!a.index_serial)
+        throw std::invalid_argument("rlz archive: append takes an archive opened by nolzss_rlz_archive_open_index");
+    if (a.index_serial != ix.serial || a.device != ix.device)
+        throw std::invalid_argument("rlz archive: the archive is bound to another index (it was opened over index " +
+                                    std::to_string(a.index_serial) + " on device " + std::to_string(a.device) +
+                                    ", this is index " + std::to_string(ix.serial) + " on device " + std::to_string(ix.device) + ")");
+    if (k && targets && target_lens) {  // the lengths alone decide: no target byte is read before this
+        uint64_t sum = 0;
+        bool overflow = false;
+        for (size_t j = 0; j < k; ++j) {
+            overflow |= sum + target_lens[j] < sum;
+            sum += target_lens[j];
+        }
+        if (!overflow && sum <= kMaxText && a.decoded + sum > kMaxText)
+            throw std::invalid_argument("rlz archive: decoded length: the archive holds " + std::to_string(a.decoded) +
+                                        " bytes and the batch " + std::to_string(sum) + ", together beyond the " +
+                                        std::to_string(kMaxText) + " positions the 32-bit device pipeline takes");
+    }
+    Batch b;
+    prepare_batch(ix, targets, target_lens, k, b);
+    if (k == 0) {
+        fill_append_info(a, info, 0, 0, 0, 0, false);
+        return;
+    }
+    const size_t n = b.tcat.size();
+    const uint64_t bases = n - k, base = (uint64_t)ix.view.B + 1;
+    a.lengths.reserve(a.lengths.size() + k);  // (the commit below cannot fail)
+    a.bases.reserve(a.bases.size() + k);
+    const size_t chunk_max = chunk_knob("NOLZSS_RLZ_APPEND_CHUNK");
+
+    DeviceRestore restore;
+    Fresh fresh_recs, fresh_sample;  // (freed while the handle's device is still current)
+    ArchiveRec *recs = a.d_recs;
+    uint32_t *sample = a.d_sample;
+    size_t cap_recs = a.cap_recs, cap_samples = a.cap_samples;
+    uint64_t z_new = 0, added = 0, lit_added = 0;
+    const uint64_t decoded_new = a.decoded + bases;
+    const size_t samples_old = archive_samples((size_t)a.decoded), samples_new = archive_samples((size_t)decoded_new);
+
+    Session ses(ix.device, nullptr);
+    Context &ctx = ses.ctx();
+    hipStream_t s = ctx.stream;
+    std::vector<uint32_t> lit_counts;
+    try {
+        ProfScope whole(ctx.profiler(), "rlz_archive_append", s);
+        reserve_arena_for(ctx, 0, (kBatchBytesPerPosition + 2) * n + 16 * k + sizeof(IndexRec) * (chunk_max < n ? chunk_max : n) +
+                                      (size_t(4) << 20));
+        const Searched m = search_batch(ctx, ix, b);
+        const uint8_t *d_T = m.d_T;
+        uint32_t *d_len = m.d_len, *d_rank = m.d_rank;
+        const Chain chain = mark_chain(ctx, (uint32_t)n, 0u, LstarCodes::of(d_len));
+        const uint32_t zb = chain.z;
+        const uint32_t *d_fpos = chain_starts(ctx, chain);
+        if (zb < k) throw HipError("rlz archive: the chain of a batch holds fewer factor starts than separators");
+        added = zb - k;  // every separator is a factor start of its own
+        z_new = a.z + added;
+        if (z_new > 0xffffffffull)
+            throw std::invalid_argument("rlz archive: z: the archive holds " + std::to_string(a.z) + " records and the batch " +
+                                        std::to_string(added) + ", the position sample indexes records in 32 bits, 2^32 or "
+                                        "more are refused");
+        // growth: max(needed, 2 x current), the old contents copied on the stream; the old array is freed at the commit
+        if (z_new > cap_recs) {
+            cap_recs = std::max<size_t>((size_t)z_new, 2 * cap_recs);
+            fresh_recs.p = device_alloc(ctx, sizeof(ArchiveRec) * cap_recs);
+            recs = static_cast<ArchiveRec *>(fresh_recs.p);
+            if (a.z) HIP_CHECK(hipMemcpyAsync(recs, a.d_recs, sizeof(ArchiveRec) * a.z, hipMemcpyDeviceToDevice, s));
+        }
+        if (samples_new > cap_samples) {
+            cap_samples = std::max<size_t>(samples_new, 2 * cap_samples);
+            fresh_sample.p = device_alloc(ctx, sizeof(uint32_t) * cap_samples);
+            sample = static_cast<uint32_t *>(fresh_sample.p);
+            if (samples_old)
+                HIP_CHECK(hipMemcpyAsync(sample, a.d_sample, sizeof(uint32_t) * samples_old, hipMemcpyDeviceToDevice, s));
+        }
+        uint32_t *d_seps = ctx.arena.alloc<uint32_t>(k);
+        upload_bytes(ctx, d_seps, b.separators.data(), sizeof(uint32_t) * k);
+        const AppendBatch ab{d_T, d_seps, (uint32_t)n, (uint32_t)k, (uint32_t)a.z, (uint32_t)a.decoded, (uint32_t)z_new};
+        const size_t chunk = zb < chunk_max ? zb : chunk_max;
+        IndexRec *d_chunk = ctx.arena.alloc<IndexRec>(chunk ? chunk : 1);
+        // one word per wavefront of the conversion launches: the literals it wrote (at most n / 64 + 4 per chunk words)
+        lit_counts.resize(chunk ? (zb / chunk) * archive_append_counts(chunk) + archive_append_counts(zb % chunk) : 0);
+        uint32_t *d_counts = ctx.arena.alloc<uint32_t>(lit_counts.size() ? lit_counts.size() : 1);
+        size_t counts_at = 0;
+        for (size_t c0 = 0; c0 < zb; c0 += chunk) {  // (one stream: a chunk's conversion has read d_chunk before the next look-up)
+            const size_t cnt = zb - c0 < chunk ? zb - c0 : chunk;
+            rlz_index_records(ctx, ix.view, d_fpos + c0, (uint32_t)cnt, d_len, d_rank, d_chunk);
+            archive_append_records(ctx, d_chunk, d_fpos + c0, (uint32_t)c0, (uint32_t)cnt, base, ab, recs, d_counts + counts_at);
+            counts_at += archive_append_counts(cnt);
+        }
+        archive_extend_sample(ctx, recs, (uint32_t)a.z, (uint32_t)z_new, (uint32_t)samples_old, (uint32_t)samples_new, sample);
+        if (counts_at != lit_counts.size()) throw HipError("rlz archive: the literal counts of an append are laid out wrongly");
+        if (counts_at)
+            HIP_CHECK(hipMemcpyAsync(lit_counts.data(), d_counts, sizeof(uint32_t) * counts_at, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        for (uint32_t c : lit_counts) lit_added += c;
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // nothing still reads the batch or writes the fresh arrays when they go
+        throw;
+    }
+    // (the whole scope recorded its stop event as the block above closed, behind that wait: collect() drops a scope whose
+    // events have not completed)
+    HIP_CHECK(hipStreamSynchronize(s));
+    ctx.prof.collect();
+    // the commit: host state only, after the device work has finished without error; the stream has drained
+    const bool moved = fresh_recs.p || fresh_sample.p;
+    if (fresh_recs.p) std::swap(fresh_recs.p, reinterpret_cast<void *&>(a.d_recs));
+    if (fresh_sample.p) std::swap(fresh_sample.p, reinterpret_cast<void *&>(a.d_sample));
+    a.cap_recs = cap_recs;
+    a.cap_samples = cap_samples;
+    a.z = z_new;
+    a.n_literals += lit_added;
+    for (size_t j = 0; j < k; ++j) {
+        a.lengths.push_back(target_lens[j]);
+        a.decoded += target_lens[j];
+        a.bases.push_back(a.decoded);
+    }
+    a.device_bytes = (a.block_len ? a.block_len : 1) + sizeof(ArchiveRec) * cap_recs + sizeof(uint32_t) * cap_samples;
+    fill_append_info(a, info, k, added, lit_added, bases, moved);
 }
 
 }  // namespace
@@ -322,6 +491,23 @@ int nolzss_rlz_archive_export(const nolzss_rlz_archive *h, uint8_t **block, size
         *block_len = *z = *n_literals = 0;
         if (!h) throw std::invalid_argument("handle is null");
         export_archive(*h, block, block_len, records, z, literals, n_literals);
+    });
+}
+
+int nolzss_rlz_archive_open_index(const nolzss_rlz_index *ix, nolzss_rlz_archive **h) {
+    return guarded([&] {
+        if (h) *h = nullptr;
+        if (!ix) throw std::invalid_argument("index handle is null");
+        archive_open_index(*ix, h);
+    });
+}
+
+int nolzss_rlz_archive_append_index(nolzss_rlz_archive *h, const nolzss_rlz_index *ix, const char *const *targets,
+                                    const size_t *target_lens, size_t k, nolzss_rlz_archive_append_info *info) {
+    return guarded([&] {
+        if (info) std::memset(info, 0, sizeof *info);
+        if (!h || !ix) throw std::invalid_argument("archive or index handle is null");
+        archive_append(*h, *ix, targets, target_lens, k, info);
     });
 }
 

@@ -272,12 +272,9 @@ void query_finder(Context &ctx, const nolzss_rlz_finder &h, const Batch &b, size
         hits.reset(static_cast<nolzss_rlz_target_hit *>(alloc_factor_block(sizeof(nolzss_rlz_target_hit) * Tout)));
         if (!hits) throw std::bad_alloc();
         TargetHit *d_recs = ctx.arena.alloc<TargetHit>(chunk);
-        for (size_t c0 = 0; c0 < Tout; c0 += chunk) {
-            const size_t c = Tout - c0 < chunk ? Tout - c0 : chunk;
+        download_produced(ctx, "hits_d2h", hits.get(), d_recs, Tout, sizeof(TargetHit), chunk, [&](size_t c0, size_t c) {
             find_hit_records(ctx, f, keys[at] + c0, vals[at] + c0, (uint32_t)c, d_recs);
-            ProfScope ps(ctx.profiler(), "hits_d2h", s, (double)(sizeof(TargetHit) * c));
-            download_bytes(ctx, hits.get() + c0, d_recs, sizeof(TargetHit) * c);  // (waits: d_recs is free again)
-        }
+        });
         num_hits = Tout;
         return;
     }

@@ -1,8 +1,11 @@
-// rlz_handles.hpp -- the resident relative-LZ handles, shared by the translation units of their entry points: an
-// append matches a batch against the index (rlz_index_api.hip) and writes into the archive (rlz_archive_api.hip owns
-// open_records, extract and export); a finder reads both (rlz_find_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches
-// appended from the index" and "Relative-LZ archive: locate through the parse".
+// rlz_handles.hpp -- the resident relative-LZ handles and what the translation units of their entry points share: the
+// index and its match (rlz_index_api.hip), its pattern queries (rlz_index_query_api.hip) and its seed queries
+// (rlz_index_seeds_api.hip); the archive (rlz_archive_api.hip), whose appends run that match; a finder reads both
+// (rlz_find_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index" and "Relative-LZ archive:
+// locate through the parse".
 #pragma once
+#include <functional>
+
 #include "api_internal.hpp"
 #include "rlz_archive.hpp"
 #include "rlz_find.hpp"
@@ -99,23 +102,62 @@ struct DeviceRestore {
 
 constexpr size_t kRecordChunk = size_t(1) << 22;  // records per look-up chunk: 96 MiB of arena whatever the batch holds
 
-// A batch of targets or patterns laid out for the device (rlz_index_api.hip)
+// A batch of targets or patterns laid out for the device
 constexpr uint8_t kSeparator = 1;  // between the targets of a batch: any byte but A, C, G, T
 struct Batch {
     HostBytes tcat;                    // T1 s T2 s .. Tk s
     std::vector<uint32_t> separators;  // k positions in tcat
     std::vector<uint64_t> offsets;     // k: the first position of each target in tcat
 };
-// What a pattern query of the index and of the finder share (rlz_index_api.hip): the checks and the layout of a pattern
-// batch, the chunk knobs, and the arena bytes of a batch of n positions and q patterns and of every expanded hit.
-void prepare_patterns(const char *const *patterns, const size_t *pattern_lens, size_t q, Batch &b);
+
+// ---- the handle and its match (rlz_index_api.hip) ------------------------------------------------------------------
 uint32_t choose_prefix(size_t index_length);  // the prefix table's key for an index text of that length
+// device memory per batch position: packed text 1/4, code 4, rank 4, the chain's exits, bitmaps and node lists (12 on
+// ordinary batches, 24 when every position is a node), the factor starts 4 -- not the 52 of a suffix sort
+constexpr size_t kBatchBytesPerPosition = 36;
+#pragma GCC visibility push(hidden)  // (between the translation units of the library: no new dynamic symbol)
+// every check of a match, in the order the header states them, and the batch laid out
+void prepare_batch(const nolzss_rlz_index &h, const char *const *targets, const size_t *target_lens, size_t k, Batch &b);
+// the batch bytes into the arena (text_h2d) and packed with the ends of its targets or patterns as terminators
+uint8_t *upload_and_pack(Context &ctx, const Batch &b, PackedText &packed);
+// What every use of a match starts with: the batch up, packed with the target ends as terminators, and searched.
+struct Searched {
+    uint8_t *d_T;              // the batch bytes (upper case, separators)
+    uint32_t *d_len, *d_rank;  // per position: the longest match and a rank that attains it
+    PackedText batch;          // the packed batch: its terminator table holds the target ends
+};
+Searched search_batch(Context &ctx, const nolzss_rlz_index &h, const Batch &b);
+// max_hits as the kernels take it: 0 and anything beyond 32 bits mean no cap
+inline uint32_t hit_cap(uint64_t max_hits) {
+    return (max_hits == 0 || max_hits >= 0xffffffffull) ? 0xffffffffu : (uint32_t)max_hits;
+}
+// true when `extra` bytes were beyond the arena: it was reserved anew and emptied, and the caller starts over in it
+bool regrow_arena(Context &ctx, size_t extra);
+// `count` records of `size` bytes from device memory into a host array, NOLZSS_RLZ_LOCATE_CHUNK records per copy
+void download_records(Context &ctx, const char *scope, void *h_dst, const void *d_src, size_t count, size_t size);
+// ... `chunk` at a time through d_stage, which produce(first, count) fills before each copy
+void download_produced(Context &ctx, const char *scope, void *h_dst, const void *d_stage, size_t count, size_t size, size_t chunk,
+                       const std::function<void(size_t, size_t)> &produce);
+// `count` zeroed entries (one for count = 0) for a result that free_block releases; throws std::bad_alloc
+template <typename T> T *calloc_array(size_t count) {
+    T *p = static_cast<T *>(std::calloc(count ? count : 1, sizeof(T)));
+    if (!p) throw std::bad_alloc();
+    return p;
+}
+// f(ctx) in a session on `device` under the whole-call scope, then the stream's late errors and the profiler; the
+// caller's device is current again on return
+void with_index_session(int device, const char *scope, const std::function<void(Context &)> &f);
+#pragma GCC visibility pop
+
+// What a pattern query of the index and of the finder share (rlz_index_query_api.hip): the checks and the layout of a
+// pattern batch, the chunk knobs, and the arena bytes of a batch of n positions and q patterns and of every expanded hit.
+void prepare_patterns(const char *const *patterns, const size_t *pattern_lens, size_t q, Batch &b);
 size_t chunk_knob(const char *name);
 size_t pattern_batch_bytes(size_t n, size_t q);
 constexpr size_t kLocateBytesPerHit = 25;
-// What the seed-chain query and its debug hook (debug_rlz.hip) share: the device's view of the parameters, and the chains
-// of a run brought down into the host blocks of a result (anchor_offsets is allocated there; chunked by
-// NOLZSS_RLZ_LOCATE_CHUNK).
+// What the seed-chain query and its debug hook (rlz_index_seeds_api.hip, debug_rlz.hip) share: the device's view of the
+// parameters, and the chains of a run brought down into the host blocks of a result (anchor_offsets is allocated there;
+// chunked by NOLZSS_RLZ_LOCATE_CHUNK).
 ChainRules chain_rules(const nolzss_rlz_chain_params &p, uint64_t records, uint64_t B);
 void deliver_chains(Context &ctx, const ChainsOut &run, nolzss_rlz_seed_chains_result &res);
 

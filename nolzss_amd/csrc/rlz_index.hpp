@@ -2,7 +2,7 @@
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
 // rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds, rlz_seed_chain.hip for
 // their colinear chains and rlz_align.hip for the base-level alignments of those;
-// the handle and its entry points: rlz_index_api.hip).
+// the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip).
 #pragma once
 #include "pipeline.hpp"
 

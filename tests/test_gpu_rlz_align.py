@@ -1,6 +1,7 @@
-"""Base-level alignments of the seed chains on the relative-LZ index, on the device (rlz_align.hip, rlz_index_api.hip).
-RlzIndex.align is compared with tests/rlz_align_model.expected -- driven from the chains RlzIndex.seed_chains returns at
-the same parameters -- by integer equality of every record, offset and op; replay rebuilds every aligned stretch."""
+"""Base-level alignments of the seed chains on the relative-LZ index, on the device (rlz_align.hip,
+rlz_index_seeds_api.hip).  RlzIndex.align is compared with tests/rlz_align_model.expected -- driven from the chains
+RlzIndex.seed_chains returns at the same parameters -- by integer equality of every record, offset and op; replay
+rebuilds every aligned stretch."""
 import random
 
 import numpy as np
@@ -96,6 +97,42 @@ def test_chunks_and_batches_change_nothing(planted, rlz, monkeypatch):
     same(ix.align(subset, batch_bases=700), exp)
     monkeypatch.setattr(rlz, "MAX_CHAIN_TARGETS", 5)  # the cut at 2^24 targets, brought within reach
     same(ix.align(subset), exp)
+
+
+def _profiled(fn):
+    from nolzss_amd import _noLZSS as native
+    native.profile_enable(True)
+    try:
+        native.profile_reset()
+        out = fn()
+        return out, native.profile_report()
+    finally:
+        native.profile_enable(False)
+        native.profile_reset()
+
+
+def _launches(report, *names):
+    return [report[name][0] if name in report else 0 for name in names]
+
+
+def test_the_batch_is_searched_again_when_the_arena_grows_for_the_hits_and_for_the_jobs(planted):
+    """with the arena empty, the first call reserves for the batch, learns the number of hits, reserves again -- the slab
+    is replaced -- and searches the batch a second time; it chains and plans, learns the DP rows and column slots,
+    reserves a third time and searches, chains and plans once more before the one DP; the next call finds room"""
+    from nolzss_amd import _noLZSS as native
+    ix, refs, targets, truth, got, chains = planted  # (the fixture compared got with the model)
+    front, back = ("rlz_index_search", "rlz_seed_flags", "rlz_seed_intervals"), ("rlz_seed_hits", "rlz_chain_recurrence")
+    plan, dp = ("rlz_align_plan", "rlz_align_sizes"), ("rlz_align_dp",)
+    native.debug_trim_arenas()
+    first, report = _profiled(lambda: ix.align(targets))
+    assert report["rlz_index_search"][0] >= 2  # (at least one regrow: else this test is not on the path)
+    assert _launches(report, *front) == [3, 3, 3] and _launches(report, *back) == [2, 2]
+    assert _launches(report, *plan) == [2, 2] and _launches(report, *dp) == [1]
+    again, report = _profiled(lambda: ix.align(targets))
+    assert _launches(report, *front) == [1, 1, 1] and _launches(report, *back) == [1, 1]
+    assert _launches(report, *plan) == [1, 1] and _launches(report, *dp) == [1]
+    same(first, got)
+    same(again, got)
 
 
 def test_max_flank_zero_clips_every_flank(planted):

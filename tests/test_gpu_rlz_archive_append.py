@@ -1,5 +1,5 @@
 """The relative-LZ archive grown from the index on the device (nolzss_rlz_archive_open_index / _append_index / _export;
-rlz_archive.hip, rlz_index_api.hip).  Oracles: plain slicing of the upper-cased targets, the host path
+rlz_archive.hip, rlz_archive_api.hip).  Oracles: plain slicing of the upper-cased targets, the host path
 absolute_records(reference, ix.factorize(targets)) record for record, and the archive ix.archive(targets) opens."""
 import re
 import threading

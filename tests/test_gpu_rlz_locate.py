@@ -1,6 +1,6 @@
-"""Pattern count and locate on the relative-LZ index, on the device (rlz_locate.hip, rlz_index_api.hip).  Every case
-compares count and locate with the brute force of the definition (tests/rlz_locate_model.brute_locate: bytes.find per
-record and strand) by integer equality: counts, offsets, and every hit field in the stated order."""
+"""Pattern count and locate on the relative-LZ index, on the device (rlz_locate.hip, rlz_index_query_api.hip).  Every
+case compares count and locate with the brute force of the definition (tests/rlz_locate_model.brute_locate: bytes.find
+per record and strand) by integer equality: counts, offsets, and every hit field in the stated order."""
 import random
 import threading
 

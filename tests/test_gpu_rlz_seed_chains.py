@@ -1,6 +1,6 @@
-"""Colinear seed chains on the relative-LZ index, on the device (rlz_seed_chain.hip, rlz_index_api.hip).  Every case
-compares RlzIndex.seed_chains with tests/rlz_seed_chain_model.expected -- the seeds of rlz_seeds_model, the recurrence in
-plain Python integers -- by integer equality of every field of every chain and anchor."""
+"""Colinear seed chains on the relative-LZ index, on the device (rlz_seed_chain.hip, rlz_index_seeds_api.hip).  Every
+case compares RlzIndex.seed_chains with tests/rlz_seed_chain_model.expected -- the seeds of rlz_seeds_model, the
+recurrence in plain Python integers -- by integer equality of every field of every chain and anchor."""
 import random
 import threading
 
@@ -157,6 +157,42 @@ def test_chunks_and_batches_change_nothing(rlz, monkeypatch):
         same(ix.seed_chains(targets, batch_bases=500, **cm.MAPPING), exp)
         monkeypatch.setattr(rlz, "MAX_CHAIN_TARGETS", 2)  # the cut at 2^24 targets, brought within reach
         same(ix.seed_chains(targets, **cm.MAPPING), exp)
+
+
+def _profiled(fn):
+    from nolzss_amd import _noLZSS as native
+    native.profile_enable(True)
+    try:
+        native.profile_reset()
+        out = fn()
+        return out, native.profile_report()
+    finally:
+        native.profile_enable(False)
+        native.profile_reset()
+
+
+def _launches(report, *names):
+    return [report[name][0] if name in report else 0 for name in names]
+
+
+def test_the_batch_is_searched_again_when_the_arena_grows_for_the_hits(rlz):
+    """an open leaves the arena empty: the first query reserves for the batch, learns the number of hits, reserves again
+    -- the slab is replaced -- and searches the batch a second time in it, before the hits are expanded and chained once;
+    the next call finds room"""
+    from nolzss_amd import _noLZSS as native
+    refs, targets, _ = cm.planted(random.Random(1001), count=9)
+    targets.insert(4, b"")
+    exp = cm.expected(refs, targets, True, **cm.MAPPING)
+    front, back = ("rlz_index_search", "rlz_seed_flags", "rlz_seed_intervals"), ("rlz_seed_hits", "rlz_chain_recurrence")
+    with rlz.RlzIndex.build(refs) as ix:
+        native.debug_trim_arenas()
+        first, report = _profiled(lambda: ix.seed_chains(targets, **cm.MAPPING))
+        assert report["rlz_index_search"][0] >= 2  # (at least one regrow: else this test is not on the path)
+        assert _launches(report, *front) == [2, 2, 2] and _launches(report, *back) == [1, 1]
+        again, report = _profiled(lambda: ix.seed_chains(targets, **cm.MAPPING))
+        assert _launches(report, *front) == [1, 1, 1] and _launches(report, *back) == [1, 1]
+        same(first, exp)
+        same(again, exp)
 
 
 def test_two_threads_query_one_handle(rlz):

@@ -1,6 +1,6 @@
-"""Maximal match seeds on the relative-LZ index, on the device (rlz_seeds.hip, rlz_index_api.hip).  Every case compares
-RlzIndex.seeds with tests/rlz_seeds_model.expected -- the ms formulation over bytes.find, the hits from the brute force of
-a locate -- by integer equality of every field: target, start, length, counts, offsets, and every hit field in order."""
+"""Maximal match seeds on the relative-LZ index, on the device (rlz_seeds.hip, rlz_index_seeds_api.hip).  Every case
+compares RlzIndex.seeds with tests/rlz_seeds_model.expected -- the ms formulation over bytes.find, the hits from the
+brute force of a locate -- by integer equality of every field: target, start, length, counts, offsets, and every hit field in order."""
 import ctypes as C
 import random
 import threading
