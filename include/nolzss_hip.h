@@ -871,6 +871,90 @@ int nolzss_debug_rlz_locate_shifts(uint64_t block_length, uint64_t q, int *shift
 /* NULL is a no-op. */
 int nolzss_rlz_index_close(nolzss_rlz_index *h);
 
+/* ---- relative-LZ index: pileup counts and variant sites of read batches ---------------------------- */
+/* Extension.  What the sample says at every position of the reference: how deep the coverage is, which base was
+ * observed, on which strand, and where the sample differs ("Relative-LZ index: pileup").  A pileup lives in
+ * device memory next to its index; batch after batch goes through the align path of the index and is reduced there:
+ * neither alignment records nor ops come down, only the table does, when it is asked for.
+ *   A pileup belongs to ONE index handle, which must outlive it, and to ONE nolzss_rlz_align_params, given at open.  It
+ *     holds NOLZSS_RLZ_PILEUP_CHANNELS = 8 uint32 counters for every position p of the block Rblk, 0 <= p < B, all zero
+ *     after open; the counters of a separator position stay zero.
+ *       channel 0..3  A, C, G, T: the base observed, written in the block's forward orientation
+ *       channel 4     DEL: deletion columns
+ *       channel 5     INS: insertion ops anchored here
+ *       channel 6     REV: columns of reverse-strand alignments that consume this base (`=`, X or D)
+ *       channel 7     BREAK: alignment ends with a clipped target remainder
+ *     Depth at p is A + C + G + T + DEL.
+ *   add: the batch is aligned exactly as nolzss_rlz_index_align aligns it with the pileup's parameters: the same
+ *     alignments in the same order.  With primary_only, alignments whose `primary` is 0 are skipped.  Every alignment kept
+ *     is walked in forward-block orientation: on the forward strand its ops are read first to last and the target bases
+ *     are taken as they are; on the reverse strand its ops are read last to first and the target bases are complemented
+ *     (the rule of nolzss_rlz_index_align: the target stretch equals the reverse complement of Rblk[r_start, r_end)
+ *     edited by the ops read back to front).  The walk starts at r = r_start and r only ascends:
+ *       `=` of n: for each of the n positions the channel of the BLOCK's base is incremented; r += n.
+ *       X of n: for each of the n positions the channel of the oriented TARGET base is incremented; r += n.
+ *       D of n: DEL is incremented at each of the n positions; r += n.
+ *       I of n: INS at clamp(r - 1, r_start, r_end - 1) is incremented ONCE per op, whatever n is; r stays.
+ *       On the reverse strand REV is also incremented at every position that `=`, X or D consume.
+ *       BREAK takes +1 at r_start if the target has bases in front of the aligned part in this orientation (forward
+ *       strand: t_start > 0; reverse strand: t_end < target length) and +1 at r_end - 1 in the mirror case.
+ *     Counters are exact.  To keep them below 2^32 an add is refused before any device work when the targets added so far
+ *     plus k would exceed 2^31 - 1 (a target has at most one chain per strand and record, so at most two alignments over
+ *     any position): NOLZSS_ERR_INVALID_ARGUMENT.  Everything nolzss_rlz_index_align refuses is refused with the same
+ *     status and message: the parameters by open, the batch by add; the refusals of a total learnt on the device (hits,
+ *     DP rows, column slots, columns) are decided before any counter is written.  A refused or failed add leaves the
+ *     counters as they were.  k == 0, or a batch without a base, succeeds without touching the device.  *info: the
+ *     alignments kept of this batch, their ops and their columns, and the targets added so far.
+ *   counts: out[(p - start) * 8 + channel] for start <= p < end, (end - start) * 8 words, the caller's.  end > B or start >
+ *     end: NOLZSS_ERR_INVALID_ARGUMENT.
+ *   variants(min_count, num, den): for every non-separator position p with block base b one record for every allele a
+ *     among the three other bases and DEL with count_a >= min_count and count_a * den >= num * depth, and one for INS
+ *     under the same rule against the same depth; the products are taken in 64 bits.  allele is 0..3 for a base, 4 for
+ *     DEL, 5 for INS; ref_base is b (0..3 = A, C, G, T); count the allele's counter, depth and rev the position's depth
+ *     and REV; record / record_offset the reference record of p and p's place inside it.  The records ascend by
+ *     (position, allele).  den == 0, num > den, min_count == 0 or den beyond 32 bits: NOLZSS_ERR_INVALID_ARGUMENT.  Free
+ *     the result with the free function below, whatever the status.
+ *   Not reported: the inserted sequence (INS counts the ops, not their bases), and no genotype is called -- a record
+ *     says that an allele passed the caller's threshold, nothing about zygosity or quality.
+ *   Memory: 44 bytes of device memory per block base, one allocation of the handle's own: 36 of counters (two difference
+ *     arrays -- `=` depth and REV are kept as +1 / -1 entries at the ends of a run and scanned on the first read after an
+ *     add --, four X counters, DEL, INS, BREAK) and 8 of resolved depths.  An out-of-memory at open or in an add leaves
+ *     the pileup (at open: none) and the index untouched.
+ *   Threads: the calls on one pileup are serialised by a mutex in the handle, so several threads may add to and read one
+ *     pileup; a reader sees every add that returned before it started.  The calling thread's current device is left as
+ *     it was.  NOLZSS_RLZ_LOCATE_CHUNK (tests): positions of counts, and variant records, per download. */
+#define NOLZSS_RLZ_PILEUP_CHANNELS 8
+typedef struct nolzss_rlz_pileup nolzss_rlz_pileup;
+typedef struct nolzss_rlz_pileup_add_info {
+    uint64_t alignments, ops, columns; /* of this batch: the alignments kept, their ops, their columns */
+    uint64_t targets;                  /* added to the pileup so far, this batch included */
+} nolzss_rlz_pileup_add_info;
+typedef struct nolzss_rlz_pileup_summary {
+    uint64_t block_length, device_bytes;
+    uint64_t targets, alignments, ops, columns, adds; /* running totals; adds: the batches that reached the device */
+    int32_t device, dirty;                            /* dirty: an add since the last read */
+    nolzss_rlz_align_params params;
+} nolzss_rlz_pileup_summary;
+typedef struct nolzss_rlz_variant {
+    uint64_t position, record_offset;
+    uint32_t record, ref_base, allele, count, depth, rev;
+} nolzss_rlz_variant;
+typedef struct nolzss_rlz_variants_result {
+    size_t num_variants;
+    nolzss_rlz_variant *variants; /* ascending by (position, allele); NULL when num_variants == 0 */
+} nolzss_rlz_variants_result;
+int nolzss_rlz_pileup_open(const nolzss_rlz_index *index, const nolzss_rlz_align_params *params, nolzss_rlz_pileup **out);
+int nolzss_rlz_pileup_add(nolzss_rlz_pileup *p, const char *const *targets, const size_t *target_lens, size_t k,
+                          int primary_only, nolzss_rlz_pileup_add_info *info);
+int nolzss_rlz_pileup_counts(nolzss_rlz_pileup *p, uint64_t start, uint64_t end, uint32_t *out);
+int nolzss_rlz_pileup_variants(nolzss_rlz_pileup *p, uint32_t min_count, uint64_t num, uint64_t den,
+                               nolzss_rlz_variants_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_variants_result(nolzss_rlz_variants_result *r);
+int nolzss_rlz_pileup_info(nolzss_rlz_pileup *p, nolzss_rlz_pileup_summary *info);
+/* NULL is a no-op. */
+int nolzss_rlz_pileup_close(nolzss_rlz_pileup *p);
+
 /* ---- relative-LZ archive: batches appended from the index ---------------------------------------- */
 /* Extension.  The index and the archive meet on the device: a batch is matched against the index as
  * nolzss_rlz_index_factorize matches it, and its records go from the match kernels straight into the archive's resident
@@ -1197,6 +1281,18 @@ int nolzss_debug_rlz_align_jobs(const char *query, size_t query_len, const char 
                                 const uint32_t *kind, const uint32_t *q0, const uint32_t *nq, const uint32_t *y0,
                                 const uint32_t *ny, size_t n, uint32_t band, int device, uint32_t *cost, uint32_t *end_col,
                                 uint64_t *col_offsets, uint8_t **cols);
+/* The pileup stages (rlz_pileup.hip: rlz_pileup_accumulate, rlz_pileup_resolve, rlz_pileup_compose, the production
+ * functions) on the caller's alignments, by the rules of nolzss_rlz_pileup_add.  block: B bytes, ACGT (case-insensitive)
+ * and any other byte for a separator between two records; targets: k plain ACGT strings, packed as a batch is; the
+ * alignment records, op_offsets (num_alignments + 1 entries) and ops as nolzss_rlz_index_align returns them.
+ * Out: counts[B x 8], the caller's.  No alignment, or B == 0, succeeds without a launch (the counts are zeroed).
+ * NOLZSS_ERR_INVALID_ARGUMENT before any launch for null pointers, B or the batch beyond 2^28 positions, an invalid target
+ * base, offsets that do not start at 0, ascend and end at num_ops, an alignment without ops, an op of length 0 or a code
+ * other than 1, 2, 7, 8, a target index >= k, an alignment whose ops do not consume exactly [t_start, t_end) and
+ * [r_start, r_end), whose stretches are empty on the block side, leave the target or the block, or cover a separator. */
+int nolzss_debug_rlz_pileup(const char *block, size_t B, const char *const *targets, const size_t *target_lens, size_t k,
+                            const nolzss_rlz_alignment *alignments, const uint64_t *op_offsets, size_t num_alignments,
+                            const uint32_t *ops, size_t num_ops, int primary_only, int device, uint32_t *counts);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

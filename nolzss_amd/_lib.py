@@ -165,6 +165,29 @@ class RlzAlignResult(C.Structure):
                 ("num_ops", C.c_size_t), ("ops", C.c_void_p), ("num_jobs", C.c_size_t), ("num_rows", C.c_size_t)]
 
 
+class RlzPileupAddInfo(C.Structure):
+    """Mirror of nolzss_rlz_pileup_add_info (include/nolzss_hip.h)."""
+    _fields_ = [("alignments", C.c_uint64), ("ops", C.c_uint64), ("columns", C.c_uint64), ("targets", C.c_uint64)]
+
+
+class RlzPileupSummary(C.Structure):
+    """Mirror of nolzss_rlz_pileup_summary (include/nolzss_hip.h)."""
+    _fields_ = [("block_length", C.c_uint64), ("device_bytes", C.c_uint64), ("targets", C.c_uint64),
+                ("alignments", C.c_uint64), ("ops", C.c_uint64), ("columns", C.c_uint64), ("adds", C.c_uint64),
+                ("device", C.c_int32), ("dirty", C.c_int32), ("params", RlzAlignParams)]
+
+
+class RlzVariant(C.Structure):
+    """Mirror of nolzss_rlz_variant (include/nolzss_hip.h)."""
+    _fields_ = [("position", C.c_uint64), ("record_offset", C.c_uint64), ("record", C.c_uint32), ("ref_base", C.c_uint32),
+                ("allele", C.c_uint32), ("count", C.c_uint32), ("depth", C.c_uint32), ("rev", C.c_uint32)]
+
+
+class RlzVariantsResult(C.Structure):
+    """Mirror of nolzss_rlz_variants_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_variants", C.c_size_t), ("variants", C.c_void_p)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -329,6 +352,15 @@ def _load():
     lib.nolzss_free_rlz_align_result.restype = None
     lib.nolzss_debug_rlz_align_jobs.argtypes = [C.c_char_p, sz, C.c_char_p, sz, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_int,
                                                 vp, vp, vp, vpp]
+    lib.nolzss_rlz_pileup_open.argtypes = [vp, C.POINTER(RlzAlignParams), vpp]
+    lib.nolzss_rlz_pileup_add.argtypes = [vp] + seqs[3:] + [C.c_int, C.POINTER(RlzPileupAddInfo)]
+    lib.nolzss_rlz_pileup_counts.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+    lib.nolzss_rlz_pileup_variants.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(RlzVariantsResult)]
+    lib.nolzss_free_rlz_variants_result.argtypes = [C.POINTER(RlzVariantsResult)]
+    lib.nolzss_free_rlz_variants_result.restype = None
+    lib.nolzss_rlz_pileup_info.argtypes = [vp, C.POINTER(RlzPileupSummary)]
+    lib.nolzss_rlz_pileup_close.argtypes = [vp]
+    lib.nolzss_debug_rlz_pileup.argtypes = [vp, sz] + seqs[3:] + [vp, vp, sz, vp, sz, C.c_int, C.c_int, vp]
     lib.nolzss_debug_rlz_locate_shifts.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
@@ -416,6 +448,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_chain", "nolzss_debug_cursor",
     "nolzss_rlz_index_seed_chains", "nolzss_free_rlz_seed_chains_result", "nolzss_debug_rlz_seed_chain",
     "nolzss_rlz_index_align", "nolzss_free_rlz_align_result", "nolzss_debug_rlz_align_jobs",
+    "nolzss_rlz_pileup_open", "nolzss_rlz_pileup_add", "nolzss_rlz_pileup_counts", "nolzss_rlz_pileup_variants",
+    "nolzss_free_rlz_variants_result", "nolzss_rlz_pileup_info", "nolzss_rlz_pileup_close", "nolzss_debug_rlz_pileup",
 ]
 
 

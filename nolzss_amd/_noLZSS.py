@@ -33,6 +33,11 @@ CHAIN_ANCHOR_DTYPE = np.dtype([("t_start", "<u8"), ("position", "<u8"), ("length
 ALIGN_DTYPE = np.dtype([("target", "<u8"), ("t_start", "<u8"), ("t_end", "<u8"), ("r_start", "<u8"), ("r_end", "<u8"),
                         ("score", "<u8"), ("edit_distance", "<u8"), ("columns", "<u8"), ("record", "<u4"), ("is_rc", "<u4"),
                         ("num_ops", "<u4"), ("primary", "<u4")])
+# nolzss_rlz_variant: an allele of the pileup that passed a variants query (RlzPileupHandle.variants)
+VARIANT_DTYPE = np.dtype([("position", "<u8"), ("record_offset", "<u8"), ("record", "<u4"), ("ref_base", "<u4"),
+                          ("allele", "<u4"), ("count", "<u4"), ("depth", "<u4"), ("rev", "<u4")])
+# NOLZSS_RLZ_PILEUP_CHANNELS: the eight counters a pileup keeps per block position, in this order
+PILEUP_CHANNELS = ("A", "C", "G", "T", "DEL", "INS", "REV", "BREAK")
 
 _default_device = int(os.environ.get("NOLZSS_DEVICE", os.environ.get("LOCAL_RANK", "0")) or 0)
 
@@ -1650,6 +1655,109 @@ class RlzIndexHandle:
             pass
 
 
+# ---- relative-LZ index: pileup counts and variant sites of read batches (genomics/rlz.py) -------------------------
+def _variant_rule(min_count, min_fraction):
+    """(min_count, num, den) of a variants query; ValueError for what the library would refuse -- before any native
+    call."""
+    min_count = operator.index(min_count)
+    try:
+        num, den = (operator.index(v) for v in min_fraction)
+    except (TypeError, ValueError):
+        raise ValueError("min_fraction is a pair of integers (num, den)") from None
+    if min_count < 1 or min_count >= 1 << 32:
+        raise ValueError("min_count must be at least 1 and fit 32 bits")
+    if den < 1 or num < 0 or num > den or den >= 1 << 32:
+        raise ValueError(f"min_fraction must be a fraction between 0 and 1 with a denominator below 2^32, not {num} / {den}")
+    return min_count, num, den
+
+
+class RlzPileupHandle:
+    """Extension: eight counters per position of the block of an index, kept on the device and fed by batches that go
+    through the align path of the index (C ABI nolzss_rlz_pileup_*).  It keeps the index handle alive.  A context
+    manager; close() may be called more than once, any other use after it raises ValueError."""
+
+    def __init__(self, handle, index_handle):
+        self._h, self._index = handle, index_handle
+
+    @classmethod
+    def open(cls, index_handle, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 31,
+             min_score: int = 40, band: int = 16, max_flank: int = 256):
+        """C ABI nolzss_rlz_pileup_open (its header states the rules)."""
+        params = _align_params(min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank)
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_pileup_open(index_handle._handle(), C.byref(params), C.byref(h)))
+        return cls(h, index_handle)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the pileup is closed")
+        self._index._handle()  # (a closed index raises here, not in the library)
+        return self._h
+
+    @property
+    def info(self) -> dict:
+        """dict(block_length, device_bytes, targets, alignments, ops, columns, adds, device, dirty) and the seven
+        align parameters.  C ABI nolzss_rlz_pileup_info."""
+        h = self._handle()
+        info = _lib.RlzPileupSummary()
+        check(lib.nolzss_rlz_pileup_info(h, C.byref(info)))
+        out = {name: int(getattr(info, name)) for name, _ in _lib.RlzPileupSummary._fields_ if name != "params"}
+        out.update({name: int(getattr(info.params, name)) for name, _ in _lib.RlzAlignParams._fields_})
+        return out
+
+    def add(self, targets, primary_only: bool = True) -> dict:
+        """One batch -> dict(alignments, ops, columns: of the alignments kept; targets: in the pileup so far).  C ABI
+        nolzss_rlz_pileup_add."""
+        h = self._handle()
+        info = _lib.RlzPileupAddInfo()
+        check(lib.nolzss_rlz_pileup_add(h, *_seq_args(targets, "target"), 1 if primary_only else 0, C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in _lib.RlzPileupAddInfo._fields_}
+
+    def counts(self, start: int = 0, end=None) -> np.ndarray:
+        """The (end - start, 8) uint32 counters of the block positions [start, end), channels in the order of
+        PILEUP_CHANNELS.  C ABI nolzss_rlz_pileup_counts."""
+        h = self._handle()
+        start = operator.index(start)
+        end = self.info["block_length"] if end is None else operator.index(end)
+        if start < 0 or end < start:
+            raise ValueError(f"counts take 0 <= start <= end, not [{start}, {end})")
+        out = np.zeros((end - start, len(PILEUP_CHANNELS)), dtype=np.uint32)
+        check(lib.nolzss_rlz_pileup_counts(h, start, end, out.ctypes.data if out.size else None))
+        return out
+
+    def variants(self, min_count: int = 2, min_fraction=(1, 2)) -> np.ndarray:
+        """The alleles that differ from the block and reach min_count observations and min_fraction = (num, den) of
+        the depth, as VARIANT_DTYPE ascending by (position, allele).  C ABI nolzss_rlz_pileup_variants."""
+        rule = _variant_rule(min_count, min_fraction)
+        h = self._handle()
+        res = _lib.RlzVariantsResult()
+        try:
+            check(lib.nolzss_rlz_pileup_variants(h, *rule, C.byref(res)))
+            out = np.zeros(res.num_variants, dtype=VARIANT_DTYPE)
+            if res.num_variants:
+                C.memmove(out.ctypes.data, res.variants, res.num_variants * VARIANT_DTYPE.itemsize)
+            return out
+        finally:
+            lib.nolzss_free_rlz_variants_result(C.byref(res))
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            check(lib.nolzss_rlz_pileup_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _roundtrip_result(z, mismatches, first, info):
     res = {"z": z.value, "mismatches": mismatches.value,
            "first_mismatch": None if first.value == (1 << 64) - 1 else first.value}
@@ -2163,3 +2271,21 @@ def debug_rlz_align_jobs(query, reference, kind, q0, nq, y0, ny, band: int):
         if cols:
             lib.nolzss_free(cols)
     return {"cost": cost[:n], "end_col": end_col[:n], "col_offsets": offsets, "cols": out}
+
+
+def debug_rlz_pileup(block, targets, alignments, op_offsets, ops, primary_only: bool = False):
+    """The pileup stages on caller alignments (nolzss_debug_rlz_pileup, test hook): block is the reference block as
+    bytes, ACGT and any other byte for a separator; targets plain ACGT strings; alignments an ALIGN_DTYPE array with its
+    len + 1 uint64 op_offsets and the uint32 ops (length << 4 | code).  Returns the (len(block), 8) uint32 counters."""
+    block = block.encode("ascii") if isinstance(block, str) else bytes(block)
+    recs = np.ascontiguousarray(alignments, dtype=ALIGN_DTYPE)
+    offsets = np.ascontiguousarray(op_offsets, dtype=np.uint64)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    if offsets.size != recs.size + 1:
+        raise ValueError("op_offsets holds one entry per alignment and one more")
+    out = np.zeros((len(block), len(PILEUP_CHANNELS)), dtype=np.uint32)
+    check(lib.nolzss_debug_rlz_pileup(block, len(block), *_seq_args(targets, "target"),
+                                      recs.ctypes.data if recs.size else None, offsets.ctypes.data, recs.size,
+                                      ops.ctypes.data if ops.size else None, ops.size, 1 if primary_only else 0,
+                                      _default_device, out.ctypes.data if out.size else None))
+    return out

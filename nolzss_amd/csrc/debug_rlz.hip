@@ -1,8 +1,9 @@
 // debug_rlz.hip -- test hooks of the relative-LZ index (part of the C ABI layer of libnolzss_hip.so, include/nolzss_hip.h,
 // the debug section): nolzss_debug_rlz_seed_chain, the seed-chain stages on a caller's anchors (the kernels:
-// rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index: colinear seed chains"), and nolzss_debug_rlz_align_jobs, the
+// rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index: colinear seed chains"), nolzss_debug_rlz_align_jobs, the
 // alignment stages on a caller's jobs (the kernels: rlz_align.hip; DESIGN.md 5, "Relative-LZ index: base-level
-// alignments").
+// alignments"), and nolzss_debug_rlz_pileup, the pileup stages on a caller's alignments (the kernels: rlz_pileup.hip;
+// DESIGN.md 5, "Relative-LZ index: pileup").
 #include "rlz_handles.hpp"
 
 using namespace nolzss;
@@ -183,9 +184,129 @@ void debug_align_jobs(const char *query, size_t query_len, const char *reference
     *cols = flat;
 }
 
+// The debug hook: the host's checks of the caller's alignments, then the production accumulate and read-out of the
+// pileup on them, with counters taken from the arena.
+void debug_pileup(const char *block, size_t B, const char *const *targets, const size_t *target_lens, size_t k,
+                  const nolzss_rlz_alignment *alignments, const uint64_t *op_offsets, size_t C, const uint32_t *ops, size_t N,
+                  bool primary_only, int device, uint32_t *counts) {
+    if ((B && (!block || !counts)) || (k && (!targets || !target_lens)) || !op_offsets || (C && !alignments) || (N && !ops))
+        throw std::invalid_argument("null argument");
+    if (B >= kAlignMaxTarget || C >= (size_t(1) << 24) || N >= kAlignMaxTarget) throw std::invalid_argument("a block, alignments or ops beyond 2^28");
+    Batch b;
+    size_t bases = 0;
+    for (size_t j = 0; j < k; ++j) {
+        if (target_lens[j] && !targets[j]) throw std::invalid_argument("null argument");
+        if (target_lens[j] >= kAlignMaxTarget || bases + target_lens[j] + k >= kAlignMaxTarget)
+            throw std::invalid_argument("a batch of 2^28 positions or more");
+        const size_t bad = first_invalid_nucleotide(targets[j], target_lens[j]);
+        if (bad < target_lens[j]) throw std::invalid_argument("target " + std::to_string(j) + ": an invalid base at " + std::to_string(bad));
+        bases += target_lens[j];
+    }
+    // the block: bases upper-cased, every other byte a separator; one more separator behind it, as a batch ends
+    HostBytes xbytes(B + 1);
+    std::vector<uint32_t> xseps;
+    for (size_t i = 0; i < B; ++i) {
+        const uint8_t c = (uint8_t)block[i] & 0xdfu;
+        const bool base = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+        xbytes[i] = base ? c : kSeparator;
+        if (!base) xseps.push_back((uint32_t)i);
+    }
+    xbytes[B] = kSeparator;
+    xseps.push_back((uint32_t)B);
+    if (op_offsets[0] != 0 || op_offsets[C] != N) throw std::invalid_argument("op_offsets do not run from 0 to num_ops");
+    for (size_t c = 0; c < C; ++c) {
+        const std::string at = "alignment " + std::to_string(c);
+        const nolzss_rlz_alignment &a = alignments[c];
+        if (op_offsets[c] >= op_offsets[c + 1] || op_offsets[c + 1] > N) throw std::invalid_argument(at + ": no ops, or offsets that do not ascend");
+        if (a.target >= k) throw std::invalid_argument(at + ": the target is beyond the batch");
+        if (a.t_start > a.t_end || a.t_end > target_lens[a.target]) throw std::invalid_argument(at + ": leaves its target");
+        if (a.r_start >= a.r_end || a.r_end > B) throw std::invalid_argument(at + ": leaves the block, or covers no base of it");
+        const auto sep = std::lower_bound(xseps.begin(), xseps.end(), (uint32_t)a.r_start);
+        if (*sep < a.r_end) throw std::invalid_argument(at + ": covers a separator");
+        uint64_t t = 0, r = 0;
+        for (uint64_t i = op_offsets[c]; i < op_offsets[c + 1]; ++i) {
+            const uint32_t code = ops[i] & 0xfu, len = ops[i] >> 4;
+            if (len == 0 || (code != kAlignI && code != kAlignD && code != kAlignEq && code != kAlignX))
+                throw std::invalid_argument(at + ": an op of length 0 or of an unknown code");
+            t += code == kAlignD ? 0 : len;
+            r += code == kAlignI ? 0 : len;
+        }
+        if (t != a.t_end - a.t_start || r != a.r_end - a.r_start)
+            throw std::invalid_argument(at + ": the ops do not consume exactly [t_start, t_end) and [r_start, r_end)");
+    }
+    if (B) std::memset(counts, 0, sizeof(uint32_t) * kPileupChannels * B);
+    if (C == 0 || B == 0) return;
+    b.tcat.resize(bases + k);
+    b.separators.resize(k);
+    b.offsets.resize(k);
+    size_t at = 0;
+    for (size_t j = 0; j < k; ++j) {
+        b.offsets[j] = at;
+        copy_upper(b.tcat.data() + at, targets[j], target_lens[j]);
+        at += target_lens[j];
+        b.separators[j] = (uint32_t)at;
+        b.tcat[at++] = kSeparator;
+    }
+    constexpr size_t kPad = 64;  // entries behind the record and op arrays, filled with 0xff bytes
+    std::vector<AlignRec> recs(C + kPad);
+    std::memcpy(recs.data(), alignments, sizeof(AlignRec) * C);
+    std::memset(recs.data() + C, 0xff, sizeof(AlignRec) * kPad);
+    std::vector<uint32_t> hops(N + kPad, 0xffffffffu);
+    std::memcpy(hops.data(), ops, sizeof(uint32_t) * N);
+    const size_t foot = rlz_pileup_footprint((uint32_t)B);
+    DeviceRestore restore;
+    Session ses(device, nullptr);
+    Context &ctx = ses.ctx();
+    hipStream_t s = ctx.stream;
+    ctx.arena.reserve(foot + 3 * (B + 1 + b.tcat.size()) + sizeof(AlignRec) * (C + kPad) + 8 * (C + 1) + 24 * (N + kPad) +
+                      sizeof(uint32_t) * kPileupChannels * B + (size_t(64) << 20));
+    ArenaRewind rewind(ctx.arena);
+    uint8_t *d_block = ctx.arena.alloc<uint8_t>(B + 1);
+    upload_bytes(ctx, d_block, xbytes.data(), B + 1);
+    HIP_CHECK(hipStreamSynchronize(s));  // (xbytes is a local)
+    PackedText xt;
+    if (!pack_independent_text(ctx, d_block, B + 1, xseps, xt)) throw std::runtime_error("block: the separators were miscounted");
+    PackedText qt;
+    upload_and_pack(ctx, b, qt);
+    AlignRec *d_recs = ctx.arena.alloc<AlignRec>(C + kPad);
+    uint64_t *d_off = ctx.arena.alloc<uint64_t>(C + 1);
+    uint32_t *d_ops = ctx.arena.alloc<uint32_t>(N + kPad);
+    void *d_counters = ctx.arena.alloc<uint8_t>(foot);
+    uint32_t *d_out = ctx.arena.alloc<uint32_t>(kPileupChannels * B);
+    unsigned long long *d_stats = ctx.arena.alloc<unsigned long long>(3);
+    HIP_CHECK(hipMemcpyAsync(d_recs, recs.data(), sizeof(AlignRec) * (C + kPad), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_off, op_offsets, 8 * (C + 1), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_ops, hops.data(), 4 * (N + kPad), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(d_counters, 0, foot, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (local vectors)
+    const PileupView view = rlz_pileup_view(d_counters, (uint32_t)B);
+    AlignOut a;
+    a.num_alignments = (uint32_t)C;
+    a.num_ops = (uint32_t)N;
+    a.recs = d_recs;
+    a.op_offsets = d_off;
+    a.ops = d_ops;
+    rlz_pileup_accumulate(ctx, view, a, qt, primary_only, d_stats);
+    rlz_pileup_resolve(ctx, view);
+    rlz_pileup_compose(ctx, view, xt, 0, (uint32_t)B, d_out);
+    HIP_CHECK(hipMemcpyAsync(counts, d_out, sizeof(uint32_t) * kPileupChannels * B, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    ctx.prof.collect();
+}
+
 }  // namespace
 
 extern "C" {
+
+int nolzss_debug_rlz_pileup(const char *block, size_t B, const char *const *targets, const size_t *target_lens, size_t k,
+                            const nolzss_rlz_alignment *alignments, const uint64_t *op_offsets, size_t num_alignments,
+                            const uint32_t *ops, size_t num_ops, int primary_only, int device, uint32_t *counts) {
+    return guarded([&] {
+        debug_pileup(block, B, targets, target_lens, k, alignments, op_offsets, num_alignments, ops, num_ops, primary_only != 0,
+                     device, counts);
+    });
+}
 
 int nolzss_debug_rlz_align_jobs(const char *query, size_t query_len, const char *reference, size_t reference_len,
                                 const uint32_t *kind, const uint32_t *q0, const uint32_t *nq, const uint32_t *y0,

@@ -1,7 +1,7 @@
 // rlz_handles.hpp -- the resident relative-LZ handles and what the translation units of their entry points share: the
 // index and its match (rlz_index_api.hip), its pattern queries (rlz_index_query_api.hip) and its seed queries
 // (rlz_index_seeds_api.hip); the archive (rlz_archive_api.hip), whose appends run that match; a finder reads both
-// (rlz_find_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index" and "Relative-LZ archive:
+// (rlz_find_api.hip); a pileup reduces the alignments of the index (rlz_pileup_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index" and "Relative-LZ archive:
 // locate through the parse".
 #pragma once
 #include <functional>
@@ -87,6 +87,30 @@ struct nolzss_rlz_finder {
     }
 };
 
+// The pileup handle: the counters of every position of the block of one index under one set of align parameters
+// (rlz_pileup_api.hip; DESIGN.md 5, "Relative-LZ index: pileup").  It points to the index it was opened over, which must
+// outlive it, and holds its counters in ONE device allocation of its own (not arena memory), zeroed at open.  `mu`
+// serialises the calls on one pileup: several threads may add to it and read it, one at a time.
+struct nolzss_rlz_pileup {
+    int device = 0;
+    const nolzss_rlz_index *index = nullptr;
+    nolzss_rlz_align_params params{};
+    void *d_base = nullptr;
+    size_t device_bytes = 0;
+    nolzss::PileupView view;
+    std::mutex mu;
+    bool dirty = false;  // difference entries were added since the last resolve
+    uint64_t targets = 0, alignments = 0, ops = 0, columns = 0, adds = 0;  // running totals
+    ~nolzss_rlz_pileup() {  // (the calling thread's current device stays what it was)
+        if (!d_base) return;
+        int current = -1;
+        const bool known = hipGetDevice(&current) == hipSuccess;
+        (void)hipSetDevice(device);
+        (void)hipFree(d_base);
+        if (known && current != device) (void)hipSetDevice(current);
+    }
+};
+
 namespace nolzss {
 namespace api {
 
@@ -160,6 +184,21 @@ constexpr size_t kLocateBytesPerHit = 25;
 // chunked by NOLZSS_RLZ_LOCATE_CHUNK).
 ChainRules chain_rules(const nolzss_rlz_chain_params &p, uint64_t records, uint64_t B);
 void deliver_chains(Context &ctx, const ChainsOut &run, nolzss_rlz_seed_chains_result &res);
+// What the align query and the pileup (rlz_index_seeds_api.hip, rlz_pileup_api.hip) share.  The refusals of the
+// parameters and of the batch's shape, each before any device work and in align's words; then, inside a session, the path
+// of a batch of k >= 1 targets with at least one base up to its alignments, which stay in the arena with the packed batch:
+// the refusals of the totals (returned as the message; `run` is then empty), the two arena reservations and the rerun
+// rule.  extra_per_slot: bytes per column slot a consumer takes behind rlz_align_ops, reserved with the second
+// reservation (an op is at most one per slot).
+void check_align_params(const nolzss_rlz_align_params *params);
+void check_align_batch_shape(const size_t *target_lens, size_t k);
+struct AlignRun {
+    AlignOut out;      // num_alignments == 0: no hit, no chain, or a refusal
+    PackedText batch;  // the packed batch the alignments were computed from
+    size_t num_jobs = 0, num_rows = 0;
+};
+std::string align_batch(Context &ctx, const nolzss_rlz_index &h, const Batch &b, size_t k, const nolzss_rlz_align_params &p,
+                        size_t extra_per_slot, AlignRun &run);
 
 }  // namespace api
 }  // namespace nolzss

@@ -1,8 +1,9 @@
 // rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
 // rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds, rlz_seed_chain.hip for
-// their colinear chains and rlz_align.hip for the base-level alignments of those;
-// the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip).
+// their colinear chains, rlz_align.hip for the base-level alignments of those and rlz_pileup.hip for the pileup counts of
+// the alignments; the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip,
+// rlz_pileup_api.hip).
 #pragma once
 #include "pipeline.hpp"
 
@@ -244,6 +245,50 @@ void rlz_align_traceback(Context &ctx, const AlignJobs &a);
 // Heads, scans, ops and one record per chain.  Waits for the stream once (the number of ops).  Arena memory: 16 bytes
 // per slot, 12 per op, 88 per chain.
 AlignOut rlz_align_ops(Context &ctx, const AlignJobs &a, const ChainsOut &chains, const ChainRules &rules);
+
+// ---- pileup counts of the alignments (rlz_pileup.hip; DESIGN.md 5, "Relative-LZ index: pileup") ---------------------
+// The counters of a pileup handle, by the rules of nolzss_rlz_pileup_add (include/nolzss_hip.h): device memory of the
+// handle's own, B + 1 entries per array (xbase: 4 per entry), zeroed at open.  `=` runs and reverse-strand spans are
+// difference entries in wrapping u32 -- +1 at the first position, -1 just past the last, so entry B takes the -1 of a
+// run that ends the block -- and rlz_pileup_resolve scans them into depths: entry p + 1 of an exclusive scan is the
+// depth of p.  X, D, I and BREAK are dense counters.
+constexpr uint32_t kPileupChannels = 8;  // A, C, G, T, DEL, INS, REV, BREAK
+constexpr uint32_t kPileupArrays = 11;   // u32 arrays of B + 1 entries: 36 bytes of counters and 8 of resolved depths
+struct PileupView {
+    uint32_t *diff_eq = nullptr, *diff_rev = nullptr;    // difference entries of the `=` depth and of REV
+    uint32_t *depth_eq = nullptr, *depth_rev = nullptr;  // their exclusive scans (rlz_pileup_resolve)
+    uint32_t *xbase = nullptr;                           // [p][base]: X columns by the oriented target base
+    uint32_t *del = nullptr, *ins = nullptr, *brk = nullptr;
+    uint32_t B = 0;
+};
+struct PileupVariantRec {  // nolzss_rlz_variant
+    uint64_t position, record_offset;
+    uint32_t record, ref_base, allele, count, depth, rev;
+};
+struct PileupRule {  // of a variants query: count >= min_count and count * den >= num * depth, in 64 bits
+    uint32_t min_count = 1;
+    uint64_t num = 0, den = 1;
+};
+// Bytes of one allocation that holds the arrays of a view (each 256-byte aligned), and the view over such an allocation.
+size_t rlz_pileup_footprint(uint32_t B);
+PileupView rlz_pileup_view(void *d_base, uint32_t B);
+// The alignments of rlz_align_ops (arena memory) added to the counters: `batch` is the packed target batch they were
+// aligned from.  d_stats (3 words, device memory, zeroed here): the alignments kept, their ops and their columns.
+// Every arena array is taken before the first kernel that writes a counter.  Arena memory: 16 bytes per op and the
+// scans' tile sums.  No position outside [r_start, r_end) of an op's alignment is written.
+void rlz_pileup_accumulate(Context &ctx, const PileupView &v, const AlignOut &a, const PackedText &batch, bool primary_only,
+                           unsigned long long *d_stats);
+// depth_eq / depth_rev from diff_eq / diff_rev: two scans over B + 1 entries
+void rlz_pileup_resolve(Context &ctx, const PileupView &v);
+// The eight channels of positions [start, start + count) of the block into d_out (count x 8), after a resolve: `block`
+// is the packed index text, whose terminator table holds the separators (their counters are written as 0).
+void rlz_pileup_compose(Context &ctx, const PileupView &v, const PackedText &block, uint32_t start, uint32_t count,
+                        uint32_t *d_out);
+// d_n[p] = the records (0 .. 5) a variants query writes for position p < B, after a resolve
+void rlz_pileup_variant_flags(Context &ctx, const PileupView &v, const PackedText &block, const PileupRule &rule, uint32_t *d_n);
+// The records [first, first + count) of the query, d_off = the exclusive scan of d_n, into d_out[0 .. count)
+void rlz_pileup_variant_records(Context &ctx, const PileupView &v, const PackedText &block, const PileupRule &rule,
+                                const uint32_t *d_off, uint64_t first, uint32_t count, PileupVariantRec *d_out);
 
 constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
 

@@ -262,11 +262,59 @@ void deliver_alignments(Context &ctx, const AlignOut &run, nolzss_rlz_align_resu
     res.num_ops = N;
 }
 
-// One batch of k >= 1 targets with at least one base against the handle, inside a session: the path of
-// query_seed_chains up to the chains, which stay on the device, then the align stages.  Returns the refusal when a total
-// is beyond the pipeline: the caller then hands back an empty result.
-std::string query_align(Context &ctx, const nolzss_rlz_index &h, const Batch &b, size_t k, const nolzss_rlz_align_params &p,
-                        nolzss_rlz_align_result &res) {
+void index_align(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
+                 const nolzss_rlz_align_params *params, nolzss_rlz_align_result *out) {
+    if (!out) throw std::invalid_argument("output pointer is null");
+    std::memset(out, 0, sizeof *out);
+    if (!h) throw std::invalid_argument("handle is null");
+    if (!params) throw std::invalid_argument("rlz index: alignments need their parameters: params is null");
+    if (k > kChainMaxTargets) check_align_batch_shape(nullptr, k);  // (the number of targets before the parameters)
+    check_align_params(params);
+    check_align_batch_shape(target_lens, k);
+    Batch b;
+    prepare_batch(*h, targets, target_lens, k, b);
+    nolzss_rlz_align_result res;
+    std::memset(&res, 0, sizeof res);
+    std::string refusal;
+    run_seed_query(*h, b, k, "rlz_index_align", res.op_offsets, [&] { nolzss_free_rlz_align_result(&res); }, [&](Context &ctx) {
+        AlignRun run;
+        refusal = align_batch(ctx, *h, b, k, *params, 0, run);
+        if (!refusal.empty()) return;
+        res.num_jobs = run.num_jobs;
+        res.num_rows = run.num_rows;
+        deliver_alignments(ctx, run.out, res);
+    });
+    if (!refusal.empty()) {  // an empty result and the status
+        nolzss_free_rlz_align_result(&res);
+        throw std::invalid_argument(refusal);
+    }
+    *out = res;  // ownership moves to the caller
+}
+
+}  // namespace
+
+// ---- what the align query shares with the pileup (rlz_handles.hpp) ---------------------------------------------------
+void nolzss::api::check_align_params(const nolzss_rlz_align_params *params) {
+    if (!params) throw std::invalid_argument("rlz index: alignments need their parameters: params is null");
+    if (params->bandwidth >= kAlignLanes || params->band >= kAlignLanes || params->bandwidth + 2 * params->band + 1 > kAlignLanes)
+        throw std::invalid_argument("rlz index: an alignment job has at most 64 diagonals, one per lane of a wavefront: bandwidth + 2 "
+                                    "band + 1 is " + std::to_string(params->bandwidth) + " + 2 * " + std::to_string(params->band) +
+                                    " + 1: lower bandwidth or band");
+}
+
+void nolzss::api::check_align_batch_shape(const size_t *target_lens, size_t k) {
+    if (k > kChainMaxTargets)
+        throw std::invalid_argument("rlz index: seed chains take at most 2^24 targets per batch, this one has " + std::to_string(k) +
+                                    " (the group sort key keeps the target in 24 bits): send fewer targets");
+    for (size_t j = 0; target_lens && j < k; ++j)  // (the lengths alone decide; a null array is the batch's refusal)
+        if (target_lens[j] >= kAlignMaxTarget)
+            throw std::invalid_argument("rlz index: alignments take targets below 2^28 bases, target " + std::to_string(j) + " has " +
+                                        std::to_string(target_lens[j]) + " (an op keeps its length in 28 bits)");
+}
+
+// The path of query_seed_chains up to the chains, which stay on the device, then the align stages.
+std::string nolzss::api::align_batch(Context &ctx, const nolzss_rlz_index &h, const Batch &b, size_t k,
+                                     const nolzss_rlz_align_params &p, size_t extra_per_slot, AlignRun &out) {
     const size_t n = b.tcat.size();
     nolzss_rlz_chain_params cp;
     cp.min_length = p.min_length;
@@ -281,11 +329,7 @@ std::string query_align(Context &ctx, const nolzss_rlz_index &h, const Batch &b,
     front.refuse_too_many();
     const uint64_t total = front.hit_total(ctx);
     const std::string refusal = hits_refusal(total, p.max_hits, p.min_length);
-    if (!refusal.empty()) return refusal;
-    if (total == 0) {
-        res.op_offsets = calloc_array<uint64_t>(1);
-        return refusal;
-    }
+    if (!refusal.empty() || total == 0) return refusal;
     const size_t T = (size_t)total;
     // the chains and the jobs of the batch, planned and sized: three totals come down
     ChainsOut run;
@@ -303,15 +347,12 @@ std::string query_align(Context &ctx, const nolzss_rlz_index &h, const Batch &b,
     const size_t per_hit = seed_batch_bytes(n, k, 0) + (kLocateBytesPerHit + kChainBytesPerHit + kAlignBytesPerHit) * T;
     if (regrow_arena(ctx, per_hit)) front.rerun(ctx, h, b, true);
     run_chains();
-    if (run.num_chains == 0) {
-        res.op_offsets = calloc_array<uint64_t>(1);
-        return refusal;
-    }
+    if (run.num_chains == 0) return refusal;
     const uint64_t rows = jobs.total_rows, slots = jobs.total_slots, weight = jobs.total_weight;
     if (rows > 0xffffffffull || slots > 0xffffffffull || weight > 0xffffffffull)
         return "rlz index: the alignments of this batch take " + std::to_string(rows) + " DP rows, " + std::to_string(slots) +
                " column slots and up to " + std::to_string(weight) + " columns, and each is counted in 32 bits: send fewer targets";
-    if (regrow_arena(ctx, per_hit + kAlignBytesPerRow * (size_t)rows + kAlignBytesPerSlot * (size_t)slots)) {
+    if (regrow_arena(ctx, per_hit + kAlignBytesPerRow * (size_t)rows + (kAlignBytesPerSlot + extra_per_slot) * (size_t)slots)) {
         front.rerun(ctx, h, b, true);
         run_chains();
         if (jobs.total_rows != rows || jobs.total_slots != slots || jobs.total_weight != weight)
@@ -320,45 +361,12 @@ std::string query_align(Context &ctx, const nolzss_rlz_index &h, const Batch &b,
     rlz_align_layout(ctx, jobs);
     rlz_align_dp(ctx, jobs, front.m.batch, h.view.text);
     rlz_align_traceback(ctx, jobs);
-    const AlignOut aligned = rlz_align_ops(ctx, jobs, run, rules);
-    res.num_jobs = jobs.J;
-    res.num_rows = (size_t)rows;
-    deliver_alignments(ctx, aligned, res);
+    out.out = rlz_align_ops(ctx, jobs, run, rules);
+    out.batch = front.m.batch;
+    out.num_jobs = jobs.J;
+    out.num_rows = (size_t)rows;
     return refusal;
 }
-
-void index_align(const nolzss_rlz_index *h, const char *const *targets, const size_t *target_lens, size_t k,
-                 const nolzss_rlz_align_params *params, nolzss_rlz_align_result *out) {
-    if (!out) throw std::invalid_argument("output pointer is null");
-    std::memset(out, 0, sizeof *out);
-    if (!h) throw std::invalid_argument("handle is null");
-    if (!params) throw std::invalid_argument("rlz index: alignments need their parameters: params is null");
-    if (k > kChainMaxTargets)
-        throw std::invalid_argument("rlz index: seed chains take at most 2^24 targets per batch, this one has " + std::to_string(k) +
-                                    " (the group sort key keeps the target in 24 bits): send fewer targets");
-    if (params->bandwidth >= kAlignLanes || params->band >= kAlignLanes || params->bandwidth + 2 * params->band + 1 > kAlignLanes)
-        throw std::invalid_argument("rlz index: an alignment job has at most 64 diagonals, one per lane of a wavefront: bandwidth + 2 "
-                                    "band + 1 is " + std::to_string(params->bandwidth) + " + 2 * " + std::to_string(params->band) +
-                                    " + 1: lower bandwidth or band");
-    for (size_t j = 0; target_lens && j < k; ++j)  // (the lengths alone decide; a null array is the batch's refusal below)
-        if (target_lens[j] >= kAlignMaxTarget)
-            throw std::invalid_argument("rlz index: alignments take targets below 2^28 bases, target " + std::to_string(j) + " has " +
-                                        std::to_string(target_lens[j]) + " (an op keeps its length in 28 bits)");
-    Batch b;
-    prepare_batch(*h, targets, target_lens, k, b);
-    nolzss_rlz_align_result res;
-    std::memset(&res, 0, sizeof res);
-    std::string refusal;
-    run_seed_query(*h, b, k, "rlz_index_align", res.op_offsets, [&] { nolzss_free_rlz_align_result(&res); },
-                   [&](Context &ctx) { refusal = query_align(ctx, *h, b, k, *params, res); });
-    if (!refusal.empty()) {  // an empty result and the status
-        nolzss_free_rlz_align_result(&res);
-        throw std::invalid_argument(refusal);
-    }
-    *out = res;  // ownership moves to the caller
-}
-
-}  // namespace
 
 // ---- what the seed-chain query shares with its debug hook (rlz_handles.hpp) -----------------------------------------
 // the chains of a run into the host blocks of a result (anchor_offsets: allocated here)

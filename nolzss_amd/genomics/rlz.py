@@ -27,6 +27,8 @@ CHAIN_DTYPE = _native.CHAIN_DTYPE  # a seed chain: one placement of a target in 
 CHAIN_ANCHOR_DTYPE = _native.CHAIN_ANCHOR_DTYPE  # (t_start, position, length): one anchor of a seed chain
 ALIGN_DTYPE = _native.ALIGN_DTYPE  # the base-level alignment of one seed chain (RlzIndex.align)
 ALIGN_LANES = _native.ALIGN_LANES  # diagonals of an alignment job: bandwidth + 2 * band + 1 must not exceed it
+VARIANT_DTYPE = _native.VARIANT_DTYPE  # an allele that passed RlzPileup.variants
+PILEUP_CHANNELS = _native.PILEUP_CHANNELS  # ("A", "C", "G", "T", "DEL", "INS", "REV", "BREAK"): the columns of RlzPileup.counts
 CIGAR_LETTERS = {1: "I", 2: "D", 7: "=", 8: "X"}  # BAM's op codes, as RlzIndex.align reports them
 MAX_CHAIN_TARGETS = 1 << 24  # targets per batch of a seed-chain query: the group sort key keeps the target in 24 bits
 
@@ -760,6 +762,16 @@ class RlzIndex:
                 "columns": r["columns"].copy(), "num_ops": r["num_ops"].copy(), "op_offsets": np.concatenate(offsets),
                 "ops": np.concatenate(ops) if ops else np.zeros(0, dtype=np.uint32)}
 
+    def pileup(self, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 31,
+               min_score: int = 40, band: int = 16, max_flank: int = 256, primary_only: bool = True):
+        """An RlzPileup over this index: per-position counts of what read batches say, accumulated on the GPU from the
+        alignments align would report at the same seven parameters (primary_only: only the best placement of every
+        target counts).  bandwidth + 2 * band + 1 must not exceed 64 (ValueError).  The index must stay open while
+        the pileup is used."""
+        params = _native._align_params(min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank)
+        args = [int(getattr(params, name)) for name, _ in type(params)._fields_]
+        return RlzPileup(_native.RlzPileupHandle.open(self._live(), *args), self, bool(primary_only))
+
     def archive(self, targets, ids=None):
         """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
         targets = list(targets)
@@ -776,6 +788,79 @@ class RlzIndex:
             arc.close()
             raise
         return arc
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h is not None:
+            h.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RlzPileup:
+    """Pileup counts and variant sites of read batches, kept on the GPU next to an RlzIndex (RlzIndex.pileup).  Every
+    add aligns a batch as RlzIndex.align would and reduces the alignments on the device: eight uint32 counters per
+    position of the reference block, in the order of PILEUP_CHANNELS -- the base observed (A, C, G, T, in the block's
+    forward orientation), DEL (deletion columns), INS (insertion ops anchored at the base in front of them), REV
+    (columns of reverse-strand alignments over this base) and BREAK (alignment ends with a clipped read remainder).
+    Depth is A + C + G + T + DEL.  Neither alignments nor ops come down; counts() and variants() bring down the table.
+    The inserted sequence is not reported and no genotype is called.  A context manager; use after close(), or after
+    the index was closed, raises ValueError."""
+
+    def __init__(self, handle, index, primary_only):
+        self._handle, self._index, self._primary_only = handle, index, primary_only
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("the pileup is closed")
+        self._index._live()
+        return self._handle
+
+    @property
+    def info(self):
+        """dict(block_length, device_bytes, targets, alignments, ops, columns, adds, device, dirty, primary_only) and
+        the seven align parameters"""
+        return dict(self._live().info, primary_only=self._primary_only)
+
+    def add(self, targets, batch_bases=None):
+        """Aligns the targets and adds their alignments to the counters -> dict(alignments, ops, columns: of the
+        alignments kept, summed over the batches; targets: in the pileup so far).  Batches as RlzIndex.align does (a
+        target is never split, so batching changes nothing); a batch the library refuses raises and leaves the
+        counters as they were before that batch."""
+        h = self._live()
+        targets = list(targets)
+        plan = plan_index_batches([len(t) for t in targets], h.info["block_length"], MAX_TEXT, batch_bases,
+                                  max_targets=MAX_CHAIN_TARGETS)
+        total = {"alignments": 0, "ops": 0, "columns": 0, "targets": h.info["targets"]}
+        for lo, hi in plan:
+            got = h.add(targets[lo:hi], self._primary_only)
+            for name in ("alignments", "ops", "columns"):
+                total[name] += got[name]
+            total["targets"] = got["targets"]
+        return total
+
+    def counts(self, start: int = 0, end=None):
+        """The (end - start, 8) uint32 counters of the block positions [start, end) (end None: the block's end);
+        separator positions are zero."""
+        return self._live().counts(start, end)
+
+    def variants(self, min_count: int = 2, min_fraction=(1, 2)):
+        """Where the sample differs -> VARIANT_DTYPE array (position, record_offset, record, ref_base, allele, count,
+        depth, rev), ascending by (position, allele): one record for every allele among the three bases other than the
+        block's and DEL (allele 4) with count >= min_count and count / depth >= num / den, min_fraction = (num, den) in
+        integers, and one for INS (allele 5) against the same depth.  A bad fraction or min_count < 1: ValueError."""
+        rule = _native._variant_rule(min_count, min_fraction)
+        return self._live().variants(rule[0], rule[1:])
 
     def close(self) -> None:
         h, self._handle = getattr(self, "_handle", None), None
@@ -815,5 +900,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "PILEUP_CHANNELS", "RlzPileup", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
