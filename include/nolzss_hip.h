@@ -914,8 +914,12 @@ int nolzss_rlz_index_close(nolzss_rlz_index *h);
  *     and REV; record / record_offset the reference record of p and p's place inside it.  The records ascend by
  *     (position, allele).  den == 0, num > den, min_count == 0 or den beyond 32 bits: NOLZSS_ERR_INVALID_ARGUMENT.  Free
  *     the result with the free function below, whatever the status.
- *   Not reported: the inserted sequence (INS counts the ops, not their bases), and no genotype is called -- a record
- *     says that an allele passed the caller's threshold, nothing about zygosity or quality.
+ *   The inserted sequence: INS counts the ops, not their bases; the bases are kept in the insertion log and reported by
+ *     nolzss_rlz_pileup_insertions, and nolzss_rlz_pileup_consensus applies them (both below).  Not reported: no genotype
+ *     is called and no quality is given -- a record says that an allele passed the caller's threshold, nothing about
+ *     zygosity; reads are not realigned; an indel is normalised only on request (nolzss_rlz_pileup_open_flags), never
+ *     across an X or a second gap, and by at most NOLZSS_RLZ_PILEUP_MAX_SHIFT positions; an inserted allele beyond
+ *     NOLZSS_RLZ_PILEUP_INS_BASES bases is reported truncated and never applied.
  *   Memory: 44 bytes of device memory per block base, one allocation of the handle's own: 36 of counters (two difference
  *     arrays -- `=` depth and REV are kept as +1 / -1 entries at the ends of a run and scanned on the first read after an
  *     add --, four X counters, DEL, INS, BREAK) and 8 of resolved depths.  An out-of-memory at open or in an add leaves
@@ -954,6 +958,92 @@ void nolzss_free_rlz_variants_result(nolzss_rlz_variants_result *r);
 int nolzss_rlz_pileup_info(nolzss_rlz_pileup *p, nolzss_rlz_pileup_summary *info);
 /* NULL is a no-op. */
 int nolzss_rlz_pileup_close(nolzss_rlz_pileup *p);
+/* Extension.  Left-normalised indels, the insertion alleles and a consensus ("Relative-LZ index:
+ * consensus").  nolzss_rlz_pileup_open is nolzss_rlz_pileup_open_flags with flags 0; an unknown flag bit is refused with
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work.
+ *   NOLZSS_RLZ_PILEUP_NORMALIZE.  The aligner's traceback takes the first of diagonal, up, left, and a reverse-strand read
+ *     is aligned on the mirrored block: an indel inside a repeat lands at one end of it for forward reads and at the other
+ *     for reverse reads.  With the flag every indel is counted at its leftmost block position on both strands.  Stated on
+ *     the walk of add: the oriented ops of a kept alignment are o_0 .. o_{m-1} (read first to last on the forward strand,
+ *     last to first on the reverse strand), S is its oriented target stretch, r ascends from r_start and q from 0; op k
+ *     has length n and the values r_k, q_k in front of it.  Its shift s_k is 0 unless the flag is set, o_k is D or I, k > 0
+ *     and o_{k-1} is `=` of length m; then, with L = min(m, NOLZSS_RLZ_PILEUP_MAX_SHIFT),
+ *       D: s_k = the largest s <= L with Rblk[r_k - j] == Rblk[r_k + n - j] for all 1 <= j <= s;
+ *       I, W = S[q_k, q_k + n): s_k = the largest s <= L with Rblk[r_k - j] == W[(n - j) mod n] for all 1 <= j <= s (the
+ *         mod is non-negative: each step rotates the inserted string by one).
+ *     A shift reads the block and the op's own target bases only.  The counters, where they differ from add's rules:
+ *       `=` op k in front of a D op: the block's base is counted at [r_k, r_k + n - s_{k+1}), possibly nowhere;
+ *       D op: DEL at [r_k - s, r_k - s + n), and the block's own base at [r_k - s + n, r_k + n) -- the `=` columns that moved
+ *         behind the gap;
+ *       I op: INS at clamp(r_k - s - 1, r_start, r_end - 1); its allele is W' with W'[i] = W[(i - s) mod n].
+ *     X, REV and BREAK are unchanged: every kept alignment still adds exactly one depth to every position of [r_start,
+ *     r_end), and no separator is touched.  With flags 0 no shift is computed and the counters are what add states.
+ *   The insertion log: every I op of a kept alignment appends one event of 24 bytes to a device buffer of the handle, with
+ *     and without the flag: the position where INS was counted, n, and the first min(n, NOLZSS_RLZ_PILEUP_INS_BASES)
+ *     bases of W' (flags 0: W' = W) as two words of big-endian 2-bit codes (A, C, G, T = 0 .. 3), zero behind them.  Two
+ *     events are the same allele iff position, n and both words are equal; an allele with n > NOLZSS_RLZ_PILEUP_INS_BASES
+ *     is truncated.  (An I run of nolzss_rlz_index_align crosses n + 1 of a job's at most NOLZSS_RLZ_ALIGN_LANES diagonals:
+ *     it stays below 64 bases.)  The buffer grows geometrically -- a new allocation, a device copy, a free --; the events
+ *     of a batch are counted on the device and their room is secured before the first counter of that add is written, so
+ *     an add that is refused or runs out of memory leaves counters and log as they were.  An add that would take the log
+ *     beyond 2^32 - 1 events is refused: NOLZSS_ERR_INVALID_ARGUMENT.  NOLZSS_RLZ_PILEUP_LOG_EVENTS (tests): the first
+ *     capacity.  log_info: the flags, the events logged and the bytes of the log's allocation (device_bytes of
+ *     nolzss_rlz_pileup_info keeps meaning the counters).
+ *   insertions(min_count, num, den): the allele table -- the distinct events with their multiplicities, built on the
+ *     device on the first read after an add and kept until the next add -- filtered: one record per allele with count >=
+ *     min_count and count * den >= num * depth (64-bit products), depth = the position's A + C + G + T + DEL, ins_total
+ *     its INS counter (the sum of the counts of all alleles there), truncated = 1 for n > NOLZSS_RLZ_PILEUP_INS_BASES;
+ *     bases as in the log.  The records ascend by (position, length, bases[0], bases[1]).  Refusals: those of variants.
+ *   consensus(params, want_map): for a non-separator position p with block base b, depth d and M the largest of its A, C,
+ *     G, T and DEL counters: p is LOW if d < min_depth or M * den < num * d; it then emits b's letter (low == 0) or N
+ *     (low == 1) and no insertion.  Otherwise the call is b if b's counter equals M, else the smallest channel that
+ *     attains M; a base emits its letter, DEL emits nothing.  Then the modal insertion allele at p -- the largest count,
+ *     ties to the first in table order -- is emitted behind the call (also behind a DEL call) if count * den >= num * d,
+ *     unless it is truncated: then it is skipped and counted in truncated_skipped.  A separator emits one 0x01.  text:
+ *     `length` bytes, the records' consensus joined by one 0x01 each, as the block is; record r is text[record_offsets[r],
+ *     record_offsets[r + 1] - 1), record_offsets has num_records + 1 entries.  starts (want_map): starts[p] = the offset
+ *     in text where p's output begins, block_length + 1 entries, starts[block_length] = length; else NULL.  called: the
+ *     positions not low; substitutions / deleted: calls of another base / of DEL; insertions / inserted_bases: alleles
+ *     emitted and their bases.  An insertion in front of an alignment's first block base is anchored by the clamp at
+ *     r_start, so it is emitted one base late (a quirk of INS's anchor, kept).  Refusals, before any device work: a null
+ *     pointer, min_depth == 0, low > 1, den == 0, num > den, den beyond 32 bits: NOLZSS_ERR_INVALID_ARGUMENT; a text of
+ *     2^32 bytes or more is refused with the same status.  Free either result with its free function, whatever the status.
+ *   NOLZSS_RLZ_LOCATE_CHUNK (tests): insertion records, text bytes, and map entries, per download. */
+#define NOLZSS_RLZ_PILEUP_NORMALIZE 1u
+#define NOLZSS_RLZ_PILEUP_MAX_SHIFT 1024 /* a constant of the ABI: it defines the result */
+#define NOLZSS_RLZ_PILEUP_INS_BASES 64
+typedef struct nolzss_rlz_insertion {
+    uint64_t position, record_offset;
+    uint32_t record, length, count, depth, ins_total, truncated;
+    uint64_t bases[2];
+} nolzss_rlz_insertion; /* 56 bytes */
+typedef struct nolzss_rlz_insertions_result {
+    size_t num_insertions;
+    nolzss_rlz_insertion *insertions; /* NULL when num_insertions == 0 */
+} nolzss_rlz_insertions_result;
+typedef struct nolzss_rlz_consensus_params {
+    uint32_t min_depth, low;
+    uint64_t num, den;
+} nolzss_rlz_consensus_params;
+typedef struct nolzss_rlz_consensus_result {
+    size_t length;
+    char *text;
+    size_t num_records;
+    uint64_t *record_offsets; /* num_records + 1 */
+    uint64_t *starts;         /* want_map: block_length + 1 entries, else NULL */
+    uint64_t called, low_positions, substitutions, deleted, insertions, inserted_bases, truncated_skipped;
+} nolzss_rlz_consensus_result;
+int nolzss_rlz_pileup_open_flags(const nolzss_rlz_index *index, const nolzss_rlz_align_params *params, uint32_t flags,
+                                 nolzss_rlz_pileup **out);
+int nolzss_rlz_pileup_log_info(nolzss_rlz_pileup *p, uint32_t *flags, uint64_t *events, uint64_t *log_bytes);
+int nolzss_rlz_pileup_insertions(nolzss_rlz_pileup *p, uint32_t min_count, uint64_t num, uint64_t den,
+                                 nolzss_rlz_insertions_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_insertions_result(nolzss_rlz_insertions_result *r);
+int nolzss_rlz_pileup_consensus(nolzss_rlz_pileup *p, const nolzss_rlz_consensus_params *params, int want_map,
+                                nolzss_rlz_consensus_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_consensus_result(nolzss_rlz_consensus_result *r);
 
 /* ---- relative-LZ archive: batches appended from the index ---------------------------------------- */
 /* Extension.  The index and the archive meet on the device: a batch is matched against the index as
@@ -1293,6 +1383,19 @@ int nolzss_debug_rlz_align_jobs(const char *query, size_t query_len, const char 
 int nolzss_debug_rlz_pileup(const char *block, size_t B, const char *const *targets, const size_t *target_lens, size_t k,
                             const nolzss_rlz_alignment *alignments, const uint64_t *op_offsets, size_t num_alignments,
                             const uint32_t *ops, size_t num_ops, int primary_only, int device, uint32_t *counts);
+/* The same with the insertion log, the allele table and the consensus (the log holds one slot per op, so no
+ * event is counted first; rlz_pileup_accumulate under `flags`, rlz_pileup_resolve, rlz_pileup_compose, rlz_pileup_alleles and the read-outs of
+ * nolzss_rlz_pileup_insertions and nolzss_rlz_pileup_consensus, the production functions) on the caller's alignments.
+ * Out: counts[B x 8]; *insertions: the whole allele table (min_count 1, fraction 0 / 1); *consensus: under *params, with
+ * its map; a record is the stretch between two separator bytes of the block.  It refuses everything
+ * nolzss_debug_rlz_pileup refuses, and an unknown flag bit, null results and the parameters nolzss_rlz_pileup_consensus
+ * refuses.  B == 0 succeeds without a launch; no alignment gives the consensus of empty counters.  Free both results with
+ * their free functions, whatever the status. */
+int nolzss_debug_rlz_pileup_consensus(const char *block, size_t B, const char *const *targets, const size_t *target_lens, size_t k,
+                                      const nolzss_rlz_alignment *alignments, const uint64_t *op_offsets, size_t num_alignments,
+                                      const uint32_t *ops, size_t num_ops, int primary_only, uint32_t flags,
+                                      const nolzss_rlz_consensus_params *params, int device, uint32_t *counts,
+                                      nolzss_rlz_insertions_result *insertions, nolzss_rlz_consensus_result *consensus);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and

@@ -188,6 +188,31 @@ class RlzVariantsResult(C.Structure):
     _fields_ = [("num_variants", C.c_size_t), ("variants", C.c_void_p)]
 
 
+class RlzInsertion(C.Structure):
+    """Mirror of nolzss_rlz_insertion (include/nolzss_hip.h)."""
+    _fields_ = [("position", C.c_uint64), ("record_offset", C.c_uint64), ("record", C.c_uint32), ("length", C.c_uint32),
+                ("count", C.c_uint32), ("depth", C.c_uint32), ("ins_total", C.c_uint32), ("truncated", C.c_uint32),
+                ("bases", C.c_uint64 * 2)]
+
+
+class RlzInsertionsResult(C.Structure):
+    """Mirror of nolzss_rlz_insertions_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_insertions", C.c_size_t), ("insertions", C.c_void_p)]
+
+
+class RlzConsensusParams(C.Structure):
+    """Mirror of nolzss_rlz_consensus_params (include/nolzss_hip.h)."""
+    _fields_ = [("min_depth", C.c_uint32), ("low", C.c_uint32), ("num", C.c_uint64), ("den", C.c_uint64)]
+
+
+class RlzConsensusResult(C.Structure):
+    """Mirror of nolzss_rlz_consensus_result (include/nolzss_hip.h)."""
+    _fields_ = [("length", C.c_size_t), ("text", C.c_void_p), ("num_records", C.c_size_t), ("record_offsets", C.c_void_p),
+                ("starts", C.c_void_p), ("called", C.c_uint64), ("low_positions", C.c_uint64), ("substitutions", C.c_uint64),
+                ("deleted", C.c_uint64), ("insertions", C.c_uint64), ("inserted_bases", C.c_uint64),
+                ("truncated_skipped", C.c_uint64)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -361,6 +386,17 @@ def _load():
     lib.nolzss_rlz_pileup_info.argtypes = [vp, C.POINTER(RlzPileupSummary)]
     lib.nolzss_rlz_pileup_close.argtypes = [vp]
     lib.nolzss_debug_rlz_pileup.argtypes = [vp, sz] + seqs[3:] + [vp, vp, sz, vp, sz, C.c_int, C.c_int, vp]
+    lib.nolzss_rlz_pileup_open_flags.argtypes = [vp, C.POINTER(RlzAlignParams), C.c_uint32, vpp]
+    lib.nolzss_rlz_pileup_log_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.nolzss_rlz_pileup_insertions.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(RlzInsertionsResult)]
+    lib.nolzss_free_rlz_insertions_result.argtypes = [C.POINTER(RlzInsertionsResult)]
+    lib.nolzss_free_rlz_insertions_result.restype = None
+    lib.nolzss_rlz_pileup_consensus.argtypes = [vp, C.POINTER(RlzConsensusParams), C.c_int, C.POINTER(RlzConsensusResult)]
+    lib.nolzss_free_rlz_consensus_result.argtypes = [C.POINTER(RlzConsensusResult)]
+    lib.nolzss_free_rlz_consensus_result.restype = None
+    lib.nolzss_debug_rlz_pileup_consensus.argtypes = [vp, sz] + seqs[3:] + [vp, vp, sz, vp, sz, C.c_int, C.c_uint32,
+                                                      C.POINTER(RlzConsensusParams), C.c_int, vp,
+                                                      C.POINTER(RlzInsertionsResult), C.POINTER(RlzConsensusResult)]
     lib.nolzss_debug_rlz_locate_shifts.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
@@ -450,6 +486,9 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_index_align", "nolzss_free_rlz_align_result", "nolzss_debug_rlz_align_jobs",
     "nolzss_rlz_pileup_open", "nolzss_rlz_pileup_add", "nolzss_rlz_pileup_counts", "nolzss_rlz_pileup_variants",
     "nolzss_free_rlz_variants_result", "nolzss_rlz_pileup_info", "nolzss_rlz_pileup_close", "nolzss_debug_rlz_pileup",
+    "nolzss_rlz_pileup_open_flags", "nolzss_rlz_pileup_log_info", "nolzss_rlz_pileup_insertions",
+    "nolzss_free_rlz_insertions_result", "nolzss_rlz_pileup_consensus", "nolzss_free_rlz_consensus_result",
+    "nolzss_debug_rlz_pileup_consensus",
 ]
 
 

@@ -36,6 +36,22 @@ ALIGN_DTYPE = np.dtype([("target", "<u8"), ("t_start", "<u8"), ("t_end", "<u8"),
 # nolzss_rlz_variant: an allele of the pileup that passed a variants query (RlzPileupHandle.variants)
 VARIANT_DTYPE = np.dtype([("position", "<u8"), ("record_offset", "<u8"), ("record", "<u4"), ("ref_base", "<u4"),
                           ("allele", "<u4"), ("count", "<u4"), ("depth", "<u4"), ("rev", "<u4")])
+# nolzss_rlz_insertion: an inserted allele of the pileup that passed an insertions query (RlzPileupHandle.insertions)
+INSERTION_DTYPE = np.dtype([("position", "<u8"), ("record_offset", "<u8"), ("record", "<u4"), ("length", "<u4"),
+                            ("count", "<u4"), ("depth", "<u4"), ("ins_total", "<u4"), ("truncated", "<u4"),
+                            ("bases", "<u8", (2,))])
+PILEUP_NORMALIZE = 1     # NOLZSS_RLZ_PILEUP_NORMALIZE
+PILEUP_INS_BASES = 64    # NOLZSS_RLZ_PILEUP_INS_BASES
+CONSENSUS_STATS = ("called", "low_positions", "substitutions", "deleted", "insertions", "inserted_bases", "truncated_skipped")
+
+
+def insertion_bases(record) -> bytes:
+    """The bases an INSERTION_DTYPE record keeps: the first min(length, 64) of the allele, as ACGT bytes."""
+    words = [int(w) for w in record["bases"]]
+    n = min(int(record["length"]), PILEUP_INS_BASES)
+    return bytes(b"ACGT"[(words[j >> 5] >> (62 - 2 * (j & 31))) & 3] for j in range(n))
+
+
 # NOLZSS_RLZ_PILEUP_CHANNELS: the eight counters a pileup keeps per block position, in this order
 PILEUP_CHANNELS = ("A", "C", "G", "T", "DEL", "INS", "REV", "BREAK")
 
@@ -1671,6 +1687,46 @@ def _variant_rule(min_count, min_fraction):
     return min_count, num, den
 
 
+def _consensus_params(min_depth, min_fraction, low):
+    """nolzss_rlz_consensus_params of a consensus query; ValueError for what the library would refuse -- before any
+    native call."""
+    min_depth = operator.index(min_depth)
+    try:
+        num, den = (operator.index(v) for v in min_fraction)
+    except (TypeError, ValueError):
+        raise ValueError("min_fraction is a pair of integers (num, den)") from None
+    if min_depth < 1 or min_depth >= 1 << 32:
+        raise ValueError("min_depth must be at least 1 and fit 32 bits")
+    if den < 1 or num < 0 or num > den or den >= 1 << 32:
+        raise ValueError(f"min_fraction must be a fraction between 0 and 1 with a denominator below 2^32, not {num} / {den}")
+    if low not in ("reference", "N"):
+        raise ValueError(f"low is 'reference' or 'N', not {low!r}")
+    return _lib.RlzConsensusParams(min_depth, 1 if low == "N" else 0, num, den)
+
+
+def _insertions_out(res):
+    out = np.zeros(res.num_insertions, dtype=INSERTION_DTYPE)
+    if res.num_insertions:
+        C.memmove(out.ctypes.data, res.insertions, res.num_insertions * INSERTION_DTYPE.itemsize)
+    return out
+
+
+def _consensus_out(res, return_map, block_length):
+    """nolzss_rlz_consensus_result -> dict(records: [bytes, ...], the seven statistics, starts with return_map)"""
+    text = C.string_at(res.text, res.length) if res.length else b""
+    offsets = np.zeros(res.num_records + 1, dtype=np.uint64)
+    if res.record_offsets:
+        C.memmove(offsets.ctypes.data, res.record_offsets, offsets.nbytes)
+    out = {"records": [text[int(offsets[r]):int(offsets[r + 1]) - 1] for r in range(res.num_records)]}
+    out.update({name: int(getattr(res, name)) for name in CONSENSUS_STATS})
+    if return_map:
+        starts = np.zeros(block_length + 1, dtype=np.uint64)
+        if res.starts:
+            C.memmove(starts.ctypes.data, res.starts, starts.nbytes)
+        out["starts"] = starts
+    return out
+
+
 class RlzPileupHandle:
     """Extension: eight counters per position of the block of an index, kept on the device and fed by batches that go
     through the align path of the index (C ABI nolzss_rlz_pileup_*).  It keeps the index handle alive.  A context
@@ -1681,11 +1737,14 @@ class RlzPileupHandle:
 
     @classmethod
     def open(cls, index_handle, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 31,
-             min_score: int = 40, band: int = 16, max_flank: int = 256):
-        """C ABI nolzss_rlz_pileup_open (its header states the rules)."""
+             min_score: int = 40, band: int = 16, max_flank: int = 256, normalize_indels: bool = False):
+        """C ABI nolzss_rlz_pileup_open / nolzss_rlz_pileup_open_flags (the header states the rules)."""
         params = _align_params(min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank)
         h = C.c_void_p()
-        check(lib.nolzss_rlz_pileup_open(index_handle._handle(), C.byref(params), C.byref(h)))
+        if normalize_indels:
+            check(lib.nolzss_rlz_pileup_open_flags(index_handle._handle(), C.byref(params), PILEUP_NORMALIZE, C.byref(h)))
+        else:
+            check(lib.nolzss_rlz_pileup_open(index_handle._handle(), C.byref(params), C.byref(h)))
         return cls(h, index_handle)
 
     def _handle(self):
@@ -1703,6 +1762,9 @@ class RlzPileupHandle:
         check(lib.nolzss_rlz_pileup_info(h, C.byref(info)))
         out = {name: int(getattr(info, name)) for name, _ in _lib.RlzPileupSummary._fields_ if name != "params"}
         out.update({name: int(getattr(info.params, name)) for name, _ in _lib.RlzAlignParams._fields_})
+        flags, events, log_bytes = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        check(lib.nolzss_rlz_pileup_log_info(h, C.byref(flags), C.byref(events), C.byref(log_bytes)))
+        out.update(normalize_indels=bool(flags.value & PILEUP_NORMALIZE), insertion_events=events.value, log_bytes=log_bytes.value)
         return out
 
     def add(self, targets, primary_only: bool = True) -> dict:
@@ -1739,6 +1801,37 @@ class RlzPileupHandle:
             return out
         finally:
             lib.nolzss_free_rlz_variants_result(C.byref(res))
+
+    def insertions(self, min_count: int = 2, min_fraction=(1, 2)) -> np.ndarray:
+        """The inserted alleles that reach min_count observations and min_fraction = (num, den) of the depth, as
+        INSERTION_DTYPE ascending by (position, length, bases).  C ABI nolzss_rlz_pileup_insertions."""
+        rule = _variant_rule(min_count, min_fraction)
+        h = self._handle()
+        res = _lib.RlzInsertionsResult()
+        try:
+            check(lib.nolzss_rlz_pileup_insertions(h, *rule, C.byref(res)))
+            return _insertions_out(res)
+        finally:
+            lib.nolzss_free_rlz_insertions_result(C.byref(res))
+
+    def consensus(self, min_depth: int = 1, min_fraction=(1, 2), low: str = "reference", return_map: bool = False) -> dict:
+        """The sample's sequence as the counters and the insertion alleles call it -> dict(records: one bytes per
+        reference record, called, low_positions, substitutions, deleted, insertions, inserted_bases,
+        truncated_skipped, and with return_map starts: block_length + 1 offsets into the records joined by one
+        separator each).  C ABI nolzss_rlz_pileup_consensus."""
+        params = _consensus_params(min_depth, min_fraction, low)
+        h = self._handle()
+        res = _lib.RlzConsensusResult()
+        try:
+            check(lib.nolzss_rlz_pileup_consensus(h, C.byref(params), 1 if return_map else 0, C.byref(res)))
+            block_length = 0
+            if return_map:
+                info = _lib.RlzPileupSummary()
+                check(lib.nolzss_rlz_pileup_info(h, C.byref(info)))
+                block_length = int(info.block_length)
+            return _consensus_out(res, return_map, block_length)
+        finally:
+            lib.nolzss_free_rlz_consensus_result(C.byref(res))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -2289,3 +2382,30 @@ def debug_rlz_pileup(block, targets, alignments, op_offsets, ops, primary_only: 
                                       ops.ctypes.data if ops.size else None, ops.size, 1 if primary_only else 0,
                                       _default_device, out.ctypes.data if out.size else None))
     return out
+
+
+def debug_rlz_pileup_consensus(block, targets, alignments, op_offsets, ops, primary_only: bool = False,
+                               normalize_indels: bool = False, min_depth: int = 1, min_fraction=(1, 2), low: str = "reference"):
+    """The pileup, allele-table and consensus stages on caller alignments (nolzss_debug_rlz_pileup_consensus, test hook);
+    the inputs of debug_rlz_pileup, the flag of an open and the parameters of a consensus.  Returns dict(counts: the
+    (len(block), 8) counters, insertions: the full allele table as INSERTION_DTYPE, consensus: as
+    RlzPileupHandle.consensus returns it, with its map)."""
+    params = _consensus_params(min_depth, min_fraction, low)
+    block = block.encode("ascii") if isinstance(block, str) else bytes(block)
+    recs = np.ascontiguousarray(alignments, dtype=ALIGN_DTYPE)
+    offsets = np.ascontiguousarray(op_offsets, dtype=np.uint64)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    if offsets.size != recs.size + 1:
+        raise ValueError("op_offsets holds one entry per alignment and one more")
+    out = np.zeros((len(block), len(PILEUP_CHANNELS)), dtype=np.uint32)
+    ins, cons = _lib.RlzInsertionsResult(), _lib.RlzConsensusResult()
+    try:
+        check(lib.nolzss_debug_rlz_pileup_consensus(block, len(block), *_seq_args(targets, "target"),
+                                                    recs.ctypes.data if recs.size else None, offsets.ctypes.data, recs.size,
+                                                    ops.ctypes.data if ops.size else None, ops.size, 1 if primary_only else 0,
+                                                    PILEUP_NORMALIZE if normalize_indels else 0, C.byref(params), _default_device,
+                                                    out.ctypes.data if out.size else None, C.byref(ins), C.byref(cons)))
+        return {"counts": out, "insertions": _insertions_out(ins), "consensus": _consensus_out(cons, bool(len(block)), len(block))}
+    finally:
+        lib.nolzss_free_rlz_insertions_result(C.byref(ins))
+        lib.nolzss_free_rlz_consensus_result(C.byref(cons))

@@ -188,7 +188,8 @@ void debug_align_jobs(const char *query, size_t query_len, const char *reference
 // pileup on them, with counters taken from the arena.
 void debug_pileup(const char *block, size_t B, const char *const *targets, const size_t *target_lens, size_t k,
                   const nolzss_rlz_alignment *alignments, const uint64_t *op_offsets, size_t C, const uint32_t *ops, size_t N,
-                  bool primary_only, int device, uint32_t *counts) {
+                  bool primary_only, int device, uint32_t *counts, uint32_t flags = 0, const ConsensusRule *rule = nullptr,
+                  nolzss_rlz_insertions_result *ins = nullptr, nolzss_rlz_consensus_result *cons = nullptr) {
     if ((B && (!block || !counts)) || (k && (!targets || !target_lens)) || !op_offsets || (C && !alignments) || (N && !ops))
         throw std::invalid_argument("null argument");
     if (B >= kAlignMaxTarget || C >= (size_t(1) << 24) || N >= kAlignMaxTarget) throw std::invalid_argument("a block, alignments or ops beyond 2^28");
@@ -235,7 +236,7 @@ void debug_pileup(const char *block, size_t B, const char *const *targets, const
             throw std::invalid_argument(at + ": the ops do not consume exactly [t_start, t_end) and [r_start, r_end)");
     }
     if (B) std::memset(counts, 0, sizeof(uint32_t) * kPileupChannels * B);
-    if (C == 0 || B == 0) return;
+    if (B == 0 || (C == 0 && !rule)) return;
     b.tcat.resize(bases + k);
     b.separators.resize(k);
     b.offsets.resize(k);
@@ -252,14 +253,17 @@ void debug_pileup(const char *block, size_t B, const char *const *targets, const
     std::memcpy(recs.data(), alignments, sizeof(AlignRec) * C);
     std::memset(recs.data() + C, 0xff, sizeof(AlignRec) * kPad);
     std::vector<uint32_t> hops(N + kPad, 0xffffffffu);
-    std::memcpy(hops.data(), ops, sizeof(uint32_t) * N);
+    if (N) std::memcpy(hops.data(), ops, sizeof(uint32_t) * N);
     const size_t foot = rlz_pileup_footprint((uint32_t)B);
     DeviceRestore restore;
     Session ses(device, nullptr);
     Context &ctx = ses.ctx();
     hipStream_t s = ctx.stream;
     ctx.arena.reserve(foot + 3 * (B + 1 + b.tcat.size()) + sizeof(AlignRec) * (C + kPad) + 8 * (C + 1) + 24 * (N + kPad) +
-                      sizeof(uint32_t) * kPileupChannels * B + (size_t(64) << 20));
+                      sizeof(uint32_t) * kPileupChannels * B + (size_t(64) << 20) +
+                      (rule ? (sizeof(PileupEvent) + kAllelesArenaPerEvent + kInsertionsArenaPerAllele + sizeof(PileupInsertionRec)) * (N + 1) +
+                                  (kConsensusArenaPerBase + 8 * (1 + (size_t)NOLZSS_RLZ_PILEUP_INS_BASES)) * (B + 1) + 8 * (xseps.size() + 1)
+                            : 0));
     ArenaRewind rewind(ctx.arena);
     uint8_t *d_block = ctx.arena.alloc<uint8_t>(B + 1);
     upload_bytes(ctx, d_block, xbytes.data(), B + 1);
@@ -273,7 +277,13 @@ void debug_pileup(const char *block, size_t B, const char *const *targets, const
     uint32_t *d_ops = ctx.arena.alloc<uint32_t>(N + kPad);
     void *d_counters = ctx.arena.alloc<uint8_t>(foot);
     uint32_t *d_out = ctx.arena.alloc<uint32_t>(kPileupChannels * B);
-    unsigned long long *d_stats = ctx.arena.alloc<unsigned long long>(3);
+    unsigned long long *d_stats = ctx.arena.alloc<unsigned long long>(kPileupStats);
+    PileupLog log;  // without a rule: no room, every event is dropped at the clamp
+    log.flags = flags;
+    if (rule) {
+        log.events = ctx.arena.alloc<PileupEvent>(N + 1);  // an alignment's I ops are among its ops
+        log.capacity = N;
+    }
     HIP_CHECK(hipMemcpyAsync(d_recs, recs.data(), sizeof(AlignRec) * (C + kPad), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_off, op_offsets, 8 * (C + 1), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_ops, hops.data(), 4 * (N + kPad), hipMemcpyHostToDevice, s));
@@ -286,11 +296,20 @@ void debug_pileup(const char *block, size_t B, const char *const *targets, const
     a.recs = d_recs;
     a.op_offsets = d_off;
     a.ops = d_ops;
-    rlz_pileup_accumulate(ctx, view, a, qt, primary_only, d_stats);
+    rlz_pileup_accumulate(ctx, view, a, qt, xt, primary_only, log, d_stats);
     rlz_pileup_resolve(ctx, view);
     rlz_pileup_compose(ctx, view, xt, 0, (uint32_t)B, d_out);
     HIP_CHECK(hipMemcpyAsync(counts, d_out, sizeof(uint32_t) * kPileupChannels * B, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
+    if (rule) {  // the allele table in full (count >= 1, fraction 0 / 1), then the consensus with its map
+        unsigned long long stats[kPileupStats];
+        download_bytes(ctx, stats, d_stats, sizeof stats);
+        const uint32_t E = (uint32_t)(stats[3] < N ? stats[3] : N);
+        uint32_t G = 0;
+        const PileupAllele *d_alleles = rlz_pileup_alleles(ctx, log.events, E, &G);
+        deliver_insertions(ctx, view, xt, d_alleles, G, PileupRule(), *ins);
+        deliver_consensus(ctx, view, xt, (uint32_t)xseps.size(), d_alleles, G, *rule, true, *cons);
+    }
     HIP_CHECK(hipGetLastError());
     ctx.prof.collect();
 }
@@ -305,6 +324,28 @@ int nolzss_debug_rlz_pileup(const char *block, size_t B, const char *const *targ
     return guarded([&] {
         debug_pileup(block, B, targets, target_lens, k, alignments, op_offsets, num_alignments, ops, num_ops, primary_only != 0,
                      device, counts);
+    });
+}
+
+int nolzss_debug_rlz_pileup_consensus(const char *block, size_t B, const char *const *targets, const size_t *target_lens, size_t k,
+                                      const nolzss_rlz_alignment *alignments, const uint64_t *op_offsets, size_t num_alignments,
+                                      const uint32_t *ops, size_t num_ops, int primary_only, uint32_t flags,
+                                      const nolzss_rlz_consensus_params *params, int device, uint32_t *counts,
+                                      nolzss_rlz_insertions_result *insertions, nolzss_rlz_consensus_result *consensus) {
+    return guarded([&] {
+        if (!insertions || !consensus) throw std::invalid_argument("output pointer is null");
+        std::memset(insertions, 0, sizeof *insertions);
+        std::memset(consensus, 0, sizeof *consensus);
+        if (flags & ~NOLZSS_RLZ_PILEUP_NORMALIZE) throw std::invalid_argument("rlz pileup: unknown flag bits");
+        const ConsensusRule rule = check_consensus_params(params);
+        try {
+            debug_pileup(block, B, targets, target_lens, k, alignments, op_offsets, num_alignments, ops, num_ops, primary_only != 0,
+                         device, counts, flags, &rule, insertions, consensus);
+        } catch (...) {
+            nolzss_free_rlz_insertions_result(insertions);
+            nolzss_free_rlz_consensus_result(consensus);
+            throw;
+        }
     });
 }
 

@@ -101,12 +101,23 @@ struct nolzss_rlz_pileup {
     std::mutex mu;
     bool dirty = false;  // difference entries were added since the last resolve
     uint64_t targets = 0, alignments = 0, ops = 0, columns = 0, adds = 0;  // running totals
+    // The insertion log: one event per I op of a kept alignment, in a device allocation of its own that grows
+    // geometrically (none until the first event).  The allele table is built from it on the first read after an add and
+    // kept, in another allocation, until the next add.
+    uint32_t flags = 0;  // NOLZSS_RLZ_PILEUP_*
+    nolzss::PileupEvent *d_log = nullptr;
+    uint64_t events = 0, log_capacity = 0;
+    nolzss::PileupAllele *d_alleles = nullptr;
+    uint64_t alleles = 0, alleles_capacity = 0;
+    bool alleles_valid = false;
     ~nolzss_rlz_pileup() {  // (the calling thread's current device stays what it was)
-        if (!d_base) return;
+        if (!d_base && !d_log && !d_alleles) return;
         int current = -1;
         const bool known = hipGetDevice(&current) == hipSuccess;
         (void)hipSetDevice(device);
-        (void)hipFree(d_base);
+        if (d_base) (void)hipFree(d_base);
+        if (d_log) (void)hipFree(d_log);
+        if (d_alleles) (void)hipFree(d_alleles);
         if (known && current != device) (void)hipSetDevice(current);
     }
 };
@@ -199,6 +210,18 @@ struct AlignRun {
 };
 std::string align_batch(Context &ctx, const nolzss_rlz_index &h, const Batch &b, size_t k, const nolzss_rlz_align_params &p,
                         size_t extra_per_slot, AlignRun &run);
+// What the insertions and consensus queries of a pileup and their debug hook (rlz_pileup_api.hip, debug_rlz.hip) share:
+// the refusals of the two rules, each before any device work, and the read-outs over resolved counters and an allele
+// table of G entries (device memory), brought down into the host blocks of a result (chunked by NOLZSS_RLZ_LOCATE_CHUNK).
+// A throw leaves what was allocated so far in the result: the caller frees it.  `records`: the reference records of
+// the block.  Arena bytes the two take: kInsertionsArenaPerAllele per allele, kConsensusArenaPerBase per block base.
+PileupRule check_pileup_rule(uint32_t min_count, uint64_t num, uint64_t den, const char *what);
+ConsensusRule check_consensus_params(const nolzss_rlz_consensus_params *params);
+constexpr size_t kAllelesArenaPerEvent = 100, kInsertionsArenaPerAllele = 9, kConsensusArenaPerBase = 9;
+void deliver_insertions(Context &ctx, const PileupView &v, const PackedText &block, const PileupAllele *d_alleles, uint32_t G,
+                        const PileupRule &rule, nolzss_rlz_insertions_result &out);
+void deliver_consensus(Context &ctx, const PileupView &v, const PackedText &block, uint32_t records, const PileupAllele *d_alleles,
+                       uint32_t G, const ConsensusRule &rule, bool want_map, nolzss_rlz_consensus_result &out);
 
 }  // namespace api
 }  // namespace nolzss

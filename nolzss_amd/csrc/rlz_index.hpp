@@ -1,8 +1,8 @@
 // rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
 // rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds, rlz_seed_chain.hip for
-// their colinear chains, rlz_align.hip for the base-level alignments of those and rlz_pileup.hip for the pileup counts of
-// the alignments; the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip,
+// their colinear chains, rlz_align.hip for the base-level alignments of those, rlz_pileup.hip for the pileup counts of
+// the alignments and rlz_consensus.hip for the insertion alleles and the consensus of a pileup; the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip,
 // rlz_pileup_api.hip).
 #pragma once
 #include "pipeline.hpp"
@@ -269,15 +269,36 @@ struct PileupRule {  // of a variants query: count >= min_count and count * den 
     uint32_t min_count = 1;
     uint64_t num = 0, den = 1;
 };
+// The insertion log of a pileup (device memory of the handle's own): one event per I op of a kept alignment -- where INS
+// was counted, the op's length and the first kPileupInsBases bases of the allele as two words of big-endian 2-bit codes.
+constexpr uint32_t kPileupNormalize = 1u;    // NOLZSS_RLZ_PILEUP_NORMALIZE
+constexpr uint32_t kPileupMaxShift = 1024;   // NOLZSS_RLZ_PILEUP_MAX_SHIFT
+constexpr uint32_t kPileupInsBases = 64;     // NOLZSS_RLZ_PILEUP_INS_BASES
+constexpr uint32_t kPileupStats = 4;         // words of d_stats: alignments kept, their ops, their columns, events logged
+struct PileupEvent {
+    uint32_t position, length;
+    uint64_t bases[2];
+};
+struct PileupLog {  // what an accumulate appends to: event j of the add goes to events[base + j] iff base + j < capacity
+    PileupEvent *events = nullptr;
+    uint64_t base = 0, capacity = 0;
+    uint32_t flags = 0;
+};
 // Bytes of one allocation that holds the arrays of a view (each 256-byte aligned), and the view over such an allocation.
 size_t rlz_pileup_footprint(uint32_t B);
 PileupView rlz_pileup_view(void *d_base, uint32_t B);
-// The alignments of rlz_align_ops (arena memory) added to the counters: `batch` is the packed target batch they were
-// aligned from.  d_stats (3 words, device memory, zeroed here): the alignments kept, their ops and their columns.
-// Every arena array is taken before the first kernel that writes a counter.  Arena memory: 16 bytes per op and the
-// scans' tile sums.  No position outside [r_start, r_end) of an op's alignment is written.
-void rlz_pileup_accumulate(Context &ctx, const PileupView &v, const AlignOut &a, const PackedText &batch, bool primary_only,
-                           unsigned long long *d_stats);
+// *d_count (device memory, zeroed here) = the I ops of the kept alignments: the events an accumulate of them appends.
+// Writes nothing else.
+void rlz_pileup_count_insertions(Context &ctx, const AlignOut &a, const PackedText &batch, uint32_t B, bool primary_only,
+                                 unsigned long long *d_count);
+// The alignments of rlz_align_ops (arena memory) added to the counters and their I ops to the log: `batch` is the packed
+// target batch they were aligned from, `block` the packed index text.  With kPileupNormalize in log.flags every D and I
+// op behind an `=` op is shifted to its leftmost block position (the rule: nolzss_rlz_pileup_open_flags).  d_stats
+// (kPileupStats words, device memory, zeroed here).  Every arena array is taken before the first kernel that writes a
+// counter.  Arena memory: 16 bytes per op and the scans' tile sums.  No position outside [r_start, r_end) of an op's
+// alignment is written, and no event outside [0, log.capacity).
+void rlz_pileup_accumulate(Context &ctx, const PileupView &v, const AlignOut &a, const PackedText &batch,
+                           const PackedText &block, bool primary_only, const PileupLog &log, unsigned long long *d_stats);
 // depth_eq / depth_rev from diff_eq / diff_rev: two scans over B + 1 entries
 void rlz_pileup_resolve(Context &ctx, const PileupView &v);
 // The eight channels of positions [start, start + count) of the block into d_out (count x 8), after a resolve: `block`
@@ -289,6 +310,46 @@ void rlz_pileup_variant_flags(Context &ctx, const PileupView &v, const PackedTex
 // The records [first, first + count) of the query, d_off = the exclusive scan of d_n, into d_out[0 .. count)
 void rlz_pileup_variant_records(Context &ctx, const PileupView &v, const PackedText &block, const PileupRule &rule,
                                 const uint32_t *d_off, uint64_t first, uint32_t count, PileupVariantRec *d_out);
+
+// ---- insertion alleles and the consensus (rlz_consensus.hip; DESIGN.md 5, "Relative-LZ index: consensus") ------------
+// The allele table of a log: its distinct events ascending by (position, length, bases[0], bases[1]), each with the
+// number of events that equal it.
+struct PileupAllele {
+    uint32_t position, length, count, pad;
+    uint64_t bases[2];
+};
+struct PileupInsertionRec {  // nolzss_rlz_insertion
+    uint64_t position, record_offset;
+    uint32_t record, length, count, depth, ins_total, truncated;
+    uint64_t bases[2];
+};
+struct ConsensusRule {  // nolzss_rlz_consensus_params
+    uint32_t min_depth = 1, low = 0;
+    uint64_t num = 0, den = 1;
+};
+constexpr uint32_t kConsensusStats = 7;  // called, low_positions, substitutions, deleted, insertions, inserted_bases, truncated_skipped
+// E >= 1 events -> the table in arena memory (E entries allocated, *count of them written).  Waits for the stream once.
+// Arena memory: 56 bytes per event and the sorts' histograms.
+const PileupAllele *rlz_pileup_alleles(Context &ctx, const PileupEvent *d_events, uint32_t E, uint32_t *count);
+// d_n[g] = 1 where allele g < G passes the rule against the depth of its position, else 0 (after a resolve)
+void rlz_pileup_insertion_flags(Context &ctx, const PileupView &v, const PackedText &block, const PileupAllele *d_alleles,
+                                uint32_t G, const PileupRule &rule, uint32_t *d_n);
+// The records [first, first + count) of the query, d_off = the exclusive scan of d_n, into d_out[0 .. count)
+void rlz_pileup_insertion_records(Context &ctx, const PileupView &v, const PackedText &block, const PileupAllele *d_alleles,
+                                  uint32_t G, const uint32_t *d_n, const uint32_t *d_off, uint64_t first, uint32_t count,
+                                  PileupInsertionRec *d_out);
+// d_len[p] = the bytes position p < B emits, d_len[B] = 0; d_stats (kConsensusStats words, zeroed here) summed over
+// the positions (after a resolve)
+void rlz_consensus_lengths(Context &ctx, const PileupView &v, const PackedText &block, const PileupAllele *d_alleles, uint32_t G,
+                           const ConsensusRule &rule, uint32_t *d_len, unsigned long long *d_stats);
+// The bytes [first, first + count) of the text, d_off = the exclusive scan of d_len, into d_out[0 .. count)
+void rlz_consensus_text(Context &ctx, const PileupView &v, const PackedText &block, const PileupAllele *d_alleles, uint32_t G,
+                        const ConsensusRule &rule, const uint32_t *d_off, uint64_t first, uint32_t count, uint8_t *d_out);
+// d_out[i] = d_off[first + i] in 64 bits, i < count
+void rlz_consensus_starts(Context &ctx, const uint32_t *d_off, uint64_t first, uint32_t count, uint64_t *d_out);
+// d_out[r] = the offset in the text where record r < records begins, d_out[records] = total + 1
+void rlz_consensus_record_offsets(Context &ctx, const PackedText &block, const uint32_t *d_off, uint32_t B, uint32_t records,
+                                  uint64_t total, uint64_t *d_out);
 
 constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
 

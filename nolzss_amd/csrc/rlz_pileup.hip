@@ -11,12 +11,15 @@
 // their length.  X, D, I and BREAK are bounded by the edit distance and the number of alignments: one atomic per column
 // (X, D) or per op (I) or per alignment end (BREAK) on dense counters.  A read resolves the difference entries by one
 // scan each (the handle keeps a dirty flag) and composes the eight channels: the `=` depth of a position is credited to
-// the channel of the block's own base.
+// the channel of the block's own base.  Every I op also appends one event -- position, length, the first 64 bases -- to the
+// handle's insertion log (the allele table and the consensus over it: rlz_consensus.hip), and on request D and I ops are
+// counted at their leftmost block position ("Relative-LZ index: consensus"): a shift is a bounded walk over
+// the block by the op's own lane, and the `=` columns it moves are difference entries again.
 //
 // No kernel here spins or communicates between workgroups; every loop bound is a field clamped on load to the arrays it
 // indexes, and no position outside [r_start, r_end) of an op's alignment is written (the -1 of a difference entry
 // falls at r_end <= B, which is why the arrays hold B + 1 entries).
-#include "rlz_index.hpp"
+#include "rlz_pileup_device.hpp"
 
 #include "scan.hpp"
 
@@ -25,10 +28,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr size_t kAlign = 256;  // bytes: every array of a view starts on such a boundary
-
-__device__ __forceinline__ uint32_t base_of(uint64_t word, uint32_t pos) {  // big-endian 2-bit codes, 32 per word
-    return (uint32_t)(word >> (62u - 2u * (pos & 31u))) & 3u;
-}
 
 // The alignment of op i: the largest c with op_offsets[c] <= i.  Loop: at most 32 halvings.
 __device__ __forceinline__ uint32_t alignment_of_op(const uint64_t *__restrict__ op_offsets, uint32_t C, uint32_t i) {
@@ -123,17 +122,44 @@ __global__ __launch_bounds__(kThreads) void rlz_pileup_alignments_kernel(const A
     }
 }
 
+// The length of the `=` op in front of op i in forward-block orientation -- op i - 1 on the forward strand, op i + 1 on
+// the reverse strand, inside the alignment's ops [o0, o_end) --, 0 if there is none or it has another code.  No loop.
+__device__ __forceinline__ uint32_t eq_run_before(const uint32_t *__restrict__ ops, uint32_t i, uint32_t o0, uint32_t o_end,
+                                                  bool rc) {
+    if (rc ? i + 1u >= o_end : i <= o0) return 0u;
+    const uint32_t op = ops[rc ? i + 1u : i - 1u];
+    return (op & 0xfu) == kAlignEq ? op >> 4 : 0u;
+}
+
+// The shift of a deletion of n >= 1 block bases at [r, r + n): the largest s <= L with X[r - j] == X[r + n - j] for all
+// 1 <= j <= s.  The caller has made sure that L <= r and L <= kPileupMaxShift.  Loop: at most L steps.
+__device__ __forceinline__ uint32_t deletion_shift(const uint64_t *__restrict__ xwords, uint32_t r, uint32_t n, uint32_t L) {
+    uint32_t s = 0;
+    while (s < L) {
+        const uint32_t a = r - s - 1u, b = a + n;
+        if (base_of(xwords[a >> 5], a) != base_of(xwords[b >> 5], b)) break;
+        ++s;
+    }
+    return s;
+}
+
 // One lane per op i < nops.  T and R: the target and block bases its alignment consumes in front of it.  Its block
 // positions are r_start + R + j on the forward strand and r_end - 1 - (R + j) on the reverse strand, j < n, where n is
-// the op's length clamped to what is left of [r_start, r_end) -- and, for X, of the aligned part of the target.
-// Loops: the bisection; the n columns of an X or a D op.
+// the op's length clamped to what is left of [r_start, r_end) -- and, for X and I, of the aligned part of the target.
+// With kPileupNormalize a D or an I op behind an `=` op moves left by its shift s (at most kPileupMaxShift, and never
+// in front of r_start); the `=` op in front of a D gives up its last s positions, which the D op counts behind the gap.
+// Every I op appends one event to the log, clamped to its capacity.
+// Loops: the bisection; the n columns of an X or a D op; a shift (at most kPileupMaxShift steps); the kPileupInsBases
+// bases of an event.
 __global__ __launch_bounds__(kThreads) void rlz_pileup_ops_kernel(const AlignRec *__restrict__ recs,
                                                                   const uint64_t *__restrict__ op_offsets, uint32_t C,
                                                                   const uint32_t *__restrict__ ops, uint32_t nops,
                                                                   const uint32_t *__restrict__ tpre,
                                                                   const uint32_t *__restrict__ rpre,
                                                                   const uint64_t *__restrict__ qwords, TermTable tt,
-                                                                  uint32_t qn, PileupView v, bool primary_only) {
+                                                                  uint32_t qn, PileupView v, bool primary_only,
+                                                                  const uint64_t *__restrict__ xwords, PileupLog log,
+                                                                  unsigned long long *__restrict__ logged) {
     const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     if (gid >= nops) return;
     const uint32_t i = (uint32_t)gid;
@@ -141,18 +167,51 @@ __global__ __launch_bounds__(kThreads) void rlz_pileup_ops_kernel(const AlignRec
     const uint64_t o64 = op_offsets[c];
     if (o64 > i) return;  // (an op of no alignment: none by construction)
     const uint32_t o0 = (uint32_t)o64;
+    const uint64_t e64 = op_offsets[c + 1u];
+    const uint32_t o_end = e64 < (uint64_t)nops ? (uint32_t)e64 : nops;
     const Geometry g = geometry_of(recs[c], tt, qn, v.B, primary_only);
     if (!g.kept) return;
     const uint32_t T = tpre[i] - tpre[o0], R = rpre[i] - rpre[o0];
     const uint32_t span = g.r_end - g.r_start;
     const uint32_t op = ops[i], code = op & 0xfu;
+    const bool normalize = (log.flags & kPileupNormalize) != 0;
     uint32_t n = op >> 4;
-    if (code == kAlignI) {  // once per op, at the base in front of the walk: clamp(r - 1, r_start, r_end - 1)
+    if (code == kAlignI) {  // once per op, at the base in front of the walk: clamp(r - s - 1, r_start, r_end - 1)
         const uint32_t Rc = R < span ? R : span;
         const uint32_t r = g.rc ? g.r_end - Rc : g.r_start + Rc;
-        uint32_t at = r > g.r_start ? r - 1u : g.r_start;
+        // the op's ni target bases, W in forward-block orientation: W[j] is the batch position below, complemented on
+        // the reverse strand (t_at + T + ni <= the target's end <= qn)
+        const uint32_t ni = T < g.t_span ? (n < g.t_span - T ? n : g.t_span - T) : 0u;
+        auto wbase = [&](uint32_t j) {
+            const uint32_t tp = g.rc ? g.t_at + T + (ni - 1u - j) : g.t_at + T + j;
+            const uint32_t b = base_of(qwords[tp >> 5], tp);
+            return g.rc ? 3u - b : b;
+        };
+        uint32_t s = 0;
+        if (normalize && ni) {
+            uint32_t L = eq_run_before(ops, i, o0, o_end, g.rc);
+            L = L < kPileupMaxShift ? L : kPileupMaxShift;
+            L = L < r - g.r_start ? L : r - g.r_start;
+            while (s < L) {  // each step rotates the inserted string by one: X[r - j] against W[(ni - j) mod ni]
+                const uint32_t j = s + 1u, a = r - j;
+                if (base_of(xwords[a >> 5], a) != wbase((ni - j % ni) % ni)) break;
+                ++s;
+            }
+        }
+        const uint32_t rs = r - s;
+        uint32_t at = rs > g.r_start ? rs - 1u : g.r_start;
         at = at < g.r_end - 1u ? at : g.r_end - 1u;
         atomicAdd(v.ins + at, 1u);
+        const uint64_t slot = log.base + atomicAdd(logged, 1ull);
+        if (slot >= log.capacity) return;  // (none by construction: the capacity was secured for the counted events)
+        PileupEvent ev;
+        ev.position = at;
+        ev.length = n;
+        ev.bases[0] = ev.bases[1] = 0;
+        const uint32_t m = ni < kPileupInsBases ? ni : kPileupInsBases, back = ni ? ni - s % ni : 0u;
+        for (uint32_t j = 0; j < m; ++j)  // W'[j] = W[(j - s) mod ni]
+            ev.bases[j >> 5] |= (uint64_t)wbase((j + back) % ni) << (62u - 2u * (j & 31u));
+        log.events[slot] = ev;
         return;
     }
     if (code != kAlignEq && code != kAlignX && code != kAlignD) return;
@@ -165,10 +224,30 @@ __global__ __launch_bounds__(kThreads) void rlz_pileup_ops_kernel(const AlignRec
     if (n == 0) return;
     const uint32_t lo = g.rc ? g.r_end - R - n : g.r_start + R;  // the op's positions are [lo, lo + n)
     if (code == kAlignEq) {
+        uint32_t keep = n;
+        if (normalize && (g.rc ? i > o0 : i + 1u < o_end)) {  // a D op behind it takes the positions it shifts over
+            const uint32_t next = ops[g.rc ? i - 1u : i + 1u];
+            uint32_t nd = next >> 4;
+            nd = nd < g.r_end - (lo + n) ? nd : g.r_end - (lo + n);
+            if ((next & 0xfu) == kAlignD && nd)
+                keep = n - deletion_shift(xwords, lo + n, nd, n < kPileupMaxShift ? n : kPileupMaxShift);
+        }
+        if (keep == 0) return;
         atomicAdd(v.diff_eq + lo, 1u);
-        atomicAdd(v.diff_eq + (lo + n), 0xffffffffu);  // (lo + n <= r_end <= B: the arrays hold B + 1 entries)
+        atomicAdd(v.diff_eq + (lo + keep), 0xffffffffu);  // (lo + keep <= r_end <= B: the arrays hold B + 1 entries)
     } else if (code == kAlignD) {
-        for (uint32_t j = 0; j < n; ++j) atomicAdd(v.del + (lo + j), 1u);
+        uint32_t s = 0;
+        if (normalize) {
+            uint32_t L = eq_run_before(ops, i, o0, o_end, g.rc);
+            L = L < kPileupMaxShift ? L : kPileupMaxShift;
+            L = L < lo - g.r_start ? L : lo - g.r_start;
+            s = deletion_shift(xwords, lo, n, L);
+        }
+        for (uint32_t j = 0; j < n; ++j) atomicAdd(v.del + (lo - s + j), 1u);
+        if (s) {  // the `=` columns that moved behind the gap: [lo - s + n, lo + n), the block's own base
+            atomicAdd(v.diff_eq + (lo - s + n), 1u);
+            atomicAdd(v.diff_eq + (lo + n), 0xffffffffu);
+        }
     } else {
         const uint32_t t0 = g.t_at + T;  // (t0 + n <= the target's end <= qn)
         uint64_t w = 0;
@@ -186,35 +265,23 @@ __global__ __launch_bounds__(kThreads) void rlz_pileup_ops_kernel(const AlignRec
     }
 }
 
-// first and record of block position p < B, and whether p is a separator
-__device__ __forceinline__ uint32_t block_record_of(const TermTable &t, uint32_t p, uint32_t &first, bool &separator) {
-    uint32_t k = term_lower_bound(t, p);
-    k = k < t.count ? k : t.count - 1;
-    separator = t.pos[k] == p;
-    first = k ? t.pos[k - 1] + 1u : 0u;
-    return k;
-}
-
-// The eight channels of position p < B after a resolve; returns the block's base there.  A separator: all zero.
-__device__ __forceinline__ uint32_t channels_of(const PileupView &v, const uint64_t *__restrict__ xwords, bool separator,
-                                                uint32_t p, uint32_t ch[kPileupChannels]) {
-    const uint32_t b = base_of(xwords[p >> 5], p);
-    if (separator) {
-#pragma unroll
-        for (uint32_t c = 0; c < kPileupChannels; ++c) ch[c] = 0u;
-        return b;
+// One lane per op: the I ops of the kept alignments, summed per wavefront -- one atomic per wavefront.  Loop: the
+// bisection.
+__global__ __launch_bounds__(kThreads) void rlz_pileup_count_insertions_kernel(const AlignRec *__restrict__ recs,
+                                                                               const uint64_t *__restrict__ op_offsets,
+                                                                               uint32_t C, const uint32_t *__restrict__ ops,
+                                                                               uint32_t nops, TermTable tt, uint32_t qn,
+                                                                               uint32_t B, bool primary_only,
+                                                                               unsigned long long *__restrict__ total) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    unsigned long long mine = 0;
+    if (gid < nops && (ops[gid] & 0xfu) == kAlignI) {
+        const uint32_t c = alignment_of_op(op_offsets, C, (uint32_t)gid);
+        if (op_offsets[c] <= gid && geometry_of(recs[c], tt, qn, B, primary_only).kept) mine = 1;
     }
-    const uint4 x = *reinterpret_cast<const uint4 *>(v.xbase + 4ull * p);
-    const uint32_t eq = v.depth_eq[p + 1u];
-    ch[0] = x.x + (b == 0u ? eq : 0u);
-    ch[1] = x.y + (b == 1u ? eq : 0u);
-    ch[2] = x.z + (b == 2u ? eq : 0u);
-    ch[3] = x.w + (b == 3u ? eq : 0u);
-    ch[4] = v.del[p];
-    ch[5] = v.ins[p];
-    ch[6] = v.depth_rev[p + 1u];
-    ch[7] = v.brk[p];
-    return b;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(total, mine);
 }
 
 // One lane per position of [start, start + count): its eight words, two 16-byte stores.  Loop: the separator search.
@@ -326,10 +393,22 @@ PileupView rlz_pileup_view(void *d_base, uint32_t B) {
     return v;
 }
 
-void rlz_pileup_accumulate(Context &ctx, const PileupView &v, const AlignOut &a, const PackedText &batch, bool primary_only,
-                           unsigned long long *d_stats) {
+void rlz_pileup_count_insertions(Context &ctx, const AlignOut &a, const PackedText &batch, uint32_t B, bool primary_only,
+                                 unsigned long long *d_count) {
     hipStream_t s = ctx.stream;
-    HIP_CHECK(hipMemsetAsync(d_stats, 0, 3 * sizeof(unsigned long long), s));
+    HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+    const uint32_t C = a.num_alignments, N = a.num_ops;
+    if (C == 0 || N == 0) return;
+    ProfScope ps(ctx.profiler(), "rlz_pileup_log_count", s, 4.0 * (double)N);
+    rlz_pileup_count_insertions_kernel<<<(unsigned)div_up((size_t)N, kThreads), kThreads, 0, s>>>(
+        a.recs, a.op_offsets, C, a.ops, N, batch.terms, batch.n, B, primary_only, d_count);
+    KERNEL_CHECK();
+}
+
+void rlz_pileup_accumulate(Context &ctx, const PileupView &v, const AlignOut &a, const PackedText &batch,
+                           const PackedText &block, bool primary_only, const PileupLog &log, unsigned long long *d_stats) {
+    hipStream_t s = ctx.stream;
+    HIP_CHECK(hipMemsetAsync(d_stats, 0, kPileupStats * sizeof(unsigned long long), s));
     const uint32_t C = a.num_alignments, N = a.num_ops;
     if (C == 0 || N == 0) return;
     uint32_t *tq = ctx.arena.alloc<uint32_t>(N), *rq = ctx.arena.alloc<uint32_t>(N);
@@ -347,7 +426,7 @@ void rlz_pileup_accumulate(Context &ctx, const PileupView &v, const AlignOut &a,
     KERNEL_CHECK();
     rlz_pileup_ops_kernel<<<(unsigned)div_up((size_t)N, kThreads), kThreads, 0, s>>>(a.recs, a.op_offsets, C, a.ops, N, tpre, rpre,
                                                                                     batch.words, batch.terms, batch.n, v,
-                                                                                    primary_only);
+                                                                                    primary_only, block.words, log, d_stats + 3);
     KERNEL_CHECK();
 }
 

@@ -28,6 +28,8 @@ CHAIN_ANCHOR_DTYPE = _native.CHAIN_ANCHOR_DTYPE  # (t_start, position, length): 
 ALIGN_DTYPE = _native.ALIGN_DTYPE  # the base-level alignment of one seed chain (RlzIndex.align)
 ALIGN_LANES = _native.ALIGN_LANES  # diagonals of an alignment job: bandwidth + 2 * band + 1 must not exceed it
 VARIANT_DTYPE = _native.VARIANT_DTYPE  # an allele that passed RlzPileup.variants
+INSERTION_DTYPE = _native.INSERTION_DTYPE  # an inserted allele that passed RlzPileup.insertions
+insertion_bases = _native.insertion_bases  # the bases such a record keeps, as bytes
 PILEUP_CHANNELS = _native.PILEUP_CHANNELS  # ("A", "C", "G", "T", "DEL", "INS", "REV", "BREAK"): the columns of RlzPileup.counts
 CIGAR_LETTERS = {1: "I", 2: "D", 7: "=", 8: "X"}  # BAM's op codes, as RlzIndex.align reports them
 MAX_CHAIN_TARGETS = 1 << 24  # targets per batch of a seed-chain query: the group sort key keeps the target in 24 bits
@@ -763,14 +765,18 @@ class RlzIndex:
                 "ops": np.concatenate(ops) if ops else np.zeros(0, dtype=np.uint32)}
 
     def pileup(self, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 31,
-               min_score: int = 40, band: int = 16, max_flank: int = 256, primary_only: bool = True):
+               min_score: int = 40, band: int = 16, max_flank: int = 256, primary_only: bool = True,
+               normalize_indels: bool = False):
         """An RlzPileup over this index: per-position counts of what read batches say, accumulated on the GPU from the
         alignments align would report at the same seven parameters (primary_only: only the best placement of every
-        target counts).  bandwidth + 2 * band + 1 must not exceed 64 (ValueError).  The index must stay open while
-        the pileup is used."""
+        target counts).  normalize_indels: every deletion and insertion behind a run of matches is counted at its
+        leftmost position in the block, on both strands alike -- what a consensus needs; off, the counters are the
+        aligner's placements.  bandwidth + 2 * band + 1 must not exceed 64 (ValueError).  The index must stay open
+        while the pileup is used."""
         params = _native._align_params(min_length, max_hits, max_gap, bandwidth, min_score, band, max_flank)
         args = [int(getattr(params, name)) for name, _ in type(params)._fields_]
-        return RlzPileup(_native.RlzPileupHandle.open(self._live(), *args), self, bool(primary_only))
+        return RlzPileup(_native.RlzPileupHandle.open(self._live(), *args, normalize_indels=bool(normalize_indels)), self,
+                         bool(primary_only))
 
     def archive(self, targets, ids=None):
         """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
@@ -814,7 +820,7 @@ class RlzPileup:
     forward orientation), DEL (deletion columns), INS (insertion ops anchored at the base in front of them), REV
     (columns of reverse-strand alignments over this base) and BREAK (alignment ends with a clipped read remainder).
     Depth is A + C + G + T + DEL.  Neither alignments nor ops come down; counts() and variants() bring down the table.
-    The inserted sequence is not reported and no genotype is called.  A context manager; use after close(), or after
+    insertions() reports the inserted alleles and consensus() the sample's sequence; no genotype is called.  A context manager; use after close(), or after
     the index was closed, raises ValueError."""
 
     def __init__(self, handle, index, primary_only):
@@ -828,8 +834,8 @@ class RlzPileup:
 
     @property
     def info(self):
-        """dict(block_length, device_bytes, targets, alignments, ops, columns, adds, device, dirty, primary_only) and
-        the seven align parameters"""
+        """dict(block_length, device_bytes, targets, alignments, ops, columns, adds, device, dirty, primary_only,
+        normalize_indels, insertion_events, log_bytes) and the seven align parameters"""
         return dict(self._live().info, primary_only=self._primary_only)
 
     def add(self, targets, batch_bases=None):
@@ -861,6 +867,27 @@ class RlzPileup:
         integers, and one for INS (allele 5) against the same depth.  A bad fraction or min_count < 1: ValueError."""
         rule = _native._variant_rule(min_count, min_fraction)
         return self._live().variants(rule[0], rule[1:])
+
+    def insertions(self, min_count: int = 2, min_fraction=(1, 2)):
+        """What was inserted -> INSERTION_DTYPE array (position, record_offset, record, length, count, depth, ins_total,
+        truncated, bases), ascending by (position, length, bases): one record for every inserted allele with count >=
+        min_count and count / depth >= num / den.  insertion_bases(record) gives its bases; an allele of more than 64
+        bases keeps its first 64 and has truncated = 1.  A bad fraction or min_count < 1: ValueError."""
+        rule = _native._variant_rule(min_count, min_fraction)
+        return self._live().insertions(rule[0], rule[1:])
+
+    def consensus(self, min_depth: int = 1, min_fraction=(1, 2), low="reference", return_map: bool = False):
+        """The sample's own sequence -> dict(records: one bytes per reference record; called, low_positions,
+        substitutions, deleted, insertions, inserted_bases, truncated_skipped; with return_map, starts: for every block
+        position the offset of its output in the records joined by one separator byte each, and the total length).
+        A position with depth below min_depth, or whose best allele stays below min_fraction = (num, den) of the depth,
+        is low: it keeps the reference base (low="reference") or becomes N (low="N").  Elsewhere the plurality allele
+        is called -- a base, or a deletion --, then the most frequent inserted allele is written behind it if it reaches
+        the fraction.  Open the pileup with normalize_indels=True for this: otherwise the two strands place an indel
+        inside a repeat at different ends of it and neither place reaches a majority.  No genotypes, no qualities, no
+        realignment.  Bad arguments: ValueError."""
+        _native._consensus_params(min_depth, min_fraction, low)
+        return self._live().consensus(min_depth, min_fraction, low, return_map)
 
     def close(self) -> None:
         h, self._handle = getattr(self, "_handle", None), None
@@ -900,5 +927,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "PILEUP_CHANNELS", "RlzPileup", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "INSERTION_DTYPE", "insertion_bases", "PILEUP_CHANNELS", "RlzPileup", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
