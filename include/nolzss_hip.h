@@ -1044,6 +1044,97 @@ int nolzss_rlz_pileup_consensus(nolzss_rlz_pileup *p, const nolzss_rlz_consensus
                                 nolzss_rlz_consensus_result *out);
 /* NULL is a no-op; the result is zeroed. */
 void nolzss_free_rlz_consensus_result(nolzss_rlz_consensus_result *r);
+/* Extension.  A cohort of samples over the block of one index: the base calls of many pileups kept on the device at 3 bits
+ * per base, their pairwise SNP distances and the sites that vary among them ("Relative-LZ index: cohort").
+ * A cohort belongs to the index it was opened over, which must outlive it, and lives on that index's device.  Align,
+ * the pileup, the consensus and their records are what they were.
+ *   Planes.  With B the block length and W = ceil(B / 64), sample s is three bit planes of W 64-bit words, ok, lo and hi;
+ *     bit p & 63 of word p >> 6 belongs to block position p.  ok: the sample has a base call at p; lo | hi << 1: the
+ *     base's code (A, C, G, T = 0 .. 3, as the packed texts have it).  Two invariants hold, and every read-out relies on
+ *     them: lo and hi are 0 wherever ok is 0, and every bit at or beyond B is 0.
+ *   add_pileup(cohort, pileup, params): the pileup must be open over the same index (the pointer and the serial number
+ *     the index got at its open are compared), else NOLZSS_ERR_INVALID_ARGUMENT.  params are refused in the words of
+ *     nolzss_rlz_pileup_consensus; `low` is checked but plays no part.  The pileup is resolved if it is dirty, as any
+ *     read of it does; its counters are not changed.  Per non-separator position with depth d and M the largest of its
+ *     A, C, G, T and DEL counters: the position is LOW exactly when the consensus says so (d < min_depth or M * den <
+ *     num * d, 64-bit products); else the call is the block's base if its counter equals M, else the smallest channel
+ *     that attains M -- the consensus' own rule, one function in the library.  ok is set iff the position is not LOW and
+ *     the call is a base: a DEL call, a LOW position and a separator are "no call".  Insertion alleles play no part:
+ *     neither the log nor the allele table is read, and an inserted base has no position in the block.  *info: the
+ *     sample's index and four counts -- called (the ok bits), low, deleted (DEL calls), differs (ok and the call is not
+ *     the block's base).  For the same rule on the same pileup, by construction: called == consensus.called -
+ *     consensus.deleted, deleted == consensus.deleted, differs == consensus.substitutions, low == consensus.low_positions.
+ *   add_calls(cohort, calls, n): a sample given as one byte per block position, a consensus computed elsewhere for one;
+ *     n must equal B.  A, C, G, T in either case are calls, any other byte is no call, and a separator position is no
+ *     call whatever its byte says.  The counts: deleted = 0, low = the non-separator positions without a call.
+ *   distances(cohort): two N x N uint32 matrices, row-major.  differences[i][j] = the positions where both samples are
+ *     ok and their codes differ; compared[i][j] = the positions where both are ok.  Both are symmetric; differences[i][i]
+ *     = 0 and compared[i][i] = called of sample i.  The counts are exact (each at most B < 2^32) and do not depend on
+ *     how the work was split.  No sample: num_samples 0 and NULL matrices.
+ *   sites(cohort, min_present, with_reference): per non-separator position, present = the samples with ok there and
+ *     counts[4] = those of every base.  With with_reference the block's base counts as one more allele in the test
+ *     that follows and nowhere else (not in present, not in counts).  A position is reported iff at least two distinct
+ *     bases occur and present >= min_present; the records ascend by position; reference: the block's base code.
+ *     min_present above N gives no record.
+ *   columns(cohort, positions, S, out): out[s * S + k] = the letter of sample s at positions[k], `N` for no call (also
+ *     at a separator), N x S bytes.  The positions may come in any order and repeat.  calls(cohort, sample, start, end,
+ *     out): the same letters of one sample over [start, end).
+ *   info: samples, capacity (samples the allocation holds), block length, device bytes.  samples(out, capacity, count):
+ *     *count = N, and the infos of the first min(N, capacity) samples go to out.
+ *   Refusals, each NOLZSS_ERR_INVALID_ARGUMENT and before any device work: a null pointer; a pileup of another index; n
+ *     != B; a sample index or a range out of bounds; a position at or beyond B; a sample beyond
+ *     NOLZSS_RLZ_COHORT_MAX_SAMPLES (a constant of the ABI: both matrices of a full cohort, 2 x N^2 cells of 4 bytes,
+ *     stay below 2^32 bytes).
+ *   Memory: the planes lie sample-major in ONE device allocation of the handle, 24 W bytes per sample -- 3 bits per
+ *     base.  Its capacity in samples grows geometrically -- a new allocation, a device copy, a free --, and the room is
+ *     secured before the first word of a new sample is written.  NOLZSS_RLZ_COHORT_SAMPLES (tests): the first capacity,
+ *     read at open; else as many samples as 256 MiB hold, at least 1 and at most 64.  Matrices, flags, scans and staging
+ *     buffers are arena memory.  An out-of-memory condition in any call leaves the cohort, the pileup and the index as
+ *     they were.
+ *   Threads: the calls on one cohort are serialised by a mutex in the handle; add_pileup takes the cohort's mutex, then
+ *     the pileup's.  The calling thread's current device is left as it was.  NOLZSS_RLZ_COHORT_SLICE (tests): the words
+ *     of a plane one workgroup of the pair kernel covers, read on every call; NOLZSS_RLZ_LOCATE_CHUNK (tests): matrix
+ *     cells, site records and letters per download.
+ *   Not done: insertions and indel alleles in the distances, DEL as a fifth state, genotypes or qualities, trees,
+ *     removing a sample, save / load, more than one GPU. */
+#define NOLZSS_RLZ_COHORT_MAX_SAMPLES 16384
+typedef struct nolzss_rlz_cohort nolzss_rlz_cohort;
+typedef struct nolzss_rlz_cohort_sample_info {
+    uint64_t sample;                         /* the sample's index in the cohort */
+    uint64_t called, low, deleted, differs;
+} nolzss_rlz_cohort_sample_info;
+typedef struct nolzss_rlz_cohort_summary {
+    uint64_t samples, capacity, block_length, device_bytes;
+    int32_t device, reserved;
+} nolzss_rlz_cohort_summary;
+typedef struct nolzss_rlz_cohort_distances_result {
+    size_t num_samples;
+    uint32_t *differences, *compared; /* num_samples x num_samples each, row-major; NULL when num_samples == 0 */
+} nolzss_rlz_cohort_distances_result;
+typedef struct nolzss_rlz_cohort_site {
+    uint64_t position, record_offset;
+    uint32_t record, present, counts[4], reference, reserved;
+} nolzss_rlz_cohort_site; /* 48 bytes */
+typedef struct nolzss_rlz_cohort_sites_result {
+    size_t num_sites;
+    nolzss_rlz_cohort_site *sites; /* ascending by position; NULL when num_sites == 0 */
+} nolzss_rlz_cohort_sites_result;
+int nolzss_rlz_cohort_open(const nolzss_rlz_index *index, nolzss_rlz_cohort **out);
+int nolzss_rlz_cohort_add_pileup(nolzss_rlz_cohort *c, nolzss_rlz_pileup *p, const nolzss_rlz_consensus_params *params,
+                                 nolzss_rlz_cohort_sample_info *info);
+int nolzss_rlz_cohort_add_calls(nolzss_rlz_cohort *c, const char *calls, size_t n, nolzss_rlz_cohort_sample_info *info);
+int nolzss_rlz_cohort_info(nolzss_rlz_cohort *c, nolzss_rlz_cohort_summary *info);
+int nolzss_rlz_cohort_samples(nolzss_rlz_cohort *c, nolzss_rlz_cohort_sample_info *out, size_t capacity, size_t *count);
+int nolzss_rlz_cohort_distances(nolzss_rlz_cohort *c, nolzss_rlz_cohort_distances_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_cohort_distances_result(nolzss_rlz_cohort_distances_result *r);
+int nolzss_rlz_cohort_sites(nolzss_rlz_cohort *c, uint64_t min_present, int with_reference, nolzss_rlz_cohort_sites_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_cohort_sites_result(nolzss_rlz_cohort_sites_result *r);
+int nolzss_rlz_cohort_columns(nolzss_rlz_cohort *c, const uint64_t *positions, size_t S, char *out);
+int nolzss_rlz_cohort_calls(nolzss_rlz_cohort *c, uint64_t sample, uint64_t start, uint64_t end, char *out);
+/* NULL is a no-op. */
+int nolzss_rlz_cohort_close(nolzss_rlz_cohort *c);
 
 /* ---- relative-LZ archive: batches appended from the index ---------------------------------------- */
 /* Extension.  The index and the archive meet on the device: a batch is matched against the index as

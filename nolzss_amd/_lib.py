@@ -213,6 +213,28 @@ class RlzConsensusResult(C.Structure):
                 ("truncated_skipped", C.c_uint64)]
 
 
+class RlzCohortSampleInfo(C.Structure):
+    """Mirror of nolzss_rlz_cohort_sample_info (include/nolzss_hip.h)."""
+    _fields_ = [("sample", C.c_uint64), ("called", C.c_uint64), ("low", C.c_uint64), ("deleted", C.c_uint64),
+                ("differs", C.c_uint64)]
+
+
+class RlzCohortSummary(C.Structure):
+    """Mirror of nolzss_rlz_cohort_summary (include/nolzss_hip.h)."""
+    _fields_ = [("samples", C.c_uint64), ("capacity", C.c_uint64), ("block_length", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RlzCohortDistancesResult(C.Structure):
+    """Mirror of nolzss_rlz_cohort_distances_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_samples", C.c_size_t), ("differences", C.c_void_p), ("compared", C.c_void_p)]
+
+
+class RlzCohortSitesResult(C.Structure):
+    """Mirror of nolzss_rlz_cohort_sites_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_sites", C.c_size_t), ("sites", C.c_void_p)]
+
+
 class Factor(C.Structure):
     """Mirror of nolzss_factor / the reference's struct Factor (factorizer.hpp:147-151)."""
     _fields_ = [("start", C.c_uint64), ("length", C.c_uint64), ("ref", C.c_uint64)]
@@ -397,6 +419,21 @@ def _load():
     lib.nolzss_debug_rlz_pileup_consensus.argtypes = [vp, sz] + seqs[3:] + [vp, vp, sz, vp, sz, C.c_int, C.c_uint32,
                                                       C.POINTER(RlzConsensusParams), C.c_int, vp,
                                                       C.POINTER(RlzInsertionsResult), C.POINTER(RlzConsensusResult)]
+    if hasattr(lib, "nolzss_rlz_cohort_open"):  # (NOLZSS_LIB: a variant built from an older commit has none)
+        lib.nolzss_rlz_cohort_open.argtypes = [vp, vpp]
+        lib.nolzss_rlz_cohort_add_pileup.argtypes = [vp, vp, C.POINTER(RlzConsensusParams), C.POINTER(RlzCohortSampleInfo)]
+        lib.nolzss_rlz_cohort_add_calls.argtypes = [vp, vp, sz, C.POINTER(RlzCohortSampleInfo)]
+        lib.nolzss_rlz_cohort_info.argtypes = [vp, C.POINTER(RlzCohortSummary)]
+        lib.nolzss_rlz_cohort_samples.argtypes = [vp, vp, sz, szp]
+        lib.nolzss_rlz_cohort_distances.argtypes = [vp, C.POINTER(RlzCohortDistancesResult)]
+        lib.nolzss_free_rlz_cohort_distances_result.argtypes = [C.POINTER(RlzCohortDistancesResult)]
+        lib.nolzss_free_rlz_cohort_distances_result.restype = None
+        lib.nolzss_rlz_cohort_sites.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(RlzCohortSitesResult)]
+        lib.nolzss_free_rlz_cohort_sites_result.argtypes = [C.POINTER(RlzCohortSitesResult)]
+        lib.nolzss_free_rlz_cohort_sites_result.restype = None
+        lib.nolzss_rlz_cohort_columns.argtypes = [vp, vp, sz, vp]
+        lib.nolzss_rlz_cohort_calls.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]
+        lib.nolzss_rlz_cohort_close.argtypes = [vp]
     lib.nolzss_debug_rlz_locate_shifts.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
@@ -489,6 +526,10 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_pileup_open_flags", "nolzss_rlz_pileup_log_info", "nolzss_rlz_pileup_insertions",
     "nolzss_free_rlz_insertions_result", "nolzss_rlz_pileup_consensus", "nolzss_free_rlz_consensus_result",
     "nolzss_debug_rlz_pileup_consensus",
+    "nolzss_rlz_cohort_open", "nolzss_rlz_cohort_add_pileup", "nolzss_rlz_cohort_add_calls", "nolzss_rlz_cohort_info",
+    "nolzss_rlz_cohort_samples", "nolzss_rlz_cohort_distances", "nolzss_free_rlz_cohort_distances_result",
+    "nolzss_rlz_cohort_sites", "nolzss_free_rlz_cohort_sites_result", "nolzss_rlz_cohort_columns",
+    "nolzss_rlz_cohort_calls", "nolzss_rlz_cohort_close",
 ]
 
 

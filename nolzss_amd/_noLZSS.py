@@ -1851,6 +1851,157 @@ class RlzPileupHandle:
             pass
 
 
+# ---- relative-LZ index: a cohort of samples, SNP distances and variable sites (genomics/rlz.py) -------------------
+# a site that varies among the samples of a cohort (RlzCohort.sites): nolzss_rlz_cohort_site, 48 bytes
+COHORT_SITE_DTYPE = np.dtype({"names": ["position", "record_offset", "record", "present", "counts", "reference"],
+                              "formats": ["<u8", "<u8", "<u4", "<u4", ("<u4", (4,)), "<u4"],
+                              "offsets": [0, 8, 16, 20, 24, 40], "itemsize": 48})
+COHORT_MAX_SAMPLES = 16384  # NOLZSS_RLZ_COHORT_MAX_SAMPLES
+
+
+class RlzCohortHandle:
+    """Extension: three bit planes per sample over the block of an index, kept on the device (C ABI
+    nolzss_rlz_cohort_*).  It keeps the index handle alive.  A context manager; close() may be called more than once,
+    any other use after it raises ValueError."""
+
+    def __init__(self, handle, index_handle):
+        self._h, self._index = handle, index_handle
+
+    @classmethod
+    def open(cls, index_handle):
+        """C ABI nolzss_rlz_cohort_open (the header states the rules)."""
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_cohort_open(index_handle._handle(), C.byref(h)))
+        return cls(h, index_handle)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the cohort is closed")
+        self._index._handle()  # (a closed index raises here, not in the library)
+        return self._h
+
+    @property
+    def info(self) -> dict:
+        """dict(samples, capacity, block_length, device_bytes, device).  C ABI nolzss_rlz_cohort_info."""
+        h = self._handle()
+        info = _lib.RlzCohortSummary()
+        check(lib.nolzss_rlz_cohort_info(h, C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in _lib.RlzCohortSummary._fields_ if name != "reserved"}
+
+    @staticmethod
+    def _sample(info) -> dict:
+        return {name: int(getattr(info, name)) for name, _ in _lib.RlzCohortSampleInfo._fields_}
+
+    def add_pileup(self, pileup_handle, min_depth: int = 1, min_fraction=(1, 2)) -> dict:
+        """The calls of a pileup under the consensus rule as the next sample -> dict(sample, called, low, deleted,
+        differs).  C ABI nolzss_rlz_cohort_add_pileup."""
+        params = _consensus_params(min_depth, min_fraction, "reference")
+        h = self._handle()
+        info = _lib.RlzCohortSampleInfo()
+        check(lib.nolzss_rlz_cohort_add_pileup(h, pileup_handle._handle(), C.byref(params), C.byref(info)))
+        return self._sample(info)
+
+    def add_calls(self, calls) -> dict:
+        """One byte per block position as the next sample -> the same dict.  C ABI nolzss_rlz_cohort_add_calls."""
+        h = self._handle()
+        if isinstance(calls, str):
+            calls = calls.encode("latin-1")
+        address, nbytes, keep = _as_buffer(calls)
+        info = _lib.RlzCohortSampleInfo()
+        check(lib.nolzss_rlz_cohort_add_calls(h, address if nbytes else None, nbytes, C.byref(info)))
+        del keep
+        return self._sample(info)
+
+    def samples(self) -> list:
+        """The dict of every sample, in order.  C ABI nolzss_rlz_cohort_samples."""
+        h = self._handle()
+        while True:
+            n = self.info["samples"]
+            out = (_lib.RlzCohortSampleInfo * max(n, 1))()
+            count = C.c_size_t()
+            check(lib.nolzss_rlz_cohort_samples(h, out, n, C.byref(count)))
+            if count.value <= n:  # (another thread may have added meanwhile)
+                return [self._sample(out[j]) for j in range(count.value)]
+
+    def distances(self):
+        """(differences, compared): two (N, N) uint32 arrays.  C ABI nolzss_rlz_cohort_distances."""
+        h = self._handle()
+        res = _lib.RlzCohortDistancesResult()
+        try:
+            check(lib.nolzss_rlz_cohort_distances(h, C.byref(res)))
+            n = res.num_samples
+            diff, cmp_ = np.zeros((n, n), dtype=np.uint32), np.zeros((n, n), dtype=np.uint32)
+            if n:
+                C.memmove(diff.ctypes.data, res.differences, diff.nbytes)
+                C.memmove(cmp_.ctypes.data, res.compared, cmp_.nbytes)
+            return diff, cmp_
+        finally:
+            lib.nolzss_free_rlz_cohort_distances_result(C.byref(res))
+
+    def sites(self, min_present: int, with_reference: bool = True) -> np.ndarray:
+        """The positions where at least two distinct bases occur among at least min_present calling samples, as
+        COHORT_SITE_DTYPE ascending by position.  C ABI nolzss_rlz_cohort_sites."""
+        min_present = operator.index(min_present)
+        if min_present < 0 or min_present >= 1 << 64:
+            raise ValueError("min_present must not be negative and fit 64 bits")
+        h = self._handle()
+        res = _lib.RlzCohortSitesResult()
+        try:
+            check(lib.nolzss_rlz_cohort_sites(h, min_present, 1 if with_reference else 0, C.byref(res)))
+            out = np.zeros(res.num_sites, dtype=COHORT_SITE_DTYPE)
+            if res.num_sites:
+                C.memmove(out.ctypes.data, res.sites, res.num_sites * COHORT_SITE_DTYPE.itemsize)
+            return out
+        finally:
+            lib.nolzss_free_rlz_cohort_sites_result(C.byref(res))
+
+    def columns(self, positions) -> np.ndarray:
+        """The (N, S) uint8 letters of every sample at the S positions (`N`: no call).  C ABI
+        nolzss_rlz_cohort_columns."""
+        h = self._handle()
+        pos = np.asarray(positions)
+        if pos.ndim != 1:
+            raise ValueError("positions is a one-dimensional sequence of block positions")
+        if pos.size and (pos.dtype.kind not in "iu" or (pos.dtype.kind == "i" and int(pos.min()) < 0)):
+            raise ValueError("positions are non-negative integers")
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        out = np.zeros((self.info["samples"], pos.size), dtype=np.uint8)
+        check(lib.nolzss_rlz_cohort_columns(h, pos.ctypes.data if pos.size else None, pos.size,
+                                            out.ctypes.data if out.size else None))
+        return out
+
+    def calls(self, sample: int, start: int = 0, end=None) -> bytes:
+        """The letters of one sample over the block positions [start, end) (end None: the block's end).  C ABI
+        nolzss_rlz_cohort_calls."""
+        h = self._handle()
+        sample, start = operator.index(sample), operator.index(start)
+        end = self.info["block_length"] if end is None else operator.index(end)
+        if sample < 0:
+            raise ValueError(f"sample index {sample} is negative")
+        if start < 0 or end < start:
+            raise ValueError(f"calls take 0 <= start <= end, not [{start}, {end})")
+        out = np.zeros(end - start, dtype=np.uint8)
+        check(lib.nolzss_rlz_cohort_calls(h, sample, start, end, out.ctypes.data if out.size else None))
+        return out.tobytes()
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            check(lib.nolzss_rlz_cohort_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _roundtrip_result(z, mismatches, first, info):
     res = {"z": z.value, "mismatches": mismatches.value,
            "first_mismatch": None if first.value == (1 << 64) - 1 else first.value}

@@ -102,10 +102,6 @@ __device__ __forceinline__ uint32_t allele_lower_bound(const PileupAllele *__res
     return lo;
 }
 
-__device__ __forceinline__ uint32_t depth_of(const uint32_t ch[kPileupChannels]) {  // (below 2^32: rlz_pileup_api.hip)
-    return ch[0] + ch[1] + ch[2] + ch[3] + ch[4];
-}
-
 // One lane per allele: whether it passes the rule against its position's depth.  Loop: the separator search.
 __global__ __launch_bounds__(kThreads) void insertion_flags_kernel(PileupView v, const uint64_t *__restrict__ xwords, TermTable xt,
                                                                    const PileupAllele *__restrict__ al, uint32_t G,
@@ -176,20 +172,13 @@ __device__ __forceinline__ Call call_of(const PileupView &v, const uint64_t *__r
         return c;
     }
     const uint32_t b = channels_of(v, xwords, false, p, ch);
-    const uint64_t d = depth_of(ch);
-    uint32_t M = ch[0], arg = 0;
-#pragma unroll
-    for (uint32_t a = 1; a < 5u; ++a)
-        if (ch[a] > M) {  // (strictly: the smallest channel that attains the maximum)
-            M = ch[a];
-            arg = a;
-        }
-    if (d < rule.min_depth || (uint64_t)M * rule.den < rule.num * d) {
+    uint32_t call;
+    uint64_t d;
+    if (base_call_of(ch, b, rule, call, d)) {  // (the rule shared with a cohort's pack: rlz_pileup_device.hpp)
         c.low = true;
         c.letter = rule.low ? 'N' : "ACGT"[b];
         return c;
     }
-    const uint32_t call = ch[b] == M ? b : arg;
     c.substitution = call < 4u && call != b;
     c.deleted = call == 4u;
     c.letter = call < 4u ? "ACGT"[call] : 0u;

@@ -1,7 +1,8 @@
 // rlz_handles.hpp -- the resident relative-LZ handles and what the translation units of their entry points share: the
 // index and its match (rlz_index_api.hip), its pattern queries (rlz_index_query_api.hip) and its seed queries
 // (rlz_index_seeds_api.hip); the archive (rlz_archive_api.hip), whose appends run that match; a finder reads both
-// (rlz_find_api.hip); a pileup reduces the alignments of the index (rlz_pileup_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index" and "Relative-LZ archive:
+// (rlz_find_api.hip); a pileup reduces the alignments of the index (rlz_pileup_api.hip); a cohort packs the calls of
+// pileups into bit planes and compares them (rlz_cohort_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index" and "Relative-LZ archive:
 // locate through the parse".
 #pragma once
 #include <functional>
@@ -118,6 +119,32 @@ struct nolzss_rlz_pileup {
         if (d_base) (void)hipFree(d_base);
         if (d_log) (void)hipFree(d_log);
         if (d_alleles) (void)hipFree(d_alleles);
+        if (known && current != device) (void)hipSetDevice(current);
+    }
+};
+
+// The cohort handle: the bit planes of the samples added so far over the block of one index (rlz_cohort_api.hip; DESIGN.md
+// 5, "Relative-LZ index: cohort").  It points to the index it was opened over, which must outlive it, and remembers its
+// serial; the planes lie sample-major in ONE device allocation of its own (not arena memory) that grows geometrically
+// in samples -- a new allocation, a device copy, a free --, none until the first add.  `mu` serialises the calls on one
+// cohort.  Lock order: add_pileup takes the cohort's mutex first, then the pileup's, then the device's session; no call
+// takes them the other way round.
+struct nolzss_rlz_cohort {
+    int device = 0;
+    const nolzss_rlz_index *index = nullptr;
+    uint64_t index_serial = 0;
+    uint32_t B = 0;
+    size_t W = 0;  // words of a plane: a sample keeps 3 W of them
+    uint64_t *d_planes = nullptr;
+    uint64_t capacity = 0, first_capacity = 1;  // in samples; first_capacity: NOLZSS_RLZ_COHORT_SAMPLES or the default, read at open
+    std::vector<nolzss_rlz_cohort_sample_info> samples;
+    std::mutex mu;
+    ~nolzss_rlz_cohort() {  // (the calling thread's current device stays what it was)
+        if (!d_planes) return;
+        int current = -1;
+        const bool known = hipGetDevice(&current) == hipSuccess;
+        (void)hipSetDevice(device);
+        (void)hipFree(d_planes);
         if (known && current != device) (void)hipSetDevice(current);
     }
 };

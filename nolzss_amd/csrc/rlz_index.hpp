@@ -2,8 +2,9 @@
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
 // rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds, rlz_seed_chain.hip for
 // their colinear chains, rlz_align.hip for the base-level alignments of those, rlz_pileup.hip for the pileup counts of
-// the alignments and rlz_consensus.hip for the insertion alleles and the consensus of a pileup; the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip,
-// rlz_pileup_api.hip).
+// the alignments, rlz_consensus.hip for the insertion alleles and the consensus of a pileup and rlz_cohort.hip for the bit planes of
+// many samples and their comparison; the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip,
+// rlz_pileup_api.hip, rlz_cohort_api.hip).
 #pragma once
 #include "pipeline.hpp"
 
@@ -350,6 +351,48 @@ void rlz_consensus_starts(Context &ctx, const uint32_t *d_off, uint64_t first, u
 // d_out[r] = the offset in the text where record r < records begins, d_out[records] = total + 1
 void rlz_consensus_record_offsets(Context &ctx, const PackedText &block, const uint32_t *d_off, uint32_t B, uint32_t records,
                                   uint64_t total, uint64_t *d_out);
+
+// ---- cohort of samples (rlz_cohort.hip; DESIGN.md 5, "Relative-LZ index: cohort") ----------------------------------
+// A sample of a cohort is three bit planes of W = ceil(B / 64) words each, `ok`, `lo`, `hi` in this order (the rules:
+// include/nolzss_hip.h, nolzss_rlz_cohort_*): bit p & 63 of word p >> 6 belongs to block position p.  The planes of all
+// samples lie sample-major in ONE device allocation of the handle: sample s begins at word 3 W s.  The two invariants
+// every reader relies on: lo and hi are 0 wherever ok is 0, and every bit at or beyond B is 0.
+constexpr uint32_t kCohortStats = 4;        // words of d_stats: called, low, deleted, differs
+constexpr uint32_t kCohortTile = 64;        // samples per side of a pair tile
+constexpr uint32_t kCohortMaxSlice = 4096;  // words of a slice at the most: a workgroup counts below 2^18 per pair
+constexpr uint64_t kCohortLaunchWordPairs = 1ull << 34;  // the work of one launch of the pair kernel, where a row allows it
+struct CohortSiteRec {  // nolzss_rlz_cohort_site
+    uint64_t position, record_offset;
+    uint32_t record, present, counts[4], reference, pad;
+};
+inline size_t cohort_words(uint32_t B) { return ((size_t)B + 63) / 64; }
+// The planes of one sample (3 W words at d_sample) from the resolved counters of a pileup under the consensus' call
+// rule (base_call_of, rlz_pileup_device.hpp); d_stats (kCohortStats words, device memory, zeroed here) summed over the
+// positions.  Writes the 3 W words and the statistics, nothing else.
+void rlz_cohort_pack_counts(Context &ctx, const PileupView &v, const PackedText &block, const ConsensusRule &rule,
+                            uint64_t *d_sample, unsigned long long *d_stats);
+// ... from one byte per block position (d_bytes, B of them): ACGT in either case is a call
+void rlz_cohort_pack_bytes(Context &ctx, const uint8_t *d_bytes, uint32_t B, const PackedText &block, uint64_t *d_sample,
+                           unsigned long long *d_stats);
+// The slice length in words a launch of the pair kernel over `row_tiles` tiles of planes of W words takes when no knob
+// names one
+uint32_t rlz_cohort_default_slice(uint32_t row_tiles, size_t W);
+// d_diff / d_cmp (N x N each, zeroed here): the pair counts over all words, both triangles.  slice_knob: the words of a
+// slice (clamped to kCohortMaxSlice), 0: rlz_cohort_default_slice per row.  One launch per row of tiles and per
+// kCohortLaunchWordPairs of it; a row of more than one slice adds its partial sums by integer atomics.
+void rlz_cohort_pairs(Context &ctx, const uint64_t *d_planes, uint32_t N, uint32_t B, uint32_t slice_knob, uint32_t *d_diff,
+                      uint32_t *d_cmp);
+// d_n[p] = 1 where position p < B is a site of the query, else 0
+void rlz_cohort_site_flags(Context &ctx, const uint64_t *d_planes, uint32_t N, uint32_t B, const PackedText &block,
+                           uint32_t min_present, bool with_reference, uint32_t *d_n);
+// The records [first, first + count) of the query, d_off = the exclusive scan of d_n, into d_out[0 .. count)
+void rlz_cohort_site_records(Context &ctx, const uint64_t *d_planes, uint32_t N, uint32_t B, const PackedText &block,
+                             const uint32_t *d_n, const uint32_t *d_off, uint64_t first, uint32_t count, CohortSiteRec *d_out);
+// Bytes [first, first + count) of the N x S letters (sample-major) at the S positions d_pos, each below B
+void rlz_cohort_columns(Context &ctx, const uint64_t *d_planes, uint32_t N, uint32_t B, const uint32_t *d_pos, uint64_t S,
+                        uint64_t first, uint32_t count, uint8_t *d_out);
+// The letters of positions [start, start + count) of one sample
+void rlz_cohort_calls(Context &ctx, const uint64_t *d_sample, uint32_t B, uint32_t start, uint32_t count, uint8_t *d_out);
 
 constexpr int kCrossWords = 4;  // words compared per step of cross_suffix_less (at most 7: the pad words)
 

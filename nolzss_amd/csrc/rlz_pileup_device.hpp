@@ -1,5 +1,6 @@
 // rlz_pileup_device.hpp -- what the kernels of rlz_pileup.hip and rlz_consensus.hip share: a base of a packed text, the
-// record of a block position, and the eight channels of a position after a resolve.
+// record of a block position, the eight channels of a position after a resolve, and the base call of a position (also
+// read by rlz_cohort.hip).
 #pragma once
 #include "rlz_index.hpp"
 
@@ -38,6 +39,28 @@ __device__ __forceinline__ uint32_t channels_of(const PileupView &v, const uint6
     ch[6] = v.depth_rev[p + 1u];
     ch[7] = v.brk[p];
     return b;
+}
+
+__device__ __forceinline__ uint32_t depth_of(const uint32_t ch[kPileupChannels]) {  // (below 2^32: rlz_pileup_api.hip)
+    return ch[0] + ch[1] + ch[2] + ch[3] + ch[4];
+}
+
+// The base call of a non-separator position with block base b (the rule: include/nolzss_hip.h,
+// nolzss_rlz_pileup_consensus), shared by the consensus (rlz_consensus.hip) and the pack of a cohort (rlz_cohort.hip):
+// d = the depth; true: the position is LOW and `call` means nothing; else call = b if b's counter equals the largest of
+// A, C, G, T, DEL, else the smallest channel that attains it (4: DEL).  Loop: the five channels.
+__device__ __forceinline__ bool base_call_of(const uint32_t ch[kPileupChannels], uint32_t b, const ConsensusRule &rule,
+                                             uint32_t &call, uint64_t &d) {
+    d = depth_of(ch);
+    uint32_t M = ch[0], arg = 0;
+#pragma unroll
+    for (uint32_t a = 1; a < 5u; ++a)
+        if (ch[a] > M) {  // (strictly: the smallest channel that attains the maximum)
+            M = ch[a];
+            arg = a;
+        }
+    call = ch[b] == M ? b : arg;
+    return d < rule.min_depth || (uint64_t)M * rule.den < rule.num * d;
 }
 
 }  // namespace nolzss

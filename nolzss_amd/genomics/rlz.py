@@ -30,6 +30,7 @@ ALIGN_LANES = _native.ALIGN_LANES  # diagonals of an alignment job: bandwidth + 
 VARIANT_DTYPE = _native.VARIANT_DTYPE  # an allele that passed RlzPileup.variants
 INSERTION_DTYPE = _native.INSERTION_DTYPE  # an inserted allele that passed RlzPileup.insertions
 insertion_bases = _native.insertion_bases  # the bases such a record keeps, as bytes
+COHORT_SITE_DTYPE = _native.COHORT_SITE_DTYPE  # a position that varies among the samples of a cohort (RlzCohort.sites)
 PILEUP_CHANNELS = _native.PILEUP_CHANNELS  # ("A", "C", "G", "T", "DEL", "INS", "REV", "BREAK"): the columns of RlzPileup.counts
 CIGAR_LETTERS = {1: "I", 2: "D", 7: "=", 8: "X"}  # BAM's op codes, as RlzIndex.align reports them
 MAX_CHAIN_TARGETS = 1 << 24  # targets per batch of a seed-chain query: the group sort key keeps the target in 24 bits
@@ -778,6 +779,11 @@ class RlzIndex:
         return RlzPileup(_native.RlzPileupHandle.open(self._live(), *args, normalize_indels=bool(normalize_indels)), self,
                          bool(primary_only))
 
+    def cohort(self):
+        """An RlzCohort over this index: the base calls of many pileups kept on the GPU at 3 bits per base, their
+        pairwise SNP distances and the sites that vary among them.  The index must stay open while the cohort is used."""
+        return RlzCohort(_native.RlzCohortHandle.open(self._live()), self)
+
     def archive(self, targets, ids=None):
         """RlzArchive.from_factors(reference, factors, rlz_literals(targets, factors), ids) for these targets."""
         targets = list(targets)
@@ -907,6 +913,142 @@ class RlzPileup:
             pass
 
 
+def _cohort_id(id, taken):
+    """The id rules of RlzCohort.add / add_calls: None, or a str (bytes are decoded as UTF-8) no sample carries yet ->
+    the id as str.  ValueError otherwise.  Pure Python."""
+    if id is None:
+        return None
+    if isinstance(id, (bytes, bytearray)):
+        id = bytes(id).decode("utf-8")
+    if not isinstance(id, str):
+        raise ValueError(f"a sample id is a str or bytes, not {type(id).__name__}")
+    if id in taken:
+        raise ValueError(f"ids must be distinct: {id!r} is in the cohort already")
+    return id
+
+
+class RlzCohort:
+    """A collection of samples over the block of an RlzIndex, kept on the GPU (RlzIndex.cohort): per sample and block
+    position a base call or none -- three bit planes, 3 bits per base.  add(pile) takes the calls of an RlzPileup under
+    the consensus rule (a deletion, a low position and a separator are no call; insertions play no part), add_calls a
+    sequence computed elsewhere.  distances() compares all pairs on the device, sites() finds the positions that vary,
+    alignment() gives their columns: the core-SNP alignment.  Samples may carry ids and are then addressed by them.  No
+    genotypes, no trees, no removal.  A context manager; use after close(), or after the index was closed, raises
+    ValueError."""
+
+    def __init__(self, handle, index):
+        self._handle, self._index, self._ids, self._by_id = handle, index, [], {}
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("the cohort is closed")
+        self._index._live()
+        return self._handle
+
+    @property
+    def info(self):
+        """dict(samples, capacity, block_length, device_bytes, device)"""
+        return self._live().info
+
+    @property
+    def ids(self):
+        """The id of every sample, in order (None where none was given)."""
+        return list(self._ids)
+
+    def __len__(self):
+        return len(self._ids)
+
+    def _added(self, got, id):
+        self._ids.append(id)
+        if id is not None:
+            self._by_id[id] = got["sample"]
+        return got
+
+    def add(self, pile, id=None, min_depth: int = 1, min_fraction=(1, 2)):
+        """The pileup's calls as the next sample -> dict(sample, called, low, deleted, differs).  A position is called
+        as RlzPileup.consensus(min_depth, min_fraction) calls it; for the same rule called = consensus called -
+        deleted, deleted = deleted, differs = substitutions, low = low_positions.  The pileup must be open over this
+        cohort's index; its counters are not changed.  Bad arguments: ValueError, before any native call."""
+        _native._consensus_params(min_depth, min_fraction, "reference")
+        h = self._live()
+        if not isinstance(pile, RlzPileup):
+            raise ValueError(f"add takes an RlzPileup, not {type(pile).__name__}")
+        id = _cohort_id(id, self._by_id)
+        return self._added(h.add_pileup(pile._live(), min_depth, min_fraction), id)
+
+    def add_calls(self, calls, id=None):
+        """One byte per block position as the next sample -> the same dict (deleted = 0): A, C, G, T in either case
+        are calls, anything else is none.  A length other than the block's: ValueError."""
+        h = self._live()
+        id = _cohort_id(id, self._by_id)
+        return self._added(h.add_calls(calls), id)
+
+    def samples(self):
+        """The dict of every sample, in order, with its id."""
+        return [dict(got, id=self._ids[got["sample"]]) for got in self._live().samples()]
+
+    def distances(self):
+        """All pairs compared on the GPU -> dict(differences, compared: (N, N) uint32 -- the positions both samples call
+        where the calls differ, and the positions both call --, called, to_reference: (N,) uint64, the calls of every
+        sample and those that differ from the reference)."""
+        h = self._live()
+        diff, cmp_ = h.distances()
+        infos = h.samples()[:len(diff)]
+        return {"differences": diff, "compared": cmp_,
+                "called": np.array([i["called"] for i in infos], dtype=np.uint64),
+                "to_reference": np.array([i["differs"] for i in infos], dtype=np.uint64)}
+
+    def _min_present(self, min_present):
+        if min_present is None:
+            return len(self._ids)
+        min_present = operator.index(min_present)
+        if min_present < 0:
+            raise ValueError("min_present must not be negative")
+        return min_present
+
+    def sites(self, min_present=None, with_reference: bool = True):
+        """The positions that vary -> COHORT_SITE_DTYPE array (position, record_offset, record, present, counts,
+        reference), ascending by position: at least two distinct bases occur there -- the reference's base counting as
+        one with with_reference -- among at least min_present samples with a call (None: all samples, the core genome).
+        present and counts (A, C, G, T) never include the reference."""
+        min_present = self._min_present(min_present)
+        return self._live().sites(min_present, with_reference)
+
+    def alignment(self, positions=None, min_present=None, with_reference: bool = True):
+        """(positions, (N, S) uint8 array): the letter of every sample at every position, `N` for no call.  positions
+        None: those of sites(min_present, with_reference), the core-SNP alignment; else any block positions, in any
+        order (a position beyond the block: ValueError)."""
+        min_present = self._min_present(min_present)
+        h = self._live()
+        if positions is None:
+            positions = h.sites(min_present, with_reference)["position"]
+        positions = np.asarray(positions)
+        letters = h.columns(positions)  # (refuses what is no position)
+        return np.ascontiguousarray(positions, dtype=np.uint64), letters
+
+    def calls(self, sample, start: int = 0, end=None):
+        """The letters of one sample (an index, or its id) over the block positions [start, end) -> bytes."""
+        h = self._live()
+        return h.calls(resolve_target(sample, self._by_id, len(self._ids)), start, end)
+
+    def close(self) -> None:
+        h, self._handle = getattr(self, "_handle", None), None
+        if h is not None:
+            h.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def target_index_map(ids):
     """ids (or None) -> {id: index}"""
     return {} if ids is None else {name: j for j, name in enumerate(ids)}
@@ -927,5 +1069,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "INSERTION_DTYPE", "insertion_bases", "PILEUP_CHANNELS", "RlzPileup", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "INSERTION_DTYPE", "insertion_bases", "PILEUP_CHANNELS", "RlzPileup", "COHORT_SITE_DTYPE", "RlzCohort", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
