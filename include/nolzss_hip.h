@@ -1178,6 +1178,68 @@ int nolzss_rlz_archive_append_index(nolzss_rlz_archive *h, const nolzss_rlz_inde
 int nolzss_rlz_archive_export(const nolzss_rlz_archive *h, uint8_t **block, size_t *block_len, nolzss_factor **records,
                               size_t *z, uint8_t **literals, size_t *n_literals);
 
+/* ---- relative-LZ archive: the compact container --------------------------------------------------- */
+/* Extension.  A compact, canonical, byte-exact form of an archive, packed on the device from the resident records and
+ * expanded on the device into them: only the compact streams cross PCIe and the file system, the 24-byte records of
+ * export / open_records do not appear ("Relative-LZ archive: the compact container").
+ *   The format.  All integers little-endian, all arithmetic unsigned 32-bit with wrap-around.  Record i, in archive
+ *     order, has a decoded start p (relative to the end of the block), a length L >= 1, a kind (literal, forward copy,
+ *     reverse-complement copy) and, a copy, the forward-strand source start x with x + L <= B, B = block_length.  For a
+ *     copy r = 1 (reverse complement) or 0, y = x (forward) or 2 B + 1 - x - L (the mirrored coordinate, in which a
+ *     reverse-complement match reads forward), g = y - p.  With c the last copy before i in the whole archive (none:
+ *     g_c = r_c = 0): e = int32(g - g_c), s = r ^ r_c, v = (zigzag32(e) << 1) | s, 33 bits, zigzag32(e) = (e << 1) ^
+ *     (e >> 31).  A copy that continues colinearly behind any number of literals, on either strand, has v = 0.
+ *   control: one nibble per record, record 2 j in the low and 2 j + 1 in the high nibble of byte j, (z + 1) / 2 bytes,
+ *     the spare nibble of an odd z is 0.  nibble = a | b << 2; a: 0 a literal (L = 1, b = 0), 1 / 2 / 3: L in 1 / 2 / 4
+ *     bytes; b: 0: v = 0, 1 / 2 / 3: v in 1 / 3 / 5 bytes.  The packer uses the smallest code that holds the value, so
+ *     the sections are a function of the archive; open_packed takes any well-formed code.
+ *   data: per record, in order, the bytes of L, then those of v; a literal has none.
+ *   literals: the symbols of the literal records in order; literal_mode 1: every one is A, C, G or T (also: there is
+ *     none) and they lie four to a byte at 2 bits (A, C, G, T = 0 .. 3), the first in the low bits, unused bits 0;
+ *     literal_mode 0: one byte each.
+ *   block: block_mode 1: every byte is A, C, G, T or 0x01 (always so over an index): (B + 3) / 4 bytes of bases at 2
+ *     bits as above, 0x01 stored as base 0, then num_separators ascending 32-bit positions of the 0x01 bytes (at no
+ *     particular alignment); block_mode 0: the B bytes raw, num_separators = 0.
+ *   The file (written and read by nolzss_amd.genomics.rlz.write_packed_archive / read_packed_archive, host only): a
+ *     112-byte header -- the magic "noLZRLZ1", uint32 version = 1, uint32 flags (bit 0 block_mode, bit 1 literal_mode,
+ *     bit 2 has_ids, the rest 0), then uint64 B, k, z, n_literals, decoded, num_separators and the byte sizes of the
+ *     six sections -- and the sections, each padded with zeros to 8 bytes: target lengths (k uint64), ids (k + 1 uint64
+ *     offsets and the UTF-8 bytes; empty without ids), block, control, data, literals.  Nothing follows.
+ *   pack: any archive handle -> the four device-made sections as malloc'ed buffers, the modes and the counts; free
+ *     with nolzss_free_rlz_archive_packed (NULL and an all-zero struct are no-ops; the struct is zeroed).  z == 0 (and
+ *     k == 0) is valid and launches no kernel.  A data section of 2^32 bytes or more is refused with
+ *     NOLZSS_ERR_INVALID_ARGUMENT before anything is written.  The handle is not changed; a pack may run beside
+ *     extracts of the same handle, not beside an append or a close.
+ *   open_packed: the sections are UNTRUSTED.  The byte size of every section is first checked on the host against the
+ *     counts (block, control, literals; NOLZSS_ERR_INVALID_ARGUMENT naming the section), and every device read is
+ *     bounded by these sizes and never by what a section says.  The rules, all checked on the device: the spare nibble
+ *     is 0; a literal nibble has b == 0; the data bytes the nibbles ask for are exactly data_bytes (compared before a
+ *     data byte is read); L >= 1; v has 33 bits; x + L <= B for a copy, which covers a recovered y outside its strand's
+ *     range; no record straddles the end of a target or lies behind the last one; the literal records are n_literals;
+ *     sum L == decoded == sum(target_lengths); the separator list ascends and stays below B.  B, decoded, their sum,
+ *     z and k beyond the 32-bit pipeline are refused as nolzss_rlz_archive_open_records refuses them.  A violation
+ *     returns NOLZSS_ERR_INVALID_ARGUMENT; the message names the smallest offending record index and the rule, whatever
+ *     the schedule (a count that falls short names record z, "behind the last"; the separator list is judged first and
+ *     names the smallest offending list index).  Nothing is opened then, and an arena or device out-of-memory leaves
+ *     nothing open either.
+ *   The handle of open_packed behaves exactly as one of nolzss_rlz_archive_open_records: info, extract, extract_device,
+ *     export, pack and close serve it, append_index and finder_open refuse it as they refuse every archive not opened
+ *     over an index; device_bytes counts the block, 16 bytes per record and the position sample.
+ *   The calling thread's current device is left as it was. */
+typedef struct nolzss_rlz_archive_packed {
+    uint32_t block_mode, literal_mode;
+    uint64_t block_length;                      /* B */
+    uint64_t z, n_literals;
+    uint64_t decoded;                           /* sum of the lengths of the records = sum of the target lengths */
+    uint64_t num_separators;                    /* entries of the separator list of a block of mode 1 */
+    uint8_t *block, *control, *data, *literals; /* malloc'ed by pack (never NULL after a success); the caller's for open_packed */
+    uint64_t block_bytes, control_bytes, data_bytes, literal_bytes;
+} nolzss_rlz_archive_packed;
+int nolzss_rlz_archive_pack(const nolzss_rlz_archive *h, nolzss_rlz_archive_packed *out);
+void nolzss_free_rlz_archive_packed(nolzss_rlz_archive_packed *p);
+int nolzss_rlz_archive_open_packed(const nolzss_rlz_archive_packed *in, const uint64_t *target_lengths, size_t k, int device,
+                                   nolzss_rlz_archive **h);
+
 /* ---- relative-LZ archive: locate patterns inside the targets, through the parse ------------------- */
 /* Extension.  In which targets of an archive, and where, does a pattern occur?  Answered on the device without decoding
  * the targets ("Relative-LZ archive: locate through the parse"; a hybrid index after Ferrada, Gagie,

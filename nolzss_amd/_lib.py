@@ -121,6 +121,15 @@ class RlzArchiveAppendInfo(C.Structure):
                 ("capacity_records", C.c_uint64), ("device_bytes", C.c_uint64), ("reallocated", C.c_int32)]
 
 
+class RlzArchivePacked(C.Structure):
+    """Mirror of nolzss_rlz_archive_packed (include/nolzss_hip.h)."""
+    _fields_ = [("block_mode", C.c_uint32), ("literal_mode", C.c_uint32), ("block_length", C.c_uint64), ("z", C.c_uint64),
+                ("n_literals", C.c_uint64), ("decoded", C.c_uint64), ("num_separators", C.c_uint64),
+                ("block", C.c_void_p), ("control", C.c_void_p), ("data", C.c_void_p), ("literals", C.c_void_p),
+                ("block_bytes", C.c_uint64), ("control_bytes", C.c_uint64), ("data_bytes", C.c_uint64),
+                ("literal_bytes", C.c_uint64)]
+
+
 class RlzFinderSummary(C.Structure):
     """Mirror of nolzss_rlz_finder_summary (include/nolzss_hip.h)."""
     _fields_ = [("num_targets", C.c_uint64), ("z", C.c_uint64), ("total_length", C.c_uint64),
@@ -438,6 +447,10 @@ def _load():
     lib.nolzss_rlz_archive_open_index.argtypes = [vp, vpp]
     lib.nolzss_rlz_archive_append_index.argtypes = [vp, vp] + seqs[3:] + [C.POINTER(RlzArchiveAppendInfo)]
     lib.nolzss_rlz_archive_export.argtypes = [vp, vpp, szp, vpp, szp, vpp, szp]
+    lib.nolzss_rlz_archive_pack.argtypes = [vp, C.POINTER(RlzArchivePacked)]
+    lib.nolzss_free_rlz_archive_packed.argtypes = [C.POINTER(RlzArchivePacked)]
+    lib.nolzss_free_rlz_archive_packed.restype = None
+    lib.nolzss_rlz_archive_open_packed.argtypes = [C.POINTER(RlzArchivePacked), vp, sz, C.c_int, vpp]
     lib.nolzss_rlz_finder_open.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vpp]
     lib.nolzss_rlz_finder_info.argtypes = [vp, C.POINTER(RlzFinderSummary)]
     lib.nolzss_rlz_finder_count.argtypes = [vp] + seqs[3:] + [vp]
@@ -514,6 +527,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_index_codes", "nolzss_rlz_index_close", "nolzss_rlz_index_count", "nolzss_rlz_index_locate",
     "nolzss_debug_rlz_locate_shifts", "nolzss_rlz_index_seeds", "nolzss_free_rlz_seeds_result",
     "nolzss_rlz_archive_open_index", "nolzss_rlz_archive_append_index", "nolzss_rlz_archive_export",
+    "nolzss_rlz_archive_pack", "nolzss_free_rlz_archive_packed", "nolzss_rlz_archive_open_packed",
     "nolzss_rlz_finder_open", "nolzss_rlz_finder_info", "nolzss_rlz_finder_count", "nolzss_rlz_finder_locate",
     "nolzss_rlz_finder_kernel", "nolzss_rlz_finder_close",
     "nolzss_debug_pyramid", "nolzss_debug_nearest", "nolzss_debug_lds_search",

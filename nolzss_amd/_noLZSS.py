@@ -1231,6 +1231,12 @@ def _ranges_array(ranges):
     return np.ascontiguousarray(r, dtype=np.uint64)
 
 
+# the fields of nolzss_rlz_archive_packed: the counts, and each section with the field that holds its size
+PACKED_COUNTS = ("block_mode", "literal_mode", "block_length", "z", "n_literals", "decoded", "num_separators")
+PACKED_SECTIONS = (("block", "block_bytes"), ("control", "control_bytes"), ("data", "data_bytes"),
+                   ("literals", "literal_bytes"))
+
+
 class RlzArchiveHandle:
     """Extension: the reference block and the records of a relative-LZ collection kept in device memory (C ABI
     nolzss_rlz_archive_*), any number of range extractions from them.  A context manager; close() may be called more
@@ -1308,6 +1314,41 @@ class RlzArchiveHandle:
             for q in (blk, rec, lit):
                 lib.nolzss_free(q)
         return block, records, literals
+
+    def pack(self) -> dict:
+        """-> the sections of the compact container, made on the device from the resident records: block_mode,
+        literal_mode, block_length, z, n_literals, decoded, num_separators and the bytes of block, control, data and
+        literals.  C ABI nolzss_rlz_archive_pack (its header states the format)."""
+        h = self._handle()
+        p = _lib.RlzArchivePacked()
+        check(lib.nolzss_rlz_archive_pack(h, C.byref(p)))
+        try:
+            out = {name: int(getattr(p, name)) for name in PACKED_COUNTS}
+            for name, size in PACKED_SECTIONS:
+                out[name] = C.string_at(getattr(p, name), getattr(p, size))
+        finally:
+            lib.nolzss_free_rlz_archive_packed(C.byref(p))
+        return out
+
+    @classmethod
+    def open_packed(cls, sections, target_lengths):
+        """What pack() returned (or a file held), expanded and checked on the device.  C ABI
+        nolzss_rlz_archive_open_packed (its header states the rules)."""
+        p = _lib.RlzArchivePacked()
+        keep = []
+        for name in PACKED_COUNTS:
+            setattr(p, name, operator.index(sections[name]))
+        for name, size in PACKED_SECTIONS:
+            raw = bytes(sections[name])
+            buf = C.create_string_buffer(raw, len(raw)) if raw else None
+            keep.append(buf)
+            setattr(p, name, C.cast(buf, C.c_void_p) if buf is not None else None)
+            setattr(p, size, len(raw))
+        lens = np.ascontiguousarray([operator.index(x) for x in target_lengths], dtype=np.uint64)
+        h = C.c_void_p()
+        check(lib.nolzss_rlz_archive_open_packed(C.byref(p), lens.ctypes.data if lens.size else None, lens.size,
+                                                 _default_device, C.byref(h)))
+        return cls(h)
 
     def extract_array(self, ranges):
         """(target index, lo, hi) rows -> (uint8 array of the ranges back to back, uint64 offsets of q + 1 entries)."""

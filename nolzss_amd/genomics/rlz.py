@@ -14,6 +14,7 @@ RlzIndex keeps the suffix structures of the reference on the GPU and matches tar
 same records, the reference sorted once, and no limit on the number of targets.
 """
 import operator
+import struct
 
 import numpy as np
 
@@ -242,6 +243,118 @@ def load_archive_arrays(path):
     return chk["block"].tobytes(), chk["records"], chk["literals"].tobytes(), chk["target_lengths"], ids
 
 
+# ---- the compact container ("Relative-LZ archive: the compact container"; the format:
+# include/nolzss_hip.h, nolzss_rlz_archive_pack) -------------------------------------------------------------------
+PACKED_MAGIC = b"noLZRLZ1"
+_PACKED_HEADER = struct.Struct("<8sII12Q")  # magic, version, flags, B, k, z, n_literals, decoded, separators, 6 sizes
+_PACKED_SECTIONS = ("block", "control", "data", "literals")
+
+
+def _packed_ids(ids, k):
+    """The id rules of archive_arrays -> the ids section (k + 1 uint64 offsets, then the UTF-8 bytes)"""
+    names = [i.encode("utf-8") if isinstance(i, str) else bytes(i) for i in ids]
+    if len(names) != k:
+        raise ValueError(f"inconsistent sizes: {len(names)} ids for {k} targets")
+    if len(set(names)) != len(names):
+        raise ValueError("ids must be distinct")
+    if any(name.endswith(b"\0") for name in names):
+        raise ValueError("an id must not end in a NUL byte")
+    offsets = np.zeros(k + 1, dtype="<u8")
+    np.cumsum([len(x) for x in names], out=offsets[1:])
+    return offsets.tobytes() + b"".join(names)
+
+
+def _packed_section_sizes(s):
+    """The byte sizes the counts of the sections ask for: (block, control, literals); data is free"""
+    B, nlit = s["block_length"], s["n_literals"]
+    return ((B + 3) // 4 + 4 * s["num_separators"] if s["block_mode"] else B, (s["z"] + 1) // 2,
+            (nlit + 3) // 4 if s["literal_mode"] else nlit)
+
+
+def write_packed_archive(path, sections, target_lengths, ids=None):
+    """One compact container file of what RlzArchiveHandle.pack returned (a dict: block_mode, literal_mode,
+    block_length, z, n_literals, decoded, num_separators and the bytes of block, control, data, literals), the target
+    lengths and the ids (None: the file carries none; the rules of archive_arrays).  ValueError for sizes that do not
+    fit the counts.  No device."""
+    s = sections
+    lengths = np.ascontiguousarray(np.asarray(target_lengths).reshape(-1), dtype="<u8")
+    want = _packed_section_sizes(s)
+    have = (len(s["block"]), len(s["control"]), len(s["literals"]))
+    if have != want or (not s["block_mode"] and s["num_separators"]):
+        raise ValueError(f"inconsistent sizes: block, control and literal sections of {have} bytes, the counts ask for {want}")
+    if sum(lengths.tolist()) != s["decoded"]:  # (exact: a uint64 sum could wrap)
+        raise ValueError(f"inconsistent sizes: the target lengths sum to {sum(lengths.tolist())} and the records cover "
+                         f"{s['decoded']} bytes behind the block")
+    parts = [lengths.tobytes(), b"" if ids is None else _packed_ids(ids, len(lengths))] + [bytes(s[n]) for n in _PACKED_SECTIONS]
+    flags = (1 if s["block_mode"] else 0) | (2 if s["literal_mode"] else 0) | (0 if ids is None else 4)
+    head = _PACKED_HEADER.pack(PACKED_MAGIC, 1, flags, s["block_length"], len(lengths), s["z"], s["n_literals"],
+                               s["decoded"], s["num_separators"], *[len(x) for x in parts])
+    with open(path, "wb") as fh:
+        fh.write(head)
+        for x in parts:
+            fh.write(x)
+            fh.write(b"\0" * (-len(x) % 8))
+
+
+def read_packed_archive(path):
+    """-> (sections, target lengths as a uint64 array, ids or None) of a file write_packed_archive wrote.  The container
+    is checked here -- magic, version, flags, every section inside the file and of the size the counts ask for, zero
+    padding, nothing behind the last section, the id table --, ValueError otherwise; what the sections SAY is checked on
+    the device at open.  No device."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+
+    def bad(why):
+        return ValueError(f"{path}: not a compact relative-LZ archive ({why})")
+
+    if len(raw) < _PACKED_HEADER.size or raw[:8] != PACKED_MAGIC:
+        raise bad("bad magic")
+    f = _PACKED_HEADER.unpack_from(raw)
+    version, flags, B, k, z, nlit, decoded, seps = f[1:9]
+    sizes = f[9:]
+    if version != 1:
+        raise bad(f"version {version}, this reader knows version 1")
+    if flags & ~7:
+        raise bad(f"unknown flags {flags:#x}")
+    at, parts = _PACKED_HEADER.size, []
+    for name, n in zip(("target lengths", "ids") + _PACKED_SECTIONS, sizes):
+        end = at + n + (-n % 8)
+        if end > len(raw):
+            raise bad(f"the {name} section ends behind the end of the file")
+        if any(raw[at + n:end]):
+            raise bad(f"non-zero padding behind the {name} section")
+        parts.append(raw[at:at + n])
+        at = end
+    if at != len(raw):
+        raise bad(f"{len(raw) - at} bytes behind the last section")
+    if sizes[0] != 8 * k:
+        raise bad(f"{sizes[0]} bytes of target lengths for {k} targets")
+    lengths = np.frombuffer(parts[0], dtype="<u8").astype(np.uint64)
+    ids = None
+    if flags & 4:
+        if sizes[1] < 8 * (k + 1):
+            raise bad("the ids section is shorter than its offsets")
+        offs = np.frombuffer(parts[1], dtype="<u8", count=k + 1).tolist()
+        names = parts[1][8 * (k + 1):]
+        if offs[0] != 0 or offs[-1] != len(names) or any(offs[j] > offs[j + 1] for j in range(k)):
+            raise bad("the id offsets do not tile the id bytes")
+        try:
+            ids = [names[offs[j]:offs[j + 1]].decode("utf-8") for j in range(k)]
+        except UnicodeDecodeError as e:
+            raise bad(f"an id is not UTF-8: {e}")
+        _packed_ids(ids, k)
+    elif sizes[1]:
+        raise bad("an ids section in a file without ids")
+    s = {"block_mode": flags & 1, "literal_mode": (flags >> 1) & 1, "block_length": B, "z": z, "n_literals": nlit,
+         "decoded": decoded, "num_separators": seps, "block": parts[2], "control": parts[3], "data": parts[4],
+         "literals": parts[5]}
+    if (len(s["block"]), len(s["control"]), len(s["literals"])) != _packed_section_sizes(s) or (not s["block_mode"] and seps):
+        raise bad("the block, control or literal section has not the size the counts ask for")
+    if sum(lengths.tolist()) != decoded:  # (exact: a uint64 sum could wrap)
+        raise bad(f"the target lengths do not sum to the {decoded} decoded bytes of the header")
+    return s, lengths, ids
+
+
 class RlzArchive:
     """A relative-LZ collection resident on the GPU: the reference block and the records of every target stay in device
     memory, and any batch of (target, lo, hi) ranges comes back as bytes with one kernel launch -- nothing the caller
@@ -277,9 +390,30 @@ class RlzArchive:
 
     @classmethod
     def load(cls, path, device=None):
-        """The file save() wrote; it is checked on the host (ValueError) before the device is touched."""
-        block, records, literals, lengths, ids = load_archive_arrays(path)
-        return cls(block, records, literals, lengths, ids=ids, device=device)
+        """The file save() wrote; it is checked on the host (ValueError) before the device is touched.  A file that
+        begins with the magic of the compact container (save(path, compact=True)) goes up as it is and is expanded and
+        checked on the device; every other file is the .npz."""
+        try:
+            with open(path, "rb") as fh:
+                magic = fh.read(len(PACKED_MAGIC))
+        except OSError:  # (the existing way reports a file that cannot be read)
+            magic = b""
+        if magic != PACKED_MAGIC:
+            block, records, literals, lengths, ids = load_archive_arrays(path)
+            return cls(block, records, literals, lengths, ids=ids, device=device)
+        sections, lengths, ids = read_packed_archive(path)
+        self = cls.__new__(cls)
+        self._handle, self._arrays, self._bound = None, None, None
+        self.ids = ids
+        self._index = target_index_map(self.ids)
+        previous = _native.get_device()
+        if device is not None:
+            _native.set_device(device)
+        try:
+            self._handle = _native.RlzArchiveHandle.open_packed(sections, lengths)
+        finally:
+            _native.set_device(previous)
+        return self
 
     @classmethod
     def from_index(cls, index, ids=None):
@@ -302,7 +436,7 @@ class RlzArchive:
         carries ids, distinct from each other and from those present.  ValueError before any device work otherwise.  If
         a later batch fails, the batches before it stay appended."""
         h = self._live()
-        if self._arrays is not None:
+        if self._bound is None:  # (host records, or a loaded file: neither is bound to an index)
             raise ValueError("append needs an archive made by RlzArchive.from_index: this one was built from host records")
         targets = list(targets)
         names = _check_append_ids(self.ids, ids, len(targets))
@@ -323,14 +457,19 @@ class RlzArchive:
         snapshot of the archive as it is now, built on the GPU from the resident records ("Relative-LZ
         archive: locate through the parse"); after an append, open a new one.  prefix_syms as in RlzIndex.build."""
         h = self._live()
-        if self._arrays is not None:
+        if self._bound is None:
             raise ValueError("finder needs an archive made by RlzArchive.from_index: this one was built from host records")
         return RlzArchiveFinder(_native.RlzFinderHandle.open(h, self._bound._live(), max_pattern_length, prefix_syms))
 
-    def save(self, path):
-        """One .npz holding block, records, literals, target lengths and ids, raw."""
+    def save(self, path, compact: bool = False):
+        """One .npz holding block, records, literals, target lengths and ids, raw.  compact=True: the compact container
+        instead, packed on the device from the resident records ("Relative-LZ archive: the compact
+        container"); load() reads both."""
         h = self._live()
-        if self._arrays is None:  # index-built: the host form comes back from the device
+        if compact:
+            write_packed_archive(path, h.pack(), h.target_lengths, self.ids)
+            return
+        if self._arrays is None:  # index-built or loaded from a container: the host form comes back from the device
             block, records, literals = h.export()
             save_archive_arrays(path, archive_arrays(block, records, literals, h.target_lengths, self.ids))
             return
@@ -1070,4 +1209,4 @@ def resolve_target(target, index, count):
 
 
 __all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "INSERTION_DTYPE", "insertion_bases", "PILEUP_CHANNELS", "RlzPileup", "COHORT_SITE_DTYPE", "RlzCohort", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
-           "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches"]
+           "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches", "write_packed_archive", "read_packed_archive"]
