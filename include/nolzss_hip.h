@@ -1551,6 +1551,9 @@ int nolzss_debug_rlz_pileup_consensus(const char *block, size_t B, const char *c
                                       nolzss_rlz_insertions_result *insertions, nolzss_rlz_consensus_result *consensus);
 /* Capacity and high-water mark (bytes) of the device arena of `device` (lane 0). */
 int nolzss_debug_arena(int device, size_t *capacity, size_t *peak);
+/* The device allocations the resident handles of this process hold at the moment (index, archive, finder, pileup,
+ * cohort, dotplot): their number and the bytes asked for.  Reads two counters and touches no device. */
+int nolzss_debug_device_buffers(size_t *buffers, size_t *bytes);
 /* The FASTA reader behind the nolzss_*fasta* entry points (host only, no device needed): records and
  * ids as NUL-terminated strings back to back; sanitize_mode 0 = remove ambiguous, 1 = strict.
  * reference: parse_fasta_sequences_and_ids, fasta_processor.cpp:28-128.  Free both with nolzss_free(). */

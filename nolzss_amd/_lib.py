@@ -480,6 +480,8 @@ def _load():
     if hasattr(lib, "nolzss_debug_cursor"):  # (NOLZSS_LIB: a variant built from an older commit has none)
         lib.nolzss_debug_cursor.argtypes = [C.c_int, vp]
     lib.nolzss_debug_arena.argtypes = [C.c_int, szp, szp]
+    if hasattr(lib, "nolzss_debug_device_buffers"):  # (NOLZSS_LIB: a variant built from an older commit has none)
+        lib.nolzss_debug_device_buffers.argtypes = [szp, szp]
     lib.nolzss_debug_trim_arenas.argtypes = [C.c_int, szp]
     lib.nolzss_debug_parse_fasta.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), szp, C.POINTER(C.c_void_p),
                                              szp, szp]
@@ -505,6 +507,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_factorize_dna_rc_w_ref_fasta_files", "nolzss_write_factors_dna_w_reference_fasta_files_to_binary",
     "nolzss_free_batch", "nolzss_profile_enable", "nolzss_profile_reset", "nolzss_profile_report",
     "nolzss_debug_arrays", "nolzss_debug_sort_pairs", "nolzss_debug_scan", "nolzss_debug_arena",
+    "nolzss_debug_device_buffers",
     "nolzss_debug_batch_counters", "nolzss_factorize_batch_dna_w_rc",
     "nolzss_debug_trim_arenas", "nolzss_debug_parse_fasta",
     "nolzss_read_nucleotide_fasta", "nolzss_free_nucleotide_fasta", "nolzss_debug_parse_nucleotide_fasta", "nolzss_debug_lpt_plan", "nolzss_debug_batch_plan", "nolzss_factorize_batch_device",

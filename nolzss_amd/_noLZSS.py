@@ -2172,6 +2172,13 @@ def debug_arena():
     return cap.value, peak.value
 
 
+def debug_device_buffers():
+    """(live buffers, live bytes) of the device allocations the resident handles of this process hold; no device is touched."""
+    buffers, nbytes = C.c_size_t(), C.c_size_t()
+    check(lib.nolzss_debug_device_buffers(C.byref(buffers), C.byref(nbytes)))
+    return buffers.value, nbytes.value
+
+
 def debug_parse_fasta(path, sanitize_mode: str = "remove_ambiguous"):
     """[(id, sequence bytes)] as the native FASTA reader sees the file (host only)."""
     ids, seqs = C.c_void_p(), C.c_void_p()

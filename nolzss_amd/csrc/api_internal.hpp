@@ -26,6 +26,7 @@
 
 #include <malloc.h>
 
+#include "device_buf.hpp"
 #include "fasta_reader.hpp"
 #include "host_util.hpp"
 #include "pipeline.hpp"
@@ -79,8 +80,6 @@ struct Session {
 };
 
 size_t trim_idle_arenas(int device, const Context *keep);
-// a device allocation of a handle's own (hipMalloc; hipFree it): one retry after trimming the idle arenas
-void *device_alloc(Context &ctx, size_t bytes);
 void reserve_arena_for(Context &ctx, size_t n, size_t extra = 0);
 uint8_t *host_stage(Context &ctx, size_t bytes);
 void upload_bytes(Context &ctx, void *d_dst, const void *h_src, size_t n);
@@ -105,7 +104,14 @@ size_t run_plain_host(Context &ctx, const uint8_t *text, size_t n, size_t start_
 struct FreeBlock {
     void operator()(void *p) const { free_block(p); }
 };
-using FactorBlock = std::unique_ptr<nolzss_factor, FreeBlock>;
+template <class T> using HostBlock = std::unique_ptr<T, FreeBlock>;
+using FactorBlock = HostBlock<nolzss_factor>;
+// `count` entries (one for count = 0) from alloc_factor_block; throws std::bad_alloc
+template <class T> HostBlock<T> host_block(size_t count) {
+    HostBlock<T> b(static_cast<T *>(alloc_factor_block(sizeof(T) * (count ? count : 1))));
+    if (!b) throw std::bad_alloc();
+    return b;
+}
 // z records from device memory into a fresh block (empty for z = 0), behind everything queued on ctx.stream; they have
 // arrived on return.  Throws std::bad_alloc or the device's error.
 FactorBlock download_factors(Context &ctx, const void *d_recs, size_t z);

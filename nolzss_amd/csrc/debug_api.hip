@@ -520,6 +520,14 @@ int nolzss_debug_arena(int device, size_t *capacity, size_t *peak) {
     });
 }
 
+int nolzss_debug_device_buffers(size_t *buffers, size_t *bytes) {
+    return guarded([&] {
+        if (!buffers || !bytes) throw std::invalid_argument("output pointer is null");
+        *buffers = g_device_buffers.load();
+        *bytes = g_device_buffer_bytes.load();
+    });
+}
+
 int nolzss_debug_scan(uint32_t *data, size_t n, int mode, int device) {
     return guarded([&] {
         if (n == 0) return;

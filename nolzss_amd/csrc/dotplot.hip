@@ -311,26 +311,18 @@ bool force_global() {  // every pixel and hover key straight to global memory, f
 using namespace nolzss;
 using namespace nolzss::api;
 
-// The handle: the records and the sorted sentinel keys in device allocations of its own (not arena memory, which the
-// next call on the device recycles), and the statistics at min_factor_length = 1.
+// The handle: the records and the sorted sentinel keys in DeviceBufs (device_buf.hpp), and the statistics at
+// min_factor_length = 1.
 struct nolzss_dotplot {
     int device = 0;
     uint64_t z = 0;
-    Rec *d_recs = nullptr;
-    uint64_t *d_sentinels = nullptr;
+    DeviceBuf recs, sentinel_keys;
     std::vector<uint64_t> sentinels;  // ascending: factor indices (by_index) or start positions
     bool by_index = false;
     MapStats st{0, 0, 0, 0, 0, 0, 0};
     std::vector<uint64_t> sentinel_starts;
-    ~nolzss_dotplot() {  // (the calling thread's current device stays what it was)
-        if (!d_recs && !d_sentinels) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        if (d_recs) (void)hipFree(d_recs);
-        if (d_sentinels) (void)hipFree(d_sentinels);
-        if (known && current != device) (void)hipSetDevice(current);
-    }
+    const Rec *d_recs() const { return recs.as<Rec>(); }
+    const uint64_t *d_sentinels() const { return sentinel_keys.as<uint64_t>(); }
 };
 
 namespace {
@@ -343,25 +335,25 @@ void adopt_records(Context &ctx, nolzss_dotplot &h, const void *recs, bool on_de
     h.z = z;
     h.device = ctx.device;
     if (z == 0) return;
-    h.d_recs = static_cast<Rec *>(device_alloc(ctx, sizeof(Rec) * z));
+    h.recs.alloc(ctx, sizeof(Rec) * z);
     if (on_device) {
-        HIP_CHECK(hipMemcpyAsync(h.d_recs, recs, sizeof(Rec) * z, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(h.recs.get(), recs, sizeof(Rec) * z, hipMemcpyDeviceToDevice, s));
     } else {
         ProfScope ps(ctx.profiler(), "records_h2d", s, 24.0 * (double)z);
-        upload_bytes(ctx, h.d_recs, recs, sizeof(Rec) * z);
+        upload_bytes(ctx, h.recs.get(), recs, sizeof(Rec) * z);
     }
     if (!h.sentinels.empty()) {
-        h.d_sentinels = static_cast<uint64_t *>(device_alloc(ctx, sizeof(uint64_t) * h.sentinels.size()));
-        HIP_CHECK(hipMemcpyAsync(h.d_sentinels, h.sentinels.data(), sizeof(uint64_t) * h.sentinels.size(),
+        h.sentinel_keys.alloc(ctx, sizeof(uint64_t) * h.sentinels.size());
+        HIP_CHECK(hipMemcpyAsync(h.sentinel_keys.get(), h.sentinels.data(), sizeof(uint64_t) * h.sentinels.size(),
                                  hipMemcpyHostToDevice, s));
     }
     MapStats *d_st = ctx.arena.alloc<MapStats>(1);
     const MapStats init{0, 0, ~0ull, 0, 0, 0, 0};
     HIP_CHECK(hipMemcpyAsync(d_st, &init, sizeof init, hipMemcpyHostToDevice, s));
-    const KeepRule keep{1, h.d_sentinels, (uint32_t)h.sentinels.size(), h.by_index ? 1u : 0u, 0};
+    const KeepRule keep{1, h.d_sentinels(), (uint32_t)h.sentinels.size(), h.by_index ? 1u : 0u, 0};
     {
         ProfScope ps(ctx.profiler(), "map_stats", s, 24.0 * (double)z);
-        map_stats_kernel<<<record_grid(z), kRecThreads, 0, s>>>(h.d_recs, z, keep, d_st);
+        map_stats_kernel<<<record_grid(z), kRecThreads, 0, s>>>(h.d_recs(), z, keep, d_st);
         KERNEL_CHECK();
     }
     HIP_CHECK(hipMemcpyAsync(&h.st, d_st, sizeof h.st, hipMemcpyDeviceToHost, s));
@@ -369,7 +361,7 @@ void adopt_records(Context &ctx, nolzss_dotplot &h, const void *recs, bool on_de
     if (!h.by_index && !h.sentinels.empty()) {  // the sentinels that begin a factor
         const uint32_t n = (uint32_t)h.sentinels.size();
         uint32_t *d_found = ctx.arena.alloc<uint32_t>(n);
-        sentinel_hits_kernel<<<(unsigned)div_up((size_t)n, (size_t)256), 256, 0, s>>>(h.d_recs, z, h.d_sentinels, n, d_found);
+        sentinel_hits_kernel<<<(unsigned)div_up((size_t)n, (size_t)256), 256, 0, s>>>(h.d_recs(), z, h.d_sentinels(), n, d_found);
         KERNEL_CHECK();
         found.resize(n);
         HIP_CHECK(hipMemcpyAsync(found.data(), d_found, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
@@ -455,7 +447,7 @@ void render(const nolzss_dotplot &h, const nolzss_dotplot_view &v, nolzss_dotplo
     dv.strip_cols = std::min(dv.strip_cols, v.width);
     dv.hover_lds = !global_form && B && dv.strip_cols * col_bytes + hover_bytes <= kLdsBudget ? 1u : 0u;
     const size_t lds_bytes = dv.strip_cols * col_bytes + (dv.hover_lds ? hover_bytes : 0);
-    const KeepRule keep{v.min_factor_length, h.d_sentinels, (uint32_t)h.sentinels.size(), h.by_index ? 1u : 0u, 0};
+    const KeepRule keep{v.min_factor_length, h.d_sentinels(), (uint32_t)h.sentinels.size(), h.by_index ? 1u : 0u, 0};
     {
         ProfScope whole(ctx.profiler(), "dotplot_render", s);
         HIP_CHECK(hipMemsetAsync(d_out, 0, raster_bytes, s));
@@ -466,11 +458,11 @@ void render(const nolzss_dotplot &h, const nolzss_dotplot_view &v, nolzss_dotplo
             ProfScope ps(ctx.profiler(), "dotplot_raster", s, 24.0 * (double)h.z);
             const uint64_t chunks = div_up((size_t)h.z, (size_t)kChunkRecords);
             const unsigned grid = (unsigned)std::min<uint64_t>(chunks, 1024);
-            dotplot_raster_kernel<<<grid, kThreads, lds_bytes, s>>>(h.d_recs, h.z, keep, dv, d_out, d_keys, d_vis);
+            dotplot_raster_kernel<<<grid, kThreads, lds_bytes, s>>>(h.d_recs(), h.z, keep, dv, d_out, d_keys, d_vis);
             KERNEL_CHECK();
         }
         if (B) {
-            hover_gather_kernel<<<(unsigned)div_up((size_t)B, (size_t)256), 256, 0, s>>>(h.d_recs, d_keys, B, d_table);
+            hover_gather_kernel<<<(unsigned)div_up((size_t)B, (size_t)256), 256, 0, s>>>(h.d_recs(), d_keys, B, d_table);
             KERNEL_CHECK();
         }
     }

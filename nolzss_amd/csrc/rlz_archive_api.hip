@@ -57,7 +57,7 @@ void open_records(const uint8_t *block, size_t block_len, const nolzss_factor *r
     if (z == 0) {  // an empty archive: no device
         if (n_literals) throw std::invalid_argument(literal_count_message(records, 0, n_literals));
         if (sum || overflow) throw std::invalid_argument(length_sum_message(0, sum, 0));
-        h->h_block.assign(block, block + block_len);  // (export hands it back; device_bytes stays 0)
+        h->h_block.assign(block, block + block_len);  // (export hands it back)
         *out = h.release();
         return;
     }
@@ -98,15 +98,12 @@ void open_records(const uint8_t *block, size_t block_len, const nolzss_factor *r
     if (chk.literals != n_literals) throw std::invalid_argument(literal_count_message(records, z, n_literals));
     if (overflow || sum != decoded) throw std::invalid_argument(length_sum_message(z, sum, decoded));
 
-    const size_t block_bytes = block_len ? block_len : 1;
-    h->d_block = static_cast<uint8_t *>(device_alloc(ctx, block_bytes));
-    h->d_recs = static_cast<ArchiveRec *>(device_alloc(ctx, sizeof(ArchiveRec) * z));
-    h->d_sample = static_cast<uint32_t *>(device_alloc(ctx, sizeof(uint32_t) * samples));
-    h->device_bytes = block_bytes + sizeof(ArchiveRec) * z + sizeof(uint32_t) * samples;
-    h->cap_recs = z;
+    h->block.alloc(ctx, block_len ? block_len : 1);
+    h->recs.alloc(ctx, sizeof(ArchiveRec) * z);
+    h->sample.alloc(ctx, sizeof(uint32_t) * samples);
     h->cap_samples = samples;
-    if (block_len) upload_bytes(ctx, h->d_block, block, block_len);
-    archive_pack(ctx, d_raw, z, block_len, n, lit_flags, d_lit, h->d_recs, h->d_sample);
+    if (block_len) upload_bytes(ctx, h->block.get(), block, block_len);
+    archive_pack(ctx, d_raw, z, block_len, n, lit_flags, d_lit, h->recs.as<ArchiveRec>(), h->sample.as<uint32_t>());
     HIP_CHECK(hipStreamSynchronize(s));
     ctx.prof.collect();
     *out = h.release();
@@ -191,8 +188,7 @@ void extract(const nolzss_rlz_archive &h, const nolzss_rlz_range *ranges, size_t
                 upload_bytes(ctx, d_plan, plan.data(), sizeof(uint32_t) * plan.size());
             }
             HIP_CHECK(hipMemsetAsync(d_err, 0xff, sizeof(unsigned long long), s));
-            const ArchiveView v{h.d_block, h.d_recs, h.d_sample, (uint32_t)h.z, (uint32_t)archive_samples((size_t)h.decoded)};
-            archive_extract(ctx, v, d_plan, d_plan + q + 1, (uint32_t)q, (uint32_t)total, d_out, d_err);
+            archive_extract(ctx, h.view(), d_plan, d_plan + q + 1, (uint32_t)q, (uint32_t)total, d_out, d_err);
             uint32_t e[2];
             ctx.read_back(reinterpret_cast<const uint32_t *>(d_err), e, 2);  // (waits for the kernel)
             const uint64_t key = (uint64_t)e[0] | ((uint64_t)e[1] << 32);
@@ -219,11 +215,9 @@ void extract(const nolzss_rlz_archive &h, const nolzss_rlz_range *ranges, size_t
 void export_archive(const nolzss_rlz_archive &h, uint8_t **block, size_t *block_len, nolzss_factor **records, size_t *z,
                     uint8_t **literals, size_t *n_literals) {
     const size_t zz = (size_t)h.z, nlit = (size_t)h.n_literals, blen = (size_t)h.block_len;
-    std::unique_ptr<uint8_t, FreeBlock> h_blk(static_cast<uint8_t *>(std::malloc(blen ? blen : 1)));
-    std::unique_ptr<uint8_t, FreeBlock> h_lit(static_cast<uint8_t *>(std::malloc(nlit ? nlit : 1)));
-    FactorBlock h_recs(static_cast<nolzss_factor *>(alloc_factor_block(sizeof(nolzss_factor) * (zz ? zz : 1))));
-    if (!h_blk || !h_lit || !h_recs) throw std::bad_alloc();
-    if (!h.d_block) {  // no records and no device memory: the host copy of the block
+    HostBlock<uint8_t> h_blk = host_block<uint8_t>(blen), h_lit = host_block<uint8_t>(nlit);
+    FactorBlock h_recs = host_block<nolzss_factor>(zz);
+    if (!h.block) {  // no records and no device memory: the host copy of the block
         if (blen) std::memcpy(h_blk.get(), h.h_block.data(), blen);
     } else {
         DeviceRestore restore;
@@ -236,17 +230,17 @@ void export_archive(const nolzss_rlz_archive &h, uint8_t **block, size_t *block_
             reserve_arena_for(ctx, 0, sizeof(uint32_t) * zz + nlit + sizeof(Rec) * chunk + (size_t(4) << 20));
             if (blen) {
                 ProfScope ps(ctx.profiler(), "block_d2h", s, (double)blen);
-                download_bytes(ctx, h_blk.get(), h.d_block, blen);
+                download_bytes(ctx, h_blk.get(), h.block.get(), blen);
             }
             if (zz) {
                 uint32_t *d_index = ctx.arena.alloc<uint32_t>(zz);
                 uint8_t *d_lit = ctx.arena.alloc<uint8_t>(nlit ? nlit : 1);
                 Rec *d_out = ctx.arena.alloc<Rec>(chunk);
-                const uint64_t found = archive_literal_index(ctx, h.d_recs, zz, d_index);
+                const uint64_t found = archive_literal_index(ctx, h.recs.as<ArchiveRec>(), zz, d_index);
                 if (found != h.n_literals)
                     throw HipError("rlz archive: the resident records do not hold the literals the handle counts");
                 download_produced(ctx, "factors_d2h", h_recs.get(), d_out, zz, sizeof(Rec), chunk, [&](size_t c0, size_t cnt) {
-                    archive_export_records(ctx, h.d_recs, c0, cnt, h.block_len, d_index, d_out, d_lit);
+                    archive_export_records(ctx, h.recs.as<ArchiveRec>(), c0, cnt, h.block_len, d_index, d_out, d_lit);
                 });
                 if (nlit) download_bytes(ctx, h_lit.get(), d_lit, nlit);
             }
@@ -271,28 +265,12 @@ void archive_open_index(const nolzss_rlz_index &ix, nolzss_rlz_archive **out) {
     h->block_len = ix.view.B;
     h->index_serial = ix.serial;
     h->bases.assign(1, 0);
-    DeviceRestore restore;
-    Session ses(ix.device, nullptr);
-    Context &ctx = ses.ctx();
-    {
-        ProfScope whole(ctx.profiler(), "rlz_archive_open_index", ctx.stream);
-        const size_t block_bytes = ix.view.B ? ix.view.B : 1;
-        h->d_block = static_cast<uint8_t *>(device_alloc(ctx, block_bytes));
-        h->device_bytes = block_bytes;
-        archive_unpack_block(ctx, ix.view.text, ix.view.B, h->d_block);
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx.stream));
-    ctx.prof.collect();
+    with_index_session(ix.device, "rlz_archive_open_index", [&](Context &ctx) {
+        h->block.alloc(ctx, ix.view.B ? ix.view.B : 1);
+        archive_unpack_block(ctx, ix.view.text, ix.view.B, h->block.as<uint8_t>());
+    });
     *out = h.release();
 }
-
-// a device array that replaces one of the handle's: freed on the way out unless it was swapped in (then the old one is)
-struct Fresh {
-    void *p = nullptr;
-    ~Fresh() {
-        if (p) (void)hipFree(p);
-    }
-};
 
 void fill_append_info(const nolzss_rlz_archive &a, nolzss_rlz_archive_append_info *info, uint64_t targets, uint64_t records,
                       uint64_t literals, uint64_t bases, bool reallocated) {
@@ -305,8 +283,8 @@ void fill_append_info(const nolzss_rlz_archive &a, nolzss_rlz_archive_append_inf
     info->num_targets = a.lengths.size();
     info->z = a.z;
     info->total_length = a.decoded;
-    info->capacity_records = a.cap_recs;
-    info->device_bytes = a.device_bytes;
+    info->capacity_records = a.cap_recs();
+    info->device_bytes = a.device_bytes();
     info->reallocated = reallocated ? 1 : 0;
 }
 
@@ -343,10 +321,11 @@ void archive_append(nolzss_rlz_archive &a, const nolzss_rlz_index &ix, const cha
     const size_t chunk_max = chunk_knob("NOLZSS_RLZ_APPEND_CHUNK");
 
     DeviceRestore restore;
-    Fresh fresh_recs, fresh_sample;  // (freed while the handle's device is still current)
-    ArchiveRec *recs = a.d_recs;
-    uint32_t *sample = a.d_sample;
-    size_t cap_recs = a.cap_recs, cap_samples = a.cap_samples;
+    // the arrays that replace the handle's when it grows: swapped in at the commit, so what they hold on the way out goes
+    DeviceBuf fresh_recs, fresh_sample;
+    ArchiveRec *recs = a.recs.as<ArchiveRec>();
+    uint32_t *sample = a.sample.as<uint32_t>();
+    size_t cap_recs = a.cap_recs(), cap_samples = a.cap_samples;
     uint64_t z_new = 0, added = 0, lit_added = 0;
     const uint64_t decoded_new = a.decoded + bases;
     const size_t samples_old = archive_samples((size_t)a.decoded), samples_new = archive_samples((size_t)decoded_new);
@@ -375,16 +354,16 @@ void archive_append(nolzss_rlz_archive &a, const nolzss_rlz_index &ix, const cha
         // growth: max(needed, 2 x current), the old contents copied on the stream; the old array is freed at the commit
         if (z_new > cap_recs) {
             cap_recs = std::max<size_t>((size_t)z_new, 2 * cap_recs);
-            fresh_recs.p = device_alloc(ctx, sizeof(ArchiveRec) * cap_recs);
-            recs = static_cast<ArchiveRec *>(fresh_recs.p);
-            if (a.z) HIP_CHECK(hipMemcpyAsync(recs, a.d_recs, sizeof(ArchiveRec) * a.z, hipMemcpyDeviceToDevice, s));
+            fresh_recs.alloc(ctx, sizeof(ArchiveRec) * cap_recs);
+            recs = fresh_recs.as<ArchiveRec>();
+            if (a.z) HIP_CHECK(hipMemcpyAsync(recs, a.recs.get(), sizeof(ArchiveRec) * a.z, hipMemcpyDeviceToDevice, s));
         }
         if (samples_new > cap_samples) {
             cap_samples = std::max<size_t>(samples_new, 2 * cap_samples);
-            fresh_sample.p = device_alloc(ctx, sizeof(uint32_t) * cap_samples);
-            sample = static_cast<uint32_t *>(fresh_sample.p);
+            fresh_sample.alloc(ctx, sizeof(uint32_t) * cap_samples);
+            sample = fresh_sample.as<uint32_t>();
             if (samples_old)
-                HIP_CHECK(hipMemcpyAsync(sample, a.d_sample, sizeof(uint32_t) * samples_old, hipMemcpyDeviceToDevice, s));
+                HIP_CHECK(hipMemcpyAsync(sample, a.sample.get(), sizeof(uint32_t) * samples_old, hipMemcpyDeviceToDevice, s));
         }
         uint32_t *d_seps = ctx.arena.alloc<uint32_t>(k);
         upload_bytes(ctx, d_seps, b.separators.data(), sizeof(uint32_t) * k);
@@ -417,10 +396,9 @@ void archive_append(nolzss_rlz_archive &a, const nolzss_rlz_index &ix, const cha
     HIP_CHECK(hipStreamSynchronize(s));
     ctx.prof.collect();
     // the commit: host state only, after the device work has finished without error; the stream has drained
-    const bool moved = fresh_recs.p || fresh_sample.p;
-    if (fresh_recs.p) std::swap(fresh_recs.p, reinterpret_cast<void *&>(a.d_recs));
-    if (fresh_sample.p) std::swap(fresh_sample.p, reinterpret_cast<void *&>(a.d_sample));
-    a.cap_recs = cap_recs;
+    const bool moved = fresh_recs || fresh_sample;
+    if (fresh_recs) a.recs.swap(fresh_recs);
+    if (fresh_sample) a.sample.swap(fresh_sample);
     a.cap_samples = cap_samples;
     a.z = z_new;
     a.n_literals += lit_added;
@@ -429,7 +407,6 @@ void archive_append(nolzss_rlz_archive &a, const nolzss_rlz_index &ix, const cha
         a.decoded += target_lens[j];
         a.bases.push_back(a.decoded);
     }
-    a.device_bytes = (a.block_len ? a.block_len : 1) + sizeof(ArchiveRec) * cap_recs + sizeof(uint32_t) * cap_samples;
     fill_append_info(a, info, k, added, lit_added, bases, moved);
 }
 
@@ -454,7 +431,7 @@ int nolzss_rlz_archive_info(const nolzss_rlz_archive *h, nolzss_rlz_archive_summ
         info->total_length = h->bases.back();
         info->target_lengths = h->lengths.empty() ? nullptr : h->lengths.data();
         info->device = h->device;
-        info->device_bytes = h->device_bytes;
+        info->device_bytes = h->device_bytes();
     });
 }
 

@@ -80,11 +80,11 @@ void pack_archive(const nolzss_rlz_archive &h, nolzss_rlz_archive_packed *out) {
     if (z == 0) {  // no record: no kernel (the block of an archive over an index comes down as it is)
         std::vector<uint8_t> tmp;
         const uint8_t *src = h.h_block.data();
-        if (h.d_block && B) {
+        if (h.block && B) {
             tmp.resize(B);
             DeviceRestore restore;
             Session ses(h.device, nullptr);
-            download_bytes(ses.ctx(), tmp.data(), h.d_block, B);
+            download_bytes(ses.ctx(), tmp.data(), h.block.as<uint8_t>(), B);
             src = tmp.data();
         }
         block_mode = pack_block_host(src, B, block, block_bytes, seps);
@@ -101,7 +101,8 @@ void pack_archive(const nolzss_rlz_archive &h, nolzss_rlz_archive_packed *out) {
             // rank, offset and literal index 4 z each, diagonals 8 z, at most 9 z data bytes and z / 2 control bytes; the
             // literals raw and packed; the block's flags 4 B, its bases B / 4, its separators at most 4 B
             reserve_arena_for(ctx, 0, 30 * z + 2 * nlit + 9 * B + (size_t(4) << 20));
-            const PackPlan plan = packed_plan(ctx, h.d_recs, z, (uint32_t)B, z - nlit);
+            const ArchiveRec *d_recs = h.recs.as<ArchiveRec>();
+            const PackPlan plan = packed_plan(ctx, d_recs, z, (uint32_t)B, z - nlit);
             if (plan.data_bytes > 0xffffffffull)
                 throw std::invalid_argument("rlz archive: the data stream of the compact form would hold " +
                                             std::to_string(plan.data_bytes) + " bytes, 2^32 or more are refused");
@@ -111,7 +112,7 @@ void pack_archive(const nolzss_rlz_archive &h, nolzss_rlz_archive_packed *out) {
             data = alloc_bytes((size_t)data_bytes);
             uint8_t *d_control = ctx.arena.alloc<uint8_t>(cb);
             uint8_t *d_data = ctx.arena.alloc<uint8_t>(data_bytes ? (size_t)data_bytes : 1);
-            packed_write(ctx, h.d_recs, z, plan, d_control, d_data);
+            packed_write(ctx, d_recs, z, plan, d_control, d_data);
             {
                 ProfScope ps(ctx.profiler(), "packed_d2h", s, (double)cb + (double)data_bytes);
                 download_bytes(ctx, control.get(), d_control, cb);
@@ -119,20 +120,20 @@ void pack_archive(const nolzss_rlz_archive &h, nolzss_rlz_archive_packed *out) {
             }
             uint8_t *d_raw = ctx.arena.alloc<uint8_t>(nlit ? nlit : 1);
             uint8_t *d_two = ctx.arena.alloc<uint8_t>(packed_quarter(nlit) + 1);
-            literal_mode = packed_literals(ctx, h.d_recs, z, nlit, d_raw, d_two);
+            literal_mode = packed_literals(ctx, d_recs, z, nlit, d_raw, d_two);
             literal_bytes = literal_mode ? packed_quarter(nlit) : nlit;
             literals = alloc_bytes((size_t)literal_bytes);
             if (literal_bytes) download_bytes(ctx, literals.get(), literal_mode ? d_two : d_raw, (size_t)literal_bytes);
             uint8_t *d_quarter = ctx.arena.alloc<uint8_t>(packed_quarter(B) + 1);
             uint32_t *d_seps = nullptr;
             uint32_t num_seps = 0;
-            block_mode = packed_block(ctx, h.d_block, B, d_quarter, &d_seps, &num_seps);
+            block_mode = packed_block(ctx, h.block.as<uint8_t>(), B, d_quarter, &d_seps, &num_seps);
             seps = block_mode ? num_seps : 0;
             block_bytes = block_mode ? packed_quarter(B) + 4 * (uint64_t)num_seps : B;
             block = alloc_bytes((size_t)block_bytes);
             ProfScope ps(ctx.profiler(), "packed_d2h", s, (double)block_bytes);
             if (!block_mode) {
-                download_bytes(ctx, block.get(), h.d_block, B);
+                download_bytes(ctx, block.get(), h.block.as<uint8_t>(), B);
             } else {
                 if (B) download_bytes(ctx, block.get(), d_quarter, packed_quarter(B));
                 if (num_seps) download_bytes(ctx, block.get() + packed_quarter(B), d_seps, 4 * (size_t)num_seps);
@@ -220,12 +221,8 @@ void open_packed(const nolzss_rlz_archive_packed *in, const uint64_t *target_len
     std::vector<uint64_t> bounds(k + 1);  // decoded positions; saturating, a sum beyond 2^64 cannot be met by the records
     for (size_t j = 0; j <= k; ++j) bounds[j] = overflow ? (j ? ~0ull : 0) : h->bases[j];
 
-    DeviceRestore restore;
-    Session ses(device, nullptr);
-    Context &ctx = ses.ctx();
-    hipStream_t s = ctx.stream;
-    {
-        ProfScope whole(ctx.profiler(), "rlz_archive_open_packed", s);
+    with_index_session(device, "rlz_archive_open_packed", [&](Context &ctx) {
+        hipStream_t s = ctx.stream;
         const size_t samples = archive_samples((size_t)decoded);
         // the sections; offset, rank, length and position 4 z each, steps and their sums 16 z at most
         reserve_arena_for(ctx, 0, a.block_bytes + a.control_bytes + a.data_bytes + a.literal_bytes + sizeof(uint64_t) * (k + 1) +
@@ -235,20 +232,18 @@ void open_packed(const nolzss_rlz_archive_packed *in, const uint64_t *target_len
         uint8_t *d_data = ctx.arena.alloc<uint8_t>(a.data_bytes ? a.data_bytes : 1);
         uint8_t *d_lit = ctx.arena.alloc<uint8_t>(a.literal_bytes ? a.literal_bytes : 1);
         uint64_t *d_bounds = ctx.arena.alloc<uint64_t>(k + 1);
-        const size_t block_bytes = B ? B : 1;
-        h->d_block = static_cast<uint8_t *>(device_alloc(ctx, block_bytes));
-        h->d_recs = static_cast<ArchiveRec *>(device_alloc(ctx, sizeof(ArchiveRec) * z));
-        h->d_sample = static_cast<uint32_t *>(device_alloc(ctx, sizeof(uint32_t) * (samples ? samples : 1)));
-        h->device_bytes = block_bytes + sizeof(ArchiveRec) * z + sizeof(uint32_t) * samples;
-        h->cap_recs = z;
+        h->block.alloc(ctx, B ? B : 1);
+        h->recs.alloc(ctx, sizeof(ArchiveRec) * z);
+        h->sample.alloc(ctx, sizeof(uint32_t) * (samples ? samples : 1));
         h->cap_samples = samples;
+        ArchiveRec *d_recs = h->recs.as<ArchiveRec>();
         {
             ProfScope ps(ctx.profiler(), "packed_h2d", s,
                          (double)(a.block_bytes + a.control_bytes + a.data_bytes + a.literal_bytes));
             if (a.block_mode) {
                 if (a.block_bytes) upload_bytes(ctx, d_section, a.block, a.block_bytes);
             } else if (B) {
-                upload_bytes(ctx, h->d_block, a.block, B);
+                upload_bytes(ctx, h->block.as<uint8_t>(), a.block, B);
             }
             upload_bytes(ctx, d_control, a.control, a.control_bytes);
             if (a.data_bytes) upload_bytes(ctx, d_data, a.data, a.data_bytes);
@@ -257,7 +252,7 @@ void open_packed(const nolzss_rlz_archive_packed *in, const uint64_t *target_len
         }
         try {
             if (a.block_mode) {
-                const uint64_t bad = unpack_block(ctx, d_section, B, (uint32_t)a.num_separators, h->d_block);
+                const uint64_t bad = unpack_block(ctx, d_section, B, (uint32_t)a.num_separators, h->block.as<uint8_t>());
                 if (bad != ~0ull) throw std::invalid_argument(rule_message(bad >> 4, (uint32_t)(bad & 15u), "separator"));
             }
             UnpackIn ui{};
@@ -270,21 +265,18 @@ void open_packed(const nolzss_rlz_archive_packed *in, const uint64_t *target_len
             ui.B = (uint32_t)B;
             ui.bounds = d_bounds;
             ui.k = (uint32_t)k;
-            const UnpackOut res = unpack_records(ctx, ui, z, h->d_recs);
+            const UnpackOut res = unpack_records(ctx, ui, z, d_recs);
             if (res.bad != ~0ull) throw std::invalid_argument(rule_message(res.bad >> 4, (uint32_t)(res.bad & 15u)));
             if (z - res.copies != nlit)
                 throw std::invalid_argument(rule_message(z, kPackLiteralCount) + ": the " + std::to_string(z) + " records hold " +
                                             std::to_string(z - res.copies) + " literals and n_literals is " + std::to_string(nlit));
             if (overflow || sum != decoded || res.covered != decoded) throw std::invalid_argument(sum_message(res.covered));
-            archive_extend_sample(ctx, h->d_recs, 0u, (uint32_t)z, 0u, (uint32_t)samples, h->d_sample);
+            archive_extend_sample(ctx, d_recs, 0u, (uint32_t)z, 0u, (uint32_t)samples, h->sample.as<uint32_t>());
         } catch (...) {
             (void)hipStreamSynchronize(s);  // nothing still reads the caller's sections or writes the handle's arrays when they go
             throw;
         }
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipGetLastError());
-    ctx.prof.collect();
+    });
     *out = h.release();
 }
 

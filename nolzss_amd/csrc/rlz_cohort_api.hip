@@ -41,27 +41,16 @@ void cohort_open(const nolzss_rlz_index *ix, nolzss_rlz_cohort **out) {
     *out = c.release();  // (no device memory until the first add)
 }
 
-// Room for one more sample: a larger allocation, the planes copied over, the old one freed.  Nothing of the handle
-// changes before the copy has arrived.
+// Room for one more sample (DeviceBuf::grow_keeping; a cohort of block length 0 never comes here, so a sample has bytes).
 void secure_room(Context &ctx, nolzss_rlz_cohort &c) {
     const uint64_t n = c.samples.size();
     if (n < c.capacity) return;
     uint64_t cap = c.capacity ? 2 * c.capacity : c.first_capacity;
     cap = cap < n + 1 ? n + 1 : cap;
     cap = cap < NOLZSS_RLZ_COHORT_MAX_SAMPLES ? cap : NOLZSS_RLZ_COHORT_MAX_SAMPLES;
-    const size_t per = sample_bytes(c), bytes = per * (size_t)cap;
+    const size_t per = sample_bytes(c);
     ProfScope ps(ctx.profiler(), "rlz_cohort_grow", ctx.stream, 2.0 * (double)per * (double)n);
-    uint64_t *d_new = static_cast<uint64_t *>(device_alloc(ctx, bytes ? bytes : 256));
-    if (n && per) {
-        const hipError_t e = hipMemcpyAsync(d_new, c.d_planes, per * (size_t)n, hipMemcpyDeviceToDevice, ctx.stream);
-        const hipError_t w = e == hipSuccess ? hipStreamSynchronize(ctx.stream) : e;
-        if (w != hipSuccess) {
-            (void)hipFree(d_new);
-            HIP_CHECK(w);
-        }
-    }
-    if (c.d_planes) (void)hipFree(c.d_planes);
-    c.d_planes = d_new;
+    c.planes.grow_keeping(ctx, per * (size_t)cap, per * (size_t)n);
     c.capacity = cap;
 }
 
@@ -106,7 +95,7 @@ void cohort_add_pileup(nolzss_rlz_cohort *c, nolzss_rlz_pileup *p, const nolzss_
             p->dirty = false;
         }
         unsigned long long *d_stats = ctx.arena.alloc<unsigned long long>(kCohortStats);
-        rlz_cohort_pack_counts(ctx, p->view, c->index->view.text, rule, c->d_planes + 3 * c->W * c->samples.size(), d_stats);
+        rlz_cohort_pack_counts(ctx, p->view, c->index->view.text, rule, c->planes.as<uint64_t>() + 3 * c->W * c->samples.size(), d_stats);
         download_bytes(ctx, stats, d_stats, sizeof stats);
     });
     commit(*c, stats, info);
@@ -136,7 +125,7 @@ void cohort_add_calls(nolzss_rlz_cohort *c, const char *calls, size_t n, nolzss_
             ProfScope ps(ctx.profiler(), "cohort_calls_h2d", ctx.stream, (double)n);
             upload_bytes(ctx, d_bytes, calls, n);
         }
-        rlz_cohort_pack_bytes(ctx, d_bytes, c->B, c->index->view.text, c->d_planes + 3 * c->W * c->samples.size(), d_stats);
+        rlz_cohort_pack_bytes(ctx, d_bytes, c->B, c->index->view.text, c->planes.as<uint64_t>() + 3 * c->W * c->samples.size(), d_stats);
         download_bytes(ctx, stats, d_stats, sizeof stats);  // (waits: the caller's bytes have gone up)
     });
     commit(*c, stats, info);
@@ -159,26 +148,21 @@ void cohort_distances(nolzss_rlz_cohort *c, nolzss_rlz_cohort_distances_result *
     std::lock_guard<std::mutex> lock(c->mu);
     const size_t N = c->samples.size(), cells = N * N;
     if (N == 0) return;
-    try {
-        out->differences = static_cast<uint32_t *>(alloc_factor_block(sizeof(uint32_t) * cells));
-        out->compared = static_cast<uint32_t *>(alloc_factor_block(sizeof(uint32_t) * cells));
-        if (!out->differences || !out->compared) throw std::bad_alloc();
-        if (c->B == 0) {
-            std::memset(out->differences, 0, sizeof(uint32_t) * cells);
-            std::memset(out->compared, 0, sizeof(uint32_t) * cells);
-        } else {
-            with_index_session(c->device, "rlz_cohort_distances_call", [&](Context &ctx) {
-                regrow_arena(ctx, 2 * sizeof(uint32_t) * cells + (size_t(4) << 20));
-                uint32_t *d_diff = ctx.arena.alloc<uint32_t>(cells), *d_cmp = ctx.arena.alloc<uint32_t>(cells);
-                rlz_cohort_pairs(ctx, c->d_planes, (uint32_t)N, c->B, slice_knob(), d_diff, d_cmp);
-                download_records(ctx, "cohort_distances_d2h", out->differences, d_diff, cells, sizeof(uint32_t));
-                download_records(ctx, "cohort_distances_d2h", out->compared, d_cmp, cells, sizeof(uint32_t));
-            });
-        }
-    } catch (...) {
-        nolzss_free_rlz_cohort_distances_result(out);
-        throw;
+    HostBlock<uint32_t> differences = host_block<uint32_t>(cells), compared = host_block<uint32_t>(cells);
+    if (c->B == 0) {
+        std::memset(differences.get(), 0, sizeof(uint32_t) * cells);
+        std::memset(compared.get(), 0, sizeof(uint32_t) * cells);
+    } else {
+        with_index_session(c->device, "rlz_cohort_distances_call", [&](Context &ctx) {
+            regrow_arena(ctx, 2 * sizeof(uint32_t) * cells + (size_t(4) << 20));
+            uint32_t *d_diff = ctx.arena.alloc<uint32_t>(cells), *d_cmp = ctx.arena.alloc<uint32_t>(cells);
+            rlz_cohort_pairs(ctx, c->planes.as<uint64_t>(), (uint32_t)N, c->B, slice_knob(), d_diff, d_cmp);
+            download_records(ctx, "cohort_distances_d2h", differences.get(), d_diff, cells, sizeof(uint32_t));
+            download_records(ctx, "cohort_distances_d2h", compared.get(), d_cmp, cells, sizeof(uint32_t));
+        });
     }
+    out->differences = differences.release();
+    out->compared = compared.release();
     out->num_samples = N;
 }
 
@@ -191,40 +175,34 @@ void cohort_sites(nolzss_rlz_cohort *c, uint64_t min_present, int with_reference
     const uint32_t B = c->B;
     if (N == 0 || B == 0 || min_present > N) return;
     const size_t chunk_max = chunk_knob("NOLZSS_RLZ_LOCATE_CHUNK");
-    nolzss_rlz_cohort_site *recs = nullptr;
-    try {
-        with_index_session(c->device, "rlz_cohort_sites_call", [&](Context &ctx) {
-            const size_t most = (size_t)B < chunk_max ? (size_t)B : chunk_max;
-            regrow_arena(ctx, 9 * (size_t)B + sizeof(CohortSiteRec) * most + (size_t(4) << 20));
-            const PackedText &block = c->index->view.text;
-            uint32_t *d_n = ctx.arena.alloc<uint32_t>(B), *d_off = ctx.arena.alloc<uint32_t>(B);
-            uint64_t *d_total = ctx.arena.alloc<uint64_t>(1);
-            uint64_t total = 0;  // at most B records: 32 bits hold every offset
-            {
-                ProfScope ps(ctx.profiler(), "rlz_cohort_sites", ctx.stream, 0.375 * (double)B * (double)N + 12.0 * (double)B);
-                rlz_cohort_site_flags(ctx, c->d_planes, (uint32_t)N, B, block, (uint32_t)min_present, with_reference != 0, d_n);
-                rlz_index_rep_total(ctx, d_n, B, d_total);
-                scan_exclusive_add_u32(d_n, d_off, B, nullptr, ctx.arena, ctx.stream);
-                download_bytes(ctx, &total, d_total, sizeof total);
-            }
-            total = total < B ? total : B;
-            if (total == 0) return;
-            recs = static_cast<nolzss_rlz_cohort_site *>(alloc_factor_block(sizeof(nolzss_rlz_cohort_site) * (size_t)total));
-            if (!recs) throw std::bad_alloc();
-            const size_t chunk = total < chunk_max ? (size_t)total : chunk_max;
-            CohortSiteRec *d_stage = ctx.arena.alloc<CohortSiteRec>(chunk);
-            download_produced(ctx, "cohort_sites_d2h", recs, d_stage, (size_t)total, sizeof(CohortSiteRec), chunk,
-                              [&](size_t c0, size_t cnt) {
-                                  rlz_cohort_site_records(ctx, c->d_planes, (uint32_t)N, B, block, d_n, d_off, c0, (uint32_t)cnt, d_stage);
-                              });
-            out->num_sites = (size_t)total;
-        });
-    } catch (...) {
-        free_block(recs);
-        std::memset(out, 0, sizeof *out);
-        throw;
-    }
-    out->sites = recs;
+    HostBlock<nolzss_rlz_cohort_site> recs;
+    uint64_t total = 0;  // at most B records: 32 bits hold every offset
+    with_index_session(c->device, "rlz_cohort_sites_call", [&](Context &ctx) {
+        const size_t most = (size_t)B < chunk_max ? (size_t)B : chunk_max;
+        regrow_arena(ctx, 9 * (size_t)B + sizeof(CohortSiteRec) * most + (size_t(4) << 20));
+        const PackedText &block = c->index->view.text;
+        const uint64_t *d_planes = c->planes.as<uint64_t>();
+        uint32_t *d_n = ctx.arena.alloc<uint32_t>(B), *d_off = ctx.arena.alloc<uint32_t>(B);
+        uint64_t *d_total = ctx.arena.alloc<uint64_t>(1);
+        {
+            ProfScope ps(ctx.profiler(), "rlz_cohort_sites", ctx.stream, 0.375 * (double)B * (double)N + 12.0 * (double)B);
+            rlz_cohort_site_flags(ctx, d_planes, (uint32_t)N, B, block, (uint32_t)min_present, with_reference != 0, d_n);
+            rlz_index_rep_total(ctx, d_n, B, d_total);
+            scan_exclusive_add_u32(d_n, d_off, B, nullptr, ctx.arena, ctx.stream);
+            download_bytes(ctx, &total, d_total, sizeof total);
+        }
+        total = total < B ? total : B;
+        if (total == 0) return;
+        recs = host_block<nolzss_rlz_cohort_site>((size_t)total);
+        const size_t chunk = total < chunk_max ? (size_t)total : chunk_max;
+        CohortSiteRec *d_stage = ctx.arena.alloc<CohortSiteRec>(chunk);
+        download_produced(ctx, "cohort_sites_d2h", recs.get(), d_stage, (size_t)total, sizeof(CohortSiteRec), chunk,
+                          [&](size_t c0, size_t cnt) {
+                              rlz_cohort_site_records(ctx, d_planes, (uint32_t)N, B, block, d_n, d_off, c0, (uint32_t)cnt, d_stage);
+                          });
+    });
+    out->num_sites = (size_t)total;  // (the result stays zeroed up to here: a throw above frees the block)
+    out->sites = recs.release();
 }
 
 void cohort_columns(nolzss_rlz_cohort *c, const uint64_t *positions, size_t S, char *out) {
@@ -250,7 +228,7 @@ void cohort_columns(nolzss_rlz_cohort *c, const uint64_t *positions, size_t S, c
         uint8_t *d_stage = ctx.arena.alloc<uint8_t>(chunk);
         upload_bytes(ctx, d_pos, pos.data(), sizeof(uint32_t) * S);
         download_produced(ctx, "cohort_columns_d2h", out, d_stage, total, 1, chunk, [&](size_t c0, size_t cnt) {
-            rlz_cohort_columns(ctx, c->d_planes, (uint32_t)N, c->B, d_pos, S, c0, (uint32_t)cnt, d_stage);
+            rlz_cohort_columns(ctx, c->planes.as<uint64_t>(), (uint32_t)N, c->B, d_pos, S, c0, (uint32_t)cnt, d_stage);
         });
     });
 }
@@ -271,7 +249,7 @@ void cohort_calls(nolzss_rlz_cohort *c, uint64_t sample, uint64_t start, uint64_
     with_index_session(c->device, "rlz_cohort_calls_call", [&](Context &ctx) {
         regrow_arena(ctx, chunk + (size_t(4) << 20));
         uint8_t *d_stage = ctx.arena.alloc<uint8_t>(chunk);
-        const uint64_t *d_sample = c->d_planes + 3 * c->W * (size_t)sample;
+        const uint64_t *d_sample = c->planes.as<uint64_t>() + 3 * c->W * (size_t)sample;
         download_produced(ctx, "cohort_calls_d2h", out, d_stage, count, 1, chunk, [&](size_t c0, size_t cnt) {
             rlz_cohort_calls(ctx, d_sample, c->B, (uint32_t)(start + c0), (uint32_t)cnt, d_stage);
         });
@@ -303,7 +281,7 @@ int nolzss_rlz_cohort_info(nolzss_rlz_cohort *c, nolzss_rlz_cohort_summary *info
         info->samples = c->samples.size();
         info->capacity = c->capacity;
         info->block_length = c->B;
-        info->device_bytes = sample_bytes(*c) * c->capacity;
+        info->device_bytes = c->planes.bytes();
         info->device = c->device;
     });
 }

@@ -13,10 +13,6 @@ constexpr uint64_t kMaxPattern = 4096;
 
 size_t padded(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
-ArchiveView view_of(const nolzss_rlz_archive &a) {
-    return ArchiveView{a.d_block, a.d_recs, a.d_sample, (uint32_t)a.z, (uint32_t)archive_samples((size_t)a.decoded)};
-}
-
 // arrays copied one behind the other into one allocation, each 256-byte aligned and padded
 struct Layout {
     char *base;
@@ -73,7 +69,7 @@ void finder_open(const nolzss_rlz_archive *ap, const nolzss_rlz_index *ip, uint6
     }
     const uint32_t z = (uint32_t)a.z, k = (uint32_t)a.lengths.size();
     std::vector<uint32_t> bases(a.bases.begin(), a.bases.end());  // (decoded <= kMaxText)
-    const ArchiveView av = view_of(a);
+    const ArchiveView av = a.view();
 
     DeviceRestore restore;
     Session ses(a.device, nullptr);
@@ -90,9 +86,9 @@ void finder_open(const nolzss_rlz_archive *ap, const nolzss_rlz_index *ip, uint6
         const uint32_t nI = find_intervals(ctx, av, d_bases, k, (uint32_t)W, d_kstart, d_dstart, &K_len);
         if (K_len == 0 || K_len > bound) throw HipError("rlz finder: the kernel text is laid out wrongly");
         const size_t table_bytes = 2 * padded(sizeof(uint32_t) * ((size_t)nI + 1)) + padded(sizeof(uint32_t) * ((size_t)k + 1));
-        h->d_tables = device_alloc(ctx, table_bytes);
-        HIP_CHECK(hipMemsetAsync(h->d_tables, 0, table_bytes, s));
-        Layout tables(ctx, h->d_tables);
+        h->tables.alloc(ctx, table_bytes);
+        HIP_CHECK(hipMemsetAsync(h->tables.get(), 0, table_bytes, s));
+        Layout tables(ctx, h->tables.get());
         FinderView &f = h->view;
         f.kstart = tables.put(d_kstart, (size_t)nI + 1);
         f.dstart = tables.put(d_dstart, (size_t)nI + 1);
@@ -112,9 +108,8 @@ void finder_open(const nolzss_rlz_archive *ap, const nolzss_rlz_index *ip, uint6
         uint8_t *d_X = ctx.arena.alloc<uint8_t>(nX);
         find_kernel_text(ctx, av, f.kstart, f.dstart, nI, K_len, with_rc, rc_sentinel(0), rc_sentinel(1), d_X);
         const RlzIndexView built = rlz_index_build(ctx, d_X, (uint32_t)nX, K_len, with_rc, P);
-        const size_t kindex_bytes = rlz_index_footprint(built);
-        h->d_kindex = device_alloc(ctx, kindex_bytes);
-        h->kview = rlz_index_copy_into(ctx, built, h->d_kindex);
+        h->kindex.alloc(ctx, rlz_index_footprint(built));
+        h->kview = rlz_index_copy_into(ctx, built, h->kindex.get());
         HIP_CHECK(hipStreamSynchronize(s));
         ctx.arena.rewind(0);
 
@@ -122,16 +117,15 @@ void finder_open(const nolzss_rlz_archive *ap, const nolzss_rlz_index *ip, uint6
         const SourceTable st = find_source_table(ctx, av, (uint32_t)a.block_len);
         size_t source_bytes = 3 * padded(sizeof(uint32_t) * (size_t)z);
         for (int l = 1; l < st.Phi.nlev; ++l) source_bytes += padded(sizeof(uint32_t) * (size_t)st.Phi.len[l]);
-        h->d_sources = device_alloc(ctx, source_bytes);
-        HIP_CHECK(hipMemsetAsync(h->d_sources, 0, source_bytes, s));  // (the padding is read, never used)
-        Layout sources(ctx, h->d_sources);
+        h->sources.alloc(ctx, source_bytes);
+        HIP_CHECK(hipMemsetAsync(h->sources.get(), 0, source_bytes, s));  // (the padding is read, never used)
+        Layout sources(ctx, h->sources.get());
         f.lo = sources.put(st.lo, z);
         f.hi = sources.put(st.hi, z);
         f.rec = sources.put(st.rec, z);
         f.Phi = st.Phi;
         f.Phi.lvl[0] = f.hi;
         for (int l = 1; l < st.Phi.nlev; ++l) f.Phi.lvl[l] = sources.put(st.Phi.lvl[l], st.Phi.len[l]);
-        h->device_bytes = table_bytes + kindex_bytes + source_bytes;
     } catch (...) {
         (void)hipStreamSynchronize(s);  // nothing still writes the handle's arrays when they go
         throw;
@@ -143,7 +137,7 @@ void finder_open(const nolzss_rlz_archive *ap, const nolzss_rlz_index *ip, uint6
     *out = h.release();
 }
 
-using TargetHitBlock = std::unique_ptr<nolzss_rlz_target_hit, FreeBlock>;
+using TargetHitBlock = HostBlock<nolzss_rlz_target_hit>;
 static_assert(sizeof(nolzss_rlz_target_hit) == sizeof(TargetHit) && sizeof(TargetHit) == 24,
               "the kernels write nolzss_rlz_target_hit");
 
@@ -158,7 +152,7 @@ void query_finder(Context &ctx, const nolzss_rlz_finder &h, const Batch &b, size
     const bool locate = hit_offsets != nullptr;
     const size_t chunk_max = chunk_knob("NOLZSS_RLZ_LOCATE_CHUNK");
     const FinderView &f = h.view;
-    const ArchiveView av = view_of(*h.archive);
+    const ArchiveView av = h.archive->view();
     const RlzIndexView *views[2] = {&h.index->view, &h.kview};
     const uint32_t records[2] = {(uint32_t)h.index->m, 1u};
     hipStream_t s = ctx.stream;
@@ -336,10 +330,8 @@ void finder_query(const nolzss_rlz_finder *h, const char *const *patterns, const
 void finder_kernel(const nolzss_rlz_finder &h, uint8_t **kernel, size_t *kernel_len, uint64_t **kstart, uint64_t **dstart,
                    size_t *intervals) {
     const size_t nI = (size_t)h.intervals, K = (size_t)h.K_len;
-    std::unique_ptr<uint8_t, FreeBlock> h_K(static_cast<uint8_t *>(std::malloc(K ? K : 1)));
-    std::unique_ptr<uint64_t, FreeBlock> h_ks(static_cast<uint64_t *>(std::malloc(sizeof(uint64_t) * (nI + 1))));
-    std::unique_ptr<uint64_t, FreeBlock> h_ds(static_cast<uint64_t *>(std::malloc(sizeof(uint64_t) * (nI + 1))));
-    if (!h_K || !h_ks || !h_ds) throw std::bad_alloc();
+    HostBlock<uint8_t> h_K = host_block<uint8_t>(K);
+    HostBlock<uint64_t> h_ks = host_block<uint64_t>(nI + 1), h_ds = host_block<uint64_t>(nI + 1);
     h_ks.get()[0] = 0;
     h_ds.get()[0] = h.decoded;
     if (h.z) {
@@ -352,7 +344,7 @@ void finder_kernel(const nolzss_rlz_finder &h, uint8_t **kernel, size_t *kernel_
         reserve_arena_for(ctx, 0, K + (size_t(4) << 20));
         uint8_t *d_X = ctx.arena.alloc<uint8_t>(K + 1);
         // (the bytes come from the archive again, as at the open: the finder keeps K packed)
-        find_kernel_text(ctx, view_of(*h.archive), h.view.kstart, h.view.dstart, (uint32_t)nI, (uint32_t)K, false, kSeparator,
+        find_kernel_text(ctx, h.archive->view(), h.view.kstart, h.view.dstart, (uint32_t)nI, (uint32_t)K, false, kSeparator,
                          kSeparator, d_X);
         download_bytes(ctx, h_K.get(), d_X, K);
         download_bytes(ctx, ks.data(), h.view.kstart, sizeof(uint32_t) * (nI + 1));
@@ -391,7 +383,7 @@ int nolzss_rlz_finder_info(const nolzss_rlz_finder *h, nolzss_rlz_finder_summary
         info->intervals = h->intervals;
         info->with_rc = h->with_rc ? 1 : 0;
         info->device = h->device;
-        info->device_bytes = h->device_bytes;
+        info->device_bytes = h->tables.bytes() + h->kindex.bytes() + h->sources.bytes();
     });
 }
 

@@ -12,57 +12,44 @@
 #include "rlz_find.hpp"
 #include "rlz_index.hpp"
 
-// The index handle: everything a match reads, in ONE device allocation (not arena memory, which the next call on the
-// device recycles); the view's pointers lead into it.  A match changes nothing here.
+// Every handle keeps its device memory in DeviceBufs (device_buf.hpp; DESIGN.md 5, "Relative-LZ handles: who owns device
+// memory"), so none has a destructor of its own, and zero bytes read as an empty handle.
+
+// The index handle: everything a match reads, in one allocation; the view's pointers lead into it.  A match changes
+// nothing here.
 struct nolzss_rlz_index {
     int device = 0;
     uint64_t m = 0;
     uint64_t serial = 0;  // process-wide, given at open: an archive opened over this index remembers it
-    void *d_base = nullptr;
-    size_t device_bytes = 0;
+    nolzss::api::DeviceBuf base;
     nolzss::RlzIndexView view;
-    ~nolzss_rlz_index() {  // (the calling thread's current device stays what it was)
-        if (!d_base) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        (void)hipFree(d_base);
-        if (known && current != device) (void)hipSetDevice(current);
-    }
 };
 
-// The archive handle: the block, the packed records and the position sample in device allocations of its own (not arena
-// memory, which the next call on the device recycles).  The per-target table stays on the host: it is read when the
-// ranges of a call are turned into decoded positions and prefix sums, which is all the kernel sees of the targets.
+// The archive handle: the block, the packed records and the position sample.  The per-target table stays on the host:
+// it is read when the ranges of a call are turned into decoded positions and prefix sums, which is all the kernel sees
+// of the targets.
 struct nolzss_rlz_archive {
     int device = 0;
     uint64_t z = 0, block_len = 0, n_literals = 0, decoded = 0;
     std::vector<uint64_t> lengths;  // k
     std::vector<uint64_t> bases;    // k + 1: decoded position of each target, then the decoded length
-    uint8_t *d_block = nullptr;
-    nolzss::ArchiveRec *d_recs = nullptr;
-    uint32_t *d_sample = nullptr;
-    size_t device_bytes = 0;
+    nolzss::api::DeviceBuf block, recs, sample;
     std::vector<uint8_t> h_block;   // an archive without records holds no device memory: its block, for export
-    // an archive opened over an index (index_serial != 0) grows by appends: what its two arrays can hold
+    // an archive opened over an index (index_serial != 0) grows by appends
     uint64_t index_serial = 0;
-    size_t cap_recs = 0, cap_samples = 0;
-    ~nolzss_rlz_archive() {  // (the calling thread's current device stays what it was)
-        if (!d_block && !d_recs && !d_sample) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        if (d_block) (void)hipFree(d_block);
-        if (d_recs) (void)hipFree(d_recs);
-        if (d_sample) (void)hipFree(d_sample);
-        if (known && current != device) (void)hipSetDevice(current);
+    size_t cap_samples = 0;  // words of the sample as reported: an open may allocate one word where it counts none
+    size_t cap_recs() const { return recs.bytes() / sizeof(nolzss::ArchiveRec); }
+    size_t device_bytes() const { return block.bytes() + recs.bytes() + sizeof(uint32_t) * cap_samples; }
+    nolzss::ArchiveView view() const {
+        return nolzss::ArchiveView{block.as<uint8_t>(), recs.as<nolzss::ArchiveRec>(), sample.as<uint32_t>(), (uint32_t)z,
+                                   (uint32_t)nolzss::archive_samples((size_t)decoded)};
     }
 };
 
 // The finder handle: a snapshot of an archive opened over an index, for pattern queries in the targets (rlz_find_api.hip;
 // DESIGN.md 5, "Relative-LZ archive: locate through the parse").  It points to the archive and the index it was opened
-// over -- both must outlive it -- and holds in device allocations of its own (not arena memory) the source table, the
-// interval tables with the targets' decoded positions, and the index over the kernel text K.
+// over -- both must outlive it -- and holds the source table, the interval tables with the targets' decoded positions,
+// and the index over the kernel text K.
 struct nolzss_rlz_finder {
     int device = 0;
     const nolzss_rlz_archive *archive = nullptr;
@@ -70,63 +57,38 @@ struct nolzss_rlz_finder {
     uint64_t z = 0, targets = 0, decoded = 0;  // of the archive at the open: a query refuses an archive that has grown
     uint64_t M = 0, K_len = 0, intervals = 0;
     bool with_rc = false;
-    void *d_tables = nullptr;  // kstart, dstart, bases
-    void *d_sources = nullptr; // lo, hi, rec and the upper levels of the max pyramid over hi
-    void *d_kindex = nullptr;  // everything kview points to
-    size_t device_bytes = 0;
+    nolzss::api::DeviceBuf tables;   // kstart, dstart, bases
+    nolzss::api::DeviceBuf sources;  // lo, hi, rec and the upper levels of the max pyramid over hi
+    nolzss::api::DeviceBuf kindex;   // everything kview points to
     nolzss::FinderView view;
     nolzss::RlzIndexView kview;
-    ~nolzss_rlz_finder() {  // (the calling thread's current device stays what it was)
-        if (!d_tables && !d_sources && !d_kindex) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_sources) (void)hipFree(d_sources);
-        if (d_kindex) (void)hipFree(d_kindex);
-        if (known && current != device) (void)hipSetDevice(current);
-    }
 };
 
 // The pileup handle: the counters of every position of the block of one index under one set of align parameters
 // (rlz_pileup_api.hip; DESIGN.md 5, "Relative-LZ index: pileup").  It points to the index it was opened over, which must
-// outlive it, and holds its counters in ONE device allocation of its own (not arena memory), zeroed at open.  `mu`
-// serialises the calls on one pileup: several threads may add to it and read it, one at a time.
+// outlive it, and holds its counters in one allocation, zeroed at open.  `mu` serialises the calls on one pileup:
+// several threads may add to it and read it, one at a time.
 struct nolzss_rlz_pileup {
     int device = 0;
     const nolzss_rlz_index *index = nullptr;
     nolzss_rlz_align_params params{};
-    void *d_base = nullptr;
-    size_t device_bytes = 0;
+    nolzss::api::DeviceBuf base;
     nolzss::PileupView view;
     std::mutex mu;
     bool dirty = false;  // difference entries were added since the last resolve
     uint64_t targets = 0, alignments = 0, ops = 0, columns = 0, adds = 0;  // running totals
-    // The insertion log: one event per I op of a kept alignment, in a device allocation of its own that grows
-    // geometrically (none until the first event).  The allele table is built from it on the first read after an add and
-    // kept, in another allocation, until the next add.
+    // The insertion log: one event per I op of a kept alignment (none until the first event).  The allele table is built
+    // from it on the first read after an add and kept until the next add.
     uint32_t flags = 0;  // NOLZSS_RLZ_PILEUP_*
-    nolzss::PileupEvent *d_log = nullptr;
-    uint64_t events = 0, log_capacity = 0;
-    nolzss::PileupAllele *d_alleles = nullptr;
-    uint64_t alleles = 0, alleles_capacity = 0;
+    nolzss::api::DeviceBuf log, allele_table;
+    uint64_t events = 0, alleles = 0;
     bool alleles_valid = false;
-    ~nolzss_rlz_pileup() {  // (the calling thread's current device stays what it was)
-        if (!d_base && !d_log && !d_alleles) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        if (d_base) (void)hipFree(d_base);
-        if (d_log) (void)hipFree(d_log);
-        if (d_alleles) (void)hipFree(d_alleles);
-        if (known && current != device) (void)hipSetDevice(current);
-    }
+    uint64_t log_capacity() const { return log.bytes() / sizeof(nolzss::PileupEvent); }
 };
 
 // The cohort handle: the bit planes of the samples added so far over the block of one index (rlz_cohort_api.hip; DESIGN.md
 // 5, "Relative-LZ index: cohort").  It points to the index it was opened over, which must outlive it, and remembers its
-// serial; the planes lie sample-major in ONE device allocation of its own (not arena memory) that grows geometrically
-// in samples -- a new allocation, a device copy, a free --, none until the first add.  `mu` serialises the calls on one
+// serial; the planes lie sample-major in one allocation, none until the first add.  `mu` serialises the calls on one
 // cohort.  Lock order: add_pileup takes the cohort's mutex first, then the pileup's, then the device's session; no call
 // takes them the other way round.
 struct nolzss_rlz_cohort {
@@ -135,19 +97,16 @@ struct nolzss_rlz_cohort {
     uint64_t index_serial = 0;
     uint32_t B = 0;
     size_t W = 0;  // words of a plane: a sample keeps 3 W of them
-    uint64_t *d_planes = nullptr;
+    nolzss::api::DeviceBuf planes;
     uint64_t capacity = 0, first_capacity = 1;  // in samples; first_capacity: NOLZSS_RLZ_COHORT_SAMPLES or the default, read at open
     std::vector<nolzss_rlz_cohort_sample_info> samples;
     std::mutex mu;
-    ~nolzss_rlz_cohort() {  // (the calling thread's current device stays what it was)
-        if (!d_planes) return;
-        int current = -1;
-        const bool known = hipGetDevice(&current) == hipSuccess;
-        (void)hipSetDevice(device);
-        (void)hipFree(d_planes);
-        if (known && current != device) (void)hipSetDevice(current);
-    }
 };
+
+// (the host tests pass 4096 zero bytes where a call hardly reads its handle)
+static_assert(sizeof(nolzss_rlz_index) <= 4096 && sizeof(nolzss_rlz_archive) <= 4096 && sizeof(nolzss_rlz_finder) <= 4096 &&
+                  sizeof(nolzss_rlz_pileup) <= 4096 && sizeof(nolzss_rlz_cohort) <= 4096,
+              "a handle stays within the stand-in buffers of the host tests");
 
 namespace nolzss {
 namespace api {

@@ -143,9 +143,8 @@ void open_index(const char *const *refs, const size_t *ref_lens, size_t m, bool 
             upload_bytes(ctx, d_X, p.S.data(), total);
         }
         const RlzIndexView built = rlz_index_build(ctx, d_X, (uint32_t)total, p.lay.block_length, with_rc, P);
-        h->device_bytes = rlz_index_footprint(built);
-        h->d_base = device_alloc(ctx, h->device_bytes);
-        h->view = rlz_index_copy_into(ctx, built, h->d_base);
+        h->base.alloc(ctx, rlz_index_footprint(built));
+        h->view = rlz_index_copy_into(ctx, built, h->base.get());
     }
     HIP_CHECK(hipStreamSynchronize(ctx.stream));
     ctx.prof.collect();
@@ -284,7 +283,7 @@ int nolzss_rlz_index_info(const nolzss_rlz_index *h, nolzss_rlz_index_summary *i
         info->with_rc = h->view.with_rc ? 1 : 0;
         info->device = h->device;
         info->prefix_syms = h->view.P;
-        info->device_bytes = h->device_bytes;
+        info->device_bytes = h->base.bytes();
     });
 }
 

@@ -80,7 +80,7 @@ size_t nolzss::api::pattern_batch_bytes(size_t n, size_t q) { return 2 * n + 24 
 
 namespace {
 
-using HitBlock = std::unique_ptr<nolzss_rlz_hit, FreeBlock>;
+using HitBlock = HostBlock<nolzss_rlz_hit>;
 static_assert(sizeof(nolzss_rlz_hit) == sizeof(LocateHit) && sizeof(LocateHit) == 16, "the kernels write nolzss_rlz_hit");
 
 // One batch of q >= 1 patterns against the handle, inside a session.  counts: q entries.  With hit_offsets (q + 1

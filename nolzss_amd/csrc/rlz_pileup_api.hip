@@ -41,28 +41,20 @@ void pileup_open(const nolzss_rlz_index *ix, const nolzss_rlz_align_params *para
     p->params = *params;
     p->flags = flags;
     const uint32_t B = ix->view.B;
-    DeviceRestore restore;
-    Session ses(ix->device, nullptr);
-    Context &ctx = ses.ctx();
-    {
-        ProfScope whole(ctx.profiler(), "rlz_pileup_open", ctx.stream);
-        p->device_bytes = rlz_pileup_footprint(B);
-        p->d_base = device_alloc(ctx, p->device_bytes);  // (a throw frees the handle: the index is untouched)
-        p->view = rlz_pileup_view(p->d_base, B);
-        HIP_CHECK(hipMemsetAsync(p->d_base, 0, p->device_bytes, ctx.stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx.stream));
-    ctx.prof.collect();
+    with_index_session(ix->device, "rlz_pileup_open", [&](Context &ctx) {
+        p->base.alloc(ctx, rlz_pileup_footprint(B));  // (a throw frees the handle: the index is untouched)
+        p->view = rlz_pileup_view(p->base.get(), B);
+        HIP_CHECK(hipMemsetAsync(p->base.get(), 0, p->base.bytes(), ctx.stream));
+    });
     *out = p.release();
 }
 
-// Room for `more` events behind those logged: a larger allocation, the events copied over, the old one freed.  Nothing
-// of the handle changes before the copy has arrived.
+// Room for `more` events behind those logged (DeviceBuf::grow_keeping).
 void grow_log(Context &ctx, nolzss_rlz_pileup &p, uint64_t more) {
-    const uint64_t need = p.events + more;
-    if (need <= p.log_capacity) return;
-    uint64_t cap = p.log_capacity ? 2 * p.log_capacity : kPileupFirstLogEvents;
-    if (!p.log_capacity)
+    const uint64_t need = p.events + more, held = p.log_capacity();
+    if (need <= held) return;
+    uint64_t cap = held ? 2 * held : kPileupFirstLogEvents;
+    if (!held)
         if (const char *e = getenv("NOLZSS_RLZ_PILEUP_LOG_EVENTS")) {
             const unsigned long long v = strtoull(e, nullptr, 10);
             if (v >= 1 && v <= kPileupMaxEvents) cap = v;
@@ -70,18 +62,7 @@ void grow_log(Context &ctx, nolzss_rlz_pileup &p, uint64_t more) {
     cap = cap < need ? need : cap;
     cap = cap < kPileupMaxEvents ? cap : kPileupMaxEvents;
     ProfScope ps(ctx.profiler(), "rlz_pileup_log_grow", ctx.stream, 2.0 * sizeof(PileupEvent) * (double)p.events);
-    PileupEvent *d_new = static_cast<PileupEvent *>(device_alloc(ctx, sizeof(PileupEvent) * (size_t)cap));
-    if (p.events) {
-        const hipError_t e = hipMemcpyAsync(d_new, p.d_log, sizeof(PileupEvent) * (size_t)p.events, hipMemcpyDeviceToDevice, ctx.stream);
-        const hipError_t w = e == hipSuccess ? hipStreamSynchronize(ctx.stream) : e;
-        if (w != hipSuccess) {
-            (void)hipFree(d_new);
-            HIP_CHECK(w);
-        }
-    }
-    if (p.d_log) (void)hipFree(p.d_log);
-    p.d_log = d_new;
-    p.log_capacity = cap;
+    p.log.grow_keeping(ctx, sizeof(PileupEvent) * (size_t)cap, sizeof(PileupEvent) * (size_t)p.events);
 }
 
 void pileup_add(nolzss_rlz_pileup *p, const char *const *targets, const size_t *target_lens, size_t k, int primary_only,
@@ -121,9 +102,9 @@ void pileup_add(nolzss_rlz_pileup *p, const char *const *targets, const size_t *
         }
         grow_log(ctx, *p, more);
         PileupLog log;
-        log.events = p->d_log;
+        log.events = p->log.as<PileupEvent>();
         log.base = p->events;
-        log.capacity = p->log_capacity;
+        log.capacity = p->log_capacity();
         log.flags = p->flags;
         // from here on the counters change: nothing below refuses, and every arena array is taken before the first write
         rlz_pileup_accumulate(ctx, p->view, run.out, run.batch, h.view.text, primary_only != 0, log, d_stats);
@@ -181,43 +162,36 @@ void pileup_variants(nolzss_rlz_pileup *p, uint32_t min_count, uint64_t num, uin
     if (B == 0) return;
     std::lock_guard<std::mutex> lock(p->mu);
     const size_t chunk_max = chunk_knob("NOLZSS_RLZ_LOCATE_CHUNK");
-    nolzss_rlz_variant *recs = nullptr;
-    try {
-        with_index_session(p->device, "rlz_pileup_variants_call", [&](Context &ctx) {
-            const size_t most = 5 * (size_t)B < chunk_max ? 5 * (size_t)B : chunk_max;
-            reserve_arena_for(ctx, 0, 9 * (size_t)B + sizeof(PileupVariantRec) * most + (size_t(4) << 20));
-            resolve(ctx, *p);
-            const PackedText &block = p->index->view.text;
-            uint32_t *d_n = ctx.arena.alloc<uint32_t>(B), *d_off = ctx.arena.alloc<uint32_t>(B);
-            uint64_t *d_total = ctx.arena.alloc<uint64_t>(1);
-            uint64_t total = 0;  // up to five records per position: summed in 64 bits, one word comes down
-            {
-                ProfScope ps(ctx.profiler(), "rlz_pileup_variants", ctx.stream, 48.0 * (double)B);
-                rlz_pileup_variant_flags(ctx, p->view, block, rule, d_n);
-                rlz_index_rep_total(ctx, d_n, B, d_total);
-                scan_exclusive_add_u32(d_n, d_off, B, nullptr, ctx.arena, ctx.stream);
-                download_bytes(ctx, &total, d_total, sizeof total);
-            }
-            if (total > 0xffffffffull)
-                throw std::invalid_argument("rlz pileup: variants would report " + std::to_string(total) +
-                                            " records, and they are counted in 32 bits: raise min_count or the fraction");
-            if (total == 0) return;
-            recs = static_cast<nolzss_rlz_variant *>(alloc_factor_block(sizeof(nolzss_rlz_variant) * (size_t)total));
-            if (!recs) throw std::bad_alloc();
-            const size_t chunk = total < chunk_max ? total : chunk_max;
-            PileupVariantRec *d_stage = ctx.arena.alloc<PileupVariantRec>(chunk);
-            download_produced(ctx, "pileup_variants_d2h", recs, d_stage, total, sizeof(PileupVariantRec), chunk,
-                              [&](size_t c0, size_t c) {
-                                  rlz_pileup_variant_records(ctx, p->view, block, rule, d_off, c0, (uint32_t)c, d_stage);
-                              });
-            out->num_variants = total;
-        });
-    } catch (...) {
-        free_block(recs);
-        std::memset(out, 0, sizeof *out);
-        throw;
-    }
-    out->variants = recs;
+    HostBlock<nolzss_rlz_variant> recs;
+    uint64_t total = 0;  // up to five records per position: summed in 64 bits, one word comes down
+    with_index_session(p->device, "rlz_pileup_variants_call", [&](Context &ctx) {
+        const size_t most = 5 * (size_t)B < chunk_max ? 5 * (size_t)B : chunk_max;
+        reserve_arena_for(ctx, 0, 9 * (size_t)B + sizeof(PileupVariantRec) * most + (size_t(4) << 20));
+        resolve(ctx, *p);
+        const PackedText &block = p->index->view.text;
+        uint32_t *d_n = ctx.arena.alloc<uint32_t>(B), *d_off = ctx.arena.alloc<uint32_t>(B);
+        uint64_t *d_total = ctx.arena.alloc<uint64_t>(1);
+        {
+            ProfScope ps(ctx.profiler(), "rlz_pileup_variants", ctx.stream, 48.0 * (double)B);
+            rlz_pileup_variant_flags(ctx, p->view, block, rule, d_n);
+            rlz_index_rep_total(ctx, d_n, B, d_total);
+            scan_exclusive_add_u32(d_n, d_off, B, nullptr, ctx.arena, ctx.stream);
+            download_bytes(ctx, &total, d_total, sizeof total);
+        }
+        if (total > 0xffffffffull)
+            throw std::invalid_argument("rlz pileup: variants would report " + std::to_string(total) +
+                                        " records, and they are counted in 32 bits: raise min_count or the fraction");
+        if (total == 0) return;
+        recs = host_block<nolzss_rlz_variant>((size_t)total);
+        const size_t chunk = total < chunk_max ? total : chunk_max;
+        PileupVariantRec *d_stage = ctx.arena.alloc<PileupVariantRec>(chunk);
+        download_produced(ctx, "pileup_variants_d2h", recs.get(), d_stage, total, sizeof(PileupVariantRec), chunk,
+                          [&](size_t c0, size_t c) {
+                              rlz_pileup_variant_records(ctx, p->view, block, rule, d_off, c0, (uint32_t)c, d_stage);
+                          });
+    });
+    out->num_variants = total;  // (the result stays zeroed up to here: a throw above frees the block)
+    out->variants = recs.release();
 }
 
 // The allele table of the log as it stands: built in the arena on the first read after an add, then kept in an
@@ -225,19 +199,15 @@ void pileup_variants(nolzss_rlz_pileup *p, uint32_t min_count, uint64_t num, uin
 const PileupAllele *cached_alleles(Context &ctx, nolzss_rlz_pileup &p, uint32_t &G) {
     if (!p.alleles_valid) {
         uint32_t count = 0;
-        const PileupAllele *d_built = rlz_pileup_alleles(ctx, p.d_log, (uint32_t)p.events, &count);
-        if (count > p.alleles_capacity) {
-            PileupAllele *d_new = static_cast<PileupAllele *>(device_alloc(ctx, sizeof(PileupAllele) * (size_t)count));
-            if (p.d_alleles) (void)hipFree(p.d_alleles);
-            p.d_alleles = d_new;
-            p.alleles_capacity = count;
-        }
-        if (count) HIP_CHECK(hipMemcpyAsync(p.d_alleles, d_built, sizeof(PileupAllele) * (size_t)count, hipMemcpyDeviceToDevice, ctx.stream));
+        const PileupAllele *d_built = rlz_pileup_alleles(ctx, p.log.as<PileupEvent>(), (uint32_t)p.events, &count);
+        const size_t bytes = sizeof(PileupAllele) * (size_t)count;
+        if (bytes > p.allele_table.bytes()) p.allele_table.grow_keeping(ctx, bytes, 0);
+        if (count) HIP_CHECK(hipMemcpyAsync(p.allele_table.get(), d_built, bytes, hipMemcpyDeviceToDevice, ctx.stream));
         p.alleles = count;
         p.alleles_valid = true;
     }
     G = (uint32_t)p.alleles;
-    return p.d_alleles;
+    return p.allele_table.as<PileupAllele>();
 }
 
 void pileup_insertions(nolzss_rlz_pileup *p, uint32_t min_count, uint64_t num, uint64_t den, nolzss_rlz_insertions_result *out) {
@@ -413,7 +383,7 @@ int nolzss_rlz_pileup_log_info(nolzss_rlz_pileup *p, uint32_t *flags, uint64_t *
         std::lock_guard<std::mutex> lock(p->mu);
         *flags = p->flags;
         *events = p->events;
-        *log_bytes = sizeof(PileupEvent) * p->log_capacity;
+        *log_bytes = p->log.bytes();
     });
 }
 
@@ -467,7 +437,7 @@ int nolzss_rlz_pileup_info(nolzss_rlz_pileup *p, nolzss_rlz_pileup_summary *info
         std::memset(info, 0, sizeof *info);
         std::lock_guard<std::mutex> lock(p->mu);
         info->block_length = p->view.B;
-        info->device_bytes = p->device_bytes;
+        info->device_bytes = p->base.bytes();
         info->targets = p->targets;
         info->alignments = p->alignments;
         info->ops = p->ops;

@@ -3,8 +3,11 @@ condition of the end-to-end test on the all-CPU path, and everything the new ent
 work.  No GPU."""
 import ctypes as C
 import functools
+import os
 import random
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -261,3 +264,18 @@ def test_refusals_before_any_device_work():
     lib.nolzss_free_rlz_cohort_distances_result(C.byref(dist))
     lib.nolzss_free_rlz_cohort_sites_result(C.byref(sites))
     assert lib.nolzss_rlz_cohort_close(None) == _lib.OK
+
+
+def test_the_device_buffer_counters_of_a_process_that_opened_nothing():
+    """nolzss_debug_device_buffers: (0, 0) in a fresh process -- this one may hold handles of other tests --, no device
+    touched, null pointers refused"""
+    lib, n = _lib.lib, C.c_size_t(7)
+    assert "nolzss_debug_device_buffers" in _lib.EXPORTED_SYMBOLS
+    assert lib.nolzss_debug_device_buffers(None, C.byref(n)) == _lib.ERR_INVALID_ARGUMENT and n.value == 7
+    assert b"output pointer is null" in lib.nolzss_last_error()
+    assert lib.nolzss_debug_device_buffers(C.byref(n), None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.nolzss_debug_device_buffers(C.byref(n), C.byref(C.c_size_t())) == _lib.OK
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    child = "from nolzss_amd import _noLZSS as native; print(native.debug_device_buffers())"
+    r = subprocess.run([sys.executable, "-c", child], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip() == "(0, 0)", r.stdout[-2000:] + r.stderr[-4000:]
