@@ -1465,6 +1465,39 @@ int nolzss_debug_text_order(const uint32_t *idx, const uint32_t *val, const uint
 int nolzss_debug_group_sort(const uint8_t *text, size_t n, uint32_t *sa, const uint32_t *slot, const uint32_t *grp, size_t m,
                             uint32_t h0, int pivot, uint32_t max_rounds, uint32_t depth_cap, const uint32_t *lcp_mark,
                             int device, uint32_t *out_lo, uint32_t *lcp_list, uint32_t *min_depth, uint32_t *info);
+/* The first direct round of the suffix-array construction (sa_direct.hip: group_refine_kernel and the compaction of what it
+ * leaves tied) on the caller's groups -- the launch function of the construction itself (direct_round_launch), which holds
+ * the only launch site of the kernel.
+ * text[n], sa[n], slot[m] / grp[m]: as for nolzss_debug_group_sort, but a group may have ANY number of members >= 2 (more
+ * than 64: the round leaves it as it is).  h0: the symbols the members of every group agree on, in front of their
+ * terminators; cap: the depth at which the round gives up (the construction: h0 + NOLZSS_REFINE_WORDS words, 4 by default).
+ * Checked of h0: every listed suffix has h0 symbols in the text (sa[slot] + h0 <= n).  NOT CHECKED, the caller's business:
+ * that the members agree on them and that no terminator lies among them.  If that does not hold the results mean nothing
+ * (the distance to the terminator minus the depth wraps around), but nothing is written outside the slots of the listed
+ * groups and the outputs, and nothing is read out of bounds: a member then fetches windows that start up to cap - h0
+ * symbols behind the end of the text, and the hook keeps 32 + 5 words of its own behind the packed text for them (the
+ * straggler rounds do not fetch behind the end at all).
+ * flags: NO_STRAGGLERS (the A/B switch NOLZSS_NO_STRAGGLERS), TIMED (the instantiation with the phase clocks, as under
+ * NOLZSS_REFINE_PHASES: one line on stderr, the same results), WITH_RANKS (rank_by_slot is handed to the kernel; else it
+ * gets none, as when the construction defers the ranks).  lcp_in[n]: what lcp holds before the call; fill: what
+ * rank_by_slot holds before the call -- so every entry the round must not touch is known afterwards.
+ * Out: sa[n]; lcp[n] (the LCP of every boundary that appeared, 0xfffffffe at a boundary inside a compared class that stays
+ * tied, the head entry of every group as it was); rank_by_slot[n] (head slot of the member's class + 1 for every listed
+ * member); new_slot / new_grp (room for m) and *new_m: the members still tied, in slot order, with the head slot of their
+ * class; min_depth[3]: [0] the least depth of the compared classes left tied, [1] h0 if a group was not touched (both
+ * 0xffffffff: none), [2] the members of untouched groups as every 64th workgroup counted them -- the raw counter, not
+ * multiplied by 64; info (optional, 3 words): bits per symbol, entries of the terminator table, segmented.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, n == 0, m > n, an unknown flag, cap <= h0,
+ * cap - h0 > 1024, a list entry with grp > slot or slot >= n, a listed slot whose sa entry + h0 is > n, slots that do not
+ * ascend, a group that does not hold consecutive list positions and the slots from its head slot on, a listed group of
+ * one member; behind the packing and in front of the round for cap - h0 beyond 32 words of the width the text has (512
+ * symbols at 4 bits, 256 at 8).  (The hook also repeats the guard of suffix_array.hip against more than 65536
+ * terminators; pack_text makes at most 251 table entries of a text handed in this way, so no call can meet it.) */
+enum { NOLZSS_DIRECT_ROUND_NO_STRAGGLERS = 1, NOLZSS_DIRECT_ROUND_TIMED = 2, NOLZSS_DIRECT_ROUND_WITH_RANKS = 4 };
+int nolzss_debug_direct_round(const uint8_t *text, size_t n, uint32_t *sa, const uint32_t *slot, const uint32_t *grp, size_t m,
+                              uint32_t h0, uint32_t cap, uint32_t flags, const uint32_t *lcp_in, uint32_t fill, int device,
+                              uint32_t *lcp, uint32_t *rank_by_slot, uint32_t *new_slot, uint32_t *new_grp, uint32_t *new_m,
+                              uint32_t *min_depth, uint32_t *info);
 /* The greedy cursor (chain.hip: mark_chain, chain_starts, chain_lengths) and the widening of 16-bit codes (lpnf.hip:
  * widened_lstar) on the caller's codes -- the production functions, which read the codes and nothing else.  codes[n]: one
  * u32 per position, length in bits 0..30 (0 = literal), bit 31 the strand.  The cursor runs p -> p + max(1, length) from

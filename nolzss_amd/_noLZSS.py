@@ -2434,6 +2434,42 @@ def debug_group_sort(text, sa, slot, grp, h0: int, pivot: bool = False, max_roun
             "terms": int(info[1]), "segmented": bool(info[2])}
 
 
+DIRECT_ROUND_NO_STRAGGLERS, DIRECT_ROUND_TIMED, DIRECT_ROUND_WITH_RANKS = 1, 2, 4
+
+
+def debug_direct_round(text, sa, slot, grp, h0: int, cap: int, flags: int = DIRECT_ROUND_WITH_RANKS, lcp_in=None,
+                       fill: int = 0):
+    """The first direct round of the suffix-array construction on the device over caller groups
+    (nolzss_debug_direct_round, test hook): group_refine_kernel and the compaction of what it leaves tied.  `text`, `sa`,
+    `slot` / `grp` as for debug_group_sort, with groups of any size >= 2; `cap`: the depth at which the round gives up;
+    `lcp_in` (n entries, default all 0xffffffff) and `fill`: what lcp and rank_by_slot hold before the call.
+    PRECONDITION, not checked: the members of every group agree on their first h0 symbols and none of them ends in front
+    of h0.  Returns {"sa", "lcp", "rank_by_slot", "new_slot", "new_grp", "new_m", "min_depth" (3 values), "bits",
+    "terms", "segmented"}."""
+    text = np.frombuffer(bytes(text), dtype=np.uint8)
+    sa = np.array(sa, dtype=np.uint32)  # (a copy: the call writes it)
+    slot = np.ascontiguousarray(slot, dtype=np.uint32)
+    grp = np.ascontiguousarray(grp, dtype=np.uint32)
+    if sa.size != text.size or slot.size != grp.size:
+        raise ValueError("sa holds one entry per symbol, slot and grp one per list entry")
+    lcp_in = np.full(text.size, 0xffffffff, dtype=np.uint32) if lcp_in is None else np.ascontiguousarray(lcp_in, dtype=np.uint32)
+    if lcp_in.size != text.size:
+        raise ValueError("lcp_in holds one entry per symbol")
+    if not (0 <= h0 < 1 << 32 and 0 <= cap < 1 << 32 and 0 <= fill < 1 << 32 and 0 <= flags < 1 << 32):
+        raise ValueError("h0, cap, flags and fill are 32-bit values")
+    n, m = text.size, slot.size
+    lcp, rank = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    new_slot, new_grp = np.zeros(max(m, 1), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+    new_m, depth, info = C.c_uint32(), np.zeros(3, dtype=np.uint32), np.zeros(3, dtype=np.uint32)
+    check(lib.nolzss_debug_direct_round(text.ctypes.data, n, sa.ctypes.data, slot.ctypes.data, grp.ctypes.data, m, h0, cap, flags,
+                                        lcp_in.ctypes.data, fill, _default_device, lcp.ctypes.data, rank.ctypes.data,
+                                        new_slot.ctypes.data, new_grp.ctypes.data, C.byref(new_m), depth.ctypes.data,
+                                        info.ctypes.data))
+    k = new_m.value
+    return {"sa": sa, "lcp": lcp[:n], "rank_by_slot": rank[:n], "new_slot": new_slot[:k], "new_grp": new_grp[:k], "new_m": k,
+            "min_depth": [int(x) for x in depth], "bits": int(info[0]), "terms": int(info[1]), "segmented": bool(info[2])}
+
+
 LDS_PLAIN, LDS_RC = 0, 1
 LDS_OVERFLOW = 0xffffffff
 

@@ -399,6 +399,86 @@ int nolzss_debug_group_sort(const uint8_t *text, size_t n, uint32_t *sa, const u
     });
 }
 
+int nolzss_debug_direct_round(const uint8_t *text, size_t n, uint32_t *sa, const uint32_t *slot, const uint32_t *grp, size_t m,
+                              uint32_t h0, uint32_t cap, uint32_t flags, const uint32_t *lcp_in, uint32_t fill, int device,
+                              uint32_t *lcp, uint32_t *rank_by_slot, uint32_t *new_slot, uint32_t *new_grp, uint32_t *new_m,
+                              uint32_t *min_depth, uint32_t *info) {
+    return guarded([&] {
+        if (!text || !sa || !lcp_in || !lcp || !rank_by_slot || !new_m || !min_depth || (m && (!slot || !grp || !new_slot || !new_grp)))
+            throw std::invalid_argument("null argument");
+        if (n == 0 || n > kMaxText) throw std::invalid_argument("1 .. 2^32 - 2^19 - 1 symbols");
+        if (m > n) throw std::invalid_argument("more list entries than suffixes");
+        if (flags & ~(uint32_t)(NOLZSS_DIRECT_ROUND_NO_STRAGGLERS | NOLZSS_DIRECT_ROUND_TIMED | NOLZSS_DIRECT_ROUND_WITH_RANKS))
+            throw std::invalid_argument("an unknown flag");
+        // (32 words of text, the deepest cap NOLZSS_REFINE_WORDS allows: 1024 symbols at 2 bits here, where the width is not
+        // known yet; once more behind the packing, for the width the text has)
+        if (cap <= h0 || cap - h0 > 32u * 32u) throw std::invalid_argument("h0 < cap <= h0 + 32 words of text");
+        // the list as the kernel relies on it: ascending slots, every group on consecutive list positions and on the slots
+        // from its head slot on, at least two members (any number of them), every suffix below n and h0 symbols long
+        for (size_t a = 0, first = 0; a < m; ++a) {
+            const uint32_t g = grp[a], s = slot[a];
+            if (g > s || s >= n) throw std::invalid_argument("a list entry with grp <= slot < n violated");
+            if (sa[s] >= n || (uint64_t)sa[s] + h0 > n) throw std::invalid_argument("a listed slot holds no suffix of h0 symbols");
+            const bool head = a == 0 || grp[a - 1] != g;
+            if (a > 0 && s <= slot[a - 1]) throw std::invalid_argument("the list is not in ascending slot order");
+            if (head) first = a;
+            if (s != g + (a - first)) throw std::invalid_argument("a group does not hold the slots from its head slot on");
+            if ((a + 1 == m || grp[a + 1] != g) && a == first) throw std::invalid_argument("a listed group of one member");
+        }
+        *new_m = 0;
+        min_depth[0] = min_depth[1] = 0xffffffffu;
+        min_depth[2] = 0;
+        Session ses(device, nullptr);
+        Context &ctx = ses.ctx();
+        hipStream_t s = ctx.stream;
+        // text and packed text, sa / lcp / ranks, the two lists, a region of kRefineThreads entries per tile (slot and head)
+        ctx.arena.reserve(n * 16 + m * 16 + 2 * 4 * (size_t)kRefineThreads * (m / kRefineTile + 1) + (size_t(64) << 20));
+        ArenaRewind rewind(ctx.arena);
+        uint8_t *d_text = ctx.arena.alloc<uint8_t>(n);
+        upload_bytes(ctx, d_text, text, n);
+        const PackedText packed = pack_text(ctx, d_text, n);
+        // (a caller whose groups do not agree on h0 symbols in front of their terminators can send a member up to cap - h0
+        // symbols past the end of the text, 32 words of it at the most, and a fetch takes kRefineWords + 1: they land here,
+        // not beyond the padding of the packed text, which is the arena's last allocation so far)
+        (void)ctx.arena.alloc<uint64_t>(32 + kRefineWords + 1);
+        if (info) {
+            info[0] = (uint32_t)packed.bits;
+            info[1] = packed.terms.count;
+            info[2] = packed.segmented;
+        }
+        // (what suffix_array.hip refuses in front of the direct rounds: the terminator index travels in 16 bits.  Only a
+        // mirror of that guard: pack_text makes at most 251 entries of a text that arrives as bytes.)
+        if (packed.terms.count > 0x10000u) throw std::invalid_argument("at most 65536 terminators");
+        if (cap - h0 > 32u * (64u / (uint32_t)packed.bits)) throw std::invalid_argument("h0 < cap <= h0 + 32 words of text");
+        uint32_t *d_sa = ctx.arena.alloc<uint32_t>(n), *d_lcp = ctx.arena.alloc<uint32_t>(n), *d_rank = ctx.arena.alloc<uint32_t>(n);
+        HIP_CHECK(hipMemcpyAsync(d_lcp, lcp_in, n * 4, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_rank), (int)fill, n, s));
+        if (m > 0) {
+            uint32_t *d_slot = ctx.arena.alloc<uint32_t>(m), *d_grp = ctx.arena.alloc<uint32_t>(m);
+            uint32_t *d_new_slot = ctx.arena.alloc<uint32_t>(m), *d_new_grp = ctx.arena.alloc<uint32_t>(m);
+            uint32_t *d_out = ctx.arena.alloc<uint32_t>(4);  // the new m, min_depth[3]
+            HIP_CHECK(hipMemcpyAsync(d_sa, sa, n * 4, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(d_slot, slot, m * 4, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(d_grp, grp, m * 4, hipMemcpyHostToDevice, s));
+            direct_round_launch(ctx, packed, d_slot, d_grp, (uint32_t)m, d_sa, d_lcp, (flags & NOLZSS_DIRECT_ROUND_WITH_RANKS) ? d_rank : nullptr,
+                                h0, cap, (flags & NOLZSS_DIRECT_ROUND_NO_STRAGGLERS) != 0, (flags & NOLZSS_DIRECT_ROUND_TIMED) != 0,
+                                d_new_slot, d_new_grp, d_out, d_out + 1);
+            uint32_t out4[4] = {0, 0, 0, 0};
+            ctx.read_back(d_out, out4, 4);
+            if (out4[0] > m) throw HipError("direct round: more survivors than list entries");
+            *new_m = out4[0];
+            for (int k = 0; k < 3; ++k) min_depth[k] = out4[k + 1];
+            HIP_CHECK(hipMemcpyAsync(sa, d_sa, n * 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(new_slot, d_new_slot, (size_t)out4[0] * 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(new_grp, d_new_grp, (size_t)out4[0] * 4, hipMemcpyDeviceToHost, s));
+        }
+        HIP_CHECK(hipMemcpyAsync(lcp, d_lcp, n * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(rank_by_slot, d_rank, n * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        ctx.prof.collect();
+    });
+}
+
 int nolzss_debug_chain(const uint32_t *codes, size_t n, size_t start_pos, int width, uint32_t poison, const uint64_t *list,
                        size_t list_len, size_t listed, uint32_t list_max, int with_strand, const uint32_t *bounds, size_t k,
                        int device, uint32_t *z, uint32_t *starts, uint32_t *lengths, uint32_t *hist, uint64_t *tail,

@@ -485,41 +485,33 @@ __global__ __launch_bounds__(kRefineThreads) __attribute__((amdgpu_waves_per_eu(
 
 }  // namespace
 
-// ---- direct round: small groups are finished by comparing packed suffixes ---------------
-// (groups larger than kSmallGroup stay as they are; rank[] is not needed before the doubling
-// rounds, so it is written once, after the direct rounds, instead of after each of them)
-void direct_round(SaBuild &b, int k_syms) {
-    const SaKnobs &knobs = sa_knobs();
-    const PackedText &text = b.text;
-    hipStream_t s = b.stream();
-    Arena &arena = b.arena();
-    const uint32_t m = b.m;
-    const size_t direct_mark = arena.mark();
+// ---- the launches of the first direct round (sa_internal.hpp): the only launch site of group_refine_kernel ----
+void direct_round_launch(Context &ctx, const PackedText &text, const uint32_t *slot, const uint32_t *grp, uint32_t m, uint32_t *sa,
+                         uint32_t *lcp, uint32_t *rank_by_slot, uint32_t h0, uint32_t cap, bool no_stragglers, bool timed,
+                         uint32_t *new_slot, uint32_t *new_grp, uint32_t *d_new_m, uint32_t *d_min_depth) {
+    hipStream_t s = ctx.stream;
+    Arena &arena = ctx.arena;
     // the members that stay tied come back in one region per workgroup (group_refine_kernel's epilogue)
     const unsigned g = (unsigned)div_up(m, kRefineTile);
     uint32_t *surv_slot = arena.alloc<uint32_t>((size_t)g * kRefineThreads);
     uint32_t *surv_head = arena.alloc<uint32_t>((size_t)g * kRefineThreads);
     uint32_t *surv_count = arena.alloc<uint32_t>(g);
     uint32_t *surv_off = arena.alloc<uint32_t>(g);
-    uint32_t *rbs = b.store_ranks ? b.rank_by_slot : nullptr;
-    const uint32_t cap = (uint32_t)k_syms + knobs.refine_words * (64u / (uint32_t)text.bits);
-    // [0] classes the round compared and left tied, [1] groups it did not touch, [2] members of such groups in every 64th workgroup
-    uint32_t *d_min_depth = arena.alloc<uint32_t>(3);
     HIP_CHECK(hipMemsetAsync(d_min_depth, 0xff, 2 * sizeof(uint32_t), s));
     HIP_CHECK(hipMemsetAsync(d_min_depth + 2, 0, sizeof(uint32_t), s));
     {
-        ProfScope ps(b.ctx.profiler(), "sa_direct_sort", s);
+        ProfScope ps(ctx.profiler(), "sa_direct_sort", s);
         unsigned long long *rphases = nullptr;
-        if (knobs.refine_phases) {
+        if (timed) {
             rphases = arena.alloc<unsigned long long>(8);
             HIP_CHECK(hipMemsetAsync(rphases, 0, 64, s));
         }
         dispatch_bits(text.bits, [&](auto B) {
             constexpr int kBits = decltype(B)::value;
-            auto launch = [&](auto timed) {
-                group_refine_kernel<kBits, decltype(timed)::value><<<g, kRefineThreads, 0, s>>>(
-                    b.slot(), b.grp(), b.sa, text.words, text.terms, m, (uint32_t)b.h, cap, b.lcp, rbs, surv_slot, surv_head,
-                    surv_count, d_min_depth, rphases, knobs.no_stragglers);
+            auto launch = [&](auto T) {
+                group_refine_kernel<kBits, decltype(T)::value><<<g, kRefineThreads, 0, s>>>(
+                    slot, grp, sa, text.words, text.terms, m, h0, cap, lcp, rank_by_slot, surv_slot, surv_head, surv_count,
+                    d_min_depth, rphases, no_stragglers);
             };
             if (rphases) launch(std::true_type{});
             else launch(std::false_type{});
@@ -534,7 +526,25 @@ void direct_round(SaBuild &b, int k_syms) {
                     hp[5], hp[0] / wn, hp[1] / wn, hp[2] / wn, hp[3] / wn, hp[6] / wn, hp[4] / wn);
         }
     }
-    compact_survivors(b, surv_slot, surv_head, surv_count, surv_off, g);
+    compact_survivors(ctx, surv_slot, surv_head, surv_count, surv_off, g, new_slot, new_grp, d_new_m);
+}
+
+// ---- direct round: small groups are finished by comparing packed suffixes ---------------
+// (groups larger than kSmallGroup stay as they are; rank[] is not needed before the doubling
+// rounds, so it is written once, after the direct rounds, instead of after each of them)
+void direct_round(SaBuild &b, int k_syms) {
+    const SaKnobs &knobs = sa_knobs();
+    const PackedText &text = b.text;
+    Arena &arena = b.arena();
+    const size_t direct_mark = arena.mark();
+    uint32_t *rbs = b.store_ranks ? b.rank_by_slot : nullptr;
+    const uint32_t cap = (uint32_t)k_syms + knobs.refine_words * (64u / (uint32_t)text.bits);
+    // [0] classes the round compared and left tied, [1] groups it did not touch, [2] members of such groups in every 64th workgroup
+    uint32_t *d_min_depth = arena.alloc<uint32_t>(3);
+    direct_round_launch(b.ctx, text, b.slot(), b.grp(), b.m, b.sa, b.lcp, rbs, (uint32_t)b.h, cap, knobs.no_stragglers,
+                        knobs.refine_phases, b.next_slot(), b.next_grp(), b.d_total, d_min_depth);
+    b.ctx.read_back(b.d_total, &b.m, 1);
+    b.a_cur ^= 1;
     // every group that is still tied agrees on at least min_depth symbols (K if a group was too large
     // for the round, more if the round left all its ties at the cap or at a bail-out depth): the
     // doubling rounds start there instead of repeating the steps K, 2K, 4K, ...

@@ -167,14 +167,26 @@ struct RegroupIn {
     bool by_slot = false;
 };
 template <bool kRound0> void regroup(SaBuild &b, const RegroupIn &in);
-// the survivors of the direct round (group_refine_kernel: one region per workgroup, g of them) become the next active list
-void compact_survivors(SaBuild &b, const uint32_t *surv_slot, const uint32_t *surv_head, uint32_t *surv_count,
-                       uint32_t *surv_off, unsigned g);
+// the survivors of the direct round (group_refine_kernel: one region per workgroup, g of them) become the next active
+// list new_slot / new_grp, *d_new_m (device) entries; surv_off[g] is work space, the scan's temporaries come from ctx.arena
+void compact_survivors(Context &ctx, const uint32_t *surv_slot, const uint32_t *surv_head, const uint32_t *surv_count,
+                       uint32_t *surv_off, unsigned g, uint32_t *new_slot, uint32_t *new_grp, uint32_t *d_new_m);
 // one pass writes rank[] for everybody: rank[sa[slot]] = rank_by_slot[slot]
 void write_all_ranks(SaBuild &b);
 
 // ---- sa_direct.hip --------------------------------------------------------------------------------------------------------
 void direct_round(SaBuild &b, int k_syms);
+// The launches of the first direct round over the active list slot[m] / grp[m] (m >= 1): group_refine_kernel -- its only
+// launch site -- and the compaction of what it leaves tied, on ctx.stream.  The members of a group agree on h0 symbols; at
+// most `cap` symbols are inspected (h0 < cap).  timed: the instantiation with the phase clocks, reported to stderr.
+// Out: the new order in sa, the boundaries that appeared (and the compared-pending code) in lcp, rank_by_slot (optional)
+// for every listed member, the next active list new_slot / new_grp (room for m), *d_new_m, and d_min_depth[3]: [0] the
+// depth of the compared classes left tied, [1] h0 if a group was not touched (0xffffffff: none), [2] the untouched members
+// counted in every 64th workgroup.  All of them device memory; the work arrays come from ctx.arena: the caller owns the
+// mark.  Shared by direct_round and the test hook nolzss_debug_direct_round.
+void direct_round_launch(Context &ctx, const PackedText &text, const uint32_t *slot, const uint32_t *grp, uint32_t m, uint32_t *sa,
+                         uint32_t *lcp, uint32_t *rank_by_slot, uint32_t h0, uint32_t cap, bool no_stragglers, bool timed,
+                         uint32_t *new_slot, uint32_t *new_grp, uint32_t *d_new_m, uint32_t *d_min_depth);
 void group_sort_passes(SaBuild &b);
 // The rounds of one group-sort pass (group_sort.hpp) over the active list slot[m] / grp[m], without the regroup behind
 // them: group_dir_kernel and the four group_sort_kernel launches, window rounds or (pivot) pivot rounds depth_cap symbols

@@ -535,19 +535,15 @@ template <bool kRound0> void regroup(SaBuild &b, const RegroupIn &in) {
 template void regroup<true>(SaBuild &, const RegroupIn &);
 template void regroup<false>(SaBuild &, const RegroupIn &);
 
-void compact_survivors(SaBuild &b, const uint32_t *surv_slot, const uint32_t *surv_head, uint32_t *surv_count,
-                       uint32_t *surv_off, unsigned g) {
-    hipStream_t s = b.stream();
-    {
-        // the next active list: the regions one after the other (they are in slot order already)
-        ProfScope ps(b.ctx.profiler(), "sa_regroup", s, 16.0 * (double)g);
-        scan_exclusive_add_u32(surv_count, surv_off, g, b.d_total, b.arena(), s);
-        compact_survivors_kernel<<<grid_for((size_t)g * 4, kThreads), kThreads, 0, s>>>(
-            surv_slot, surv_head, surv_count, surv_off, g, b.next_slot(), b.next_grp());
-        KERNEL_CHECK();
-    }
-    b.ctx.read_back(b.d_total, &b.m, 1);
-    b.a_cur ^= 1;
+void compact_survivors(Context &ctx, const uint32_t *surv_slot, const uint32_t *surv_head, const uint32_t *surv_count,
+                       uint32_t *surv_off, unsigned g, uint32_t *new_slot, uint32_t *new_grp, uint32_t *d_new_m) {
+    hipStream_t s = ctx.stream;
+    // the next active list: the regions one after the other (they are in slot order already)
+    ProfScope ps(ctx.profiler(), "sa_regroup", s, 16.0 * (double)g);
+    scan_exclusive_add_u32(surv_count, surv_off, g, d_new_m, ctx.arena, s);
+    compact_survivors_kernel<<<grid_for((size_t)g * 4, kThreads), kThreads, 0, s>>>(
+        surv_slot, surv_head, surv_count, surv_off, g, new_slot, new_grp);
+    KERNEL_CHECK();
 }
 
 // (rank_by_slot is not needed afterwards: it serves as one of the ping-pong buffers)
