@@ -1498,6 +1498,37 @@ int nolzss_debug_direct_round(const uint8_t *text, size_t n, uint32_t *sa, const
                               uint32_t h0, uint32_t cap, uint32_t flags, const uint32_t *lcp_in, uint32_t fill, int device,
                               uint32_t *lcp, uint32_t *rank_by_slot, uint32_t *new_slot, uint32_t *new_grp, uint32_t *new_m,
                               uint32_t *min_depth, uint32_t *info);
+/* The two arithmetic passes of the suffix-array construction over repetitive texts (sa_repeats.hip: the pair-run pass and
+ * the periodic pass, with the regroup behind the latter) and the counts in front of them, on the caller's partial state --
+ * periodic_pass and pair_run_pass of the construction themselves, behind the driver's own set-up (set_up_late_rounds:
+ * work arrays of n entries, count_large_groups, the LCP pyramid, the radix shifts; the pair-run arrays are forced on,
+ * whatever NOLZSS_PAIR_RUNS_MIN says).
+ * text[n]: packed as every text is (pack_text; bytes only: no mirrored text, no merged batch).  The state as it stands
+ * behind write_all_ranks: sa[n]; lcp[n + 1], a decided value (< 0xffffffbf) at the first slot of every group and a pending
+ * code (>= 0xffffffbf: 0xffffffff, or 0xfffffffe inside a class the direct round compared) at every other slot of it;
+ * rank[n] by position, head slot of the suffix's group + 1; slot[m] / grp[m]: the active list as for
+ * nolzss_debug_group_sort, EXACTLY the slots of the groups of two and more members.  lcp[n] goes to the device as the
+ * caller gives it: the driver has memory there that nothing has written yet (it clears the entry when the construction is
+ * over), and no range minimum of the passes reaches it.  h: the symbols every group agrees on.  NOT CHECKED, the caller's
+ * business: that the state is a true partial order of the text (each group a range of the true suffix array whose members
+ * agree on h symbols, every decided LCP the true one).
+ * which: NOLZSS_REPEAT_PASS_COUNTS (arg 0), _PERIODIC (arg = per_attempts on entry, 0 .. 3: 0 the first call with its
+ * gate, 1 a later call, 3 "never again"), _PAIR_RUNS (arg = passes, 1 .. 10; they stop when nothing is tied any more --
+ * the NOLZSS_PAIR_RUNS_* knobs play no part).  NOLZSS_NO_PERIODIC is honoured as the construction honours it.
+ * Out: sa, lcp (n + 1), rank over all entries; new_slot / new_grp (room for m) and *new_m: the next active list;
+ * counts[4]: what count_large_groups returns for the limit 16 (members beyond the first 16 of their group, groups of more
+ * than 16, groups, members next to a member of their group at most 4096 symbols away; zero for m == 0); info (optional,
+ * 3 words): bits per symbol, entries of the terminator table, segmented; periodic[3]: the return value of periodic_pass
+ * (0 for the other two), per_hint and per_attempts afterwards.
+ * NOLZSS_ERR_INVALID_ARGUMENT before any device work for null pointers, n == 0, n >= 2^31, m > n, another `which`, an
+ * `arg` outside its range, a list entry with grp > slot or slot >= n, slots that do not ascend, a group that does not hold
+ * consecutive list positions and the slots from its head slot on, a listed group of one member, an sa that is no
+ * permutation, a pending lcp[0], a rank that is not the head slot (by lcp) + 1, a slot inside a group (by lcp) that is not
+ * listed, a listed group without a decided entry at its head or with a decided entry inside it. */
+enum { NOLZSS_REPEAT_PASS_COUNTS = 0, NOLZSS_REPEAT_PASS_PERIODIC = 1, NOLZSS_REPEAT_PASS_PAIR_RUNS = 2 };
+int nolzss_debug_repeat_pass(const uint8_t *text, size_t n, uint32_t *sa, uint32_t *lcp, uint32_t *rank, const uint32_t *slot,
+                             const uint32_t *grp, size_t m, uint32_t h, int which, int arg, int device, uint32_t *new_slot,
+                             uint32_t *new_grp, uint32_t *new_m, uint32_t *counts, uint32_t *info, uint32_t *periodic);
 /* The greedy cursor (chain.hip: mark_chain, chain_starts, chain_lengths) and the widening of 16-bit codes (lpnf.hip:
  * widened_lstar) on the caller's codes -- the production functions, which read the codes and nothing else.  codes[n]: one
  * u32 per position, length in bits 0..30 (0 = literal), bit 31 the strand.  The cursor runs p -> p + max(1, length) from

@@ -477,6 +477,9 @@ def _load():
                                             vp, vp, vp, vp]
     lib.nolzss_debug_direct_round.argtypes = [vp, sz, vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32,
                                               C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "nolzss_debug_repeat_pass"):  # (NOLZSS_LIB: a variant built from an older commit has none)
+        lib.nolzss_debug_repeat_pass.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.c_uint32, C.c_int, C.c_int, C.c_int, vp,
+                                                 vp, vp, vp, vp, vp]
     lib.nolzss_debug_chain.argtypes = [vp, sz, sz, C.c_int, C.c_uint32, vp, sz, sz, C.c_uint32, C.c_int, vp, sz, C.c_int,
                                        vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "nolzss_debug_cursor"):  # (NOLZSS_LIB: a variant built from an older commit has none)
@@ -537,7 +540,7 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_finder_kernel", "nolzss_rlz_finder_close",
     "nolzss_debug_pyramid", "nolzss_debug_nearest", "nolzss_debug_lds_search",
     "nolzss_debug_local_sort", "nolzss_debug_text_order", "nolzss_debug_group_sort",
-    "nolzss_debug_direct_round",
+    "nolzss_debug_direct_round", "nolzss_debug_repeat_pass",
     "nolzss_debug_chain", "nolzss_debug_cursor",
     "nolzss_rlz_index_seed_chains", "nolzss_free_rlz_seed_chains_result", "nolzss_debug_rlz_seed_chain",
     "nolzss_rlz_index_align", "nolzss_free_rlz_align_result", "nolzss_debug_rlz_align_jobs",

@@ -2470,6 +2470,43 @@ def debug_direct_round(text, sa, slot, grp, h0: int, cap: int, flags: int = DIRE
             "min_depth": [int(x) for x in depth], "bits": int(info[0]), "terms": int(info[1]), "segmented": bool(info[2])}
 
 
+REPEAT_PASS_COUNTS, REPEAT_PASS_PERIODIC, REPEAT_PASS_PAIR_RUNS = 0, 1, 2
+
+
+def debug_repeat_pass(text, sa, lcp, rank, slot, grp, h: int, which: int, arg: int = 0):
+    """The periodic pass or the pair-run passes of the suffix-array construction on the device over a caller's partial
+    state (nolzss_debug_repeat_pass, test hook): periodic_pass / pair_run_pass of sa_repeats.hip behind the driver's own
+    set-up.  `sa` (n), `lcp` (n + 1: a decided value at the first slot of every group, a pending code inside; lcp[n] goes
+    in as it is) and `rank` (n, by position: head slot + 1) as they stand behind write_all_ranks; `slot` / `grp`: exactly
+    the slots of the groups of two and more, as for debug_group_sort; `h`: the symbols every group agrees on.  `which`:
+    REPEAT_PASS_COUNTS, REPEAT_PASS_PERIODIC (`arg` = per_attempts on entry, 0 .. 3) or REPEAT_PASS_PAIR_RUNS (`arg`
+    passes, 1 .. 10).  PRECONDITION, not checked: the state is a true partial order of the text.  Returns {"sa", "lcp",
+    "rank", "new_slot", "new_grp", "new_m", "counts" (4 values), "ret", "per_hint", "per_attempts", "bits", "terms",
+    "segmented"}."""
+    text = np.frombuffer(bytes(text), dtype=np.uint8)
+    sa = np.array(sa, dtype=np.uint32)  # (copies: the call writes the three)
+    lcp = np.array(lcp, dtype=np.uint32)
+    rank = np.array(rank, dtype=np.uint32)
+    slot = np.ascontiguousarray(slot, dtype=np.uint32)
+    grp = np.ascontiguousarray(grp, dtype=np.uint32)
+    n, m = text.size, slot.size
+    if sa.size != n or rank.size != n or lcp.size != n + 1 or grp.size != m:
+        raise ValueError("sa and rank hold one entry per symbol, lcp one more, slot and grp one per list entry")
+    if not (0 <= h < 1 << 32 and -(1 << 31) <= which < 1 << 31 and -(1 << 31) <= arg < 1 << 31):
+        raise ValueError("h is a 32-bit value, which and arg are ints")
+    new_slot, new_grp = np.zeros(max(m, 1), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+    new_m, counts = C.c_uint32(), np.zeros(4, dtype=np.uint32)
+    info, per = np.zeros(3, dtype=np.uint32), np.zeros(3, dtype=np.uint32)
+    check(lib.nolzss_debug_repeat_pass(text.ctypes.data, n, sa.ctypes.data, lcp.ctypes.data, rank.ctypes.data, slot.ctypes.data,
+                                       grp.ctypes.data, m, h, which, arg, _default_device, new_slot.ctypes.data,
+                                       new_grp.ctypes.data, C.byref(new_m), counts.ctypes.data, info.ctypes.data,
+                                       per.ctypes.data))
+    k = new_m.value
+    return {"sa": sa, "lcp": lcp, "rank": rank, "new_slot": new_slot[:k], "new_grp": new_grp[:k], "new_m": k,
+            "counts": [int(x) for x in counts], "ret": bool(per[0]), "per_hint": int(per[1]), "per_attempts": int(per[2]),
+            "bits": int(info[0]), "terms": int(info[1]), "segmented": bool(info[2])}
+
+
 LDS_PLAIN, LDS_RC = 0, 1
 LDS_OVERFLOW = 0xffffffff
 

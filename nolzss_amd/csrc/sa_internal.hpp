@@ -204,6 +204,15 @@ void group_sort_rounds(Context &ctx, const PackedText &text, const uint32_t *slo
 // [3] = members next to a member of their group at most kPerVerifyMax symbols away (per_count_large_kernel)
 void count_large_groups(SaBuild &b, uint32_t limit, uint32_t *d_cnt, uint32_t out[4]);
 bool periodic_pass(SaBuild &b);
+// one pair-run pass over the whole text (b.pair_runs, b.m > 0): the sweep, the active list without the suffixes it
+// finished and the pyramid over the LCP values it decided.  false: no progress, another pass is not worth it.
+bool pair_run_pass(SaBuild &b);
 void pair_run_passes(SaBuild &b);
+
+// ---- suffix_array.hip -----------------------------------------------------------------------------------------------------
+// What the rounds behind write_all_ranks start from: the work arrays, the counts of count_large_groups, the LCP pyramid
+// and the radix shifts.  Shared by the driver and the test hook nolzss_debug_repeat_pass (force_pair_runs: b.pair_runs
+// and work arrays of n entries for every m > 0, whatever the knobs say).
+void set_up_late_rounds(SaBuild &b, bool force_pair_runs = false);
 
 }  // namespace nolzss

@@ -660,36 +660,40 @@ void pair_run_sweep(SaBuild &b) {
 // of what was tied, where the doubling rounds from the depth the direct round reached take 85 ms; three genomes:
 // 115 ms with two passes, 92 ms with the doubling rounds; two genomes: 72 against 82 ms, two exact copies 79 against
 // 279 ms -- the passes run where the tied suffixes sit in pairs: mean group size at most 2.5)
+bool pair_run_pass(SaBuild &b) {
+    hipStream_t s = b.stream();
+    const uint32_t n = b.n;
+    ProfScope ps(b.ctx.profiler(), "sa_pair_runs", s);
+    pair_run_sweep(b);
+    ProfScope p5(b.ctx.profiler(), "runs_compact", s);
+    // the active list without the suffixes that are done, with the new group heads of the others
+    const uint32_t m = b.m;
+    uint32_t *keep = b.tmp_a, *pos = b.tmp_b, *head = b.tmp_c;
+    still_tied_kernel<<<grid_for(m, kThreads), kThreads, 0, s>>>(b.slot(), b.grp(), m, b.lcp, n, head, keep);
+    KERNEL_CHECK();
+    scan_exclusive_add_u32(keep, pos, m, b.d_total, b.arena(), s);
+    compact_active_kernel<<<grid_for(m, kThreads), kThreads, 0, s>>>(b.slot(), head, keep, pos, m, b.next_slot(), b.next_grp());
+    KERNEL_CHECK();
+    uint32_t left = 0;
+    b.ctx.read_back(b.d_total, &left, 1);
+    if (sa_knobs().trace) fprintf(stderr, "[nolzss]   pair runs: %u of %u tied suffixes finished\n", m - left, m);
+    b.m = left;
+    b.a_cur ^= 1;
+    if (left > 0) {
+        b.arena().rewind(b.pyr_mark);
+        b.Plcp = build_pyramid(b.lcp, n + 1, false, b.arena(), s);
+    }
+    return left < m - m / 8;  // (else: no progress)
+}
+
 void pair_run_passes(SaBuild &b) {
     const SaKnobs &knobs = sa_knobs();
-    hipStream_t s = b.stream();
     const uint32_t n = b.n;
     const bool runs_can_help = knobs.pair_runs_min >= 0 ||
                                (b.large_members <= b.m / 2 && (uint64_t)b.m * 4 <= (uint64_t)b.tied_groups * knobs.runs_avg4);
     for (int pass = 0; b.pair_runs && runs_can_help && pass < 10 && b.m > 0 &&
-                       (knobs.pair_runs_min >= 0 ? (long long)b.m >= knobs.pair_runs_min : b.m >= n / 16); ++pass) {
-        ProfScope ps(b.ctx.profiler(), "sa_pair_runs", s);
-        pair_run_sweep(b);
-        ProfScope p5(b.ctx.profiler(), "runs_compact", s);
-        // the active list without the suffixes that are done, with the new group heads of the others
-        const uint32_t m = b.m;
-        uint32_t *keep = b.tmp_a, *pos = b.tmp_b, *head = b.tmp_c;
-        still_tied_kernel<<<grid_for(m, kThreads), kThreads, 0, s>>>(b.slot(), b.grp(), m, b.lcp, n, head, keep);
-        KERNEL_CHECK();
-        scan_exclusive_add_u32(keep, pos, m, b.d_total, b.arena(), s);
-        compact_active_kernel<<<grid_for(m, kThreads), kThreads, 0, s>>>(b.slot(), head, keep, pos, m, b.next_slot(), b.next_grp());
-        KERNEL_CHECK();
-        uint32_t left = 0;
-        b.ctx.read_back(b.d_total, &left, 1);
-        if (sa_knobs().trace) fprintf(stderr, "[nolzss]   pair runs: %u of %u tied suffixes finished\n", m - left, m);
-        b.m = left;
-        b.a_cur ^= 1;
-        if (left > 0) {
-            b.arena().rewind(b.pyr_mark);
-            b.Plcp = build_pyramid(b.lcp, n + 1, false, b.arena(), s);
-        }
-        if (!(left < m - m / 8)) break;  // no progress
-    }
+                       (knobs.pair_runs_min >= 0 ? (long long)b.m >= knobs.pair_runs_min : b.m >= n / 16); ++pass)
+        if (!pair_run_pass(b)) break;
 }
 
 }  // namespace nolzss

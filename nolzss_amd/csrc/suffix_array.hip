@@ -420,15 +420,18 @@ void key_sort_round0(SaBuild &b, const KeyPlan &plan) {
     arena.rewind(sort_mark);  // keys and the second value buffer are done
 }
 
+}  // namespace
+
 // Work arrays of the rounds behind write_all_ranks, one entry per tied suffix -- or per text position when the
 // pair-run pass will run (it works in text order; the rounds behind it then use the same arrays) --, the counts
 // that tell which of the passes of sa_repeats.hip can do anything, and the pyramid over the LCP values known so far.
-void set_up_late_rounds(SaBuild &b) {
+// (force_pair_runs: the test hook nolzss_debug_repeat_pass, whatever NOLZSS_PAIR_RUNS_MIN says)
+void set_up_late_rounds(SaBuild &b, bool force_pair_runs) {
     const SaKnobs &knobs = sa_knobs();
     hipStream_t s = b.stream();
     Arena &arena = b.arena();
     const uint32_t n = b.n, m = b.m;
-    b.pair_runs = m > 0 && (knobs.pair_runs_min >= 0 ? (long long)m >= knobs.pair_runs_min : m >= n / 16);
+    b.pair_runs = m > 0 && (force_pair_runs || (knobs.pair_runs_min >= 0 ? (long long)m >= knobs.pair_runs_min : m >= n / 16));
     b.wlen = m == 0 ? 0 : (b.pair_runs ? (size_t)n : (size_t)m);
     if (m > 0) {
         try {
@@ -465,6 +468,8 @@ void set_up_late_rounds(SaBuild &b) {
     for (int p = 0; p < b.half_passes; ++p) b.shifts[b.npasses++] = p * kRadixBits;
     for (int p = 0; p < b.half_passes; ++p) b.shifts[b.npasses++] = 32 + p * kRadixBits;
 }
+
+namespace {
 
 // Members of the large groups: the group of an element is known from where it lies (a group's members are
 // consecutive in the list, so also in the gathered array), so the groups are the BUCKETS of a segmented
