@@ -554,6 +554,81 @@ int nolzss_roundtrip_device(const void *d_text, size_t n, int with_rc, int devic
 int nolzss_debug_count_mismatches(const uint8_t *a, const uint8_t *b, size_t n, int device,
                                   uint64_t *count, uint64_t *first);
 
+/* ---- factor records: the compact container ------------------------------------------------------ */
+/* Extension.  A compact, canonical, byte-exact form of the records of nolzss_factorize, nolzss_factorize_dna_w_rc, the
+ * multi-sequence forms and the reference + target forms (every mode whose records obey the contract of nolzss_decode
+ * above), packed on the device and expanded on the device: with nolzss_factorize_packed the 24-byte records never cross
+ * PCIe ("Factor records: the compact container").  It is a factor file, not a compressor: a factor of a
+ * non-repetitive genome is about 18 bases long and carries a far reference, so the container comes out near the size of
+ * the text at 2 bits per base, not below it; the gain is against the 24-byte records, and on repetitive collections.
+ *   The format.  All integers little-endian, all arithmetic unsigned 32-bit with wrap-around unless stated otherwise.
+ *     The records tile [first_start, first_start + decoded): p_0 = first_start, p_{i + 1} = p_i + L_i, so p is not
+ *     stored; first_start is 0 for the plain and reverse-complement forms and start_pos for the reference + target
+ *     forms.  Record i is a literal (ref == start, no mask, L = 1), a forward copy (ref = x) or a reverse-complement
+ *     copy (ref = x | NOLZSS_RC_MASK); every copy has x + L <= p, the rule of nolzss_decode.  For a copy r = 1 (reverse
+ *     complement) or 0, y = x (forward) or -(x + L) (the mirrored coordinate, in which a reverse-complement match reads
+ *     forward), g = y - p.  With c the last copy before i (none: g_c = r_c = 0): e = g - g_c, v = (zigzag32(e) << 1) |
+ *     (r ^ r_c), 33 bits, zigzag32(e) = (e << 1) ^ (int32(e) >> 31).  A copy that goes on colinearly behind any number
+ *     of literals, on either strand, has v = 0.
+ *   control: one nibble per record, record 2 j in the low and 2 j + 1 in the high nibble of byte j, (z + 1) / 2 bytes,
+ *     the spare nibble of an odd z is 0.  nibble = a | b << 2; a: 0 a literal (b must be 0), 1 / 2 / 3: L in 1 / 2 / 4
+ *     bytes; b: 0: v = 0, 1 / 2 / 3: v in 2 / 4 / 5 bytes (not the archive's 1 / 3 / 5: on one strand |e| < n, so 4
+ *     bytes always suffice up to 2^30 symbols).  The packer uses the smallest class that holds the value, so the
+ *     sections are a function of the records; the expander takes any well-formed code.
+ *   data: per record, in order, the bytes of L, then those of v; a literal has none.
+ *   literals: literal_mode 1: every literal symbol is A, C, G or T (also: there is none) and they lie four to a byte
+ *     at 2 bits (A, C, G, T = 0 .. 3), the first in the low bits, unused bits 0; literal_mode 0: one byte per literal;
+ *     literal_mode 2: the literals are not stored (a factor file like v2), n_literals is still the number of literal
+ *     records.  The packer chooses 1 or 0, canonically; 2 is the caller's choice (store_literals == 0).
+ *   The file (written and read by nolzss_amd.write_packed_factors / read_packed_factors, host only): a 72-byte header
+ *     -- the magic "noLZFAC1", uint32 version = 1, uint32 flags (bits 0-1 literal_mode, the rest 0), then uint64
+ *     first_start, z, n_literals, decoded, control_bytes, data_bytes, literal_bytes -- and control, data and literals,
+ *     each padded with zeros to 8 bytes.  Nothing follows; sequence names and sentinel indices of the v2 footer are
+ *     out of scope.
+ *   nolzss_factors_pack: host records -> the three device-made sections as malloc'ed buffers (never NULL after a
+ *     success); free with nolzss_free_packed_factors (NULL and an all-zero struct are no-ops; the struct is zeroed).
+ *     first_start = start[0].  Whatever the format cannot carry is refused on the device before a byte is packed, in
+ *     the words of nolzss_decode and naming the first offending record: tiling (start[k + 1] != start[k] + length[k],
+ *     length == 0, an end beyond the 32-bit pipeline), literal length, source range (ref + length > start), and, with
+ *     store_literals, a literal count other than n_literals.  Without store_literals `literals` is not read.  A data
+ *     section of 2^32 bytes or more is refused before anything is written.  z == 0 is valid and launches nothing.
+ *   nolzss_factorize_packed / _device: factorize as nolzss_roundtrip does (with_rc: as nolzss_factorize_dna_w_rc, with
+ *     its refusals, the literals taken from the upper-cased strand), leave the records in device memory above the work
+ *     arrays, gather the literals and pack there: only the three sections come down.  If the device arena cannot hold
+ *     the pack behind the factorization the call fails with NOLZSS_ERR_NOMEM and names the sizes; there is no
+ *     fallback.  An empty text gives z = 0.  `stream` as nolzss_factorize_device.
+ *   nolzss_factors_unpack: the sections are UNTRUSTED.  The byte sizes of control and literals are first checked on
+ *     the host against the counts, first_start, decoded, their sum, z and n_literals against the 32-bit pipeline, and
+ *     every device read is bounded by these sizes and never by what a section says.  The rules, all checked on the
+ *     device, judged in three steps of which the first that finds a violation names its smallest offending record,
+ *     whatever the schedule: (1) from the nibbles alone: a literal nibble has b == 0, the spare nibble is 0, the data
+ *     bytes the nibbles ask for are exactly data_bytes (compared before a data byte is read); (2) L >= 1, v has 33
+ *     bits, then the exact 64-bit sum of L equals `decoded` (before a position is formed); (3) x + L <= p for a copy,
+ *     in 64 bits after the 32-bit recovery, and no more literal records than n_literals.  A count that falls short
+ *     names record z, "behind the last".  A violation returns NOLZSS_ERR_INVALID_ARGUMENT and nothing is returned.
+ *     *factors: nolzss_free; *literals: malloc'ed, nolzss_free, NULL for literal_mode 2.
+ *   nolzss_decode_packed: unpack into device memory and decode there as nolzss_decode does (its rule on complements
+ *     included): the 24-byte records never cross PCIe.  literal_mode 2 and prefix_len != first_start are refused.
+ *   The calling thread's current device is left as it was. */
+typedef struct nolzss_packed_factors {
+    uint32_t literal_mode, reserved;            /* reserved: 0 */
+    uint64_t first_start, z, n_literals;
+    uint64_t decoded;                           /* sum of the lengths of the records */
+    uint8_t *control, *data, *literals;         /* malloc'ed by the packers; the caller's for unpack and decode_packed */
+    uint64_t control_bytes, data_bytes, literal_bytes;
+} nolzss_packed_factors;
+int nolzss_factors_pack(const nolzss_factor *factors, size_t z, const uint8_t *literals, size_t n_literals,
+                        int store_literals, int device, nolzss_packed_factors *out);
+int nolzss_factorize_packed(const uint8_t *text, size_t n, int with_rc, int store_literals, int device,
+                            nolzss_packed_factors *out);
+int nolzss_factorize_packed_device(const void *d_text, size_t n, int with_rc, int store_literals, int device,
+                                   void *stream, nolzss_packed_factors *out);
+void nolzss_free_packed_factors(nolzss_packed_factors *p);
+int nolzss_factors_unpack(const nolzss_packed_factors *in, int device, nolzss_factor **factors, size_t *z,
+                          uint8_t **literals, size_t *n_literals);
+int nolzss_decode_packed(const nolzss_packed_factors *in, const uint8_t *prefix, size_t prefix_len, int device,
+                         uint8_t **text, size_t *n, nolzss_decode_info *info);
+
 /* ---- relative-LZ archive: ranges of the targets from resident records --------------------------- */
 /* Extension.  Every copy of a relative-LZ parse points into the reference block and never into a target, so any byte of
  * any target is one hop from the record that covers it.  A handle keeps the block and the records in device memory of

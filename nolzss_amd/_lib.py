@@ -130,6 +130,14 @@ class RlzArchivePacked(C.Structure):
                 ("literal_bytes", C.c_uint64)]
 
 
+class PackedFactors(C.Structure):
+    """Mirror of nolzss_packed_factors (include/nolzss_hip.h)."""
+    _fields_ = [("literal_mode", C.c_uint32), ("reserved", C.c_uint32), ("first_start", C.c_uint64), ("z", C.c_uint64),
+                ("n_literals", C.c_uint64), ("decoded", C.c_uint64),
+                ("control", C.c_void_p), ("data", C.c_void_p), ("literals", C.c_void_p),
+                ("control_bytes", C.c_uint64), ("data_bytes", C.c_uint64), ("literal_bytes", C.c_uint64)]
+
+
 class RlzFinderSummary(C.Structure):
     """Mirror of nolzss_rlz_finder_summary (include/nolzss_hip.h)."""
     _fields_ = [("num_targets", C.c_uint64), ("z", C.c_uint64), ("total_length", C.c_uint64),
@@ -382,6 +390,15 @@ def _load():
     lib.nolzss_roundtrip.argtypes = [vp, sz, C.c_int, C.c_int, szp, u64p, u64p, dip]
     lib.nolzss_roundtrip_device.argtypes = [vp, sz, C.c_int, C.c_int, vp, szp, u64p, u64p, dip]
     lib.nolzss_debug_count_mismatches.argtypes = [vp, vp, sz, C.c_int, u64p, u64p]
+    if hasattr(lib, "nolzss_factors_pack"):  # (NOLZSS_LIB: a variant built from an older commit has none)
+        pfp = C.POINTER(PackedFactors)
+        lib.nolzss_factors_pack.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, pfp]
+        lib.nolzss_factorize_packed.argtypes = [vp, sz, C.c_int, C.c_int, C.c_int, pfp]
+        lib.nolzss_factorize_packed_device.argtypes = [vp, sz, C.c_int, C.c_int, C.c_int, vp, pfp]
+        lib.nolzss_free_packed_factors.argtypes = [pfp]
+        lib.nolzss_free_packed_factors.restype = None
+        lib.nolzss_factors_unpack.argtypes = [pfp, C.c_int, vpp, szp, vpp, szp]
+        lib.nolzss_decode_packed.argtypes = [pfp, vp, sz, C.c_int, vpp, szp, dip]
     lib.nolzss_rlz_archive_open_records.argtypes = [vp, sz, vp, sz, vp, sz, vp, sz, C.c_int, vpp]
     lib.nolzss_rlz_archive_info.argtypes = [vp, C.POINTER(RlzArchiveSummary)]
     lib.nolzss_rlz_archive_extract.argtypes = [vp, vp, sz, vpp, vpp, u64p]
@@ -529,6 +546,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_debug_rlz_codes",
     "nolzss_literal_symbols", "nolzss_decode", "nolzss_roundtrip", "nolzss_roundtrip_device",
     "nolzss_debug_count_mismatches",
+    "nolzss_factors_pack", "nolzss_factorize_packed", "nolzss_factorize_packed_device", "nolzss_free_packed_factors",
+    "nolzss_factors_unpack", "nolzss_decode_packed",
     "nolzss_rlz_archive_open_records", "nolzss_rlz_archive_info", "nolzss_rlz_archive_extract",
     "nolzss_rlz_archive_extract_device", "nolzss_rlz_archive_close",
     "nolzss_rlz_index_open", "nolzss_rlz_index_open_fasta", "nolzss_rlz_index_info", "nolzss_rlz_index_factorize",

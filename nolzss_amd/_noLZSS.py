@@ -1218,6 +1218,99 @@ def decode_array(factors, literals, prefix=b""):
     return np.frombuffer(raw, dtype=np.uint8), _info_dict(info)
 
 
+# ---- factor records: the compact container (extension) ------------------------------------------------
+# the fields of nolzss_packed_factors: the counts, and each section with the field that holds its size
+PACKED_FACTOR_COUNTS = ("literal_mode", "first_start", "z", "n_literals", "decoded")
+PACKED_FACTOR_SECTIONS = (("control", "control_bytes"), ("data", "data_bytes"), ("literals", "literal_bytes"))
+
+
+def _packed_factors_out(p):
+    """a filled nolzss_packed_factors -> the dict of sections; the struct is freed"""
+    try:
+        out = {name: int(getattr(p, name)) for name in PACKED_FACTOR_COUNTS}
+        for name, size in PACKED_FACTOR_SECTIONS:
+            out[name] = C.string_at(getattr(p, name), getattr(p, size))
+    finally:
+        lib.nolzss_free_packed_factors(C.byref(p))
+    return out
+
+
+def _packed_factors_in(sections):
+    """the dict of sections -> (nolzss_packed_factors over buffers of this process, keepalive)"""
+    p, keep = _lib.PackedFactors(), []
+    for name in PACKED_FACTOR_COUNTS:
+        setattr(p, name, operator.index(sections[name]))
+    for name, size in PACKED_FACTOR_SECTIONS:
+        raw = bytes(sections[name])
+        buf = C.create_string_buffer(raw, len(raw)) if raw else None
+        keep.append(buf)
+        setattr(p, name, C.cast(buf, C.c_void_p) if buf is not None else None)
+        setattr(p, size, len(raw))
+    return p, keep
+
+
+def factorize_packed(data, with_rc: bool = False, literals: bool = True) -> dict:
+    """Extension: factorize (with_rc: as factorize_dna_w_rc) and pack the records on the device -> the sections of the
+    compact container: literal_mode, first_start, z, n_literals, decoded and the bytes of control, data and literals
+    (`literals` False: literal_mode 2, a factor file without the symbols).  Only the sections cross PCIe.  C ABI
+    nolzss_factorize_packed (its header states the format)."""
+    ptr, n, keep = _as_buffer(data)
+    p = _lib.PackedFactors()
+    check(lib.nolzss_factorize_packed(ptr if n else None, n, 1 if with_rc else 0, 1 if literals else 0, _default_device,
+                                      C.byref(p)))
+    return _packed_factors_out(p)
+
+
+def factorize_packed_device(data_ptr: int, n: int, with_rc: bool = False, literals: bool = True, stream: int = 0) -> dict:
+    """factorize_packed over n bytes resident in device memory (C ABI nolzss_factorize_packed_device)."""
+    p = _lib.PackedFactors()
+    check(lib.nolzss_factorize_packed_device(C.c_void_p(data_ptr), n, 1 if with_rc else 0, 1 if literals else 0,
+                                             _default_device, C.c_void_p(stream), C.byref(p)))
+    return _packed_factors_out(p)
+
+
+def pack_factors(factors, literals=None) -> dict:
+    """Extension: host records (a FACTOR_DTYPE array or tuples, as decode takes them) and their literal symbols
+    (literal_symbols; None: literal_mode 2) -> the sections of the compact container, packed on the device.  C ABI
+    nolzss_factors_pack (its header states what is refused)."""
+    f = _decode_records(factors)
+    lp, ln, keep = _as_buffer(literals) if literals is not None else (None, 0, None)
+    p = _lib.PackedFactors()
+    check(lib.nolzss_factors_pack(f.ctypes.data if f.size else None, f.size, lp if ln else None, ln,
+                                  0 if literals is None else 1, _default_device, C.byref(p)))
+    return _packed_factors_out(p)
+
+
+def unpack_factors(sections):
+    """Extension: the sections of the compact container (UNTRUSTED) -> (FACTOR_DTYPE records, literal bytes or None
+    for literal_mode 2), expanded and checked on the device.  C ABI nolzss_factors_unpack (its header states the rules)."""
+    p, keep = _packed_factors_in(sections)
+    rec, lit, z, ln = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+    check(lib.nolzss_factors_unpack(C.byref(p), _default_device, C.byref(rec), C.byref(z), C.byref(lit), C.byref(ln)))
+    try:
+        literals = None if p.literal_mode == 2 else C.string_at(lit, ln.value) if lit.value else b""
+    finally:
+        lib.nolzss_free(lit)
+    return _take(rec, z.value), literals
+
+
+def decode_packed_array(sections, prefix=b""):
+    """Extension: the text of packed factors -> (np.uint8 array of first_start + decoded bytes, info dict); the records
+    are expanded and decoded in device memory.  `prefix`: the first_start known bytes in front of the first record.
+    C ABI nolzss_decode_packed."""
+    p, keep = _packed_factors_in(sections)
+    pp, pn, keep_p = _as_buffer(prefix)
+    out, n, info = C.c_void_p(), C.c_size_t(), _lib.DecodeInfo()
+    check(lib.nolzss_decode_packed(C.byref(p), pp if pn else None, pn, _default_device, C.byref(out), C.byref(n),
+                                   C.byref(info)))
+    owner = _Owned(out)
+    if n.value == 0:
+        return np.zeros(0, dtype=np.uint8), _info_dict(info)
+    raw = (C.c_uint8 * n.value).from_address(out.value)
+    raw._owner = owner
+    return np.frombuffer(raw, dtype=np.uint8), _info_dict(info)
+
+
 # ---- relative-LZ archive: ranges of the targets from resident records (genomics/rlz.py) ------------------------
 def _ranges_array(ranges):
     """-> contiguous (q, 3) uint64 array of (target index, lo, hi) rows, the layout of nolzss_rlz_range"""

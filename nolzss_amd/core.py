@@ -1,8 +1,9 @@
 """The user-facing factorize API of the hot path, written once for both import names.
 
 `bind(native)` builds the seven functions of the reference's `noLZSS.core` (reference:
-src/noLZSS/core.py:25-257 -- names, argument meaning, error behaviour) and the two of the decoder (extension:
-`decode`, `literal_symbols`) over a native module:
+src/noLZSS/core.py:25-257 -- names, argument meaning, error behaviour), the two of the decoder (extension:
+`decode`, `literal_symbols`) and the four of the compact container of factor records (extension: `factorize_packed`,
+`pack_factors`, `unpack_factors`, `decode_packed`) over a native module:
 `nolzss_amd.core` binds them to the ctypes mirror `nolzss_amd._noLZSS`, `noLZSS.core` to the compiled
 pybind11 module `noLZSS._noLZSS`.  Both native modules call the same C ABI (include/nolzss_hip.h).
 """
@@ -12,7 +13,8 @@ from typing import List, Tuple, Union
 from .utils import validate_input
 
 __all__ = ["factorize", "factorize_file", "count_factors", "count_factors_file", "write_factors_binary_file",
-           "factorize_w_reference", "factorize_w_reference_file", "decode", "literal_symbols"]
+           "factorize_w_reference", "factorize_w_reference_file", "decode", "literal_symbols", "factorize_packed",
+           "pack_factors", "unpack_factors", "decode_packed"]
 
 Factors = List[Tuple[int, int, int]]
 Text = Union[str, bytes]
@@ -90,6 +92,28 @@ def bind(native) -> dict:
         forms (4-tuples with is_rc) return, or a structured array; `literals`: `literal_symbols` of the text;
         `prefix`: the known bytes in front of the first factor (for `factorize_w_reference`: reference + '\x01')."""
         return native.decode_array(factors, as_bytes(literals), as_bytes(prefix))[0].tobytes()
+
+    def factorize_packed(data: Text, with_rc: bool = False, literals: bool = True) -> dict:
+        """Extension: factorize `data` (with_rc: as `factorize_dna_w_rc`) and pack the factors on the GPU -> the sections
+        of the compact container (a dict: literal_mode, first_start, z, n_literals, decoded, control, data, literals);
+        only they leave the device.  `literals` False leaves the literal symbols out (a factor file like v2).
+        `utils.write_packed_factors` writes the sections to a file."""
+        return native.factorize_packed(as_bytes(data), with_rc, literals)
+
+    def pack_factors(factors, literals=None) -> dict:
+        """Extension: the sections of the compact container from factors any mode returned (3-tuples, 4-tuples with
+        is_rc, or a structured array) and, optionally, `literal_symbols` of the text."""
+        return native.pack_factors(factors, None if literals is None else as_bytes(literals))
+
+    def unpack_factors(sections):
+        """Extension: sections -> (structured array of (start, length, ref), ref carrying the reverse-complement mask;
+        the literal symbols, or None when the sections hold none).  The sections are checked on the GPU."""
+        return native.unpack_factors(sections)
+
+    def decode_packed(sections, prefix: Text = b"") -> bytes:
+        """Extension: the text of the sections, expanded and decoded on the GPU; `prefix`: the first_start known bytes in
+        front of the first factor (for `factorize_w_reference`: reference + '\x01')."""
+        return native.decode_packed_array(sections, as_bytes(prefix))[0].tobytes()
 
     fns = locals()
     return {name: fns[name] for name in __all__}

@@ -514,4 +514,19 @@ UnpackOut unpack_records(Context &ctx, const UnpackIn &in, size_t z, ArchiveRec 
     return res;
 }
 
+// What the container of the factor records of the other modes shares with this one (factor_pack.hip)
+void packed_sum_u32(Context &ctx, const uint32_t *d_in, size_t n, unsigned long long *d_out) { sum_u32(ctx, d_in, n, d_out); }
+
+void packed_quarter_pack(Context &ctx, const uint8_t *d_in, size_t n, uint8_t *d_out) {
+    if (n == 0) return;
+    pack_quarter_kernel<<<record_grid(packed_quarter(n)), kThreads, 0, ctx.stream>>>(d_in, n, d_out);
+    KERNEL_CHECK();
+}
+
+void packed_quarter_unpack(Context &ctx, const uint8_t *d_in, size_t n, uint8_t *d_out) {
+    if (n == 0) return;
+    unpack_quarter_kernel<<<record_grid(packed_quarter(n)), kThreads, 0, ctx.stream>>>(d_in, n, d_out);
+    KERNEL_CHECK();
+}
+
 }  // namespace nolzss

@@ -63,4 +63,11 @@ struct UnpackOut {
 // the data size is compared with what the nibbles ask for before a data byte is read.  Waits for the stream.
 UnpackOut unpack_records(Context &ctx, const UnpackIn &in, size_t z, ArchiveRec *d_recs);
 
+// ---- shared with the container of the factor records of the other modes (factor_pack.hip) ---------------------------
+// *d_out (one 64-bit word in device memory) = the sum of d_in[0 .. n), exact in 64 bits, on the stream
+void packed_sum_u32(Context &ctx, const uint32_t *d_in, size_t n, unsigned long long *d_out);
+// n symbols <-> packed_quarter(n) bytes at 2 bits (A, C, G, T = 0 .. 3, anything else packs as 0); n == 0 launches nothing
+void packed_quarter_pack(Context &ctx, const uint8_t *d_in, size_t n, uint8_t *d_out);
+void packed_quarter_unpack(Context &ctx, const uint8_t *d_in, size_t n, uint8_t *d_out);
+
 }  // namespace nolzss
