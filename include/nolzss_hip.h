@@ -765,6 +765,65 @@ int nolzss_rlz_index_count(const nolzss_rlz_index *h, const char *const *pattern
 int nolzss_rlz_index_locate(const nolzss_rlz_index *h, const char *const *patterns, const size_t *pattern_lens, size_t q,
                             uint64_t max_hits, uint64_t *counts, uint64_t *hit_offsets, nolzss_rlz_hit **hits,
                             size_t *num_hits);
+/* Maximal repeats: what is repeated inside the reference itself, on either strand, how often and where (DESIGN.md 5,
+ * "Relative-LZ index: maximal repeats").  Nothing goes up and nothing is added to the handle: the answer is read off the
+ * resident suffix array, LCP array and pyramids.  Rblk, B, X, "forward occurrence at position a" and "reverse-strand
+ * occurrence at position a" are those of the locate above.
+ *   Occ(w), for a nucleotide string w, is the set of (a, is_rc) the locate would report for the pattern w without a cap;
+ *     count(w) = |Occ(w)|.  A reverse-strand occurrence exists only on an index opened with reverse complement.
+ *   Extensions of an occurrence of w, L = |w|.  Forward at a: the right extension is Rblk[a + L], or a unique end mark
+ *     if the record ends there; the left extension is Rblk[a - 1], or a unique end mark if the record starts at a.
+ *     Reverse strand at a: the right extension is the complement of Rblk[a - 1], the left extension the complement of
+ *     Rblk[a + L], or a unique end mark each.  An end mark differs from every base and from every other end mark.
+ *   Maximal repeat: count(w) >= 2, the occurrences do not all share one right extension, and they do not all share one
+ *     left extension -- the strand-aware definition of DNA repeat finders.
+ *   Reported: every maximal repeat w with |w| >= min_length and count(w) >= min_count, under two rules on an index with
+ *     reverse complement.  (1) One of a mirror pair: Occ(rc(w)) is Occ(w) with the strands flipped, so w and rc(w) are
+ *     the same repeat; with p(w) = the smallest forward position in Occ(w) (infinite without one), w is reported iff
+ *     p(w) <= p(rc(w)).  Equality happens exactly when w == rc(w): such a record carries palindrome = 1.  (2) A
+ *     palindrome at one locus is no repeat: a record with palindrome = 1 lists every locus on both strands and is
+ *     reported only if count >= 4, i.e. at least two loci.  min_count applies to count as stated, before and
+ *     independently of rule (2).
+ *   Record: position = p(w) in Rblk coordinates, length = |w|, count = count(w), record = the 0-based reference record
+ *     that holds position, palindrome.  The records ascend by (position, length): the key is unique and does not depend
+ *     on how tied suffixes are ordered.
+ *   Hits: as in the locate.  Every record with count <= max_hits (0: no cap) lists all of Occ(w) as nolzss_rlz_hit,
+ *     CSR-style: record j owns hits [hit_offsets[j], hit_offsets[j + 1]), ascending by (position, is_rc), forward first;
+ *     they are sorted on the device.  A record above the cap reports its count and NO hits.  repeats is NULL when
+ *     num_repeats is 0, hits is NULL when num_hits is 0, hit_offsets holds its num_repeats + 1 entries after a success.
+ *     Free the result with the free function below, whatever the status.
+ *   repeat_count: *num_repeats = the records nolzss_rlz_index_repeats would report for the same min_length and
+ *     min_count; only the flags are computed and one word comes down.  It is how a caller picks min_length.
+ *   Refusals before any device work, NOLZSS_ERR_INVALID_ARGUMENT: a null handle or output pointer; min_length == 0;
+ *     min_count < 2.
+ *   Refusals once the counts are known and before anything is expanded, NOLZSS_ERR_INVALID_ARGUMENT: 2^31 or more
+ *     records (the sort key of a hit keeps its record in 31 bits; the result is then empty); a hit total beyond the
+ *     32-bit pipeline: the message names the total and points at max_hits and min_length, and the records, their counts
+ *     and hit_offsets are still returned (hits is NULL and num_hits 0).
+ *   An arena out-of-memory leaves the handle untouched, as a match does.  Several threads may query one handle; the
+ *     calling thread's current device is left as it was.  NOLZSS_RLZ_LOCATE_CHUNK (tests): repeat records, and hit
+ *     records, per download. */
+typedef struct nolzss_rlz_repeat {
+    uint64_t position, length, count;
+    uint32_t record, palindrome;
+} nolzss_rlz_repeat;
+typedef struct nolzss_rlz_repeats_result {
+    size_t num_repeats;
+    nolzss_rlz_repeat *repeats; /* ascending by (position, length) */
+    uint64_t *hit_offsets;      /* num_repeats + 1 entries */
+    nolzss_rlz_hit *hits;       /* NULL when num_hits == 0 */
+    size_t num_hits;
+} nolzss_rlz_repeats_result;
+int nolzss_rlz_index_repeat_count(const nolzss_rlz_index *h, uint64_t min_length, uint64_t min_count, uint64_t *num_repeats);
+int nolzss_rlz_index_repeats(const nolzss_rlz_index *h, uint64_t min_length, uint64_t min_count, uint64_t max_hits,
+                             nolzss_rlz_repeats_result *out);
+/* NULL is a no-op; the result is zeroed. */
+void nolzss_free_rlz_repeats_result(nolzss_rlz_repeats_result *out);
+/* Host only (tests): the decision of nolzss_rlz_index_repeats once its counts are known -- NOLZSS_OK, or
+ * NOLZSS_ERR_INVALID_ARGUMENT with the message of the call -- and the bit offsets of the 8-bit digits the sort of its
+ * records runs for a block of block_length bases (shifts: room for 8). */
+int nolzss_debug_rlz_repeats_refusal(uint64_t num_repeats, uint64_t total_hits, uint64_t max_hits, uint64_t min_length);
+int nolzss_debug_rlz_repeat_shifts(uint64_t block_length, int *shifts, int *npasses);
 /* Maximal match seeds: which stretches of the targets occur in the reference, maximally extended, and where (DESIGN.md
  * 5, "Relative-LZ index: maximal match seeds").  Nothing is added to the handle; the batch goes up as a match lays it
  * out, Tcat = T1 s T2 s .. Tk s, and is searched once.

@@ -157,6 +157,12 @@ class RlzSeedsResult(C.Structure):
                 ("hits", C.c_void_p)]
 
 
+class RlzRepeatsResult(C.Structure):
+    """Mirror of nolzss_rlz_repeats_result (include/nolzss_hip.h)."""
+    _fields_ = [("num_repeats", C.c_size_t), ("repeats", C.c_void_p), ("hit_offsets", C.c_void_p), ("hits", C.c_void_p),
+                ("num_hits", C.c_size_t)]
+
+
 class RlzChainParams(C.Structure):
     """Mirror of nolzss_rlz_chain_params (include/nolzss_hip.h)."""
     _fields_ = [("min_length", C.c_uint64), ("max_hits", C.c_uint64), ("max_gap", C.c_uint64), ("bandwidth", C.c_uint64),
@@ -415,6 +421,13 @@ def _load():
     lib.nolzss_rlz_index_seeds.argtypes = [vp] + seqs[3:] + [C.c_uint64, C.c_uint64, C.POINTER(RlzSeedsResult)]
     lib.nolzss_free_rlz_seeds_result.argtypes = [C.POINTER(RlzSeedsResult)]
     lib.nolzss_free_rlz_seeds_result.restype = None
+    if hasattr(lib, "nolzss_rlz_index_repeats"):  # (NOLZSS_LIB: a variant built from an older commit has none)
+        lib.nolzss_rlz_index_repeat_count.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
+        lib.nolzss_rlz_index_repeats.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(RlzRepeatsResult)]
+        lib.nolzss_free_rlz_repeats_result.argtypes = [C.POINTER(RlzRepeatsResult)]
+        lib.nolzss_free_rlz_repeats_result.restype = None
+        lib.nolzss_debug_rlz_repeats_refusal.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+        lib.nolzss_debug_rlz_repeat_shifts.argtypes = [C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.nolzss_rlz_index_seed_chains.argtypes = [vp] + seqs[3:] + [C.POINTER(RlzChainParams), C.POINTER(RlzSeedChainsResult)]
     lib.nolzss_free_rlz_seed_chains_result.argtypes = [C.POINTER(RlzSeedChainsResult)]
     lib.nolzss_free_rlz_seed_chains_result.restype = None
@@ -553,6 +566,8 @@ EXPORTED_SYMBOLS = [
     "nolzss_rlz_index_open", "nolzss_rlz_index_open_fasta", "nolzss_rlz_index_info", "nolzss_rlz_index_factorize",
     "nolzss_rlz_index_codes", "nolzss_rlz_index_close", "nolzss_rlz_index_count", "nolzss_rlz_index_locate",
     "nolzss_debug_rlz_locate_shifts", "nolzss_rlz_index_seeds", "nolzss_free_rlz_seeds_result",
+    "nolzss_rlz_index_repeat_count", "nolzss_rlz_index_repeats", "nolzss_free_rlz_repeats_result",
+    "nolzss_debug_rlz_repeats_refusal", "nolzss_debug_rlz_repeat_shifts",
     "nolzss_rlz_archive_open_index", "nolzss_rlz_archive_append_index", "nolzss_rlz_archive_export",
     "nolzss_rlz_archive_pack", "nolzss_free_rlz_archive_packed", "nolzss_rlz_archive_open_packed",
     "nolzss_rlz_finder_open", "nolzss_rlz_finder_info", "nolzss_rlz_finder_count", "nolzss_rlz_finder_locate",

@@ -25,6 +25,8 @@ HIT_DTYPE = np.dtype([("position", "<u8"), ("record", "<u4"), ("is_rc", "<u4")])
 TARGET_HIT_DTYPE = np.dtype([("target", "<u8"), ("position", "<u8"), ("is_rc", "<u4"), ("primary", "<u4")])
 # nolzss_rlz_seed: a maximal exact match of a target with the reference block
 SEED_DTYPE = np.dtype([("target", "<u8"), ("start", "<u8"), ("length", "<u8"), ("count", "<u8")])
+# nolzss_rlz_repeat: a maximal repeat of the reference block itself
+REPEAT_DTYPE = np.dtype([("position", "<u8"), ("length", "<u8"), ("count", "<u8"), ("record", "<u4"), ("palindrome", "<u4")])
 # nolzss_rlz_chain and nolzss_rlz_chain_anchor (include/nolzss_hip.h): a seed chain and one of its anchors
 CHAIN_DTYPE = np.dtype([("target", "<u8"), ("t_start", "<u8"), ("t_end", "<u8"), ("r_start", "<u8"), ("r_end", "<u8"),
                         ("score", "<u8"), ("record", "<u4"), ("is_rc", "<u4"), ("num_anchors", "<u4"), ("primary", "<u4")])
@@ -1748,6 +1750,49 @@ class RlzIndexHandle:
         finally:
             lib.nolzss_free_rlz_seeds_result(C.byref(res))
         return seeds, offsets, hits
+
+    @staticmethod
+    def _repeat_rules(min_length, min_count):
+        min_length, min_count = operator.index(min_length), operator.index(min_count)
+        if min_length < 0:
+            raise ValueError("min_length must not be negative")
+        if min_count < 0:
+            raise ValueError("min_count must not be negative")
+        return min_length, min_count
+
+    def repeat_count(self, min_length: int = 20, min_count: int = 2) -> int:
+        """The records repeats(min_length, min_count) would report; only the flags are computed.  C ABI
+        nolzss_rlz_index_repeat_count (its header states the rules)."""
+        h = self._handle()
+        min_length, min_count = self._repeat_rules(min_length, min_count)
+        out = C.c_uint64()
+        check(lib.nolzss_rlz_index_repeat_count(h, min_length, min_count, C.byref(out)))
+        return int(out.value)
+
+    def repeats(self, min_length: int = 20, min_count: int = 2, max_hits: int = 64):
+        """-> (repeats, offsets, hits): the maximal repeats of the reference itself, both strands, as REPEAT_DTYPE
+        (position, length, count, record, palindrome), ascending by (position, length); the len(repeats) + 1 uint64 offsets
+        of their hits; the hits as HIT_DTYPE, per repeat ascending by (position, is_rc).  A repeat with more than max_hits
+        occurrences (0: no cap) reports its count and no hits.  C ABI nolzss_rlz_index_repeats (its header states the
+        rules)."""
+        h = self._handle()
+        min_length, min_count = self._repeat_rules(min_length, min_count)
+        max_hits = operator.index(max_hits)
+        if max_hits < 0:
+            raise ValueError("max_hits must not be negative")
+        res = _lib.RlzRepeatsResult()
+        try:
+            check(lib.nolzss_rlz_index_repeats(h, min_length, min_count, max_hits, C.byref(res)))
+            S, T = res.num_repeats, res.num_hits
+            offsets = np.ctypeslib.as_array(C.cast(res.hit_offsets, C.POINTER(C.c_uint64)), shape=(S + 1,)).copy()
+            repeats, hits = np.zeros(S, dtype=REPEAT_DTYPE), np.zeros(T, dtype=HIT_DTYPE)
+            if S:
+                C.memmove(repeats.ctypes.data, res.repeats, S * REPEAT_DTYPE.itemsize)
+            if T:
+                C.memmove(hits.ctypes.data, res.hits, T * HIT_DTYPE.itemsize)
+        finally:
+            lib.nolzss_free_rlz_repeats_result(C.byref(res))
+        return repeats, offsets, hits
 
     def seed_chains(self, targets, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 500,
                     min_score: int = 40):

@@ -1,5 +1,6 @@
 // rlz_handles.hpp -- the resident relative-LZ handles and what the translation units of their entry points share: the
-// index and its match (rlz_index_api.hip), its pattern queries (rlz_index_query_api.hip) and its seed queries
+// index and its match (rlz_index_api.hip), its pattern queries (rlz_index_query_api.hip), the repeats of its reference
+// (rlz_index_repeats_api.hip) and its seed queries
 // (rlz_index_seeds_api.hip); the archive (rlz_archive_api.hip), whose appends run that match; a finder reads both
 // (rlz_find_api.hip); a pileup reduces the alignments of the index (rlz_pileup_api.hip); a cohort packs the calls of
 // pileups into bit planes and compares them (rlz_cohort_api.hip).  DESIGN.md 5, "Relative-LZ archive: batches appended from the index" and "Relative-LZ archive:

@@ -1,6 +1,7 @@
 // rlz_index.hpp -- the relative-LZ index: the suffix structures of the reference kept resident, target batches matched
 // against them by search ("Relative-LZ index: targets matched against a resident reference"; the kernels:
-// rlz_index.hip, rlz_locate.hip for pattern queries, rlz_seeds.hip for maximal match seeds, rlz_seed_chain.hip for
+// rlz_index.hip, rlz_locate.hip for pattern queries, rlz_repeats.hip for the maximal repeats of the reference itself
+// (its entry points: rlz_index_repeats_api.hip), rlz_seeds.hip for maximal match seeds, rlz_seed_chain.hip for
 // their colinear chains, rlz_align.hip for the base-level alignments of those, rlz_pileup.hip for the pileup counts of
 // the alignments, rlz_consensus.hip for the insertion alleles and the consensus of a pileup and rlz_cohort.hip for the bit planes of
 // many samples and their comparison; the handle and its entry points: rlz_index_api.hip, rlz_index_query_api.hip, rlz_index_seeds_api.hip,
@@ -98,6 +99,41 @@ void rlz_index_seed_intervals(Context &ctx, const RlzIndexView &ix, const Packed
 LocateSorted rlz_index_seed_hits(Context &ctx, const RlzIndexView &ix, uint32_t records, uint32_t n, const uint32_t *d_seeds,
                                  const uint32_t *d_len, uint32_t S, const uint32_t *d_rep, const uint32_t *d_first,
                                  uint32_t T);
+
+// ---- maximal repeats of the reference (rlz_repeats.hip; DESIGN.md 5, "Relative-LZ index: maximal repeats") -----------
+// A reported repeat is one LCP interval of X: its representative is the leftmost rank r in (lo, hi] with lcp[r] = the
+// interval's value.  The rules of the reported set: include/nolzss_hip.h, nolzss_rlz_index_repeats.
+struct RepeatRec {  // nolzss_rlz_repeat
+    uint64_t position, length, count;
+    uint32_t record, palindrome;
+};
+// Stages 1 and 2 over the n = |X| ranks.  d_left (n + 1 entries): the left-context flags, scanned in place -- entry
+// r + 1 = D[r], the ranks up to r whose suffix has another base in front of it than its left neighbour's, or none.
+// d_flag[r] = 1 iff rank r represents a reported repeat of at least min_len >= 1 bases with at least min_count
+// occurrences, d_slot[r] = the flags in front of r (n entries each); *d_total = their number S (device memory).
+void rlz_repeat_flags(Context &ctx, const RlzIndexView &ix, uint32_t min_len, uint32_t min_count, uint32_t *d_left,
+                      uint32_t *d_flag, uint32_t *d_slot, uint32_t *d_total);
+// The S repeats ascending by keys[j] = (position << 32) | length: first[j] = the first rank of the interval, count[j] =
+// its members, rep[j] = count[j] where count[j] <= cap, else 0 (the hits that are reported), pal[j] = 1 for a palindrome.
+// Arena memory, 37 bytes per repeat and the sort's histograms.
+struct RepeatList {
+    const uint64_t *keys = nullptr;
+    const uint32_t *first = nullptr, *count = nullptr, *rep = nullptr;
+    const uint8_t *pal = nullptr;
+    uint32_t S = 0;
+};
+// The bit offsets of the 8-bit digits the sort of the repeats runs, least significant first, for a block of B bases (host
+// only): at most kLocateMaxPasses, none of them across bit 32 of the key.  Returns their number.
+int rlz_repeat_sort_shifts(uint64_t B, int *shifts);
+RepeatList rlz_repeat_list(Context &ctx, const RlzIndexView &ix, uint32_t min_len, uint32_t min_count, uint32_t cap,
+                           const uint32_t *d_left, const uint32_t *d_flag, const uint32_t *d_slot, uint32_t S);
+// repeats [first, first + count) of the list as records
+void rlz_repeat_records(Context &ctx, const RlzIndexView &ix, const RepeatList &list, size_t first, uint32_t count,
+                        RepeatRec *d_out);
+// The T = sum(rep) hits of the list expanded and sorted by (repeat, position, strand), laid out as rlz_index_hits lays
+// out the hits of patterns (the caller has made sure that T stays below 2^32 and S below 2^31).  Arena memory: 4 bytes
+// per repeat, 24 per hit and the sort's histograms.
+LocateSorted rlz_repeat_hits(Context &ctx, const RlzIndexView &ix, uint32_t records, const RepeatList &list, uint32_t T);
 
 // ---- colinear seed chains (rlz_seed_chain.hip; DESIGN.md 5, "Relative-LZ index: colinear seed chains") ---------------
 // An anchor is one reported hit of one seed: q = the seed's start inside its target, y = its coordinate in X (the hit's

@@ -24,6 +24,7 @@ RLZ_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("ref", "<u8"), ("is_
 TARGET_HIT_DTYPE = _native.TARGET_HIT_DTYPE  # (target, position, is_rc, primary): RlzArchiveFinder.locate
 HIT_DTYPE = _native.HIT_DTYPE  # (position, record, is_rc): an occurrence of a pattern (RlzIndex.locate)
 SEED_DTYPE = _native.SEED_DTYPE  # (target, start, length, count): a maximal exact match of a target (RlzIndex.seeds)
+REPEAT_DTYPE = _native.REPEAT_DTYPE  # (position, length, count, record, palindrome): a maximal repeat (RlzIndex.repeats)
 CHAIN_DTYPE = _native.CHAIN_DTYPE  # a seed chain: one placement of a target in a record and strand (RlzIndex.seed_chains)
 CHAIN_ANCHOR_DTYPE = _native.CHAIN_ANCHOR_DTYPE  # (t_start, position, length): one anchor of a seed chain
 ALIGN_DTYPE = _native.ALIGN_DTYPE  # the base-level alignment of one seed chain (RlzIndex.align)
@@ -818,6 +819,31 @@ class RlzIndex:
                 "record": f["record"].copy(), "record_offset": f["position"] - starts[f["record"]],
                 "is_rc": f["is_rc"].astype(bool)}
 
+    def repeat_count(self, min_length: int = 20, min_count: int = 2) -> int:
+        """How many records repeats(min_length, min_count) would report: the flags are computed on the GPU and one word
+        comes down.  It is how to pick min_length before asking for the records."""
+        return self._live().repeat_count(min_length, min_count)
+
+    def repeats(self, min_length: int = 20, min_count: int = 2, max_hits: int = 64):
+        """The maximal repeats of the reference itself, on either strand -> dict(position, length, count, record,
+        record_offset, palindrome, offsets, hit_position, hit_record, hit_record_offset, hit_is_rc).  A maximal repeat is
+        a string with at least two occurrences (both strands together on an index with reverse complement) that do not
+        all continue with the same base to the right, nor all to the left; a record's end is a continuation of its own.
+        Reported are those of at least min_length bases and min_count occurrences.  With reverse complement w and rc(w)
+        are one repeat, reported once at its leftmost forward occurrence; a string that is its own reverse complement
+        has palindrome set, lists every locus on both strands, and is reported only with two loci (count >= 4).  position
+        is the leftmost forward occurrence in the reference block, record and record_offset say where that lies; the
+        repeats ascend by (position, length).  Repeat j owns the hits [offsets[j], offsets[j + 1]), every occurrence laid
+        out and sorted as locate lays out the hits of a pattern; a repeat with more than max_hits occurrences (0: no
+        cap) reports its count and no hits.  Everything is read off the resident arrays on the GPU; nothing goes up."""
+        r, offsets, f = self._live().repeats(min_length, min_count, max_hits)
+        starts = np.cumsum([0] + [len(x) + 1 for x in self._reference[:-1]], dtype=np.uint64)  # of every record in Rblk
+        return {"position": r["position"].copy(), "length": r["length"].copy(), "count": r["count"].copy(),
+                "record": r["record"].copy(), "record_offset": r["position"] - starts[r["record"]],
+                "palindrome": r["palindrome"].astype(bool), "offsets": offsets, "hit_position": f["position"].copy(),
+                "hit_record": f["record"].copy(), "hit_record_offset": f["position"] - starts[f["record"]],
+                "hit_is_rc": f["is_rc"].astype(bool)}
+
     def seed_chains(self, targets, min_length: int = 15, max_hits: int = 64, max_gap: int = 5000, bandwidth: int = 500,
                     min_score: int = 40, batch_bases=None):
         """Where every target lies in the reference: its seeds (as seeds(targets, min_length, max_hits) finds them; a seed
@@ -1208,5 +1234,5 @@ def resolve_target(target, index, count):
     return j
 
 
-__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "INSERTION_DTYPE", "insertion_bases", "PILEUP_CHANNELS", "RlzPileup", "COHORT_SITE_DTYPE", "RlzCohort", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
+__all__ = ["RLZ_DTYPE", "HIT_DTYPE", "SEED_DTYPE", "REPEAT_DTYPE", "CHAIN_DTYPE", "CHAIN_ANCHOR_DTYPE", "ALIGN_DTYPE", "VARIANT_DTYPE", "INSERTION_DTYPE", "insertion_bases", "PILEUP_CHANNELS", "RlzPileup", "COHORT_SITE_DTYPE", "RlzCohort", "cigar_string", "TARGET_HIT_DTYPE", "RlzArchiveFinder", "split_and_rebase", "rebase", "rlz_factorize", "rlz_count_factors", "rlz_factorize_fasta",
            "rlz_summary", "rlz_literals", "rlz_decode", "RlzArchive", "RlzIndex", "plan_index_batches", "write_packed_archive", "read_packed_archive"]
